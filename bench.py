@@ -14,6 +14,9 @@ Three ways to run N > 1:
   * `python -m torch.distributed.run ... bench.py --gpus N`   one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE from
                                                     the environment), gloo only for the timing bracket;
   * FTMPC_BENCH_SINGLE_DEVICE=1 (tests)             either of the above with every rank / slot on device 0.
+
+`--dump-outputs DIR` writes what the last timed step returned (u0, status, iters of every instance, float64) to
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -189,6 +192,29 @@ def cpu_baseline(N, NT, x0, ub, stuck, xref, u0_gpu, f32):
             "parallel_speedup": (sample / cpu_t) / (n1 / one_t)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed path handed back in its last step (one row per instance), as float64
+    `<name>.npy` files under `out_dir`.  A batch whose rows exceed `limit` bytes in all is cut to a fixed, seeded
+    sample of instances (the same rows on every run with the same arguments); `instance.npy` then lists them."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = B
+    if B * row_bytes > limit:
+        keep = max(1, limit // (row_bytes + 8))          # (+ 8: the float64 instance index of every kept row)
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instance"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(a))
+    return keep
+
+
 def make_line(args, world, elapsed, B, N, NT, iters, status, ub, kernel_ms, parallelism):
     lin_ms = kernel_ms.pop("ftmpc_linearize_kernel", 0.0)
     dom = max(kernel_ms, key=kernel_ms.get)
@@ -261,6 +287,9 @@ def run_multi_inprocess(args):
     m.upload(x0, ub, stuck, xr)
     m.step(args.warmup)
     elapsed = timed(m, args.steps)
+    if args.dump_outputs:
+        last = m.download()          # the whole batch as the last timed step left it on the devices
+        dump_outputs(args.dump_outputs, {k: last[k] for k in ("u0", "status", "iters")})
     m.set_profiling(True)
     kms = []
     for _ in range(3):
@@ -354,6 +383,19 @@ def run_rank(args):
         step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs:
+        # what the last timed step returned, before the steps below overwrite it; ranks concatenate in rank order, the
+        # layout of the in-process multi-GPU path (device g solves rank g's seeded batch)
+        last = {"u0": d_u0, "status": d_status, "iters": d_iters}
+        if world > 1:
+            gathered = {}
+            for k, t in last.items():
+                parts = [torch.empty_like(t, device="cpu") for _ in range(world)]
+                dist.all_gather(parts, t.cpu())
+                gathered[k] = torch.cat(parts)
+            last = gathered
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in last.items()})
 
     # per-kernel device time of three more (untimed) steps: hipEvents on the launch stream
     mpc.set_profiling(True)
@@ -418,7 +460,11 @@ def main():
     ap.add_argument("--faults", type=int, default=2)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"], help="arithmetic of the KKT/IPM solve")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (u0, status, iters) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup not negative")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world == 1:
         run_multi_inprocess(args)       # no launcher: fan out inside this process, before anything here touches a GPU

@@ -1,6 +1,8 @@
-"""Diagnostic: the two-stage step on an fp32 handle; dumps the wrenches whose allocation does not end with status 0."""
+"""Diagnostic: the two-stage step on an fp32 handle; dumps the wrenches whose allocation does not end with status 0
+(to build/alloc_fail.npy, or to the path given as the first argument)."""
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd')
 import numpy as np
 import ft_mpc_amd
 from ft_mpc_amd.controllers.tools.input_bounds import hull_tables
@@ -20,4 +22,6 @@ for (N, NT, B, nf, seed) in ((10, 16, 16384, 3, 7900), (15, 16, 16384, 2, 7900),
         print("  inst", b, "hull slack of tau0: min %.3e, rows within 1e-6: %d" % (sl.min(), (sl < 1e-6).sum()), "iters", out["iters"][b])
         rows.append(np.r_[out["tau0"][b], ub[b], stuck[b], out["u0"][b], out["alloc_status"][b]])
     m.close()
-np.save("/root/repo/gpurun_out/r04_alloc_fail.npy", np.array(rows))
+dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "build", "alloc_fail.npy")
+os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+np.save(dst, np.array(rows))

@@ -1,6 +1,7 @@
 """Closed-loop Monte-Carlo campaign throughput: B vehicles x T steps on the device (ftmpc_simulate_batch)."""
 import sys, time
-sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0,'/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0,ROOT)
 import numpy as np, ft_mpc_amd
 B=int(sys.argv[1]) if len(sys.argv)>1 else 65536
 T=int(sys.argv[2]) if len(sys.argv)>2 else 20

@@ -1,6 +1,7 @@
 """Diagnostic: fp32 headline kernel against the (polished, exact) C oracle on a batch: error distribution, worst instances.  args: B nfault seed"""
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd')
 import numpy as np
 import ft_mpc_amd
 from oracle import qp_oracle as qo, c_oracle as co, refmath as rm

@@ -1,7 +1,8 @@
 """Throughput of the float64 shapes (device-resident buffers) for the library FTMPC_LIB names (default: the shipped one).
 Usage: [FTMPC_LIB=...] python scripts/f64_perf.py [kernel_select]"""
 import sys, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np, torch, ft_mpc_amd
 sel = sys.argv[1] if len(sys.argv) > 1 else "auto"
 def run(name, B, N, NT, nf, seed, reps=3):

@@ -1,6 +1,7 @@
 """Diagnostic: PCIe-inclusive rate of the host-buffer entry point (ftmpc_solve_batch) next to the device-pointer one."""
 import sys, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np
 import ft_mpc_amd
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536

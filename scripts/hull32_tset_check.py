@@ -1,7 +1,8 @@
 """Diagnostic: the two-stage form with the terminal set (kernel 11 + hand-over on an fp32 handle, the float64 kernel on a float64
 handle) against the NumPy oracle with its active-set polish, vehicles with the tracking error on the boundary of the set."""
 import sys, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo/tests')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT + '/tests')
 import numpy as np
 import ft_mpc_amd
 from ft_mpc_amd.controllers.tools.input_bounds import hull_tables

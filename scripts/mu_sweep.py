@@ -1,6 +1,7 @@
 """Diagnostic: accuracy and rate of the fp32 path against the IPM stopping threshold mu_stop (full config-3 batch)."""
 import sys, time, os
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np, torch, ft_mpc_amd
 from oracle import c_oracle as co, qp_oracle as qo
 B, N, NT = 65536, 20, 8

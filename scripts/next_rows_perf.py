@@ -1,7 +1,8 @@
 """Throughput of the SURVEY section 8(f) "next" rows on one GPU (parity-test shapes, not bench lines):
 generalized-force formulation (hull rows + allocation), terminal-set modes, the cost kernel and the line-search SQP."""
 import sys, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np
 import ft_mpc_amd
 from ft_mpc_amd.controllers.tools.input_bounds import hull_tables

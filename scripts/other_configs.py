@@ -1,6 +1,7 @@
 """Throughput of the non-headline BASELINE configs on one GPU (parity-test shapes, not bench lines)."""
 import sys, time
-sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0,'/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0,ROOT)
 import numpy as np, torch, ft_mpc_amd
 ONLY=sys.argv[1:]     # substrings of the names to run (default: all)
 def run(name,B,N,NT,nf,dtype,seed,reps=3,sel="auto"):

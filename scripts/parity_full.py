@@ -1,6 +1,7 @@
 """Full-batch parity study: GPU u0 vs the exact (mu 1e-13) float64 oracle; error percentiles."""
 import sys, time, os
-sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0,'/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0,ROOT)
 import numpy as np
 import ft_mpc_amd
 from oracle import c_oracle as co, qp_oracle as qo

@@ -1,7 +1,8 @@
 """Study (numpy, fp32 emulation): leave the box-QP interior-point iteration early (mu < thr) and finish by an active-set polish with a
 diagonal penalty -- iterations saved, rounds needed, distance from the exact solution.  Headline shape by default."""
 import sys
-sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 from oracle import qp_oracle as qo
 

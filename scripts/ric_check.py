@@ -1,6 +1,7 @@
 """Diagnostic: the float64 kernels (Riccati = auto, wrench-space = workgroup) and the C oracle on one config-5 batch: statuses, iterations."""
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd')
 import numpy as np
 import ft_mpc_amd
 from oracle import c_oracle as co, qp_oracle as qo

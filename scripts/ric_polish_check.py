@@ -1,7 +1,8 @@
 """Diagnostic: kernel 12 (early polish) against the C oracle's iteration at mu 1e-13 AND the independent exact solver (BVLS) on the
 instances where the two differ most -- which of them is nearer the exact solution?   args: N NT B seed"""
 import sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd')
 import numpy as np
 import ft_mpc_amd
 from oracle import qp_oracle as qo, c_oracle as co, refmath as rm

@@ -1,6 +1,7 @@
 """Diagnostic: latency of ONE MPC step (the reference's own use: examples/sim.py solves one QP per 0.1 s tick)."""
 import sys, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np
 import ft_mpc_amd
 for (N, NT, nf, dt) in ((15, 16, 2, "f32"), (20, 8, 2, "f32"), (15, 16, 2, "f64")):

@@ -1,7 +1,8 @@
 """Diagnostic: ftmpc_solve_sqp_batch, direct launches against the replayed hipGraph (FTMPC_SQP_GRAPH=0 / 1), per batch size."""
 import os, sys, time, subprocess
 if len(sys.argv) > 1 and sys.argv[1] == "child":
-    sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd')
+    import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd')
     import numpy as np
     import ft_mpc_amd
     from oracle import qp_oracle as qo

@@ -1,5 +1,6 @@
 import sys
-sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0,'/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0,ROOT)
 import numpy as np, ft_mpc_amd
 from oracle import c_oracle as co, qp_oracle as qo
 N,NT,B=20,8,65536

@@ -1,6 +1,7 @@
 """Diagnostic: per-phase cycle shares of the fp32 solve kernel (stamps build, see csrc/Makefile)."""
 import sys, ctypes as C
-sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0,'/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0,ROOT)
 import numpy as np
 from ft_mpc_amd import _lib
 import os

@@ -1,6 +1,7 @@
 """Diagnostic: per-phase cycle shares of kernel 11 (ftmpc_solve_hull32_kernel; stamps build, see csrc/Makefile) and device-side timing of the two-stage step."""
 import sys, ctypes as C, os, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np
 from pathlib import Path
 from ft_mpc_amd import _lib

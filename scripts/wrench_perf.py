@@ -1,7 +1,8 @@
 """Throughput and accuracy of the two-stage step (generalized-force MPC with hull rows [+ terminal set], then allocation) on an fp32
 handle (kernel 11 + hand-over) and a float64 handle, regular random batch (scripts/hull32_tset_check.py: the boundary batch)."""
 import sys, time
-sys.path.insert(0, '/root/repo/fault-tolerant-mpc_amd'); sys.path.insert(0, '/root/repo')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT + '/fault-tolerant-mpc_amd'); sys.path.insert(0, ROOT)
 import numpy as np
 import ft_mpc_amd
 from ft_mpc_amd.controllers.tools.input_bounds import hull_tables

@@ -1,6 +1,7 @@
 import os, sys
 import numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/fault-tolerant-mpc_amd')
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT); sys.path.insert(0,ROOT + '/fault-tolerant-mpc_amd')
 import ft_mpc_amd
 from oracle import qp_oracle as qo, c_oracle as co
 N,NT,seed=21,11,5

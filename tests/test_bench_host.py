@@ -31,6 +31,30 @@ def test_usable_cores_and_source_hash():
     assert len(h) == 16 and h == bench.csrc_hash()
 
 
+def test_dump_outputs_whole_batch_and_seeded_sample(tmp_path):
+    rng = np.random.default_rng(1)
+    u0 = rng.standard_normal((1000, 8))
+    status = rng.integers(0, 3, 1000).astype(np.int32)
+    assert bench.dump_outputs(tmp_path / "all", {"u0": u0, "status": status}) == 1000
+    assert sorted(p.name for p in (tmp_path / "all").iterdir()) == ["status.npy", "u0.npy"]
+    got = np.load(tmp_path / "all" / "status.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, status)
+    assert np.array_equal(np.load(tmp_path / "all" / "u0.npy"), u0)
+    # over the limit: the same seeded rows every time, their instance numbers beside them, within the limit
+    limit = 100 * 9 * 8
+    kept = [bench.dump_outputs(tmp_path / d, {"u0": u0, "status": status}, limit=limit) for d in ("a", "b")]
+    assert kept[0] == kept[1] == limit // (9 * 8 + 8)
+    idx = np.load(tmp_path / "a" / "instance.npy").astype(np.int64)
+    assert len(idx) == kept[0] and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "b" / "instance.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "u0.npy"), u0[idx]) and np.array_equal(np.load(tmp_path / "b" / "u0.npy"), u0[idx])
+    assert sum((tmp_path / "a" / f).stat().st_size - 128 for f in ("u0.npy", "status.npy", "instance.npy")) <= limit
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_gpus_flag_fails_loudly_without_a_gpu():
     import torch
     if torch.cuda.is_available():

@@ -34,6 +34,29 @@ def test_single_gpu_line():
     assert j["warm_start"]["value"] > 1e5 and j["warm_start"]["ipm_iters_mean"] > 1
 
 
+def test_single_gpu_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's u0 / status / iters as float64 .npy; two runs with the same
+    arguments (and a different step count) solve the same inputs and return the same thrust commands."""
+    import numpy as np
+    got = []
+    for steps in (1, 3):
+        d = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", str(steps), "--warmup", "0", "--batch", "4096",
+                            "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        assert j["steps"] == steps
+        out = {k: np.load(d / f"{k}.npy") for k in ("u0", "status", "iters")}
+        assert sorted(p.name for p in d.iterdir()) == ["iters.npy", "status.npy", "u0.npy"]
+        assert all(a.dtype == np.float64 for a in out.values())
+        assert out["u0"].shape == (4096, 8) and out["status"].shape == (4096,) and out["iters"].shape == (4096,)
+        assert int((out["status"] != 0).sum()) == j["config"]["not_converged"] and out["iters"].max() == j["config"]["ipm_iters_max"]
+        assert np.isfinite(out["u0"]).all() and np.abs(out["u0"]).max() <= 3.4 + 1e-6
+        got.append(out)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
 def test_two_ranks_on_one_gpu():
     env = dict(os.environ, FTMPC_BENCH_SINGLE_DEVICE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
