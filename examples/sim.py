@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--formulation", default="thruster", choices=["thruster", "wrench"],
                     help="wrench: the reference's own two-stage structure (6-D MPC with the input hull, then allocation)")
     ap.add_argument("--terminal-set", action="store_true", help="add the 72-row terminal set of config/terminal.yaml")
+    ap.add_argument("--sqp-iters", type=int, default=None,
+                    help="major iterations of the line-search SQP towards the nonlinear program per step (1: one QP step)")
     args = ap.parse_args()
     params = yaml.safe_load(open(ROOT / "fault-tolerant-mpc_amd" / "ft_mpc_amd" / "config" / "reactive.yaml"))
     dt, duration = params["time_step"], params["traj_duration"]
@@ -44,6 +46,8 @@ def main():
             model.set_fault(BrokenThruster(f["act_id"], f["intensity"]))
     spiral_model = SpiralModel.from_system_model(model)
     tuning = dict(params["tuning"]["spiraling"], formulation=args.formulation, terminal_set=args.terminal_set)
+    if args.sqp_iters is not None:
+        tuning["sqp_iters"] = args.sqp_iters
     controller = SpiralingController(spiral_model, tuning, history, quiet=True)
     controller.load_trajectory(params["traj_shape"], duration)
     env = SimulationEnvironment(model, controller, seed=args.seed)

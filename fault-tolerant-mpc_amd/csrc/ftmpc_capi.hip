@@ -164,6 +164,11 @@ struct ftmpc_handle {
     hipGraphExec_t sqp_exec = nullptr;
     int64_t sqp_graph_launches = 0;    // (diagnostic: ftmpc_sqp_graph_launches)
     int64_t cap_hullA = 0, cap_wrench = 0;
+    // line-search SQP of the generalized-force formulation (ftmpc_solve_sqp_wrench_batch): iterate, next iterate | merit, -, alpha,
+    // cost and terminal-set violation of the start point and of the result | flags and counters (as d_sqF) | merits of all trial points
+    double *d_swG = nullptr, *d_swT = nullptr, *d_swJ = nullptr, *d_swJall = nullptr, *d_swX = nullptr;
+    int32_t* d_swF = nullptr;
+    int64_t cap_swsqp = 0, cap_swJall = 0, cap_swX = 0;
     // kernel 13: the two-stage form in float64 by the Riccati recursion (no terminal set, N <= 40, up to 128 hull rows)
     double* ricw_slot = nullptr;
     int64_t ricw_slot_doubles = 0;
@@ -547,7 +552,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 430; }
+int32_t ftmpc_version(void) { return 440; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -859,7 +864,8 @@ int ftmpc_destroy(ftmpc_handle* h) {
     void* ptrs[] = {h->rec, h->d_x0, h->d_ub, h->d_stuck, h->d_xref, h->d_uref, h->d_warm, h->d_u0, h->d_U,
                     h->d_status, h->d_iters, h->hs[0], h->hs[1], h->hs[2], h->d_dbgH, h->d_dbgv, h->Hs, h->Ls, h->Eall, h->d_dbgH64, h->d_dbgv64,
                     h->d_atau, h->d_aub, h->d_au, h->d_ast, h->d_ait, h->d_qlist, h->d_qctl, h->d_term, h->d_eN, h->gHs, h->gLs,
-                    h->gEall, h->wg_slot, h->ws_slot, h->ws64_slot, h->ric_slot, h->ricw_slot, h->d_cbar, h->wsw_slot, h->hull_slot, h->d_tcost, h->d_cost, h->d_sqU, h->d_sqQ, h->d_sqT, h->d_sqJ, h->d_sqJall, h->d_sqF, h->d_hullA, h->d_hullb, h->d_warmG, h->d_tau0, h->d_G, h->d_taud, h->d_hullset, h->d_ast2};
+                    h->gEall, h->wg_slot, h->ws_slot, h->ws64_slot, h->ric_slot, h->ricw_slot, h->d_cbar, h->wsw_slot, h->hull_slot, h->d_tcost, h->d_cost, h->d_sqU, h->d_sqQ, h->d_sqT, h->d_sqJ, h->d_sqJall, h->d_sqF, h->d_hullA, h->d_hullb, h->d_warmG, h->d_tau0, h->d_G, h->d_taud, h->d_hullset, h->d_ast2,
+                    h->d_swG, h->d_swT, h->d_swJ, h->d_swJall, h->d_swF, h->d_swX};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->sqp_exec) (void)hipGraphExecDestroy(h->sqp_exec);
@@ -1427,11 +1433,15 @@ static int wrench_prepare(ftmpc_handle* h, int64_t B, const double* hull_A, int3
     return FTMPC_OK;
 }
 
-// One two-stage step over DEVICE buffers (h->d_x0 / d_ub / d_stuck, the staged hull tables, the given reference windows):
-// linearise, the 6N-variable QP with the hull rows, allocation.  Leaves u0 in h->d_u0, tau_0 in h->d_tau0, the wrenches in h->d_G.
-static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_set, const double* d_xref, int64_t xref_stride,
-                          const double* d_uref, int64_t uref_stride, const double* d_warmG) {
+// The QP half of a two-stage step over DEVICE buffers (h->d_x0 / d_ub / d_stuck, the staged hull tables, the given reference
+// windows): linearise about d_warmG (NULL: D stuck), the 6N-variable QP with the hull rows.  Leaves tau_0 in h->d_tau0, the wrenches in
+// h->d_G, status / iterations in h->d_status / d_iters.  fork_alloc: where kernel 11 hands over to kernel 13, the allocation of what
+// kernel 11 certified starts on the second stream before kernel 13's pass (*forked reports it; wrench_alloc_enqueue finishes it);
+// otherwise everything stays on the handle's stream.
+static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_set, const double* d_xref, int64_t xref_stride,
+                             const double* d_uref, int64_t uref_stride, const double* d_warmG, bool fork_alloc, bool* forked) {
     hipStream_t s = h->stream;
+    *forked = false;
     LinParams lp;
     lp.B = B;
     lp.x0 = h->d_x0; lp.ub = h->d_ub; lp.stuck = h->d_stuck;
@@ -1490,7 +1500,8 @@ static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool ha
     h->wrench_handed = handed;
     // allocation of the batch on a second stream, beside kernel 13's pass over the hand-over list (not while profiling: the
     // event pairs of ftmpc_last_kernel_ms sit on one stream)
-    const bool overlap = handed && hull_ricw(h, hull_rows) && !h->profiling && h->stream2 != nullptr;
+    const bool overlap = fork_alloc && handed && hull_ricw(h, hull_rows) && !h->profiling && h->stream2 != nullptr;
+    *forked = overlap;
     if (overlap) {
         HIP_TRY(h, hipEventRecord(h->ev_fork, s));
         HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
@@ -1573,6 +1584,13 @@ static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool ha
         hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<4, 1, 1>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, dcg, q);
     HIP_TRY(h, hipGetLastError());
     }
+    return FTMPC_OK;
+}
+
+// The allocation half: u0 in h->d_u0 = min-norm allocation of h->d_tau0 - D stuck, status / iterations in h->d_ast2.  forked: the
+// QP half started it on the second stream; only the instances kernel 11 handed over remain (list mode).
+static int wrench_alloc_enqueue(ftmpc_handle* h, int64_t B, bool forked) {
+    hipStream_t s = h->stream;
     // second stage: min-norm allocation of the wrench the healthy thrusters have to produce
     ftmpc::AllocParams ap;
     ap.B = B;
@@ -1591,7 +1609,7 @@ static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool ha
         a.count = count;
         hipLaunchKernelGGL(ftmpc::ftmpc_allocate_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, h->dc, a);
     };
-    if (overlap) {
+    if (forked) {
         // the handed-over instances (a few dozen of a regular batch, one wave each: ~2 ms of latency, the device nearly idle) run
         // on kernel 13 while the second stream allocates everything kernel 11 certified; their own allocation follows in list mode
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_alloc, 0));
@@ -1601,6 +1619,15 @@ static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool ha
     }
     HIP_TRY(h, hipGetLastError());
     return FTMPC_OK;
+}
+
+// One two-stage step: the QP half, then the allocation half (beside kernel 13's hand-over pass where that applies).
+static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_set, const double* d_xref, int64_t xref_stride,
+                          const double* d_uref, int64_t uref_stride, const double* d_warmG) {
+    bool forked = false;
+    int rc = wrench_qp_enqueue(h, B, hull_rows, has_set, d_xref, xref_stride, d_uref, uref_stride, d_warmG, true, &forked);
+    if (rc != FTMPC_OK) return rc;
+    return wrench_alloc_enqueue(h, B, forked);
 }
 
 int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
@@ -1644,6 +1671,223 @@ int ftmpc_last_handed_over(ftmpc_handle* h, int64_t* count) {
     HIP_TRY(h, hipMemcpyAsync(&c, h->d_qctl, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *count = c;
+    return FTMPC_OK;
+}
+
+// ---- the line-search SQP of the generalized-force formulation -------------------------------------------------------------
+// Default weight sigma of the terminal-set violation in the merit (penalty <= 0).  An exact l1 penalty needs sigma above the
+// largest terminal-row multiplier of the QPs; the largest one oracle/qp_oracle.py:ipm_general returns on the batches of
+// tests/test_gpu_wrench_sqp.py is 9.4e3; the default is ten times that, rounded.
+#define FTMPC_SQPW_PENALTY 1.0e5
+
+// the rows of the terminal set on the device (term_A | term_b), once per handle
+static int term_upload(ftmpc_handle* h) {
+    if (!h->cfg.terminal_set || h->d_term) return FTMPC_OK;
+    if (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS) return fail(h, FTMPC_ERR_ARG, "term_rows out of range");
+    int rc = grow(h, &h->d_term, (int64_t)h->cfg.term_rows * 10);
+    if (rc != FTMPC_OK) return rc;
+    std::vector<double> t((size_t)h->cfg.term_rows * 10);
+    std::memcpy(t.data(), h->cfg.term_A, (size_t)h->cfg.term_rows * 9 * sizeof(double));
+    std::memcpy(t.data() + (size_t)h->cfg.term_rows * 9, h->cfg.term_b, (size_t)h->cfg.term_rows * sizeof(double));
+    HIP_TRY(h, hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    return FTMPC_OK;
+}
+
+// workspace of the wrench SQP: iterates [B*N*6] x 2, per-instance doubles [6B] (merit | alpha | cost0 | cost | violation | spare),
+// flags [6B] (the layout of d_sqF), trial merits [B*backtracks], centre states [B*(N+1)*13] when wanted
+static int sqpw_grow(ftmpc_handle* h, int64_t B, int32_t backtracks, bool want_X) {
+    const int N = h->cfg.N;
+    int rc;
+    if (B > h->cap_swsqp) {
+        h->cap_swsqp = 0;   // (a failed growth must not leave a stale capacity)
+        if ((rc = grow(h, &h->d_swG, B * N * 6)) != FTMPC_OK || (rc = grow(h, &h->d_swT, B * N * 6)) != FTMPC_OK ||
+            (rc = grow(h, &h->d_swJ, 6 * B)) != FTMPC_OK || (rc = grow(h, &h->d_swF, 6 * B)) != FTMPC_OK)
+            return rc;
+        h->cap_swsqp = B;
+    }
+    if (B * backtracks > h->cap_swJall) {
+        h->cap_swJall = 0;
+        if ((rc = grow(h, &h->d_swJall, B * backtracks)) != FTMPC_OK) return rc;
+        h->cap_swJall = B * backtracks;
+    }
+    if (want_X && B > h->cap_swX) {
+        h->cap_swX = 0;
+        if ((rc = grow(h, &h->d_swX, B * (N + 1) * 13)) != FTMPC_OK) return rc;
+        h->cap_swX = B;
+    }
+    return FTMPC_OK;
+}
+
+static ftmpc::CostWrenchParams cost_wrench_params(const ftmpc_handle* h, int64_t B, const double* d_xref, int64_t xref_stride,
+                                                  const double* d_uref, int64_t uref_stride, double sigma) {
+    ftmpc::CostWrenchParams cw;
+    cw.B = B;
+    cw.x0 = h->d_x0;
+    cw.xref = d_xref; cw.xref_stride = xref_stride;
+    cw.uref = d_uref; cw.uref_stride = uref_stride;
+    cw.G = nullptr;
+    cw.tcost = h->d_tcost;
+    cw.termA = h->cfg.terminal_set ? h->d_term : nullptr;
+    cw.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
+    cw.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
+    cw.sigma = sigma;
+    cw.out_merit = cw.out_cost = cw.out_tviol = cw.out_X = nullptr;
+    return cw;
+}
+
+// One wrench SQP solve over DEVICE buffers (h->d_x0 / d_ub / d_stuck, the hull tables staged by wrench_prepare, the given reference
+// windows), direct launches on the handle's stream, no second stream.  Per major iteration: the wrench QP linearised about the iterate
+// (wrench_qp_enqueue: kernel 11 with its hand-over, kernel 13 or the dense float64 kernel), every trial point of the line search in one
+// launch, the first acceptable one picked.  After the last iteration: the cost, the violation and (d_X) the centre states of the final
+// iterate, u0 = allocation of its tau_0 - D stuck in h->d_u0.  On return S.U is the final iterate, S.status / nmajor / ipm the counters.
+static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_set, const double* d_xref, int64_t xref_stride,
+                        const double* d_uref, int64_t uref_stride, const double* d_warm, int32_t sqp_iters, int32_t backtracks, double tol,
+                        double sigma, bool want_X, ftmpc::SqpState& S) {
+    const int N = h->cfg.N;
+    int rc = sqpw_grow(h, B, backtracks, want_X);
+    if (rc != FTMPC_OK) return rc;
+    if ((rc = term_upload(h)) != FTMPC_OK) return rc;
+    hipStream_t s = h->stream;
+    S.B = B; S.N = N; S.NT = 6;
+    S.ub = nullptr;
+    S.U = h->d_swG; S.Uq = h->d_G; S.Ut = h->d_swT;
+    S.J = h->d_swJ; S.Jt = nullptr; S.alpha = h->d_swJ + B;
+    S.active = h->d_swF; S.todo = h->d_swF + B; S.improved = h->d_swF + 2 * B; S.nmajor = h->d_swF + 3 * B; S.ipm = h->d_swF + 4 * B;
+    S.status = h->d_swF + 5 * B;
+    S.qstatus = h->d_status; S.qiters = h->d_iters;
+    S.tol = tol;
+    S.Jall = h->d_swJall;
+    S.ntrial = backtracks;
+    const int64_t nw = (int64_t)N * 6;
+    const unsigned gE = (unsigned)((B * nw + 255) / 256), gB = (unsigned)((B + 255) / 256);
+    const ftmpc::CostWrenchParams cw = cost_wrench_params(h, B, d_xref, xref_stride, d_uref, uref_stride, sigma);
+    hipLaunchKernelGGL(ftmpc::ftmpc_sqpw_init_kernel, dim3(gE > gB ? gE : gB), dim3(256), 0, s, h->dc, S, d_warm, (const double*)h->d_stuck);
+    {   // merit and cost of the start point
+        ftmpc::CostWrenchParams c0 = cw;
+        c0.G = S.U;
+        c0.out_merit = S.J;
+        c0.out_cost = h->d_swJ + 2 * B;
+        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, c0);
+    }
+    HIP_TRY(h, hipGetLastError());
+    for (int it = 0; it < sqp_iters; ++it) {
+        // the QP linearised about the current iterate (every instance: a stopped one costs a solve but changes nothing)
+        bool forked = false;
+        if ((rc = wrench_qp_enqueue(h, B, hull_rows, has_set, d_xref, xref_stride, d_uref, uref_stride, S.U, false, &forked)) != FTMPC_OK)
+            return rc;
+        hipLaunchKernelGGL(ftmpc::ftmpc_sqp_open_kernel, dim3(gB), dim3(256), 0, s, S);
+        ftmpc::CostWrenchParams ct = cw;
+        ct.G = S.U;
+        ct.Gq = S.Uq;
+        ct.todo = S.todo;
+        ct.ntrial = backtracks;
+        ct.out_merit = h->d_swJall;
+        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B * backtracks + 63) / 64)), dim3(64), 0, s, h->dc, ct);
+        hipLaunchKernelGGL(ftmpc::ftmpc_sqp_pick_kernel, dim3(gB), dim3(256), 0, s, S);
+        hipLaunchKernelGGL(ftmpc::ftmpc_sqpw_close_kernel, dim3(gE), dim3(256), 0, s, S);     // new iterate -> Ut
+        hipLaunchKernelGGL(ftmpc::ftmpc_sqp_count_kernel, dim3(gB), dim3(256), 0, s, S);
+        std::swap(S.U, S.Ut);
+        HIP_TRY(h, hipGetLastError());
+    }
+    {   // cost, violation and rollout of the result
+        ftmpc::CostWrenchParams cf = cw;
+        cf.G = S.U;
+        cf.out_merit = h->d_swJ + 5 * B;
+        cf.out_cost = h->d_swJ + 3 * B;
+        cf.out_tviol = h->d_swJ + 4 * B;
+        cf.out_X = want_X ? h->d_swX : nullptr;
+        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, cf);
+    }
+    // second stage, once: allocation of the final tau_0 (on an fp32 handle pulled inside the float64 hull first, as kernel 11 does)
+    if (hull_fp32(h, hull_rows))
+        hipLaunchKernelGGL(ftmpc::ftmpc_sqpw_tau0_kernel, dim3(gB * 4), dim3(64), 0, s, h->dc, B, (const double*)S.U,
+                           (const double*)h->d_ub, (const double*)h->d_stuck, (const double*)h->d_hullA,
+                           (const int32_t*)(has_set ? h->d_hullset : nullptr), (const double*)h->d_hullb, hull_rows, h->d_tau0);
+    else
+        HIP_TRY(h, hipMemcpy2DAsync(h->d_tau0, 6 * sizeof(double), S.U, nw * sizeof(double), 6 * sizeof(double), (size_t)B,
+                                    hipMemcpyDeviceToDevice, s));
+    return wrench_alloc_enqueue(h, B, false);
+}
+
+int ftmpc_eval_cost_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck, const double* xref,
+                                 int64_t xref_stride, const double* uref, int64_t uref_stride, const double* G, double* out_cost,
+                                 double* out_tviol) {
+    (void)ub;
+    (void)stuck;
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0 || !x0 || !xref || !G || !out_cost) return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
+    if (B == 0) return FTMPC_OK;
+    int rc = check_strides(h, xref_stride, uref_stride, uref);
+    if (rc != FTMPC_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
+    if ((rc = sqpw_grow(h, B, 1, false)) != FTMPC_OK) return rc;
+    if ((rc = term_upload(h)) != FTMPC_OK) return rc;
+    const int N = h->cfg.N;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_swG, G, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    ftmpc::CostWrenchParams cw = cost_wrench_params(h, B, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride, 0.0);
+    cw.G = h->d_swG;
+    cw.out_merit = h->d_swJ;
+    cw.out_tviol = h->d_swJ + B;
+    hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, cw);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_cost, h->d_swJ, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_tviol) HIP_TRY(h, hipMemcpyAsync(out_tviol, h->d_swJ + B, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return FTMPC_OK;
+}
+
+// the arguments every entry of the wrench SQP refuses alike
+static int sqpw_check(ftmpc_handle* h, int32_t sqp_iters, int32_t backtracks, double tol, double penalty) {
+    if (sqp_iters < 0 || (sqp_iters > 0 && backtracks < 1) || !(tol >= 0) || std::isnan(penalty) || std::isinf(penalty))
+        return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts, tolerance or penalty");
+    if (h->cfg.state_bounds)
+        return fail(h, FTMPC_ERR_ARG, "the generalized-force SQP has no state-bound rows (state_bounds must be 0)");
+    return FTMPC_OK;
+}
+
+int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                 const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                 const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, const double* warmG,
+                                 int32_t sqp_iters, int32_t backtracks, double tol, double penalty, double* out_u0, double* out_tau0,
+                                 double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol, int32_t* out_sqp_iters,
+                                 int32_t* out_iters, int32_t* status, int32_t* alloc_status) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0 || !x0 || !ub || !stuck || !xref || !out_u0 || !hull_A || !hull_b)
+        return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    if (rc != FTMPC_OK) return rc;
+    if (backtracks < 1) return fail(h, FTMPC_ERR_ARG, "backtracks must be at least 1");
+    if (B == 0) return FTMPC_OK;
+    const int N = h->cfg.N, NT = h->cfg.NT;
+    if ((rc = check_strides(h, xref_stride, uref_stride, uref)) != FTMPC_OK) return rc;
+    if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
+    if (warmG) HIP_TRY(h, hipMemcpyAsync(h->d_warmG, warmG, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    ftmpc::SqpState S;
+    if ((rc = sqpw_enqueue(h, B, hull_rows, hull_set != nullptr, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride,
+                           warmG ? h->d_warmG : nullptr, sqp_iters, backtracks, tol, penalty > 0 ? penalty : FTMPC_SQPW_PENALTY,
+                           out_X != nullptr, S)) != FTMPC_OK)
+        return rc;
+    HIP_TRY(h, hipMemcpyAsync(out_u0, h->d_u0, B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_tau0) HIP_TRY(h, hipMemcpyAsync(out_tau0, h->d_tau0, B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_G) HIP_TRY(h, hipMemcpyAsync(out_G, S.U, B * N * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_X) HIP_TRY(h, hipMemcpyAsync(out_X, h->d_swX, B * (N + 1) * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_cost) HIP_TRY(h, hipMemcpyAsync(out_cost, h->d_swJ + 3 * B, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_cost0) HIP_TRY(h, hipMemcpyAsync(out_cost0, h->d_swJ + 2 * B, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_tviol) HIP_TRY(h, hipMemcpyAsync(out_tviol, h->d_swJ + 4 * B, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_sqp_iters) HIP_TRY(h, hipMemcpyAsync(out_sqp_iters, S.nmajor, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (out_iters) HIP_TRY(h, hipMemcpyAsync(out_iters, S.ipm, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (status) HIP_TRY(h, hipMemcpyAsync(status, S.status, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (alloc_status) HIP_TRY(h, hipMemcpyAsync(alloc_status, h->d_ast2, B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return FTMPC_OK;
 }
 
@@ -1805,6 +2049,7 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
     int32_t hull_rows;
     bool has_set;
     int32_t* alloc_failed;   // host [T] or null
+    double penalty;          // the wrench SQP's merit weight (sqp_iters > 0)
 };
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
@@ -1833,8 +2078,26 @@ int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
     if (B == 0 || T == 0) return FTMPC_OK;
     int rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows);
     if (rc != FTMPC_OK) return rc;
-    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed};
+    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, 0, 0, 0.0, &wl, u_hist, not_converged);
+}
+
+int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                   double* u_hist, int32_t* not_converged, int32_t* alloc_failed) {
+    if (!h) return FTMPC_ERR_ARG;
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    if (rc != FTMPC_OK) return rc;
+    if (sqp_iters == 0)
+        return ftmpc_simulate_wrench_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                           seed, u_hist, not_converged, alloc_failed);
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    if (B == 0 || T == 0) return FTMPC_OK;
+    if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
+    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, penalty > 0 ? penalty : FTMPC_SQPW_PENALTY};
+    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, &wl, u_hist, not_converged);
 }
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
@@ -1892,7 +2155,19 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     for (int t = 0; t < T; ++t) {
         // window t..t+N of the reference (column-major, so a plain pointer offset); warm start from step 1 on
         const double* Ufin = h->d_U;
-        if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
+        const double* Gfin = h->d_G;
+        if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
+            ftmpc::SqpState S;
+            rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
+                              t > 0 ? h->d_warmG : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
+            if (rc == FTMPC_OK) {
+                Gfin = S.U;
+                sp.status = S.status;
+                if (d_abad)
+                    hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B,
+                                       (const int32_t*)h->d_ast2, d_abad + t);
+            }
+        } else if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
             ftmpc::SqpState S;
             double* J0 = nullptr;
             rc = sqp_enqueue(h, B, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0, t > 0 ? d_warmB : nullptr, sqp_iters,
@@ -1921,7 +2196,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
         if (wl)     // wrench warm start: shifted by one stage, the last stage repeats
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((B * N * 6 + 255) / 256)), dim3(256), 0, s, B, N, 6,
-                               (const double*)h->d_G, h->d_warmG, 1);
+                               Gfin, h->d_warmG, 1);
         else
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, B, N, NT, Ufin, d_warmB, 0);
         SIM_TRY(hipGetLastError());

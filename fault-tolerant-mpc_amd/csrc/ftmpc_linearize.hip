@@ -503,4 +503,124 @@ __global__ void __launch_bounds__(64) ftmpc_cost_kernel(const DeviceConsts C, co
     P.out[lane_id] = cost;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The same cost in the GENERALIZED-FORCE formulation (include/ftmpc.h ftmpc_eval_cost_wrench_batch; merit function of
+// ftmpc_solve_sqp_wrench_batch): the decision is the total wrench tau_k per stage, ut_k = tau_k - ur_k(q_k) - [f_virt; 0],
+// no rho term (the wrench QP has none), plus the terminal-set violation sum_r max(0, (term_A e_N - term_b)_r).
+// One lane per instance, float64.
+// ---------------------------------------------------------------------------------------------------------
+struct CostWrenchParams {
+    int64_t B;
+    const double* x0;
+    const double* xref;
+    int64_t xref_stride;
+    const double* uref;
+    int64_t uref_stride;
+    const double* G;        // [B*N*6] total wrenches
+    const TermCost* tcost;  // or nullptr
+    const double* termA;    // [term_rows*9] or nullptr (no terminal set: violation 0)
+    const double* termb;
+    int32_t term_rows;
+    double sigma;           // merit = cost + sigma * violation
+    double* out_merit;      // [B]  (ntrial > 0: [B*ntrial])
+    double* out_cost;       // or nullptr; indexed as out_merit
+    double* out_tviol;      // or nullptr; indexed as out_merit
+    double* out_X;          // [B*(N+1)*13] centre states of the rollout, or nullptr (ntrial == 0 only)
+    // line search (ntrial > 0): lane b * ntrial + j evaluates G + 2^-j (Gq - G) of instance b, for the instances with todo set
+    const double* Gq = nullptr;
+    const int32_t* todo = nullptr;
+    int32_t ntrial = 0;
+};
+
+__global__ void __launch_bounds__(64) ftmpc_cost_wrench_kernel(const DeviceConsts C, const CostWrenchParams P) {
+    const int64_t lane_id = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int64_t b = P.ntrial > 0 ? lane_id / P.ntrial : lane_id;
+    if (b >= P.B) return;
+    const int jt = P.ntrial > 0 ? (int)(lane_id - b * P.ntrial) : 0;
+    if (P.ntrial > 0 && !P.todo[b]) return;
+    const double alpha = ldexp(1.0, -jt);      // (a power of two: the point is the one ftmpc_sqpw_close_kernel stores)
+    const int N = C.N;
+    double s[13];
+    {
+        double x[13];
+        for (int i = 0; i < 13; ++i) x[i] = P.x0[b * 13 + i];
+        double RT[9], wxr[3], a[3], c[3];
+        rotT(x + 6, RT);
+        cross3(x + 10, C.r, wxr);
+        mat3vec(RT, C.r, a);
+        mat3vec(RT, wxr, c);
+        for (int i = 0; i < 3; ++i) {
+            s[i] = x[i] + a[i];
+            s[3 + i] = x[3 + i] + c[i];
+            s[6 + i] = x[10 + i];
+        }
+        for (int i = 0; i < 4; ++i) s[9 + i] = x[6 + i];
+    }
+    double* X = P.out_X ? P.out_X + b * (int64_t)(N + 1) * 13 : nullptr;
+    if (X)
+        for (int i = 0; i < 13; ++i) X[i] = s[i];
+    const double* xref = P.xref + b * P.xref_stride;
+    const double* uref = P.uref ? P.uref + b * P.uref_stride : nullptr;
+    const double dt = C.dt;
+    double cost = 0.0, viol = 0.0;
+    for (int k = 0; k < N; ++k) {
+        double gen[6];
+        for (int g = 0; g < 6; ++g) {
+            const double t = P.G[(b * N + k) * 6 + g];
+            gen[g] = P.ntrial > 0 ? t + alpha * (P.Gq[(b * N + k) * 6 + g] - t) : t;
+        }
+        double ur[6] = {0, 0, 0, 0, 0, 0};
+        if (uref) {
+            double RT[9], f3[3] = {uref[6 * k], uref[6 * k + 1], uref[6 * k + 2]}, o[3];
+            rotT(s + 9, RT);
+            mat3vec(RT, f3, o);
+            ur[0] = o[0]; ur[1] = o[1]; ur[2] = o[2];
+            ur[3] = uref[6 * k + 3]; ur[4] = uref[6 * k + 4]; ur[5] = uref[6 * k + 5];
+        }
+        for (int g = 0; g < 6; ++g) {
+            const double ut = gen[g] - ur[g] - (g < 3 ? C.fvirt[g] : 0.0);
+            cost += C.R[g] * ut * ut;
+        }
+        // RK4 (sys_model.py:152-158), no quaternion renormalisation; the stage sum k1 + 2 k2 + 2 k3 + k4 accumulated in
+        // the order ftmpc_cost_kernel evaluates it (four 13-vectors live instead of six)
+        double acc[13], kk[13], t[13];
+        centre_rhs(C, s, gen, kk);
+        for (int i = 0; i < 13; ++i) {
+            acc[i] = kk[i];
+            t[i] = s[i] + 0.5 * dt * kk[i];
+        }
+        centre_rhs(C, t, gen, kk);
+        for (int i = 0; i < 13; ++i) {
+            acc[i] += 2.0 * kk[i];
+            t[i] = s[i] + 0.5 * dt * kk[i];
+        }
+        centre_rhs(C, t, gen, kk);
+        for (int i = 0; i < 13; ++i) {
+            acc[i] += 2.0 * kk[i];
+            t[i] = s[i] + dt * kk[i];
+        }
+        centre_rhs(C, t, gen, kk);
+        for (int i = 0; i < 13; ++i) s[i] += dt / 6.0 * (acc[i] + kk[i]);
+        if (X)
+            for (int i = 0; i < 13; ++i) X[(k + 1) * 13 + i] = s[i];
+        double e[9];
+        for (int a = 0; a < 9; ++a) e[a] = s[a] - xref[9 * (k + 1) + a];
+        if (k + 1 < N) {
+            for (int a = 0; a < 9; ++a) cost += C.Q[a] * e[a] * e[a];
+        } else {
+            for (int a = 0; a < 9; ++a)
+                for (int c = 0; c < 9; ++c) cost += e[a] * C.P[9 * a + c] * e[c];
+            if (P.tcost) cost += term_cost_nq(*P.tcost, e, nullptr);
+            for (int r = 0; r < P.term_rows; ++r) {
+                double v = -P.termb[r];
+                for (int a = 0; a < 9; ++a) v += P.termA[9 * r + a] * e[a];
+                viol += fmax(v, 0.0);
+            }
+        }
+    }
+    P.out_merit[lane_id] = cost + P.sigma * viol;
+    if (P.out_cost) P.out_cost[lane_id] = cost;
+    if (P.out_tviol) P.out_tviol[lane_id] = viol;
+}
+
 }  // namespace ftmpc

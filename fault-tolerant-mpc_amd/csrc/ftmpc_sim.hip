@@ -241,4 +241,70 @@ __global__ void ftmpc_sqp_count_kernel(const SqpState S) {
     S.active[b] = S.active[b] && S.improved[b];
 }
 
+// The same SQP in the GENERALIZED-FORCE formulation (ftmpc_solve_sqp_wrench_batch): the iterate is the total wrench per stage
+// (S.NT = 6, no box: the hull rows hold at the iterate and at the QP solution, so they hold on the segment between).  open, pick
+// and count are the kernels above; S.J / S.Jall hold the merit cost + sigma * terminal-set violation.
+// G = warm, or tau_k = D stuck for every stage (the wrench QP's own default linearisation point); flags as ftmpc_sqp_init_kernel
+__global__ void ftmpc_sqpw_init_kernel(const DeviceConsts C, const SqpState S, const double* warm, const double* stuck) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nw = (int64_t)S.N * 6;
+    if (i < S.B * nw) {
+        if (warm) {
+            S.U[i] = warm[i];
+        } else {
+            const int64_t b = i / nw;
+            const int g = (int)(i % 6);
+            double t = 0.0;
+            for (int k = 0; k < C.NT; ++k) t += C.D[g * MAX_NT + k] * stuck[b * C.NT + k];
+            S.U[i] = t;
+        }
+    }
+    if (i < S.B) {
+        S.active[i] = 1;
+        S.todo[i] = 0;
+        S.improved[i] = 0;
+        S.nmajor[i] = 0;
+        S.ipm[i] = 0;
+        S.status[i] = 0;
+        S.alpha[i] = 1.0;
+    }
+}
+// tau_0 of the final iterate for the allocation: on an fp32 handle the iterate comes from kernel 11, whose active facets are met to fp32
+// accuracy only (a few 1e-7 outside as often as inside); as kernel 11 does for its own tau_0, pull it towards the hull centre
+// D (ub/2 + stuck) by the smallest factor that leaves every facet a relative margin of 1e-8.  One lane per instance.
+__global__ void __launch_bounds__(64) ftmpc_sqpw_tau0_kernel(const DeviceConsts C, int64_t B, const double* G, const double* ub,
+                                                             const double* stuck, const double* hullA, const int32_t* hull_set,
+                                                             const double* hullb, int32_t hull_rows, double* tau0) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double t[6], ctr[6];
+    for (int g = 0; g < 6; ++g) {
+        t[g] = G[b * (int64_t)C.N * 6 + g];
+        double acc = 0.0;
+        for (int i = 0; i < C.NT; ++i) acc += C.D[g * MAX_NT + i] * (0.5 * ub[b * C.NT + i] + stuck[b * C.NT + i]);
+        ctr[g] = acc;
+    }
+    const int64_t set = hull_set ? hull_set[b] : 0;
+    double eps = 0.0;
+    for (int r = 0; r < hull_rows; ++r) {
+        const double* a = hullA + (set * hull_rows + r) * 6;
+        double s0 = hullb[b * hull_rows + r], st = s0;
+        for (int g = 0; g < 6; ++g) {
+            s0 -= a[g] * ctr[g];
+            st -= a[g] * t[g];
+        }
+        if (st < 1e-8 * s0 && s0 > st) eps = fmax(eps, (1e-8 * s0 - st) / (s0 - st) * 1.0001);
+    }
+    for (int g = 0; g < 6; ++g) tau0[b * 6 + g] = ctr[g] + (1.0 - eps) * (t[g] - ctr[g]);
+}
+// close the line search: Ut = U + alpha (Uq - U) where a trial point was accepted (the point ftmpc_cost_wrench_kernel evaluated), else U
+__global__ void ftmpc_sqpw_close_kernel(const SqpState S) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nw = (int64_t)S.N * 6;
+    if (i >= S.B * nw) return;
+    const int64_t b = i / nw;
+    const double u = S.U[i];
+    S.Ut[i] = S.improved[b] ? u + S.alpha[b] * (S.Uq[i] - u) : u;
+}
+
 }  // namespace ftmpc

@@ -373,13 +373,81 @@ class BatchedMPC:
             warmG.reshape(B, N, 6)[sel] = W
         return dict(u0=u0, tau0=tau0, G=G, status=status, iters=iters, alloc_status=ast)
 
+    # -- the reference's nonlinear program in its own formulation: line-search SQP over the wrench sequences --------------
+    def eval_cost_wrench(self, x0, xref, G, uref=None, return_tviol=False):
+        """Cost of the NONLINEAR program in the generalized-force formulation for total-wrench sequences G [B,N,6] -> [B]
+        (include/ftmpc.h ftmpc_eval_cost_wrench_batch: nonlinear rollout, no rho term, full terminal cost when
+        MPCConfig.terminal_cost is set).  return_tviol: (cost, terminal-set violation sum_r max(0, A e_N - b)) instead."""
+        N = self.cfg.N
+        x0 = _f64(x0).reshape(-1, 13)
+        B = x0.shape[0]
+        G = _f64(G, (B, N, 6))
+        xref, xs, uref, us = self._refs(B, xref, uref)
+        J, V = np.empty(B), np.empty(B)
+        self._check(self.lib.ftmpc_eval_cost_wrench_batch(self._h, B, _ptr(x0), None, None, _ptr(xref), xs, _ptr(uref), us, _ptr(G),
+                                                          _ptr(J), _ptr(V)))
+        return (J, V) if return_tviol else J
+
+    def solve_sqp_wrench(self, x0, ub, stuck, xref, uref=None, warmG=None, hull=None, sqp_iters=10, backtracks=8, tol=1e-9,
+                         penalty=0.0, return_X=False):
+        """Line-search SQP towards the reference's NLP in its own formulation (spiraling_mpc.py:87-238: generalized-force decision,
+        input hull at every stage, terminal set and full terminal cost when configured, RK4 dynamics), entirely on the device
+        (include/ftmpc.h ftmpc_solve_sqp_wrench_batch): each major iteration solves the wrench QP of solve_wrench linearised about
+        the current G, then backtracks along G_qp - G on the merit J + penalty * terminal-set violation (penalty <= 0: the library
+        default); u0 is the min-norm allocation of the final tau_0.  warmG [B,N,6] or None (tau_k = D stuck; read only); hull as
+        solve_wrench.  Returns dict(u0 [B,NT], tau0 [B,6], G [B,N,6], X [B,N+1,13] | None (centre states under G), cost [B],
+        cost0 [B] (at the start point), tviol [B], sqp_iters [B], iters [B] (IPM iterations summed), status [B] of the last QP,
+        alloc_status [B]); instances whose healthy thrusters do not span R^6 have no hull: status 3, NaN outputs."""
+        from .controllers.tools.input_bounds import hull_tables
+        N, NT = self.cfg.N, self.cfg.NT
+        x0 = _f64(x0).reshape(-1, 13)
+        B = x0.shape[0]
+        ub = _f64(ub, (B, NT))
+        stuck = _f64(stuck, (B, NT))
+        if hull is None:
+            hull = hull_tables(self.D, ub, stuck)
+        ok = ~np.asarray(hull["degenerate"], bool)
+        nan = lambda *shape: np.full((B,) + shape, np.nan)
+        out = dict(u0=nan(NT), tau0=nan(6), G=nan(N, 6), X=nan(N + 1, 13) if return_X else None, cost=nan(), cost0=nan(), tviol=nan(),
+                   sqp_iters=np.zeros(B, np.int32), iters=np.zeros(B, np.int32), status=np.full(B, 3, np.int32),
+                   alloc_status=np.zeros(B, np.int32))
+        if not ok.any():
+            return out
+        sel = np.flatnonzero(ok)
+        full = sel.size == B
+        take = (lambda a: a) if full else (lambda a: np.ascontiguousarray(a[sel]))
+        xref, xs, uref, us = self._refs(B, xref, uref)
+        if xs:
+            xref = take(xref.reshape(B, -1))
+        if uref is not None and us:
+            uref = take(uref.reshape(B, -1))
+        W = None if warmG is None else take(_f64(warmG, (B, N, 6)))
+        b = sel.size
+        A = np.ascontiguousarray(hull["A"], dtype=np.float64)
+        hs = np.ascontiguousarray(take(hull["set"]), dtype=np.int32)
+        hb = np.ascontiguousarray(take(hull["b"]), dtype=np.float64)
+        o = dict(u0=np.empty((b, NT)), tau0=np.empty((b, 6)), G=np.empty((b, N, 6)), X=np.empty((b, N + 1, 13)) if return_X else None,
+                 cost=np.empty(b), cost0=np.empty(b), tviol=np.empty(b), sqp_iters=np.empty(b, np.int32), iters=np.empty(b, np.int32),
+                 status=np.empty(b, np.int32), alloc_status=np.empty(b, np.int32))
+        ip = lambda a: _ptr(a, C.c_int32)
+        self._check(self.lib.ftmpc_solve_sqp_wrench_batch(
+            self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], ip(hs), _ptr(hb), int(hull["rows"]),
+            _ptr(xref), xs, _ptr(uref), us, _ptr(W), int(sqp_iters), int(backtracks), float(tol), float(penalty),
+            _ptr(o["u0"]), _ptr(o["tau0"]), _ptr(o["G"]), _ptr(o["X"]), _ptr(o["cost"]), _ptr(o["cost0"]), _ptr(o["tviol"]),
+            ip(o["sqp_iters"]), ip(o["iters"]), ip(o["status"]), ip(o["alloc_status"])))
+        for k, v in o.items():
+            if v is not None:
+                out[k][sel] = v
+        return out
+
     # -- closed loop on the device (SimulationEnvironment.run_simulation, batched) ------------
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
-                 return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None):
+                 return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
-        (solve_wrench: generalized-force MPC with the input hull, then allocation); every vehicle's healthy thrusters must span R^6.
+        (solve_wrench: generalized-force MPC with the input hull, then allocation); every vehicle's healthy thrusters must span R^6;
+        with sqp_iters > 0 every step runs that many major iterations of solve_sqp_wrench (merit weight `penalty`) instead.
         xref_traj: 9 x (T+N) (column t..t+N is the window of step t), uref_traj: 6 x (T+N) or None.
         Returns dict(x [B,13] final states, u [T,B,NT]|None, not_converged [T])."""
         N, NT = self.cfg.N, self.cfg.NT
@@ -401,8 +469,6 @@ class BatchedMPC:
         uh = np.empty((T, B, NT)) if return_inputs else None
         bad = np.zeros(T, np.int32)
         if formulation == "wrench":
-            if sqp_iters:
-                raise ValueError("the two-stage loop solves one QP per step (sqp_iters must be 0)")
             from .controllers.tools.input_bounds import hull_tables
             if hull is None:
                 hull = hull_tables(self.D, ub, stuck)
@@ -412,6 +478,12 @@ class BatchedMPC:
             hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
             hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
             abad = np.zeros(T, np.int32)
+            if sqp_iters:
+                self._check(self.lib.ftmpc_simulate_wrench_batch_ex(
+                    self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                    int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                    float(penalty), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
+                return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
             self._check(self.lib.ftmpc_simulate_wrench_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0],
                                                              _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                              C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))

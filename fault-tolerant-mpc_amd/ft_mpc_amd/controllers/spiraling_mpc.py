@@ -10,6 +10,9 @@ force stages instead of 6-D generalized deviation inputs, and `status` is an IPM
 with the input hull (tools/input_bounds.py, built once per fault set like the reference's InputBounds) followed by the
 min-norm allocation; `params["terminal_set"] = True` adds the 72-row terminal set of config/terminal.yaml;
 `params["xub"]` / `params["xlb"]` (13 values, the reference's own optional keys) bound the orbit-centre state of the stages.
+With the wrench formulation, `params["sqp_iters"]` > 1 solves the reference's nonlinear program at every step by that many major
+iterations of the line-search SQP (BatchedMPC.solve_sqp_wrench), and `solve_mpc` returns the reference's own tuple: centre
+states and 6-D deviation inputs.
 """
 import copy
 import time
@@ -19,6 +22,7 @@ import numpy as np
 from ..batch import BatchedMPC, MPCConfig
 from ..util.controller_debug import DebugVal, Logger
 from ..util.get_trajectory import load_trajectory
+from ..util.utils import RotInv
 from .tools.spiral_parameters import SpiralParameters
 
 _STATUS = {0: "Solve_Succeeded", 1: "Maximum_Iterations_Exceeded", 2: "Numerical_Failure"}
@@ -82,13 +86,22 @@ class SpiralingController:
         return self.trajectory[:, s:s + self.Nt + 1], self.nominal_input[:, s:s + self.Nt + 1]
 
     # -- one MPC step ------------------------------------------------------------------------
-    def _solve(self, x0):
+    def _solve(self, x0, sqp_iters=None):
         ub = np.asarray(self.model.u_ub_physical, float).reshape(1, -1)
         stuck = np.asarray(self.model.faulty_force, float).reshape(1, -1)
         if self.formulation == "wrench":
             warm = None
             if self.optimal_wrench is not None:    # shifted like the reference's warm start; the last stage repeats
                 warm = np.vstack([self.optimal_wrench[1:], self.optimal_wrench[-1:]])[None].copy()
+            if sqp_iters is None and int(self.params.get("sqp_iters", 1)) > 1:
+                sqp_iters = int(self.params["sqp_iters"])
+            if sqp_iters is not None:              # the nonlinear program (solve_mpc always: it needs the predicted states)
+                out = self.mpc.solve_sqp_wrench(np.asarray(x0, float).reshape(1, 13), ub, stuck, self.x_sp.reshape(-1),
+                                                uref=self.u_sp.reshape(-1), warmG=warm, hull=self.hull, sqp_iters=sqp_iters,
+                                                return_X=True)
+                self.optimal_wrench = out["G"][0]
+                out["U"] = None
+                return out
             out = self.mpc.solve_wrench(np.asarray(x0, float).reshape(1, 13), ub, stuck, self.x_sp.reshape(-1),
                                         uref=self.u_sp.reshape(-1), warmG=warm, return_G=True, hull=self.hull)
             self.optimal_wrench = out["G"][0]
@@ -127,16 +140,24 @@ class SpiralingController:
 
     def solve_mpc(self, c0):
         """Reference signature (spiraling_mpc.py:319-354): centre state in,
-        (x_list, u_list, solve_time, cost, status) out.  u_list holds thruster-force stages."""
+        (x_list, u_list, solve_time, cost, status) out.  Thruster formulation: u_list holds thruster-force stages.  Wrench
+        formulation: the reference's own outputs -- N+1 predicted centre states and N deviation inputs
+        u_t = tau_k - ur_k - [f_virt; 0] of the nonlinear program solved by max(1, params["sqp_iters"]) SQP iterations, and its cost."""
         if self.x_sp is None:
             x_ref, u_ref = self.get_next_trajectory_part(0.0)
             self.x_sp = x_ref.reshape(-1, 1, order="F")
             self.u_sp = u_ref.reshape(-1, 1, order="F")
         t0 = time.time()
         x0 = self.model.center_to_robot(np.asarray(c0, float).flatten())
-        out = self._solve(x0)
         if self.formulation == "wrench":
-            raise NotImplementedError("solve_mpc returns thruster stages; with formulation='wrench' use get_control / mpc.solve_wrench")
+            out = self._solve(x0, sqp_iters=max(1, int(self.params.get("sqp_iters", 1))))
+            G, X = out["G"][0], out["X"][0]
+            ur = self.u_sp.reshape(6, -1, order="F")
+            fv = np.concatenate([self.spiral_params.f_virt, np.zeros(3)])
+            us = [G[k] - np.concatenate([RotInv(X[k][9:13]) @ ur[0:3, k], ur[3:6, k]]) - fv for k in range(self.Nt)]
+            return ([X[k].copy() for k in range(self.Nt + 1)], us, time.time() - t0, float(out["cost"][0]),
+                    _STATUS[int(out["status"][0])])
+        out = self._solve(x0)
         U = out["U"][0]
         xs = [np.asarray(c0, float).flatten()]
         x = x0

@@ -279,6 +279,50 @@ int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B,
                              double* out_u0, double* out_tau0, double* out_G,
                              int32_t* status, int32_t* iters, int32_t* alloc_status);
 
+/*
+ * Cost of the NONLINEAR program in the generalized-force formulation for given wrench sequences -- the merit function of
+ * ftmpc_solve_sqp_wrench_batch: nonlinear RK4 rollout of the orbit-centre model from robot_to_center(x0) under gen_k = tau_k, then
+ *     sum_{k=1}^{N-1} e_k'Q e_k + V(e_N) + sum_{k<N} ut_k'R ut_k,   ut_k = tau_k - [Rot(q_k)^T uref_k[0:3]; uref_k[3:6]] - [f_virt; 0]
+ * (V as ftmpc_eval_cost_batch; no rho term, as the wrench QP has none), and the violation of the terminal set
+ *     sum_r max(0, (term_A e_N - term_b)_r)   (0 when the handle has no terminal set).
+ *   G [B*N*6] total wrenches;  out_cost [B];  out_tviol NULL or [B].  ub and stuck may be NULL (the cost of a total wrench does
+ *   not depend on them; the arguments keep the shape of ftmpc_eval_cost_batch).   HOST buffers.
+ */
+int ftmpc_eval_cost_wrench_batch(ftmpc_handle* h, int64_t B,
+                                 const double* x0, const double* ub, const double* stuck,
+                                 const double* xref, int64_t xref_stride,
+                                 const double* uref, int64_t uref_stride,
+                                 const double* G, double* out_cost, double* out_tviol);
+
+/*
+ * Line-search sequential QP towards the reference's NONLINEAR program in its own formulation (spiraling_mpc.py:87-238: the 6-D
+ * generalized force as decision, the input hull at every stage, the terminal set, the full terminal cost, RK4 dynamics; IPOPT at
+ * :346).  Iterate G = (tau_0 .. tau_{N-1}), started at warmG (NULL: tau_k = D stuck; warmG is assumed inside the hull, as the shifted
+ * previous solution is).  Per major iteration: the QP of ftmpc_solve_wrench_batch linearised about G (same routing; Hessian with the
+ * quadratic terminal weight, gradient exact), then the trial points G + 2^-j (G_qp - G), j < backtracks, all evaluated in one launch,
+ * the first with merit below phi - tol (1 + |phi|) accepted, on the merit
+ *     phi(G) = J(G) + sigma * violation(G)      (J and the violation of ftmpc_eval_cost_wrench_batch)
+ * (the hull rows hold at G and at G_qp, so they stay out of the merit).  An instance without an acceptable point, or whose QP ends
+ * with FTMPC_STATUS_NUMERIC, stops.  After the last iteration, once: u0 = min-norm allocation of tau_0 - D stuck (on an fp32 handle
+ * tau_0 is first pulled towards the hull centre by a relative 1e-8, as ftmpc_solve_wrench_batch's fp32 kernel does).  Direct launches on
+ * the handle's stream (no graph replay).  Refuses a handle with state_bounds != 0 (FTMPC_ERR_ARG: the wrench kernels have no state rows).
+ *   hull_A .. hull_rows, xref .. uref_stride: as ftmpc_solve_wrench_batch;  warmG NULL or [B*N*6] (read only)
+ *   sqp_iters >= 0, backtracks >= 1, tol >= 0;  penalty: sigma (<= 0: the library default, 1e5)
+ *   out_u0 [B*NT];  out_tau0 NULL or [B*6];  out_G NULL or [B*N*6];  out_X NULL or [B*(N+1)*13] centre states of the rollout under the
+ *   returned G (stage 0 = robot_to_center(x0));  out_cost / out_cost0 / out_tviol NULL or [B]: J of the returned G / of the start point,
+ *   violation of the returned G;  out_sqp_iters [B] major iterations that made progress;  out_iters [B] interior-point iterations
+ *   summed;  status [B] of the last QP;  alloc_status [B] as ftmpc_allocate_batch.  Each output but out_u0 may be NULL.   HOST buffers.
+ */
+int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B,
+                                 const double* x0, const double* ub, const double* stuck,
+                                 const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                 const double* xref, int64_t xref_stride,
+                                 const double* uref, int64_t uref_stride,
+                                 const double* warmG, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                 double* out_u0, double* out_tau0, double* out_G, double* out_X,
+                                 double* out_cost, double* out_cost0, double* out_tviol,
+                                 int32_t* out_sqp_iters, int32_t* out_iters, int32_t* status, int32_t* alloc_status);
+
 /* Number of instances of the LAST ftmpc_solve_wrench_batch / ftmpc_simulate_wrench_batch step on this handle that the one-wave fp32
  * kernel handed over to the float64 kernel (its active-set polish did not settle, or hull and terminal rows were active together);
  * 0 where the float64 kernel solved the whole batch anyway.  Blocks until that step's kernels have finished. */
@@ -341,6 +385,15 @@ int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
                                 const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
                                 const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                 double* u_hist, int32_t* not_converged, int32_t* alloc_failed);
+
+/* ftmpc_simulate_wrench_batch with the NONLINEAR program solved at every step: sqp_iters > 0 major iterations of
+ * ftmpc_solve_sqp_wrench_batch (backtracks, tol, penalty as there), started from the previous wrench solution shifted by one stage with
+ * its last stage repeated; not_converged counts the status of each instance's last QP.  sqp_iters = 0: ftmpc_simulate_wrench_batch. */
+int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                   double* u_hist, int32_t* not_converged, int32_t* alloc_failed);
 
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
