@@ -103,23 +103,35 @@ typedef __attribute__((address_space(3))) volatile unsigned char lds_vu8;
 // offset and every lane contributes the same 16 * lane bytes -- one VGPR for all tiles.  As plain pointers the compiler
 // forms one 64-bit per-lane address per tile, hoists the lot out of the interior-point loop and spills it, so that every
 // tile load waited for a scratch reload of its own address first.
+// The descriptor is built at every use from the two halves of the slot address, each through v_readfirstlane: kept as one
+// long-lived descriptor value, the divergence analysis lost its uniformity on the way through the instance and interior-point
+// loops, the descriptor sat in four VGPRs, and every tile load and store became a waterfall loop (four v_readfirstlane, two
+// 64-bit compares, an exec save and a branch -- per buffer operation, serialising the requests).  A readfirstlane of a value
+// the compiler already holds in SGPRs folds away.
 template <int NLDS>
 struct TileStore {
     float* p;                    // LDS, tiles [0, NLDS)
-    __amdgpu_buffer_rsrc_t r;    // global slot, tiles [NLDS, ..)
+    unsigned ga_lo, ga_hi;       // global slot, tiles [NLDS, ..): its address, wave-uniform
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
     static constexpr bool is_global(int tile) { return tile >= NLDS; }
     static constexpr bool any_global(int ntiles) { return ntiles > NLDS; }
     __device__ __forceinline__ void bind(float* slot_tiles) {
-        r = __builtin_amdgcn_make_buffer_rsrc(slot_tiles, 0, 0x7fffffff, 0x00020000);
+        const unsigned long long a = reinterpret_cast<unsigned long long>(slot_tiles);
+        ga_lo = (unsigned)a;
+        ga_hi = (unsigned)(a >> 32);
+    }
+    __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc() const {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane(ga_lo), hi = (unsigned)__builtin_amdgcn_readfirstlane(ga_hi);   // (int: unsigned before widening)
+        const unsigned long long a = ((unsigned long long)hi << 32) | lo;
+        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a), 0, 0x7fffffff, 0x00020000);
     }
     __device__ __forceinline__ f32x4 ld(int tile, int lane) const {
         if (tile < NLDS) return *reinterpret_cast<const f32x4*>(p + tile * 256 + 4 * lane);
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, 16 * lane, (tile - NLDS) * 1024, 0));
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc(), 16 * lane, (tile - NLDS) * 1024, 0));
     }
     __device__ __forceinline__ void st(int tile, int lane, f32x4 v) const {
         if (tile < NLDS) *reinterpret_cast<f32x4*>(p + tile * 256 + 4 * lane) = v;
-        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), r, 16 * lane, (tile - NLDS) * 1024, 0);
+        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, v), rsrc(), 16 * lane, (tile - NLDS) * 1024, 0);
     }
 };
 
@@ -134,10 +146,12 @@ __device__ __forceinline__ unsigned long long stamp_now() {
     __builtin_amdgcn_sched_barrier(0);
     return t;
 }
+// the comment after the s_memtime names the phase that just ended: scripts/phase_census.py splits the assembly there
 #define STAMP_START() st_t0 = stamp_now()
 #define STAMP(i)                                  \
     do {                                          \
         const unsigned long long st_t1 = stamp_now(); \
+        asm volatile("; phase_census stamp %0" ::"n"(i)); \
         st_acc[i] += st_t1 - st_t0;               \
         st_t0 = st_t1;                            \
     } while (0)
@@ -223,8 +237,8 @@ __device__ __forceinline__ double quad_sum_d(double x) {
 // The inverse is built alongside: E starts as I, row j of W is E[j]/sqrt(d_j), and
 //     E[r][col] += bcast_j(c[r]) * nw[col],   nw = -E[j][col] / d_j            (c still unscaled -> 1/d, not 1/sqrt d)
 // again on every lane (rows <= j of E are dead once row j has been copied out).  Per step: one
-// v_readlane (pivot), one v_rsq, two row broadcasts through the permlane swaps, 8 fused DPP FMAs,
-// one select.  No LDS, no barrier, no compare: a non-positive pivot d makes rsq(d) NaN or inf, every
+// v_readlane (pivot), one v_rsq, two row broadcasts through the LDS crossbar (ds_bpermute), 8 fused DPP FMAs,
+// one select.  No barrier, no compare: a non-positive pivot d makes rsq(d) NaN or inf, every
 // later nw = -E[j][col]/d has a 0 * inf in it, and W[15][15] (lane 63, register 3) ends up NaN (inf
 // when only the last pivot is bad).
 template <class F>
@@ -268,14 +282,17 @@ template <int J, class Work>
 __device__ __forceinline__ void potrf_inv_step(float (&c)[4], float (&e)[4], float (&w)[4], int bperm_base, const Work& work) {
     constexpr int QJ = J >> 2, RJ = J & 3;
     // row J of E to every row-group through the LDS crossbar (ds_bpermute: no VALU slot, ~100 cycles of latency that
-    // the pivot chain below covers); row J of the tile itself, which IS on the pivot chain, through the permlane swaps
+    // the pivot chain below covers).  Row J of the tile itself, which IS on the pivot chain, goes the same way: through the
+    // v_permlane16/32_swap pair it took five VALU issues (two swaps, three copies, as a swap overwrites both of its registers)
+    // against the one readlane + rsq it runs beside, and the pipe the two resident waves share is the bound, not this
+    // chain (12.24 -> 11.85 ms on the headline batch, the same bits)
     const float ej = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, e[RJ])));
     const float d = readlane_f(c[RJ], 16 * QJ + J);
     const float inv = __builtin_amdgcn_rsqf(d);
     const float nrd = -inv * inv;
     work.template run<5 * J + 0>();
     if constexpr (J < 15) {
-        const float rowj = group_bcast<QJ>(c[RJ]);    // A[J][col] (= A[col][J]) in every row-group
+        const float rowj = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, c[RJ])));   // A[J][col] in every row-group
         work.template run<5 * J + 1>();
         // the pivot column itself stays as it is (multiplier 0): the inverse below still needs it unscaled
         fmac4_rowbcast<J>(c, c, sel<StepMasks<J>::piv>(rowj * nrd, 0.f));
@@ -1120,6 +1137,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         // INTO the MFMA accumulator that collects the Schur terms (sum T'T - H), so no VALU instruction touches it.
         float* const mtab = work;     // MAX_NT x MAX_NT words; the vector workspace is idle until the interior-point iterations
         auto finish_tile = [&](int I, int J) {     // I, J are constants after unrolling
+            // the lane's table addresses recomputed here (lane_now): taken from the kernel-long li / lq, they were reloaded
+            // from scratch before every table read and every tile store of the peeled last stage
+            const int lane = lane_now();
+            const int li = lane & 15, lq = lane >> 4;
             f32x4 h = acc[(I * (I + 1)) / 2 + J];
             if (J >= I - 1) {
 #pragma unroll
