@@ -2,7 +2,10 @@
 300 closed-loop steps of the 16-thruster vehicle, hover reference, faults from reactive.yaml,
 initial condition of examples/sim.py:49-54 -- with the MPC step on the MI355X.
 
-    python examples/sim.py [--nominal] [--steps 300] [--seed 0]
+    python examples/sim.py [--nominal] [--steps 300] [--seed 0] [--detect-delay STEPS]
+
+A failure with start_time != 0 breaks the thruster at that time (env.set_fault); with --detect-delay the
+controller learns of it that many steps after the plant.
 """
 import argparse
 import sys
@@ -33,17 +36,24 @@ def main():
     ap.add_argument("--terminal-set", action="store_true", help="add the 72-row terminal set of config/terminal.yaml")
     ap.add_argument("--sqp-iters", type=int, default=None,
                     help="major iterations of the line-search SQP towards the nonlinear program per step (1: one QP step)")
+    ap.add_argument("--detect-delay", type=int, default=0,
+                    help="steps between a mid-run thruster failure and the controller's set_fault")
     args = ap.parse_args()
     params = yaml.safe_load(open(ROOT / "fault-tolerant-mpc_amd" / "ft_mpc_amd" / "config" / "reactive.yaml"))
     dt, duration = params["time_step"], params["traj_duration"]
     history = ControllerDebug()
     model = SystemModel(dt)
+    later = []      # (plant step, controller step, fault) of the failures that start mid-run
+    if args.detect_delay < 0:
+        ap.error("--detect-delay must be >= 0")
     if not args.nominal:
         for f in params["actuator_failures"]:
+            fault = BrokenThruster(f["act_id"], f["intensity"])
             if f["start_time"] != 0:
-                print("WARNING: Actuator failures are not supported yet at times other than 0. Skipping.")
+                k = int(round(f["start_time"] / dt))
+                later.append((k, k + args.detect_delay, fault))
                 continue
-            model.set_fault(BrokenThruster(f["act_id"], f["intensity"]))
+            model.set_fault(fault)
     spiral_model = SpiralModel.from_system_model(model)
     tuning = dict(params["tuning"]["spiraling"], formulation=args.formulation, terminal_set=args.terminal_set)
     if args.sqp_iters is not None:
@@ -56,6 +66,13 @@ def main():
                           angular_velocity=[0.3, 0.8, -0.1])
     n = args.steps if args.steps is not None else int(duration / dt)
     for i in range(n):
+        for k_plant, k_ctrl, fault in later:
+            if k_plant == i == k_ctrl:
+                env.set_fault(fault)
+            elif k_plant == i:
+                env.model.set_fault(fault)
+            elif k_ctrl == i:
+                env.controller.set_fault(fault)
         env.step()
         if (i + 1) % 50 == 0:
             c = spiral_model.robot_to_center(env.state)

@@ -552,7 +552,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 440; }
+int32_t ftmpc_version(void) { return 450; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -2054,7 +2054,85 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged);
+                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
+                         double* x_hist = nullptr);
+
+// A fault schedule's layout and values (include/ftmpc.h, ftmpc_fault_schedule).  wrench: the wrench form, whose call has n_sets hull
+// tables of hull_rows rows and its own hull_set (call_set) or not.
+static int check_schedule(ftmpc_handle* h, int64_t B, const ftmpc_fault_schedule* fs, bool wrench, int32_t n_sets, bool call_set) {
+    if (!fs) return FTMPC_OK;
+    if (fs->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: bad struct_size");
+    if (fs->n_events < 0 || fs->n_events > FTMPC_MAX_FAULT_EVENTS)
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: n_events outside [0, FTMPC_MAX_FAULT_EVENTS]");
+    const int E = fs->n_events, NT = h->cfg.NT;
+    if (E == 0) return FTMPC_OK;
+    if (!fs->onset || !fs->ub || !fs->stuck) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: null onset / ub / stuck");
+    if (wrench && !fs->hull_b) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: the wrench form needs hull_b");
+    if (wrench && fs->hull_set && !call_set)
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: per-event hull_set, but the call's hull_set is NULL (one table)");
+    if (wrench && !fs->hull_set && call_set)
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: the call has a hull_set per instance, the schedule needs one per event");
+    for (int64_t b = 0; b < B; ++b) {
+        int32_t pon = -1, pde = -1;
+        bool unused = false;
+        for (int e = 0; e < E; ++e) {
+            const int64_t i = b * E + e;
+            const int32_t on = fs->onset[i];
+            if (on == -1) {
+                unused = true;
+                continue;
+            }
+            if (on < -1) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: onset below -1");
+            if (unused) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: a used slot after an unused one");
+            const int32_t de = fs->detect ? fs->detect[i] : on;
+            if (de < on) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: detect < onset");
+            if (on < pon || de < pde) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: slots not sorted by onset and detect");
+            pon = on;
+            pde = de;
+            for (int k = 0; k < NT; ++k) {
+                const double u = fs->ub[i * NT + k], st = fs->stuck[i * NT + k];
+                if (!std::isfinite(u) || u < 0.0) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: negative or non-finite ub");
+                if (!std::isfinite(st)) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: non-finite stuck");
+            }
+            if (wrench && fs->hull_set && (fs->hull_set[i] < 0 || fs->hull_set[i] >= n_sets))
+                return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: hull_set outside [0, n_sets)");
+        }
+    }
+    return FTMPC_OK;
+}
+
+int ftmpc_simulate_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    int rc = check_schedule(h, B, faults, false, 0, false);
+    if (rc != FTMPC_OK) return rc;
+    if (B == 0 || T == 0) return FTMPC_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
+    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
+                         faults, x_hist);
+}
+
+int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed) {
+    if (!h) return FTMPC_ERR_ARG;
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    if (rc != FTMPC_OK) return rc;
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
+    if (B == 0 || T == 0) return FTMPC_OK;
+    if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
+    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
+    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist);
+}
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                             const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
@@ -2102,14 +2180,23 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged) {
+                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
     const int64_t ncol = (int64_t)T + N;   // windows t .. t+N for t < T
-    double *d_xr = nullptr, *d_ur = nullptr, *d_warmB = nullptr, *d_hist = nullptr;
+    double *d_xr = nullptr, *d_ur = nullptr, *d_warmB = nullptr, *d_hist = nullptr, *d_xhist = nullptr;
     int32_t *d_bad = nullptr, *d_abad = nullptr;
+    // fault schedule (E > 0): events [on | de | hull_set], patterns [ub | stuck], hull offsets, the plant's own pattern [ub | stuck]
+    const int E = fs ? fs->n_events : 0;
+    int32_t* d_fev = nullptr;
+    double *d_fpat = nullptr, *d_fhb = nullptr, *d_plant = nullptr;
     auto cleanup = [&]() {
+        if (d_fev) (void)hipFree(d_fev);
+        if (d_fpat) (void)hipFree(d_fpat);
+        if (d_fhb) (void)hipFree(d_fhb);
+        if (d_plant) (void)hipFree(d_plant);
+        if (d_xhist) (void)hipFree(d_xhist);
         if (d_abad) (void)hipFree(d_abad);
         if (d_xr) (void)hipFree(d_xr);
         if (d_ur) (void)hipFree(d_ur);
@@ -2151,8 +2238,69 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     sp.u_hist = d_hist;
     sp.status = h->d_status;
     sp.bad_count = d_bad;
+    if (x_hist) {
+        SIM_TRY(hipMalloc(&d_xhist, (size_t)T * B * 13 * sizeof(double)));
+        sp.x_hist = d_xhist;
+    }
     const int64_t nw = B * (int64_t)N * NT;
+    std::vector<char> ev_step;         // steps at which some instance switches its plant or controller pattern
+    ftmpc::FaultEvents fe{};
+    if (E > 0) {
+        const int64_t BE = B * E;
+        std::vector<int32_t> ev((size_t)BE * 3, 0);
+        ev_step.assign((size_t)T, 0);
+        for (int64_t i = 0; i < BE; ++i) {
+            ev[i] = fs->onset[i];
+            ev[BE + i] = fs->detect ? fs->detect[i] : fs->onset[i];
+            if (wl && fs->hull_set) ev[2 * BE + i] = fs->hull_set[i];
+            if (ev[i] >= 0 && ev[i] < T) ev_step[ev[i]] = 1;
+            if (ev[i] >= 0 && ev[BE + i] < T) ev_step[ev[BE + i]] = 1;
+        }
+        SIM_TRY(hipMalloc(&d_fev, ev.size() * sizeof(int32_t)));
+        SIM_TRY(hipMalloc(&d_fpat, (size_t)BE * NT * 2 * sizeof(double)));
+        SIM_TRY(hipMalloc(&d_plant, (size_t)B * NT * 2 * sizeof(double)));
+        SIM_TRY(hipMemcpyAsync(d_fev, ev.data(), ev.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SIM_TRY(hipMemcpyAsync(d_fpat, fs->ub, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        SIM_TRY(hipMemcpyAsync(d_fpat + BE * NT, fs->stuck, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        SIM_TRY(hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        SIM_TRY(hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        if (wl) {
+            SIM_TRY(hipMalloc(&d_fhb, (size_t)BE * wl->hull_rows * sizeof(double)));
+            SIM_TRY(hipMemcpyAsync(d_fhb, fs->hull_b, (size_t)BE * wl->hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        fe.B = B;
+        fe.E = E;
+        fe.onset = d_fev;
+        fe.detect = d_fev + BE;
+        fe.ev_ub = d_fpat;
+        fe.ev_stuck = d_fpat + BE * NT;
+        fe.plant_ub = d_plant;
+        fe.plant_stuck = d_plant + B * NT;
+        fe.ub = h->d_ub;
+        fe.stuck = h->d_stuck;
+        fe.warmU = wl ? nullptr : d_warmB;
+        if (wl) {
+            fe.warmG = h->d_warmG;
+            fe.hullA = h->d_hullA;
+            fe.ev_hullset = fs->hull_set ? d_fev + 2 * BE : nullptr;
+            fe.ev_hullb = d_fhb;
+            fe.hullset = wl->has_set ? h->d_hullset : nullptr;
+            fe.hullb = h->d_hullb;
+            fe.hull_rows = wl->hull_rows;
+        }
+        sp.ub = d_plant;
+        sp.stuck = d_plant + B * NT;
+    }
     for (int t = 0; t < T; ++t) {
+        if (E > 0 && ev_step[t]) {     // some instance switches its pattern at this step: before the solve
+            fe.t = t;
+            fe.repair = t > 0;
+            hipLaunchKernelGGL(ftmpc::ftmpc_fault_event_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, fe);
+            SIM_TRY(hipGetLastError());
+            // the work lists follow the new patterns: no small grid for a list that was empty the step before
+            h->qcnt_valid = false;
+            h->qcnt_pending = false;
+        }
         // window t..t+N of the reference (column-major, so a plain pointer offset); warm start from step 1 on
         const double* Ufin = h->d_U;
         const double* Gfin = h->d_G;
@@ -2203,6 +2351,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     }
     SIM_TRY(hipMemcpyAsync(x, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (u_hist) SIM_TRY(hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (x_hist) SIM_TRY(hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) SIM_TRY(hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (d_abad) SIM_TRY(hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SIM_TRY(hipStreamSynchronize(s));

@@ -59,6 +59,7 @@ struct SimParams {
     double* u_hist;       // nullptr or [T*B*NT]
     const int32_t* status;
     int32_t* bad_count;   // nullptr or [T]
+    double* x_hist = nullptr;   // nullptr or [T*B*13]: the state after each step (after noise and renormalisation)
 };
 
 __global__ void __launch_bounds__(64) ftmpc_plant_step_kernel(const DeviceConsts C, const SimParams S) {
@@ -91,6 +92,8 @@ __global__ void __launch_bounds__(64) ftmpc_plant_step_kernel(const DeviceConsts
     const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
     for (int i = 6; i < 10; ++i) x[i] *= qn;
     for (int i = 0; i < 13; ++i) S.x[b * 13 + i] = x[i];
+    if (S.x_hist)
+        for (int i = 0; i < 13; ++i) S.x_hist[(S.step * S.B + b) * 13 + i] = x[i];
     if (S.bad_count && S.status && S.status[b] != 0) atomicAdd(&S.bad_count[S.step], 1);
 }
 
@@ -269,6 +272,32 @@ __global__ void ftmpc_sqpw_init_kernel(const DeviceConsts C, const SqpState S, c
         S.alpha[i] = 1.0;
     }
 }
+// The hull pull shared by the tau_0 kernel and the fault-event kernel: the hull centre D (ub/2 + stuck) of an instance's pattern, and the
+// smallest factor eps that pulls a wrench t towards it far enough to leave every facet a relative margin of 1e-8:
+//   out = ctr + (1 - eps) (t - ctr)   (eps = 0 where t already keeps the margin on every facet)
+__device__ __forceinline__ void hull_centre(const DeviceConsts& C, const double* ub, const double* stuck, double* ctr) {
+    for (int g = 0; g < 6; ++g) {
+        double acc = 0.0;
+        for (int i = 0; i < C.NT; ++i) acc += C.D[g * MAX_NT + i] * (0.5 * ub[i] + stuck[i]);
+        ctr[g] = acc;
+    }
+}
+__device__ __forceinline__ double hull_pull(const double* t, const double* ctr, const double* A, const double* hb, int32_t hull_rows,
+                                            double* out) {
+    double eps = 0.0;
+    for (int r = 0; r < hull_rows; ++r) {
+        const double* a = A + r * 6;
+        double s0 = hb[r], st = s0;
+        for (int g = 0; g < 6; ++g) {
+            s0 -= a[g] * ctr[g];
+            st -= a[g] * t[g];
+        }
+        if (st < 1e-8 * s0 && s0 > st) eps = fmax(eps, (1e-8 * s0 - st) / (s0 - st) * 1.0001);
+    }
+    for (int g = 0; g < 6; ++g) out[g] = ctr[g] + (1.0 - eps) * (t[g] - ctr[g]);
+    return eps;
+}
+
 // tau_0 of the final iterate for the allocation: on an fp32 handle the iterate comes from kernel 11, whose active facets are met to fp32
 // accuracy only (a few 1e-7 outside as often as inside); as kernel 11 does for its own tau_0, pull it towards the hull centre
 // D (ub/2 + stuck) by the smallest factor that leaves every facet a relative margin of 1e-8.  One lane per instance.
@@ -278,25 +307,12 @@ __global__ void __launch_bounds__(64) ftmpc_sqpw_tau0_kernel(const DeviceConsts 
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double t[6], ctr[6];
-    for (int g = 0; g < 6; ++g) {
-        t[g] = G[b * (int64_t)C.N * 6 + g];
-        double acc = 0.0;
-        for (int i = 0; i < C.NT; ++i) acc += C.D[g * MAX_NT + i] * (0.5 * ub[b * C.NT + i] + stuck[b * C.NT + i]);
-        ctr[g] = acc;
-    }
+    for (int g = 0; g < 6; ++g) t[g] = G[b * (int64_t)C.N * 6 + g];
+    hull_centre(C, ub + b * C.NT, stuck + b * C.NT, ctr);
     const int64_t set = hull_set ? hull_set[b] : 0;
-    double eps = 0.0;
-    for (int r = 0; r < hull_rows; ++r) {
-        const double* a = hullA + (set * hull_rows + r) * 6;
-        double s0 = hullb[b * hull_rows + r], st = s0;
-        for (int g = 0; g < 6; ++g) {
-            s0 -= a[g] * ctr[g];
-            st -= a[g] * t[g];
-        }
-        if (st < 1e-8 * s0 && s0 > st) eps = fmax(eps, (1e-8 * s0 - st) / (s0 - st) * 1.0001);
-    }
-    for (int g = 0; g < 6; ++g) tau0[b * 6 + g] = ctr[g] + (1.0 - eps) * (t[g] - ctr[g]);
+    (void)hull_pull(t, ctr, hullA + set * hull_rows * 6, hullb + b * hull_rows, hull_rows, tau0 + b * 6);
 }
+
 // close the line search: Ut = U + alpha (Uq - U) where a trial point was accepted (the point ftmpc_cost_wrench_kernel evaluated), else U
 __global__ void ftmpc_sqpw_close_kernel(const SqpState S) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -305,6 +321,91 @@ __global__ void ftmpc_sqpw_close_kernel(const SqpState S) {
     const int64_t b = i / nw;
     const double u = S.U[i];
     S.Ut[i] = S.improved[b] ? u + S.alpha[b] * (S.Uq[i] - u) : u;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------
+// Thruster faults that start mid-run (ftmpc_simulate_faults_batch / ftmpc_simulate_wrench_faults_batch).  Each instance has up to E
+// events (full after-event patterns, onset and detection steps; slots sorted, onset = -1 unused).  Launched before the solve of a
+// step t at which some instance switches; per instance:
+//   - an event with onset == t: the plant pattern becomes that of the last event with onset <= t
+//   - an event with detect == t: the controller pattern (d_ub / d_stuck, on the wrench form the hull table number and offsets)
+//     becomes that of the last event with detect <= t, and, repair != 0 (t > 0), the shifted warm start is repaired for it:
+//     thruster form U clipped to [0, ub]; wrench form every stage pulled into the new hull as hull_pull does for tau_0.
+// ---------------------------------------------------------------------------------------------------------
+struct FaultEvents {
+    int64_t B;
+    int32_t E, t, repair;
+    const int32_t* onset;    // [B*E]
+    const int32_t* detect;   // [B*E]
+    const double* ev_ub;     // [B*E*NT]
+    const double* ev_stuck;  // [B*E*NT]
+    double* plant_ub;        // [B*NT]
+    double* plant_stuck;     // [B*NT]
+    double* ub;              // [B*NT] the controller's
+    double* stuck;           // [B*NT]
+    double* warmU;           // thruster form: [B*N*NT] or nullptr
+    // wrench form (warmG != nullptr)
+    double* warmG;           // [B*N*6]
+    const double* hullA;     // [n_sets*hull_rows*6]
+    const int32_t* ev_hullset;   // nullptr (one table) or [B*E]
+    const double* ev_hullb;  // [B*E*hull_rows]
+    int32_t* hullset;        // nullptr or [B]
+    double* hullb;           // [B*hull_rows]
+    int32_t hull_rows;
+};
+
+// One lane per (instance, stage): the lane of stage 0 switches the patterns, every lane repairs its own stage of the warm start (from the
+// event's pattern, never from the buffers stage 0 writes).
+__global__ void __launch_bounds__(64) ftmpc_fault_event_kernel(const DeviceConsts C, const FaultEvents F) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int NT = C.NT, N = C.N;
+    if (i >= F.B * N) return;
+    const int64_t b = i / N;
+    const int k = (int)(i % N);
+    int ep = -1, ec = -1;
+    bool sp = false, sc = false;
+    for (int e = 0; e < F.E; ++e) {
+        const int on = F.onset[b * F.E + e], de = F.detect[b * F.E + e];
+        if (on < 0) break;
+        if (on <= F.t) ep = e;
+        if (de <= F.t) ec = e;
+        sp |= on == F.t;
+        sc |= de == F.t;
+    }
+    if (sp && k == 0) {
+        const int64_t src = (b * F.E + ep) * NT;
+        for (int j = 0; j < NT; ++j) {
+            F.plant_ub[b * NT + j] = F.ev_ub[src + j];
+            F.plant_stuck[b * NT + j] = F.ev_stuck[src + j];
+        }
+    }
+    if (!sc) return;
+    const int64_t src = (b * F.E + ec) * NT;
+    if (k == 0) {
+        for (int j = 0; j < NT; ++j) {
+            F.ub[b * NT + j] = F.ev_ub[src + j];
+            F.stuck[b * NT + j] = F.ev_stuck[src + j];
+        }
+    }
+    if (F.warmG) {
+        const int R = F.hull_rows;
+        const int64_t set = F.ev_hullset ? F.ev_hullset[b * F.E + ec] : 0;
+        if (k == 0) {
+            for (int r = 0; r < R; ++r) F.hullb[b * R + r] = F.ev_hullb[(b * F.E + ec) * R + r];
+            if (F.hullset) F.hullset[b] = (int32_t)set;
+        }
+        if (!F.repair) return;
+        double ctr[6], t[6], p[6];
+        hull_centre(C, F.ev_ub + src, F.ev_stuck + src, ctr);
+        double* g = F.warmG + (b * N + k) * 6;
+        for (int j = 0; j < 6; ++j) t[j] = g[j];
+        if (hull_pull(t, ctr, F.hullA + set * R * 6, F.ev_hullb + (b * F.E + ec) * R, R, p) > 0.0)
+            for (int j = 0; j < 6; ++j) g[j] = p[j];
+    } else if (F.repair && F.warmU) {
+        double* w = F.warmU + (b * N + k) * NT;
+        for (int j = 0; j < NT; ++j) w[j] = fmin(fmax(w[j], 0.0), F.ev_ub[src + j]);
+    }
 }
 
 }  // namespace ftmpc

@@ -19,13 +19,14 @@ MAX_NT = 16
 MAX_TERM_ROWS = 80
 MAX_HULL_ROWS = 128
 MAX_TCOST = 24
+MAX_FAULT_EVENTS = 8
 KERNEL_SLOTS = 7
 KERNEL_AUTO, KERNEL_DENSE, KERNEL_WORKGROUP = 0, 1, 2
 
 # every symbol include/ftmpc.h declares (tests check the list against the header)
 SYMBOLS = (
     "ftmpc_default_config", "ftmpc_create", "ftmpc_destroy", "ftmpc_last_error", "ftmpc_reserve",
-    "ftmpc_solve_batch", "ftmpc_solve_batch_device", "ftmpc_solve_sqp_batch", "ftmpc_sqp_graph_launches", "ftmpc_solve_wrench_batch", "ftmpc_eval_cost_batch", "ftmpc_simulate_batch", "ftmpc_simulate_batch_ex", "ftmpc_simulate_wrench_batch", "ftmpc_simulate_wrench_batch_ex", "ftmpc_eval_cost_wrench_batch", "ftmpc_solve_sqp_wrench_batch", "ftmpc_last_handed_over", "ftmpc_allocate_batch", "ftmpc_shift_warm", "ftmpc_set_profiling",
+    "ftmpc_solve_batch", "ftmpc_solve_batch_device", "ftmpc_solve_sqp_batch", "ftmpc_sqp_graph_launches", "ftmpc_solve_wrench_batch", "ftmpc_eval_cost_batch", "ftmpc_simulate_batch", "ftmpc_simulate_batch_ex", "ftmpc_simulate_wrench_batch", "ftmpc_simulate_wrench_batch_ex", "ftmpc_simulate_faults_batch", "ftmpc_simulate_wrench_faults_batch", "ftmpc_eval_cost_wrench_batch", "ftmpc_solve_sqp_wrench_batch", "ftmpc_last_handed_over", "ftmpc_allocate_batch", "ftmpc_shift_warm", "ftmpc_set_profiling",
     "ftmpc_last_kernel_ms", "ftmpc_kernel_name", "ftmpc_routed_kernel_name", "ftmpc_multi_routed_kernel_name", "ftmpc_debug_build_qp", "ftmpc_version", "ftmpc_build_id",
     "ftmpc_multi_create", "ftmpc_multi_destroy", "ftmpc_multi_last_error", "ftmpc_multi_device_count", "ftmpc_multi_worker_cpus",
     "ftmpc_multi_shard_bounds", "ftmpc_multi_solve_batch", "ftmpc_multi_upload", "ftmpc_multi_step",
@@ -55,6 +56,15 @@ class ftmpc_config(C.Structure):
         ("tc_root_exp", C.c_int32 * (MAX_TCOST * 9)), ("tc_const", C.c_double),
         ("kernel_select", C.c_int32), ("stage_chunks", C.c_int32), ("lin_split_max", C.c_int64),
         ("state_bounds", C.c_int32), ("sb_reserved", C.c_int32), ("xlb", C.c_double * 13), ("xub", C.c_double * 13),
+    ]
+
+
+class ftmpc_fault_schedule(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_events", C.c_int32),
+        ("onset", C.POINTER(C.c_int32)), ("detect", C.POINTER(C.c_int32)),
+        ("ub", C.POINTER(C.c_double)), ("stuck", C.POINTER(C.c_double)),
+        ("hull_set", C.POINTER(C.c_int32)), ("hull_b", C.POINTER(C.c_double)),
     ]
 
 
@@ -104,6 +114,11 @@ def load_library() -> C.CDLL:
     lib.ftmpc_simulate_wrench_batch.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, dp, dp, C.c_uint64, dp, ip, ip]
     lib.ftmpc_simulate_wrench_batch_ex.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, dp, dp, C.c_uint64,
                                                    C.c_int32, C.c_int32, C.c_double, C.c_double, dp, ip, ip]
+    fsp = C.POINTER(ftmpc_fault_schedule)
+    lib.ftmpc_simulate_faults_batch.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_uint64, C.c_int32, C.c_int32, C.c_double,
+                                                fsp, dp, dp, ip]
+    lib.ftmpc_simulate_wrench_faults_batch.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, dp, dp,
+                                                       C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double, fsp, dp, dp, ip, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
                                                  dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, ip]

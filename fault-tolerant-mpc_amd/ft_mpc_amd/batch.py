@@ -442,14 +442,20 @@ class BatchedMPC:
 
     # -- closed loop on the device (SimulationEnvironment.run_simulation, batched) ------------
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
-                 return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0):
+                 return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
+                 faults=None, detect_delay=0, return_states=False):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
         (solve_wrench: generalized-force MPC with the input hull, then allocation); every vehicle's healthy thrusters must span R^6;
         with sqp_iters > 0 every step runs that many major iterations of solve_sqp_wrench (merit weight `penalty`) instead.
         xref_traj: 9 x (T+N) (column t..t+N is the window of step t), uref_traj: 6 x (T+N) or None.
-        Returns dict(x [B,13] final states, u [T,B,NT]|None, not_converged [T])."""
+        faults: thruster faults that start mid-run (include/ftmpc.h, ftmpc_fault_schedule): dict(onset [B,E] int (-1: unused slot),
+        ub [B,E,NT], stuck [B,E,NT]) -- the full pattern after each event; a leading B may be left out (broadcast).  The plant switches
+        at the onset step, the controller detect_delay steps later (int, [B] or [B,E]) and repairs its warm start then.  On the wrench
+        form the hull tables are built over all patterns together (hull None, or ft_mpc_amd.faults.fault_hull_tables of the same
+        schedule built beforehand).  return_states: also x_hist [T,B,13], the state after each step.
+        Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist])."""
         N, NT = self.cfg.N, self.cfg.NT
         x = _f64(x0).reshape(-1, 13).copy()
         B = x.shape[0]
@@ -467,7 +473,25 @@ class BatchedMPC:
             ur = np.ascontiguousarray(ur.reshape(-1, order="F"))
         nz = _f64(noise, 4)
         uh = np.empty((T, B, NT)) if return_inputs else None
+        xh = np.empty((T, B, 13)) if return_states else None
         bad = np.zeros(T, np.int32)
+        ext = faults is not None or return_states      # the entries with a fault schedule and x_hist
+        sched, keep, fh = None, None, None
+        if faults is not None:
+            from .faults import fault_hull_tables, normalize_schedule
+            onset, detect, eub, est = normalize_schedule(faults, B, NT, T, detect_delay)
+            keep = [onset, detect, eub, est]
+            sched = _lib.ftmpc_fault_schedule(struct_size=C.sizeof(_lib.ftmpc_fault_schedule), n_events=onset.shape[1],
+                                              onset=_ptr(onset, C.c_int32), detect=_ptr(detect, C.c_int32), ub=_ptr(eub), stuck=_ptr(est))
+            if formulation == "wrench":
+                if hull is not None and ("ev_set" not in hull or np.shape(hull["ev_set"]) != onset.shape):
+                    raise ValueError("with faults `hull` must be None or ft_mpc_amd.faults.fault_hull_tables of the same schedule")
+                fh = fault_hull_tables(self.D, ub, stuck, eub, est, onset) if hull is None else hull
+                hull = fh
+                evs, evb = fh["ev_set"], np.ascontiguousarray(fh["ev_b"], dtype=np.float64)
+                keep += [evs, evb]
+                sched.hull_set, sched.hull_b = _ptr(evs, C.c_int32), _ptr(evb)
+        sp = C.byref(sched) if sched is not None else None
         if formulation == "wrench":
             from .controllers.tools.input_bounds import hull_tables
             if hull is None:
@@ -478,6 +502,15 @@ class BatchedMPC:
             hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
             hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
             abad = np.zeros(T, np.int32)
+            if ext:
+                self._check(self.lib.ftmpc_simulate_wrench_faults_batch(
+                    self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                    int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                    float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
+                out = dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+                if return_states:
+                    out["x_hist"] = xh
+                return out
             if sqp_iters:
                 self._check(self.lib.ftmpc_simulate_wrench_batch_ex(
                     self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -490,6 +523,14 @@ class BatchedMPC:
             return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
         if formulation != "thruster":
             raise ValueError("formulation must be 'thruster' or 'wrench'")
+        if ext:
+            self._check(self.lib.ftmpc_simulate_faults_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
+                                                             _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                                                             sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32)))
+            out = dict(x=x, u=uh, not_converged=bad)
+            if return_states:
+                out["x_hist"] = xh
+            return out
         self._check(self.lib.ftmpc_simulate_batch_ex(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
                                                      _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
                                                      _ptr(uh), _ptr(bad, C.c_int32)))

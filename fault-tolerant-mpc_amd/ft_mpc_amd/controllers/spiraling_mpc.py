@@ -70,6 +70,29 @@ class SpiralingController:
         self.optimal_solution = None               # warm start: previous U*, [N, NT]
         self.x_sp = self.u_sp = None
 
+    def set_fault(self, broken_thruster):
+        """The controller learns of a broken thruster (SimulationEnvironment.set_fault, sim_env.py:67-75): its model copy and the
+        spiral parameters (the compensation force) take the fault; on the wrench form the input hull is rebuilt (ValueError when the
+        healthy thrusters no longer span R^6).  The warm start is repaired for the new constraints, as the on-device loops do
+        (include/ftmpc.h, ftmpc_fault_schedule): thruster form clipped to [0, ub], wrench form pulled into the new hull."""
+        from .tools.input_bounds import hull_tables
+        from ..faults import clip_warm, pull_into_hull
+        self.model.set_fault(broken_thruster)
+        self.spiral_params = SpiralParameters(self.model)
+        self.u_comp = self.spiral_params.compensation_force
+        ub = np.asarray(self.model.u_ub_physical, float).reshape(-1)
+        stuck = np.asarray(self.model.faulty_force, float).reshape(-1)
+        if self.formulation == "wrench":
+            hull = hull_tables(self.model.D, ub.reshape(1, -1), stuck.reshape(1, -1))
+            if hull["degenerate"][0]:
+                raise ValueError("the healthy thrusters do not span R^6: no input hull (use formulation='thruster')")
+            self.hull = hull
+            if self.optimal_wrench is not None:
+                self.optimal_wrench = pull_into_hull(self.optimal_wrench, self.model.D, ub, stuck, hull["A"][hull["set"][0]],
+                                                     hull["b"][0])
+        elif self.optimal_solution is not None:
+            self.optimal_solution = clip_warm(self.optimal_solution, ub)
+
     # -- reference trajectory (spiraling_mpc.py:240-286, 356-365) --------------------------
     def load_trajectory(self, cmd, duration, fpath=None):
         self.assign_trajectory(load_trajectory(cmd, self.dt, duration, file_path=fpath))

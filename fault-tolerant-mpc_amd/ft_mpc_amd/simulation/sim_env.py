@@ -17,6 +17,11 @@ class SimulationEnvironment:
     def set_controller(self, controller):
         self.controller = controller
 
+    def set_fault(self, fault):
+        """A thruster breaks now (sim_env.py:67-75): the plant model and the controller both take the fault."""
+        self.model.set_fault(fault)
+        self.controller.set_fault(fault)
+
     def set_initial_state(self, position=None, velocity=None, orientation=None, angular_velocity=None):
         if position is not None:
             self.state[0:3] = np.array(position)

@@ -379,7 +379,7 @@ int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, co
 /* The same closed loop in the reference's TWO-STAGE structure (ftmpc_solve_wrench_batch at every step: generalized-force MPC with
  * the input hull -- and the terminal set when the handle's config has one -- then the min-norm allocation): the wrench warm start
  * is the previous solution shifted by one stage with its last stage repeated.  The hull tables are those of
- * ftmpc_solve_wrench_batch and stay fixed over the run (the fault pattern does not change inside a run).
+ * ftmpc_solve_wrench_batch and stay fixed over the run (faults that start mid-run: ftmpc_simulate_wrench_faults_batch).
  *   alloc_failed  NULL or [T]: number of instances whose allocation status was not 0 at each step */
 int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                                 const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
@@ -394,6 +394,52 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
                                    const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                    int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
                                    double* u_hist, int32_t* not_converged, int32_t* alloc_failed);
+
+/*
+ * Thruster faults that start mid-run: a schedule of up to E = n_events fault events per vehicle for the closed loops above.
+ * Event e of vehicle b carries the FULL pattern after the event (ub / stuck as BrokenThruster / SystemModel.set_fault leave them,
+ * sys_model.py:237-250), an onset step and a detection step detect >= onset:
+ *   - onset[b*E+e] = -1 marks an unused slot; used slots come first and are non-decreasing in onset and in detect.  An onset >= T
+ *     never fires.
+ *   - at loop step t the PLANT integrates with the pattern of the last event with onset <= t (none: the call's ub / stuck), applying
+ *     (ub > 0 ? u : 0) + stuck as always: between onset and detection the controller may command a thruster that is dead in the plant.
+ *   - at loop step t the CONTROLLER solves with the pattern of the last event with detect <= t (none: the call's ub / stuck); on the
+ *     wrench form that includes the event's hull table number hull_set[b*E+e] (indexing the call's hull_A) and offsets
+ *     hull_b[(b*E+e)*hull_rows ..].  The switch happens before step t's solve.
+ *   - when the controller's pattern changes at a step t > 0 the shifted warm start is repaired: thruster form (one QP or SQP) U
+ *     clipped elementwise to [0, ub_new]; wrench form (one QP or SQP) every stage of G pulled towards the new hull centre
+ *     D (ub_new/2 + stuck_new) by the smallest factor that leaves every new facet a relative margin of 1e-8 (the tau_0 rule of
+ *     ftmpc_solve_sqp_wrench_batch, applied per stage; a stage that keeps the margin is not moved).  The wrench SQP needs this: its
+ *     warm start must lie inside the hull.
+ * All buffers are HOST buffers, staged once per call.  A NULL schedule or n_events = 0 is exactly the loop without one.
+ */
+#define FTMPC_MAX_FAULT_EVENTS 8
+typedef struct ftmpc_fault_schedule {
+    int32_t struct_size;      /* sizeof(ftmpc_fault_schedule) */
+    int32_t n_events;         /* E, 0 <= E <= FTMPC_MAX_FAULT_EVENTS */
+    const int32_t* onset;     /* [B*E] */
+    const int32_t* detect;    /* NULL (detect = onset) or [B*E] */
+    const double* ub;         /* [B*E*NT] >= 0, finite */
+    const double* stuck;      /* [B*E*NT] finite */
+    const int32_t* hull_set;  /* wrench form: NULL exactly when the call's hull_set is NULL (one table), else [B*E] in [0, n_sets) */
+    const double* hull_b;     /* wrench form: [B*E*hull_rows] */
+} ftmpc_fault_schedule;
+
+/* ftmpc_simulate_batch_ex with the fault schedule `faults` (NULL: none) and
+ *   x_hist  NULL or [T*B*13]: the state after each step, after noise and renormalisation (x_hist[T-1] is the returned x).
+ * u_hist keeps its meaning: what the controller commanded. */
+int ftmpc_simulate_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged);
+
+/* ftmpc_simulate_wrench_batch_ex with the fault schedule `faults` (NULL: none; its hull_b is required when n_events > 0) and x_hist as
+ * ftmpc_simulate_faults_batch. */
+int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed);
 
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was

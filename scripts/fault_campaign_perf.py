@@ -1,0 +1,127 @@
+"""Closed-loop campaign throughput with and without a fault schedule (BatchedMPC.simulate(faults=...)): every vehicle gets one
+event at a random step in [1, T) that breaks one more healthy thruster (stuck at a random intensity), detected at its onset.
+
+    python scripts/fault_campaign_perf.py [--case thruster|wrench64|wrench32|all] [--reps 3] [--json out.json]
+    python scripts/fault_campaign_perf.py --once            # one call per case with the schedule (under rocprofv3)
+    python scripts/fault_campaign_perf.py --stats kernel_stats.csv   # the event kernel's share of the kernel time
+
+Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
+pattern from step 0 on, which brackets what the fault itself does to the QPs.
+Cases: thruster form N = 20, NT = 8, B = 65 536, fp32, T = 20; wrench form N = 15, NT = 16, B = 16 384, T = 20 on an fp32 and a
+float64 handle (vehicles whose hull would be flat in either pattern are dropped from both runs)."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "fault-tolerant-mpc_amd"))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+CASES = {"thruster": dict(N=20, NT=8, B=65536, dtype="f32", formulation="thruster"),
+         "wrench32": dict(N=15, NT=16, B=16384, dtype="f32", formulation="wrench"),
+         "wrench64": dict(N=15, NT=16, B=16384, dtype="f64", formulation="wrench")}
+T = 20
+
+
+def batch(c, seed=4040):
+    import ft_mpc_amd
+    from ft_mpc_amd import faults as fl
+    from ft_mpc_amd.models.sys_model import allocation_matrix_8, allocation_matrix_16
+    N, NT, B = c["N"], c["NT"], c["B"]
+    x0, ub, stuck, _ = ft_mpc_amd.make_synthetic_batch(B, N, NT, 1, seed)
+    rng = np.random.default_rng(seed)
+    eub, est = ub.copy(), stuck.copy()
+    for b in range(B):
+        i = rng.choice(np.flatnonzero(ub[b] > 0))
+        eub[b, i], est[b, i] = 0.0, 3.4 * rng.uniform()
+    onset = rng.integers(1, T, (B, 1)).astype(np.int32)
+    if c["formulation"] == "wrench":
+        D = allocation_matrix_16() if NT == 16 else allocation_matrix_8()
+        ok = ~fl.fault_hull_tables(D, ub, stuck, eub[:, None], est[:, None], onset)["degenerate"]
+        x0, ub, stuck, eub, est, onset = x0[ok], ub[ok], stuck[ok], eub[ok], est[ok], onset[ok]
+    return x0, ub, stuck, dict(onset=onset, ub=eub[:, None], stuck=est[:, None])
+
+
+def run(name, reps, once=False):
+    import ft_mpc_amd
+    c = CASES[name]
+    mpc = ft_mpc_amd.BatchedMPC(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
+    x0, ub, stuck, f = batch(c)
+    B = x0.shape[0]
+    xr = np.zeros((9, T + c["N"]))
+    xr[8] = 0.6
+    kw = dict(seed=3, formulation=c["formulation"])
+    plain, withf = {}, dict(faults=f)
+    if c["formulation"] == "wrench":     # the hull tables are host work done once per campaign: built here, outside the timing
+        from ft_mpc_amd import faults as fl
+        from ft_mpc_amd.controllers.tools.input_bounds import hull_tables
+        plain["hull"] = hull_tables(mpc.D, ub, stuck)
+        withf["hull"] = fl.fault_hull_tables(mpc.D, ub, stuck, f["ub"], f["stuck"], f["onset"])
+    if once:
+        mpc.simulate(x0, ub, stuck, xr, T, **withf, **kw)
+        mpc.close()
+        return None
+    res = {}
+    after = dict(plain)                  # the after-event pattern from step 0 on (a fault makes some QPs harder or easier)
+    if c["formulation"] == "wrench":
+        h = withf["hull"]
+        after["hull"] = dict(A=h["A"], set=h["ev_set"][:, 0], b=np.ascontiguousarray(h["ev_b"][:, 0]), rows=h["rows"],
+                             degenerate=np.zeros(B, bool))
+    for label, extra, u, s in (("without", plain, ub, stuck), ("with", withf, ub, stuck),
+                               ("without_after_pattern", after, f["ub"][:, 0], f["stuck"][:, 0])):
+        u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
+        mpc.simulate(x0, u, s, xr, T, **extra, **kw)          # warm-up: workspaces, code objects, grid hints
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            out = mpc.simulate(x0, u, s, xr, T, **extra, **kw)
+            ts.append(time.perf_counter() - t0)
+        ms = float(np.median(ts)) * 1e3
+        res[label] = dict(ms=ms, steps_per_s=B * T / (ms * 1e-3), not_converged=int(out["not_converged"].sum()),
+                          alloc_failed=int(out.get("alloc_failed", np.zeros(1)).sum()))
+    mpc.close()
+    res["ratio_with_over_without"] = res["with"]["steps_per_s"] / res["without"]["steps_per_s"]
+    res.update(case=name, B=B, T=T, **{k: c[k] for k in ("N", "NT", "dtype", "formulation")})
+    return res
+
+
+def stats(path):
+    """Share of ftmpc_fault_event_kernel in the total kernel time of a rocprofv3 --stats kernel_stats.csv."""
+    rows = list(csv.DictReader(open(path)))
+    tot = sum(float(r["TotalDurationNs"]) for r in rows)
+    ev = [r for r in rows if "ftmpc_fault_event_kernel" in r["Name"]]
+    evt = sum(float(r["TotalDurationNs"]) for r in ev)
+    calls = sum(int(r["Calls"]) for r in ev)
+    return dict(total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
+                event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default="all", choices=["all"] + list(CASES))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--once", action="store_true")
+    ap.add_argument("--stats", default=None)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if a.stats:
+        print(json.dumps(stats(a.stats)))
+        return
+    names = list(CASES) if a.case == "all" else [a.case]
+    out = []
+    for n in names:
+        r = run(n, a.reps, a.once)
+        if r is not None:
+            print(json.dumps(r))
+            out.append(r)
+    if a.json and out:
+        json.dump(out, open(a.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
