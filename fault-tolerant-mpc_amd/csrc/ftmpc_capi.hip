@@ -1333,14 +1333,15 @@ int ftmpc_solve_batch_device(ftmpc_handle* h, int64_t B, const double* x0, const
 // lane; the instances kernel 11 does not certify, and everything else (dtype FTMPC_DTYPE_F64, kernel_select =
 // FTMPC_KERNEL_DENSE, longer horizons), on the float64 kernel.
 static bool hull_fp32(const ftmpc_handle* h, int32_t hull_rows) {
+    if (h->sbounds) return false;      // kernel 11 has no state rows: a state-bound handle runs the whole batch on kernel 13
     return h->cfg.dtype != FTMPC_DTYPE_F64 && h->cfg.kernel_select != FTMPC_KERNEL_DENSE && 6 * h->cfg.N <= 96 && hull_rows <= 32 &&
            (int64_t)h->cfg.N * 32 <= 64 * ftmpc::hullk::nvc_of(6) && (!h->cfg.terminal_set || h->cfg.term_rows <= 80);
 }
 
 // ... and on kernel 13 (float64, Riccati recursion, one wave per instance: any horizon up to 40, up to 128 hull rows, with or
 // without the terminal set) unless kernel_select is FTMPC_KERNEL_DENSE: the whole batch where kernel 11 does not apply (float64
-// handles, N > 16, more than 32 rows), and otherwise the instances kernel 11 hands over.  The dense float64 kernel keeps
-// kernel_select = FTMPC_KERNEL_DENSE and N > 40.
+// handles, N > 16, more than 32 rows, a handle with state bounds: kernel 13's state-bound instantiation), and otherwise the
+// instances kernel 11 hands over.  The dense float64 kernel keeps kernel_select = FTMPC_KERNEL_DENSE and N > 40 (no state bounds there).
 static bool hull_ricw(const ftmpc_handle* h, int32_t hull_rows) {
     return h->cfg.kernel_select != FTMPC_KERNEL_DENSE && h->cfg.N <= 40 && hull_rows <= ftmpc::rickw::MHMAX &&
            (!h->cfg.terminal_set || h->cfg.term_rows <= 80);
@@ -1355,6 +1356,8 @@ static int wrench_prepare(ftmpc_handle* h, int64_t B, const double* hull_A, int3
     if (!hull_ricw(h, hull_rows) && (hull_rows > 32 || (int64_t)N * hull_rows > 1024))
         return fail(h, FTMPC_ERR_ARG, "with kernel_select = FTMPC_KERNEL_DENSE or N > 40 the generalized-force formulation needs hull_rows <= 32 and N * hull_rows <= 1024");
     if (h->cfg.terminal_set && (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS)) return fail(h, FTMPC_ERR_ARG, "term_rows out of range");
+    if (h->sbounds && !hull_ricw(h, hull_rows))      // (ftmpc_create keeps state_bounds to N <= 40 without terminal_set)
+        return fail(h, FTMPC_ERR_ARG, "state_bounds on the generalized-force formulation run on the Riccati kernel only (kernel_select must not be FTMPC_KERNEL_DENSE)");
     if (hull_set)   // the kernel indexes hull_A by these: a table number outside [0, n_sets) would be an out-of-bounds device read
         for (int64_t b = 0; b < B; ++b)
             if (hull_set[b] < 0 || hull_set[b] >= n_sets)
@@ -1373,10 +1376,12 @@ static int wrench_prepare(ftmpc_handle* h, int64_t B, const double* hull_A, int3
         }
     }
     if (hull_ricw(h, hull_rows)) {     // kernel 13's per-wave slots (sized by the row count)
-        const int64_t need = ftmpc::rickw::slot_doubles(N, hull_rows);
+        const int64_t need = ftmpc::rickw::slot_doubles(N, hull_rows, h->sbounds);
         if (!h->ricw_slot || need > h->ricw_slot_doubles) {
             int per = 0;
-            if (h->cfg.terminal_set && N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6, true>, 64, 0);
+            if (h->sbounds && N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6, false, true>, 64, 0);
+            else if (h->sbounds) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10, false, true>, 64, 0);
+            else if (h->cfg.terminal_set && N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6, true>, 64, 0);
             else if (h->cfg.terminal_set) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10, true>, 64, 0);
             else if (N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6>, 64, 0);
             else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10>, 64, 0);
@@ -1453,7 +1458,7 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
     lp.warmG = d_warmG;
     lp.out_eN = h->d_eN;
     lp.tcost = h->d_tcost;
-    lp.out_cbar = nullptr;
+    lp.out_cbar = h->sbounds ? h->d_cbar : nullptr;      // the linearisation trajectory (about warmG, or D stuck) for the state rows
     launch_linearize(h, B, (int)((B + 63) / 64), s, lp);
     HIP_TRY(h, hipGetLastError());
     // the wrench problem stops at mu 1e-10 unless the caller asked otherwise (general rows: see ftmpc_config.mu_stop)
@@ -1544,8 +1549,15 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
         q.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
         q.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
         q.eN = h->d_eN;
+        for (int i = 0; i < FTMPC_NX; ++i) {
+            q.xlb[i] = h->cfg.xlb[i];
+            q.xub[i] = h->cfg.xub[i];
+        }
+        q.cbar = h->sbounds ? h->d_cbar : nullptr;
         const int grid = (int)std::min<int64_t>(B, h->grid_ricw);
-        if (h->cfg.terminal_set && h->cfg.N <= 24) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<6, true>), dim3(grid), dim3(64), 0, s, dcg, q);
+        if (h->sbounds && h->cfg.N <= 24) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<6, false, true>), dim3(grid), dim3(64), 0, s, dcg, q);
+        else if (h->sbounds) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<10, false, true>), dim3(grid), dim3(64), 0, s, dcg, q);
+        else if (h->cfg.terminal_set && h->cfg.N <= 24) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<6, true>), dim3(grid), dim3(64), 0, s, dcg, q);
         else if (h->cfg.terminal_set) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<10, true>), dim3(grid), dim3(64), 0, s, dcg, q);
         else if (h->cfg.N <= 24) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ricw64_kernel<6>, dim3(grid), dim3(64), 0, s, dcg, q);
         else hipLaunchKernelGGL(ftmpc::ftmpc_solve_ricw64_kernel<10>, dim3(grid), dim3(64), 0, s, dcg, q);
@@ -1840,11 +1852,12 @@ int ftmpc_eval_cost_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, c
     return FTMPC_OK;
 }
 
-// the arguments every entry of the wrench SQP refuses alike
-static int sqpw_check(ftmpc_handle* h, int32_t sqp_iters, int32_t backtracks, double tol, double penalty) {
+// the arguments every entry of the wrench SQP refuses alike.  sqp_used: the call runs the SQP (the closed loops with sqp_iters = 0
+// run one QP step per control step, which has the state-bound rows: kernel 13's state-bound instantiation)
+static int sqpw_check(ftmpc_handle* h, int32_t sqp_iters, int32_t backtracks, double tol, double penalty, bool sqp_used) {
     if (sqp_iters < 0 || (sqp_iters > 0 && backtracks < 1) || !(tol >= 0) || std::isnan(penalty) || std::isinf(penalty))
         return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts, tolerance or penalty");
-    if (h->cfg.state_bounds)
+    if (h->cfg.state_bounds && sqp_used)
         return fail(h, FTMPC_ERR_ARG, "the generalized-force SQP has no state-bound rows (state_bounds must be 0)");
     return FTMPC_OK;
 }
@@ -1858,7 +1871,7 @@ int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, c
     if (!h) return FTMPC_ERR_ARG;
     if (B < 0 || !x0 || !ub || !stuck || !xref || !out_u0 || !hull_A || !hull_b)
         return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
-    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, true);
     if (rc != FTMPC_OK) return rc;
     if (backtracks < 1) return fail(h, FTMPC_ERR_ARG, "backtracks must be at least 1");
     if (B == 0) return FTMPC_OK;
@@ -2123,7 +2136,7 @@ int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed) {
     if (!h) return FTMPC_ERR_ARG;
-    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
     if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
@@ -2166,7 +2179,7 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
                                    int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
                                    double* u_hist, int32_t* not_converged, int32_t* alloc_failed) {
     if (!h) return FTMPC_ERR_ARG;
-    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty);
+    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
     if (sqp_iters == 0)
         return ftmpc_simulate_wrench_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,

@@ -33,7 +33,13 @@ __host__ __device__ constexpr int64_t xdev_off(int N, int MH) { return row_off(N
 constexpr int NTROW = 8;          // (+ the carried residual of the iterate kept while the early polish runs)
 __host__ __device__ constexpr int64_t trow_off(int N, int MH) { return xdev_off(N, MH) + (int64_t)N * 16; }
 __host__ __device__ constexpr int64_t xdev0_off(int N, int MH) { return trow_off(N, MH) + (int64_t)NTROW * 2 * 64; }      // dx of that iterate
-__host__ __device__ constexpr int64_t slot_doubles(int N, int MH) { return xdev0_off(N, MH) + (int64_t)N * 16; }
+// state-bound rows (template SB), after everything else so that the layout above does not move: per (stage, state component) -- at
+// v * 64 + lane as the wrench variables -- s | z | carried primal residual | ds_a | dz_a of the upper row, the same of the lower
+// row; then per stage the diagonal Sx_j of the rows' barrier term, natural order at 16 k
+constexpr int NXROW = 10;
+__host__ __device__ constexpr int64_t xrow_off(int N, int MH) { return xdev0_off(N, MH) + (int64_t)N * 16; }
+__host__ __device__ constexpr int64_t sxd_off(int N, int MH) { return xrow_off(N, MH) + (int64_t)NXROW * ((N + 3) / 4) * 64; }
+__host__ __device__ constexpr int64_t slot_doubles(int N, int MH, bool sb = false) { return sb ? sxd_off(N, MH) + (int64_t)N * 16 : xrow_off(N, MH); }
 }  // namespace rickw
 
 struct SolveRicwParams {
@@ -52,13 +58,24 @@ struct SolveRicwParams {
     const double* termb;       // [term_rows]
     const double* eN;          // [B*9] terminal tracking error at the linearisation point (ftmpc_linearize.hip)
     int32_t term_rows;         // <= 80
+    // state bounds (template SB; spiraling_mpc.py:129-130,179-185): xlb <= c_j <= xub on the orbit-centre state of the stages
+    // j = 1 .. N-1; |bound| >= 1e299 = no row.  cbar: [B*N*13] the linearisation trajectory c_1 .. c_N (ftmpc_linearize.hip)
+    double xlb[13], xub[13];
+    const double* cbar;
 };
 
 // TS: with the terminal set.  Its rows act on the terminal state only: a 9 x 9 term A_T' diag(z / s) A_T on the terminal weight S_N
 // and a 9-vector on the terminal state-linear term -- where the condensed kernels carry a rank-9 dense update of every tile.
-template <int NV, bool TS = false>      // N <= 4 NV
+// SB: the reference's optional STATE BOUNDS as two more row families  +-dx_j[i] <= h  on the stages j = 1 .. N-1 (kernel 12's SB
+// mode in this formulation).  The states are already variables of the recursion, so a row on a state component is a diagonal
+// entry Sx_j[i] = z_u / s_u + z_l / s_l on that stage's state weight and an entry of its state-linear term q_j: no dense rows, no
+// extra factorisation.  The rows need not hold at the start point: as the terminal rows they start at s = max(residual, 0.1) and
+// carry the primal residual, which every step shrinks by (1 - alpha_p).  Their state lives in the per-wave global slot.  There is
+// no active-set polish in this mode: the iteration runs to mu_stop (the host: 1e-10) and the iterate is the result.
+template <int NV, bool TS = false, bool SB = false>      // N <= 4 NV
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_RIC_WAVES, FTMPC_RIC_WAVES))) ftmpc_solve_ricw64_kernel(const DeviceConsts C, const SolveRicwParams Q) {
     using namespace rickw;
+    static_assert(!(TS && SB), "state bounds together with the terminal set are not built");
     constexpr int NS = 4 * NV;
     constexpr int MTP = 80;
     __shared__ double s_tA[TS ? MTP * 9 : 2];                             // rows of term_A
@@ -169,6 +186,29 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         auto tref = [&](int arr, int j) -> double& { return tst[(int64_t)(arr * 2 + j) * 64 + lane]; };
         enum { T_S = 0, T_Z = 1, T_RP = 2, T_DSA = 3, T_DZA = 4, T_ACT = 5, T_W = 6, T_RP0 = 7 };
         auto tvalid = [&](int j) { return TS && lane + 64 * j < MT; };
+        // state rows of (stage j = 4 v + lq + 1, component li): xdev, wst and the row state share the index 16 (j - 1) + li
+        [[maybe_unused]] double* const xst = slot + xrow_off(N, MH);
+        [[maybe_unused]] double* const sxd = slot + sxd_off(N, MH);
+        [[maybe_unused]] auto xrow = [&](int arr, int v) -> double& { return xst[(int64_t)(arr * nv + v) * 64 + lane]; };
+        enum { X_S = 0, X_Z = 1, X_RP = 2, X_DSA = 3, X_DZA = 4, X_LO = 5 };      // (+ X_LO: the lower row)
+        [[maybe_unused]] bool xhu = false, xhl = false;      // this lane's component has an upper / a lower bound
+        if constexpr (SB) {
+            xhu = li < 13 && Q.xub[li < 13 ? li : 0] < 1e299;
+            xhl = li < 13 && Q.xlb[li < 13 ? li : 0] > -1e299;
+        }
+        [[maybe_unused]] auto xvalid = [&](int v) { return 4 * v + lq < N - 1; };      // (the terminal state has no bound rows)
+        // per-row values t of both rows (`tof(v, arr0)`, arr0 = 0 upper | X_LO lower) -> the state-linear term q_j = -(t_u - t_l) of the
+        // Newton problem, in wst where the backward sweep picks it up (position 4 q + rr = element q + 4 rr)
+        [[maybe_unused]] auto state_linear = [&](auto tof) {
+            wave_lds_fence();
+            for (int v = 0; v < nv; ++v)
+                if (4 * v + lq < N) {
+                    double t = 0.0;
+                    if (xvalid(v)) t = (xhu ? tof(v, 0) : 0.0) - (xhl ? tof(v, (int)X_LO) : 0.0);
+                    wst[(4 * v + lq) * 16 + v64pos(li)] = -t;
+                }
+            wave_lds_fence();
+        };
         if constexpr (TS) {
             for (int i = lane; i < MTP * 9; i += 64) s_tA[i] = (i < MT * 9) ? Q.termA[i] : 0.0;
             if (lane < 16) qT[lane] = 0.0;
@@ -255,6 +295,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 p.xd = xdev[k * 16 + li];
             }
         };
+        [[maybe_unused]] auto request_sx = [&](Pre& p, int k) { p.xd = sxd[k * 16 + li]; };      // (SB, factor sweep) the diagonal Sx_{k+1}
         auto commit = [&](const Pre& p, int buf) {
             wave_lds_fence();
             recbuf[buf][lane] = p.r0;
@@ -309,6 +350,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 if constexpr (TS) {
                     if (k + 1 == N) s += *reinterpret_cast<const f64x4*>(&qT[4 * lq]);
                 }
+                if constexpr (SB) s += *reinterpret_cast<const f64x4*>(&wst[k * 16 + 4 * lq]);      // (state_linear; w replaces it below)
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr)
                     if (lq + 4 * rr < 9) s[rr] += 2.0 * rb[REC_WE + lq + 4 * rr];
@@ -354,12 +396,26 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             Pre p0, p1;
             request(p0, N - 1, false);
             if (N >= 2) request(p1, N - 2, false);
+            if constexpr (SB) {
+                request_sx(p0, N - 1);
+                if (N >= 2) request_sx(p1, N - 2);
+            }
             auto fac = [&](int k, Pre& p) {
                 commit(p, k & 1);
+                [[maybe_unused]] double sx = 0.0;
+                if constexpr (SB) sx = p.xd;
                 if (k >= 2) request(p, k - 2, false);
+                if constexpr (SB) {
+                    if (k >= 2) request_sx(p, k - 2);
+                }
                 f64x4 A, Bt;
                 stage_tiles(recbuf[k & 1], A, Bt);
                 f64x4 S = Pm + weight_tile(k + 1 == N);
+                if constexpr (SB) {      // the state rows' barrier term on the diagonal of the state weight
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr)
+                        if (lq + 4 * rr == li) S[rr] += sx;
+                }
                 if constexpr (TS) {
                     if (k + 1 == N) {
 #pragma unroll
@@ -577,6 +633,32 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                     tref(T_RP, j) = rp;
                 }
             }
+            if constexpr (SB) {      // state rows: residual at the start point (wst: dx of the start point), slack max(residual, 0.1), carried residual
+                for (int v = 0; v < nv; ++v) {
+                    double su = 1.0, rpu = 0.0, sl = 1.0, rpl = 0.0;
+                    if (xvalid(v) && li < 13) {
+                        const double cb = Q.cbar[(inst * N + 4 * v + lq) * 13 + li], dx = wst[(4 * v + lq) * 16 + li];
+                        if (xhu) {
+                            const double res = Q.xub[li] - cb - dx;
+                            su = fmax(res, 0.1);
+                            rpu = su - res;
+                            smax = fmax(smax, su);
+                            mrows += 1.0;
+                        }
+                        if (xhl) {
+                            const double res = cb + dx - Q.xlb[li];
+                            sl = fmax(res, 0.1);
+                            rpl = sl - res;
+                            smax = fmax(smax, sl);
+                            mrows += 1.0;
+                        }
+                    }
+                    xrow(X_S, v) = su;
+                    xrow(X_RP, v) = rpu;
+                    xrow(X_LO + X_S, v) = sl;
+                    xrow(X_LO + X_RP, v) = rpl;
+                }
+            }
             smax = wave_red<DMax>(smax);
             const double mu0 = fmax(0.02 * gm * smax, 1e-3);
             for (int v = 0; v < nv; ++v)
@@ -587,6 +669,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
             if constexpr (TS)
                 for (int j = 0; j < 2; ++j) tref(T_Z, j) = tvalid(j) ? mu0 / tref(T_S, j) : 0.0;
+            if constexpr (SB)
+                for (int v = 0; v < nv; ++v) {
+                    xrow(X_Z, v) = (xvalid(v) && xhu) ? mu0 / xrow(X_S, v) : 0.0;
+                    xrow(X_LO + X_Z, v) = (xvalid(v) && xhl) ? mu0 / xrow(X_LO + X_S, v) : 0.0;
+                }
             mrows = wave_red<DAdd>(mrows);
         }
         const double inv_m = 1.0 / mrows;
@@ -599,7 +686,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         // where the polish is tried once more.
         int status = 1, nit = 0, it = 0;
         bool verified = false;
-        double mu_target = fmax(C.mu_stop, 1e-7);
+        double mu_target = SB ? C.mu_stop : fmax(C.mu_stop, 1e-7);      // (SB: no polish to leave early for)
         double* const xdev0 = slot + xdev0_off(N, MH);
         for (int phase = 0; phase < 2; ++phase) {
         for (; it <= C.max_iters; ++it) {
@@ -616,6 +703,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                     }
                 rpn = wave_red<DMax>(rpn);
             }
+            if constexpr (SB) {
+                for (int v = 0; v < nv; ++v)
+                    if (xvalid(v)) {
+                        if (xhu) {
+                            csum += xrow(X_S, v) * xrow(X_Z, v);
+                            rpn = fmax(rpn, fabs(xrow(X_RP, v)));
+                        }
+                        if (xhl) {
+                            csum += xrow(X_LO + X_S, v) * xrow(X_LO + X_Z, v);
+                            rpn = fmax(rpn, fabs(xrow(X_LO + X_RP, v)));
+                        }
+                    }
+                rpn = wave_red<DMax>(rpn);
+            }
             const double mu = wave_red<DAdd>(csum) * inv_m;
             if (!(mu == mu) || !(rpn == rpn)) {
                 status = 2;
@@ -629,6 +730,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             ++nit;
             form_blocks([&](int v, int c) { return rref(R_Z, v, c) / rref(R_S, v, c); });
             term_blocks([&](int j) { return tref(T_Z, j) / tref(T_S, j); });
+            if constexpr (SB) {      // Sx_j = z_u / s_u + z_l / s_l (zero where there is no row) for the factor sweep
+                for (int v = 0; v < nv; ++v)
+                    if (4 * v + lq < N) {
+                        double w = 0.0;
+                        if (xvalid(v)) w = (xhu ? xrow(X_Z, v) / xrow(X_S, v) : 0.0) + (xhl ? xrow(X_LO + X_Z, v) / xrow(X_LO + X_S, v) : 0.0);
+                        sxd[(4 * v + lq) * 16 + li] = w;
+                    }
+                wave_global_fence();
+            }
             if (__builtin_amdgcn_readfirstlane(!ric_factor())) {
                 status = (mu < 1e-7 && rpn < 1e-9) ? 0 : 2;      // (as the float64 kernel: a breakdown this close to the solution ends the iteration as converged)
                 --nit;
@@ -640,8 +750,28 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             for (int v = 0; v < nv; ++v)
                 if (4 * v + lq < NS) rvec[(4 * v + lq) * 16 + li] = wvalid(v) ? -(vref(V_CL, v) + r2 * vref(V_D, v)) : 0.0;
             wave_lds_fence();
+            if constexpr (SB) state_linear([&](int v, int a0) { return -xrow(a0 + X_Z, v) * xrow(a0 + X_RP, v) / xrow(a0 + X_S, v); });
             ric_solve();
             double ap = 1.0, ad = 1.0;
+            if constexpr (SB) {      // ds = -rp -+ ddx,  dz = -z - z ds / s
+                for (int v = 0; v < nv; ++v) {
+                    const double ddx = (4 * v + lq < N) ? wst[(4 * v + lq) * 16 + li] : 0.0;
+#pragma unroll
+                    for (int lo = 0; lo < 2; ++lo) {
+                        const int a0 = lo ? (int)X_LO : 0;
+                        double ds = 0.0, dz = 0.0;
+                        if (xvalid(v) && (lo ? xhl : xhu)) {
+                            const double s_ = xrow(a0 + X_S, v), z = xrow(a0 + X_Z, v);
+                            ds = -xrow(a0 + X_RP, v) - (lo ? -ddx : ddx);
+                            dz = -z - z * ds / s_;
+                            if (ds < 0.0) ap = fmin(ap, -s_ / ds);
+                            if (dz < 0.0) ad = fmin(ad, -z / dz);
+                        }
+                        xrow(a0 + X_DSA, v) = ds;
+                        xrow(a0 + X_DZA, v) = dz;
+                    }
+                }
+            }
             if constexpr (TS) {
                 for (int j = 0; j < 2; ++j) {
                     double ds = 0.0, dz = 0.0;
@@ -678,6 +808,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             if constexpr (TS)
                 for (int j = 0; j < 2; ++j)
                     if (tvalid(j)) csum += (tref(T_S, j) + ap * tref(T_DSA, j)) * (tref(T_Z, j) + ad * tref(T_DZA, j));
+            if constexpr (SB)
+                for (int v = 0; v < nv; ++v)
+                    if (xvalid(v)) {
+                        if (xhu) csum += (xrow(X_S, v) + ap * xrow(X_DSA, v)) * (xrow(X_Z, v) + ad * xrow(X_DZA, v));
+                        if (xhl) csum += (xrow(X_LO + X_S, v) + ap * xrow(X_LO + X_DSA, v)) * (xrow(X_LO + X_Z, v) + ad * xrow(X_LO + X_DZA, v));
+                    }
             const double mu_aff = wave_red<DAdd>(csum) * inv_m;
             double sigma = mu_aff / mu;
             sigma = fmin(fmax(sigma * sigma * sigma, 0.0), 1.0);
@@ -686,9 +822,30 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             term_linear([&](int j) { return (tref(T_DSA, j) * tref(T_DZA, j) - sm - tref(T_Z, j) * tref(T_RP, j)) / tref(T_S, j); });
             rhs_with_rows([&](int v) { return -(vref(V_CL, v) + r2 * vref(V_D, v)); },
                           [&](int v, int c) { return (rref(R_DSA, v, c) * rref(R_DZA, v, c) - sm) / rref(R_S, v, c); });
+            if constexpr (SB)
+                state_linear([&](int v, int a0) { return (xrow(a0 + X_DSA, v) * xrow(a0 + X_DZA, v) - sm - xrow(a0 + X_Z, v) * xrow(a0 + X_RP, v)) / xrow(a0 + X_S, v); });
             ric_solve();
             ap = 1e300;
             ad = 1e300;
+            // (SB) the corrector's steps of the state rows: ds = -rp -+ ddx,  dz = (-(s z + ds_a dz_a - sigma mu) - z ds) / s
+            [[maybe_unused]] auto xstep = [&](int v, int lo, double& ds, double& dz) {
+                const int a0 = lo ? (int)X_LO : 0;
+                const double ddx = wst[(4 * v + lq) * 16 + li];
+                const double s_ = xrow(a0 + X_S, v), z = xrow(a0 + X_Z, v);
+                ds = -xrow(a0 + X_RP, v) - (lo ? -ddx : ddx);
+                dz = (-(s_ * z + xrow(a0 + X_DSA, v) * xrow(a0 + X_DZA, v) - sm) - z * ds) / s_;
+            };
+            if constexpr (SB) {
+                for (int v = 0; v < nv; ++v)
+#pragma unroll
+                    for (int lo = 0; lo < 2; ++lo)
+                        if (xvalid(v) && (lo ? xhl : xhu)) {
+                            double ds, dz;
+                            xstep(v, lo, ds, dz);
+                            if (ds < 0.0) ap = fmin(ap, -xrow((lo ? (int)X_LO : 0) + X_S, v) / ds);
+                            if (dz < 0.0) ad = fmin(ad, -xrow((lo ? (int)X_LO : 0) + X_Z, v) / dz);
+                        }
+            }
             for (int v = 0; v < nv; ++v)
                 for (int c = 0; c < MHS; ++c)
                     if (rvalid(v, c)) {
@@ -720,6 +877,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                         tref(T_RP, j) *= (1.0 - ap);
                     }
             }
+            if constexpr (SB) {
+                for (int v = 0; v < nv; ++v)
+#pragma unroll
+                    for (int lo = 0; lo < 2; ++lo)
+                        if (xvalid(v) && (lo ? xhl : xhu)) {
+                            const int a0 = lo ? (int)X_LO : 0;
+                            double ds, dz;
+                            xstep(v, lo, ds, dz);
+                            xrow(a0 + X_S, v) += ap * ds;
+                            xrow(a0 + X_Z, v) += ad * dz;
+                            xrow(a0 + X_RP, v) *= (1.0 - ap);
+                        }
+            }
             for (int v = 0; v < nv; ++v) {
                 for (int c = 0; c < MHS; ++c)
                     if (rvalid(v, c)) {
@@ -736,6 +906,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         }
 
         // ---------------- active-set polish (oracle/qp_oracle.py:polish_general; ftmpc_solve_f64.hip MODE 1) ----------------
+        if constexpr (!SB)      // (a polish that fixed hull rows and ignored an active state row would be wrong: none in this mode)
         if (status == 0) {
             constexpr double PW0 = 1e6, PRES_TOL = 1e-10;
             const double pw = PW0 * hs;
@@ -834,7 +1005,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 verified = __builtin_amdgcn_readfirstlane(!__any(changed));
             }
         }
-        if (status != 0 || verified || !(mu_target > C.mu_stop)) break;
+        if (SB || status != 0 || verified || !(mu_target > C.mu_stop)) break;
         // the early polish did not settle: back to the interior-point iterate, on to mu_stop
         for (int i = lane; i < N * 16; i += 64) xdev[i] = xdev0[i];
         for (int v = 0; v < nv; ++v) {
@@ -858,7 +1029,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         // ---------------- outputs ----------------
         wave_lds_fence();
         for (int v = 0; v < nv; ++v) {
-            const double dd = (status == 2) ? 0.0 : ((status == 0 && !verified) ? vref(V_D0, v) : vref(V_D, v));
+            const double dd = (status == 2) ? 0.0 : ((!SB && status == 0 && !verified) ? vref(V_D0, v) : vref(V_D, v));
             const double tau = tbar_of(v) + dd;
             if (4 * v + lq < NS) rvec[(4 * v + lq) * 16 + li] = wvalid(v) ? tau : 0.0;
             if (wvalid(v) && Q.out_G) Q.out_G[(inst * N + 4 * v + lq) * 6 + li] = tau;
@@ -896,5 +1067,7 @@ template __global__ void ftmpc_solve_ricw64_kernel<6>(const DeviceConsts, const 
 template __global__ void ftmpc_solve_ricw64_kernel<10>(const DeviceConsts, const SolveRicwParams);    // N <= 40
 template __global__ void ftmpc_solve_ricw64_kernel<6, true>(const DeviceConsts, const SolveRicwParams);      // + the terminal set
 template __global__ void ftmpc_solve_ricw64_kernel<10, true>(const DeviceConsts, const SolveRicwParams);
+template __global__ void ftmpc_solve_ricw64_kernel<6, false, true>(const DeviceConsts, const SolveRicwParams);     // + the state bounds
+template __global__ void ftmpc_solve_ricw64_kernel<10, false, true>(const DeviceConsts, const SolveRicwParams);
 
 }  // namespace ftmpc

@@ -9,7 +9,8 @@ force stages instead of 6-D generalized deviation inputs, and `status` is an IPM
 `params["formulation"] = "wrench"` switches to the reference's own two-stage structure: a 6-D generalized-force QP
 with the input hull (tools/input_bounds.py, built once per fault set like the reference's InputBounds) followed by the
 min-norm allocation; `params["terminal_set"] = True` adds the 72-row terminal set of config/terminal.yaml;
-`params["xub"]` / `params["xlb"]` (13 values, the reference's own optional keys) bound the orbit-centre state of the stages.
+`params["xub"]` / `params["xlb"]` (13 values, the reference's own optional keys) bound the orbit-centre state of the stages, on
+either formulation (on the wrench formulation in the QP step of `get_control`; not together with the wrench SQP).
 With the wrench formulation, `params["sqp_iters"]` > 1 solves the reference's nonlinear program at every step by that many major
 iterations of the line-search SQP (BatchedMPC.solve_sqp_wrench), and `solve_mpc` returns the reference's own tuple: centre
 states and 6-D deviation inputs.
@@ -53,8 +54,10 @@ class SpiralingController:
                                         terminal_set=True if params.get("terminal_set") else None,
                                         # Bounds on x, default is None (spiraling_mpc.py:129-130; rows :179-185)
                                         xub=params.get("xub", None), xlb=params.get("xlb", None)))
-        if (params.get("xub") is not None or params.get("xlb") is not None) and self.formulation == "wrench":
-            raise ValueError("state bounds (params 'xub' / 'xlb') are built for formulation='thruster'")
+        # the wrench formulation carries the state bounds in its QP step (kernel 13's state-bound mode); the wrench SQP has no such rows
+        self.state_bounded = params.get("xub") is not None or params.get("xlb") is not None
+        if self.state_bounded and self.formulation == "wrench" and int(params.get("sqp_iters", 1)) > 1:
+            raise ValueError("state bounds (params 'xub' / 'xlb') with formulation='wrench' need sqp_iters <= 1: the wrench SQP has no state-bound rows")
         self.hull = None
         if self.formulation == "wrench":           # spiraling_mpc.py:49: self.bounds = InputBounds(self.model), once
             from .tools.input_bounds import hull_tables
@@ -173,6 +176,9 @@ class SpiralingController:
         t0 = time.time()
         x0 = self.model.center_to_robot(np.asarray(c0, float).flatten())
         if self.formulation == "wrench":
+            if self.state_bounded:
+                raise ValueError("solve_mpc on formulation='wrench' solves the nonlinear program by the wrench SQP, which has no state-bound rows "
+                                 "(params 'xub' / 'xlb'); get_control applies them")
             out = self._solve(x0, sqp_iters=max(1, int(self.params.get("sqp_iters", 1))))
             G, X = out["G"][0], out["X"][0]
             ur = self.u_sp.reshape(6, -1, order="F")

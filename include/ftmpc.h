@@ -136,6 +136,10 @@ typedef struct ftmpc_config {
      * no terminal set; kernel_select is ignored): there the rows are a diagonal barrier term on the state weight of their stage,
      * not dense rows through the sensitivities.  Bounds that cannot be met within the horizon end with FTMPC_STATUS_MAXITER /
      * _NUMERIC (the reference logs IPOPT's failure and carries on, spiraling_mpc.py:347-352).
+     * The generalized-force formulation (ftmpc_solve_wrench_batch and the closed loops built on it) carries the same rows: a
+     * state-bound handle runs its whole batch in float64 on the Riccati kernel of that formulation whatever the dtype; with
+     * kernel_select = FTMPC_KERNEL_DENSE those entries return FTMPC_ERR_ARG (the dense kernel has no state rows), and so do the
+     * entries of the generalized-force SQP.  No entry accepts a state-bound handle without applying the rows.
      */
     int32_t state_bounds;
     int32_t sb_reserved;
@@ -268,6 +272,9 @@ int ftmpc_solve_batch_device(ftmpc_handle* h, int64_t B,
  *   warmG     NULL (linearise about thrusters off: tau = D stuck) or [B*N*6] in/out: previous wrench solution, already shifted
  *   out_u0    [B*NT] allocated thruster forces;  out_tau0 NULL or [B*6];  out_G NULL or [B*N*6] whole-horizon wrenches
  *   status / iters: IPM (as above);  alloc_status NULL or [B]: as ftmpc_allocate_batch
+ * A handle with state_bounds != 0: the rows xlb <= c_k <= xub of the stages 1 .. N-1 are part of the program (linearised about warmG
+ * as everything else; iteration to mu 1e-10 unless mu_stop is set, no active-set polish); FTMPC_ERR_ARG with kernel_select =
+ * FTMPC_KERNEL_DENSE.
  * HOST buffers.
  */
 int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B,
@@ -380,6 +387,7 @@ int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, co
  * the input hull -- and the terminal set when the handle's config has one -- then the min-norm allocation): the wrench warm start
  * is the previous solution shifted by one stage with its last stage repeated.  The hull tables are those of
  * ftmpc_solve_wrench_batch and stay fixed over the run (faults that start mid-run: ftmpc_simulate_wrench_faults_batch).
+ * State bounds of the handle apply at every step, as in ftmpc_solve_wrench_batch.
  *   alloc_failed  NULL or [T]: number of instances whose allocation status was not 0 at each step */
 int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                                 const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
@@ -388,7 +396,8 @@ int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
 
 /* ftmpc_simulate_wrench_batch with the NONLINEAR program solved at every step: sqp_iters > 0 major iterations of
  * ftmpc_solve_sqp_wrench_batch (backtracks, tol, penalty as there), started from the previous wrench solution shifted by one stage with
- * its last stage repeated; not_converged counts the status of each instance's last QP.  sqp_iters = 0: ftmpc_simulate_wrench_batch. */
+ * its last stage repeated; not_converged counts the status of each instance's last QP.  sqp_iters = 0: ftmpc_simulate_wrench_batch.
+ * A handle with state_bounds != 0 is refused for sqp_iters > 0 only (FTMPC_ERR_ARG: the SQP has no state rows). */
 int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                                    const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
                                    const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
@@ -434,7 +443,7 @@ int ftmpc_simulate_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
                                 double* u_hist, double* x_hist, int32_t* not_converged);
 
 /* ftmpc_simulate_wrench_batch_ex with the fault schedule `faults` (NULL: none; its hull_b is required when n_events > 0) and x_hist as
- * ftmpc_simulate_faults_batch. */
+ * ftmpc_simulate_faults_batch.  State bounds of the handle: as ftmpc_simulate_wrench_batch_ex. */
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
