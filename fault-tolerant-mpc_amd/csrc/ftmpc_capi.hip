@@ -1,9 +1,9 @@
 // ftmpc_capi.hip -- host side of the C-ABI declared in include/ftmpc.h.
 //
-// Owns the device workspace, converts the double-precision problem constants into the
-// kernel argument block and enqueues the two kernels of the path:
-//   ftmpc_linearize_kernel  (one lane per instance)      ftmpc_linearize.hip
-//   ftmpc_solve_f32_kernel  (one wavefront per instance)  ftmpc_solve.hip
+// Owns the device workspace (DevBuf: every device allocation frees itself with its owner), converts the double-precision
+// problem constants into the kernel argument blocks and enqueues, per entry point, ftmpc_linearize_kernel and the solve kernel
+// the handle's shape is routed to (the instantiation of a templated family is picked in ONE place, pick_*,
+// for the occupancy query that sizes its persistent grid and for the launch alike), the allocation, cost, SQP and plant kernels.
 // There is deliberately NO CPU fallback: every entry point fails with FTMPC_ERR_NODEVICE /
 // FTMPC_ERR_HIP when the gfx950 device or the code object is unusable.
 #include <hip/hip_runtime.h>
@@ -44,6 +44,21 @@ using ftmpc::SolveWs64Params;
 
 static thread_local std::string g_create_error;
 
+// A device allocation and its capacity in elements.  Freed with its owner; reads as the pointer it holds.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    operator T*() const { return p; }
+    int ensure(ftmpc_handle* h, int64_t count);      // room for `count` elements (contents are not kept)
+};
+
 struct ftmpc_handle {
     ftmpc_config cfg;
     DeviceConsts dc;
@@ -53,23 +68,22 @@ struct ftmpc_handle {
     std::string err;
     hipStream_t stream = nullptr;  // internal stream of the host-buffer entry point
     // workspace
-    int64_t cap_batch = 0;
-    void* rec = nullptr;
+    int64_t cap_batch = 0;      // instances the ftmpc_reserve set holds: rec, d_x0 .. d_iters (not the reference windows), d_qlist, d_eN, d_cbar
+    DevBuf<float> rec;          // (float64 records)
     // device mirrors of host buffers
-    double *d_x0 = nullptr, *d_ub = nullptr, *d_stuck = nullptr, *d_xref = nullptr, *d_uref = nullptr;
-    double *d_warm = nullptr, *d_u0 = nullptr, *d_U = nullptr;
-    int32_t *d_status = nullptr, *d_iters = nullptr;
+    DevBuf<double> d_x0, d_ub, d_stuck, d_xref, d_uref;
+    DevBuf<double> d_warm, d_u0, d_U;
+    DevBuf<int32_t> d_status, d_iters;
     // allocation operator (ftmpc_allocate_batch)
-    double *d_atau = nullptr, *d_aub = nullptr, *d_au = nullptr;
-    int32_t *d_ast = nullptr, *d_ait = nullptr;
+    DevBuf<double> d_atau, d_aub, d_au;
+    DevBuf<int32_t> d_ast, d_ait;
     int64_t cap_alloc = 0;
-    int64_t cap_xref = 0, cap_uref = 0;
     // per-instantiation Hessian slots
-    float* hs[3] = {nullptr, nullptr, nullptr};   // NB = 8, 9, 10 instantiations
+    DevBuf<float> hs[3];   // NB = 8, 9, 10 instantiations
     int grid[3] = {0, 0, 0};
     // work lists of the fp32 instantiations: qlist [3][cap_batch], qctl = {count[3], pad, head[3], pad}
-    int32_t* d_qlist = nullptr;
-    int32_t* d_qctl = nullptr;
+    DevBuf<int32_t> d_qlist;
+    DevBuf<int32_t> d_qctl;
     // Hint from the previous step: the list lengths it ended with, copied to pinned memory behind its kernels.  A list that was
     // empty then gets a SMALL grid now (the kernels are persistent: any grid drains any list, a small one just slower if the hint
     // is wrong: one step, then the hint is right again) -- most batches fill one list, and an idle launch of a full grid costs
@@ -92,58 +106,60 @@ struct ftmpc_handle {
     // fp32 workgroup-per-instance kernel with the factor in LDS (160 < N*NT <= 240)
     bool use_ws = false;            // kernel 8 (wrench-space Schur form) takes the lists of NB = 9, 10 and of the workgroup kernel
     int ws_nb = 8, grid_ws = 0;
-    float* ws_slot = nullptr;
+    DevBuf<float> ws_slot;
     int64_t ws_slot_words = 0;
     // kernel 10: the wrench-space form on ONE wave per instance (takes kernel 8's list when it applies)
     bool use_wsw = false;
     int grid_wsw = 0;
-    float* wsw_slot = nullptr;
+    DevBuf<float> wsw_slot;
     int64_t wsw_slot_words = 0;
     // kernel 11 (the generalized-force formulation with hull rows, one wave per instance, fp32): float64 scratch of its reference gradient
-    float* hull_slot = nullptr;
+    DevBuf<float> hull_slot;
     int64_t hull_slot_words = 0;
     int grid_hull = 0;
     bool use_wg = false;
-    float* wg_slot = nullptr;
+    DevBuf<float> wg_slot;
     int grid_wg = 0;
     int64_t wg_slot_words = 0;
     // float64 through the wrench-space form (kernel 9): 6 N <= 256, N * NT <= 768, ten or more thrusters
     bool tset_thruster = true;         // the thruster form with the terminal set fits the dense float64 kernel's general-constraint mode
     bool sbounds = false;              // state bounds: the thruster-space solve runs on kernel 12's state-bound instantiation
-    double* d_cbar = nullptr;          // [B*N*13] linearisation trajectory (state bounds only)
+    DevBuf<double> d_cbar;             // [B*N*13] linearisation trajectory (state bounds only)
     bool use_ric64 = false;            // kernel 12: float64, Newton systems by the Riccati recursion, one wave per instance
     int ric_nv = 10;
     int grid_ric = 0;
-    double* ric_slot = nullptr;
+    DevBuf<double> ric_slot;
     int64_t ric_slot_doubles = 0;
     bool use_ws64 = false;
     int ws64_nvt = 1, grid_ws64 = 0;
-    double* ws64_slot = nullptr;
+    DevBuf<double> ws64_slot;
     int64_t ws64_slot_doubles = 0;
     // float64 general-size path
     bool use_f64 = false;
     int npad_max = 0;
     int grid64 = 0;
     int64_t tile_doubles = 0, e_doubles = 0;
-    double *Hs = nullptr, *Ls = nullptr, *Eall = nullptr;
-    double *d_dbgH64 = nullptr, *d_dbgv64 = nullptr;
+    DevBuf<double> Hs, Ls, Eall;
+    DevBuf<double> d_dbgH64, d_dbgv64;
     // general-constraint modes of the float64 kernel (terminal set; generalized-force formulation)
     bool tset = false;
-    double* d_term = nullptr;          // [term_rows*9 | term_rows]
-    double* d_eN = nullptr;            // [cap_batch*9]
+    DevBuf<double> d_term;             // [term_rows*9 | term_rows]
+    DevBuf<double> d_eN;               // [cap_batch*9]
     int grid_gen = 0, npad_gen = 0;
     int64_t tile_doubles_gen = 0, e_doubles_gen = 0;
-    double *gHs = nullptr, *gLs = nullptr, *gEall = nullptr;     // slots of the wrench formulation (n = 6 N)
-    double *d_hullA = nullptr, *d_hullb = nullptr, *d_warmG = nullptr, *d_tau0 = nullptr, *d_G = nullptr, *d_taud = nullptr;
-    int32_t* d_hullset = nullptr;
-    int32_t* d_ast2 = nullptr;
-    TermCost* d_tcost = nullptr;       // non-quadratic terminal-cost terms (terminal_cost_terms != 0)
-    double* d_cost = nullptr;
-    int64_t cap_cost = 0;
-    // on-device SQP (ftmpc_solve_sqp_batch): iterate, QP solution, trial point | J, Jt, J0, alpha | flags and counters
-    double *d_sqU = nullptr, *d_sqQ = nullptr, *d_sqT = nullptr, *d_sqJ = nullptr, *d_sqJall = nullptr;
-    int64_t cap_sqJall = 0;
-    int32_t* d_sqF = nullptr;
+    DevBuf<double> gHs, gLs, gEall;    // slots of the wrench formulation (n = 6 N)
+    // the two-stage step.  cap_wrench instances: d_hullb, d_hullset, d_warmG, d_tau0, d_G, d_taud, d_ast2; the last is [allocation
+    // status | iterations | kernel 11's hand-over list], the list at 2 * cap_wrench (handover_list)
+    DevBuf<double> d_hullA, d_hullb, d_warmG, d_tau0, d_G, d_taud;
+    DevBuf<int32_t> d_hullset;
+    DevBuf<int32_t> d_ast2;
+    int64_t cap_wrench = 0;
+    DevBuf<TermCost> d_tcost;          // non-quadratic terminal-cost terms (terminal_cost_terms != 0)
+    DevBuf<double> d_cost;
+    // on-device SQP (ftmpc_solve_sqp_batch): iterate, QP solution, trial point | J, Jt, J0, alpha | flags and counters (cap_sqp
+    // instances); the merits of all trial points on their own
+    DevBuf<double> d_sqU, d_sqQ, d_sqT, d_sqJ, d_sqJall;
+    DevBuf<int32_t> d_sqF;
     int64_t cap_sqp = 0;
     // ... its launch sequence (a few hundred small launches per call) as a hipGraph: recorded the second time a call repeats the
     // previous one's shape, replayed from then on; any reallocation or change of the constants starts over
@@ -163,19 +179,19 @@ struct ftmpc_handle {
     } sqp_key, sqp_seen;
     hipGraphExec_t sqp_exec = nullptr;
     int64_t sqp_graph_launches = 0;    // (diagnostic: ftmpc_sqp_graph_launches)
-    int64_t cap_hullA = 0, cap_wrench = 0;
     // line-search SQP of the generalized-force formulation (ftmpc_solve_sqp_wrench_batch): iterate, next iterate | merit, -, alpha,
     // cost and terminal-set violation of the start point and of the result | flags and counters (as d_sqF) | merits of all trial points
-    double *d_swG = nullptr, *d_swT = nullptr, *d_swJ = nullptr, *d_swJall = nullptr, *d_swX = nullptr;
-    int32_t* d_swF = nullptr;
-    int64_t cap_swsqp = 0, cap_swJall = 0, cap_swX = 0;
+    // (cap_swsqp instances: d_swG, d_swT, d_swJ, d_swF)
+    DevBuf<double> d_swG, d_swT, d_swJ, d_swJall, d_swX;
+    DevBuf<int32_t> d_swF;
+    int64_t cap_swsqp = 0;
     // kernel 13: the two-stage form in float64 by the Riccati recursion (no terminal set, N <= 40, up to 128 hull rows)
-    double* ricw_slot = nullptr;
+    DevBuf<double> ricw_slot;
     int64_t ricw_slot_doubles = 0;
     int grid_ricw = 0;
     bool wrench_handed = false;        // the last two-stage step ran kernel 11 with its hand-over list (d_qctl[0] = its length)
     // debug
-    float *d_dbgH = nullptr, *d_dbgv = nullptr;
+    DevBuf<float> d_dbgH, d_dbgv;
     // profiling
     bool profiling = false;
     hipEvent_t ev[2 * FTMPC_KERNEL_SLOTS] = {};  // start/stop per kernel slot
@@ -276,18 +292,155 @@ int build_consts(const ftmpc_config& c, DeviceConsts& d, std::string& why) {
     return FTMPC_OK;
 }
 
+}  // namespace
+
 template <typename T>
-int grow(ftmpc_handle* h, T** p, int64_t count) {
+int DevBuf<T>::ensure(ftmpc_handle* h, int64_t count) {
+    if (count <= cap) return FTMPC_OK;
+    cap = 0;   // (a failed growth must not leave a stale capacity)
     ++h->alloc_epoch;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    if (count <= 0) return FTMPC_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), (size_t)count * sizeof(T));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), (size_t)count * sizeof(T));
     if (e != hipSuccess) {
         (void)hipGetLastError();   // the runtime keeps the failure as its "last error": left there, the next launch check would report it
         return fail(h, FTMPC_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
+    cap = count;
     return FTMPC_OK;
+}
+
+namespace {
+
+// Buffers that share ONE capacity `cap`, in instances (layouts and entry points read it: handover_list, ftmpc_reserve): it is 0 while
+// `each` grows them, so after a failure part-way the next call grows them again instead of launching on freed pointers.
+template <typename F>
+int ensure_group(int64_t& cap, int64_t n, F&& each) {
+    if (n <= cap) return FTMPC_OK;
+    cap = 0;
+    const int rc = each();
+    if (rc == FTMPC_OK) cap = n;
+    return rc;
+}
+
+// kernel 11's hand-over list (written by kernel 11, read by kernel 13 / the dense float64 kernel and by the allocation in list
+// mode): behind the allocation status and iterations in d_ast2, at the CAPACITY of that buffer, whatever the batch
+int32_t* handover_list(const ftmpc_handle* h) { return h->d_ast2 + 2 * h->cap_wrench; }
+
+// the rows of the terminal set on the device (term_A | term_b), once per handle: at create for the thruster form, at the first call
+// of the generalized-force formulation otherwise
+int term_upload(ftmpc_handle* h) {
+    if (!h->cfg.terminal_set || h->d_term) return FTMPC_OK;
+    if (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS) return fail(h, FTMPC_ERR_ARG, "term_rows out of range");
+    int rc = h->d_term.ensure(h, (int64_t)h->cfg.term_rows * 10);
+    if (rc != FTMPC_OK) return rc;
+    std::vector<double> t((size_t)h->cfg.term_rows * 10);
+    std::memcpy(t.data(), h->cfg.term_A, (size_t)h->cfg.term_rows * 9 * sizeof(double));
+    std::memcpy(t.data() + (size_t)h->cfg.term_rows * 9, h->cfg.term_b, (size_t)h->cfg.term_rows * sizeof(double));
+    HIP_TRY(h, hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+    return FTMPC_OK;
+}
+
+// ---- one pick per templated kernel family: the occupancy query that sizes a persistent grid (and its per-workgroup slots) and the
+// launch both take the instantiation from here, so they cannot disagree.  The wrench-side families also take the hull row count.
+using F32Kernel = void (*)(DeviceConsts, SolveParams);
+using WgKernel = void (*)(DeviceConsts, SolveWgParams);
+using Ws64Kernel = void (*)(DeviceConsts, SolveWs64Params);
+using Ric64Kernel = void (*)(DeviceConsts, ftmpc::SolveRicParams);
+using F64Kernel = void (*)(DeviceConsts, Solve64Params);
+using HullKernel = void (*)(DeviceConsts, ftmpc::SolveHullParams);
+using RicwKernel = void (*)(DeviceConsts, ftmpc::SolveRicwParams);
+
+F32Kernel pick_f32(int v) {      // work list v: ceil(n / 16) <= 8 + v
+    return v == 0 ? ftmpc::ftmpc_solve_f32_kernel<8> : (v == 1 ? ftmpc::ftmpc_solve_f32_kernel<9> : ftmpc::ftmpc_solve_f32_kernel<10>);
+}
+WgKernel pick_ws32(const ftmpc_handle* h) { return h->ws_nb == 6 ? ftmpc::ftmpc_solve_ws32_kernel<6> : ftmpc::ftmpc_solve_ws32_kernel<8>; }
+F32Kernel pick_wsw32(const ftmpc_handle* h) { return h->ws_nb == 6 ? ftmpc::ftmpc_solve_wsw32_kernel<6> : ftmpc::ftmpc_solve_wsw32_kernel<8>; }
+Ws64Kernel pick_ws64(const ftmpc_handle* h) { return h->ws64_nvt == 1 ? ftmpc::ftmpc_solve_ws64_kernel<1> : ftmpc::ftmpc_solve_ws64_kernel<3>; }
+Ric64Kernel pick_ric64(const ftmpc_handle* h) {
+    if (h->sbounds && h->ric_nv == 6) return ftmpc::ftmpc_solve_ric64_kernel<6, true>;
+    if (h->sbounds) return ftmpc::ftmpc_solve_ric64_kernel<10, true>;
+    if (h->ric_nv == 4) return ftmpc::ftmpc_solve_ric64_kernel<4>;
+    if (h->ric_nv == 6) return ftmpc::ftmpc_solve_ric64_kernel<6>;
+    return ftmpc::ftmpc_solve_ric64_kernel<10>;
+}
+// the dense float64 kernel; wrench: the generalized-force formulation (6 N variables, hull rows) instead of the thruster form
+F64Kernel pick_f64(const ftmpc_handle* h, bool wrench) {
+    if (wrench) return h->cfg.terminal_set ? ftmpc::ftmpc_solve_f64_kernel<4, 1, 3> : ftmpc::ftmpc_solve_f64_kernel<4, 1, 1>;
+    if (h->tset) return ftmpc::ftmpc_solve_f64_kernel<4, 1, 2>;
+    if (h->npad_max <= 256) return ftmpc::ftmpc_solve_f64_kernel<4, 1>;
+    if (h->npad_max <= 640) return ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, 3>;
+    return ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, ftmpc::f64k::NVT_MAX>;
+}
+HullKernel pick_hull32(const ftmpc_handle* h, int32_t /*hull_rows*/) {
+    return h->cfg.terminal_set ? ftmpc::ftmpc_solve_hull32_kernel<6, true> : ftmpc::ftmpc_solve_hull32_kernel<6, false>;
+}
+RicwKernel pick_ricw64(const ftmpc_handle* h, int32_t /*hull_rows*/) {
+    if (h->sbounds && h->cfg.N <= 24) return ftmpc::ftmpc_solve_ricw64_kernel<6, false, true>;
+    if (h->sbounds) return ftmpc::ftmpc_solve_ricw64_kernel<10, false, true>;
+    if (h->cfg.terminal_set && h->cfg.N <= 24) return ftmpc::ftmpc_solve_ricw64_kernel<6, true>;
+    if (h->cfg.terminal_set) return ftmpc::ftmpc_solve_ricw64_kernel<10, true>;
+    if (h->cfg.N <= 24) return ftmpc::ftmpc_solve_ricw64_kernel<6>;
+    return ftmpc::ftmpc_solve_ricw64_kernel<10>;
+}
+
+// resident workgroups of `block` threads per CU (0 when the query fails: every caller clamps)
+template <typename K>
+int blocks_per_cu(K kernel, int block) {
+    int per = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, block, 0);
+    return per;
+}
+
+// One launch inside the event pair of kernel slot k (ftmpc_last_kernel_ms: events 2k and 2k + 1, ev_used[k]) when profiling is on.
+template <typename L>
+int profiled(ftmpc_handle* h, int k, hipStream_t s, L&& launch) {
+    if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[2 * k], s));
+    launch();
+    HIP_TRY(h, hipGetLastError());
+    if (h->profiling) {
+        HIP_TRY(h, hipEventRecord(h->ev[2 * k + 1], s));
+        h->ev_used[k] = true;
+    }
+    return FTMPC_OK;
+}
+
+// ---- argument-block fields that several kernels take alike
+template <typename P>
+void fill_term(const ftmpc_handle* h, P& q) {      // the rows of the terminal set (term_upload)
+    q.termA = h->cfg.terminal_set ? h->d_term.p : nullptr;
+    q.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
+    q.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
+}
+
+template <typename P>
+void fill_state_bounds(const ftmpc_handle* h, P& q) {
+    for (int i = 0; i < FTMPC_NX; ++i) {
+        q.xlb[i] = h->cfg.xlb[i];
+        q.xub[i] = h->cfg.xub[i];
+    }
+    q.cbar = h->sbounds ? h->d_cbar.p : nullptr;
+}
+
+// a zeroed block of the generalized-force formulation (kernels 11 and 13, the dense float64 kernel's wrench mode): batch, hull
+// rows, terminal set and outputs
+template <typename P>
+void fill_wrench(const ftmpc_handle* h, P& q, int64_t B, int32_t hull_rows, bool has_set, const double* d_warmG) {
+    std::memset(&q, 0, sizeof(q));
+    q.base.B = B;
+    q.base.rec = h->rec;
+    q.base.ub = h->d_ub; q.base.stuck = h->d_stuck;
+    q.base.status = h->d_status; q.base.iters = h->d_iters;
+    q.base.dbg_inst = -1;
+    q.warmG = d_warmG;
+    q.hullA = h->d_hullA;
+    q.hull_set = has_set ? h->d_hullset.p : nullptr;
+    q.hullb = h->d_hullb;
+    q.hull_rows = hull_rows;
+    q.out_tau0 = h->d_tau0;
+    q.out_G = h->d_G;
+    fill_term(h, q);
+    q.eN = h->d_eN;
 }
 
 int tiles_of(int nb) { return nb * (nb + 1) / 2; }
@@ -347,13 +500,8 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
     };
     const int lin_blocks = (int)((B + 63) / 64);
     for (bool& u : h->ev_used) u = false;
-    if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    launch_linearize(h, B, lin_blocks, s, lp);
-    HIP_TRY(h, hipGetLastError());
-    if (h->profiling) {
-        HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        h->ev_used[0] = true;
-    }
+    int rc = profiled(h, 0, s, [&] { launch_linearize(h, B, lin_blocks, s, lp); });
+    if (rc != FTMPC_OK) return rc;
     SolveParams sp;
     sp.B = B;
     sp.rec = h->rec;
@@ -362,182 +510,92 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
     sp.dbg_inst = dbg_inst;
     sp.dbg_H = h->d_dbgH;
     sp.dbg_vec = h->d_dbgv;
-    if (h->use_f64 && h->use_ric64) {
-        ftmpc::SolveRicParams w;
-        sp.hscratch = nullptr;
-        sp.tile_words = 0;
-        sp.qlist = nullptr;
-        sp.qcount = nullptr;
-        HIP_TRY(h, hipMemsetAsync(h->d_qctl + 4, 0, sizeof(int32_t), s));
-        sp.qhead = h->d_qctl + 4;       // shared instance cursor
-        sp.dbg_H = reinterpret_cast<float*>(h->d_dbgH64);     // (diagnostic build: phase stamps)
-        w.base = sp;
-        w.slot = h->ric_slot;
-        w.slot_doubles = h->ric_slot_doubles;
-        for (int i = 0; i < FTMPC_NX; ++i) {
-            w.xlb[i] = h->cfg.xlb[i];
-            w.xub[i] = h->cfg.xub[i];
-        }
-        w.cbar = h->sbounds ? h->d_cbar : nullptr;
-        // with state bounds the iteration stops at mu 1e-10 unless the caller asked otherwise, as the other general-constraint
-        // modes do: the barrier weight of an active state row enters the Riccati recursion's state weight (see the kernel)
-        DeviceConsts dcr = h->dc;
-        if (h->sbounds && !(h->cfg.mu_stop > 0)) dcr.mu_stop = 1e-10;
-        const int grid = (int)std::min<int64_t>(B, h->grid_ric);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[12], s));
-        if (h->sbounds && h->ric_nv == 6) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ric64_kernel<6, true>), dim3(grid), dim3(64), 0, s, dcr, w);
-        else if (h->sbounds) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ric64_kernel<10, true>), dim3(grid), dim3(64), 0, s, dcr, w);
-        else if (h->ric_nv == 4) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ric64_kernel<4>, dim3(grid), dim3(64), 0, s, h->dc, w);
-        else if (h->ric_nv == 6) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ric64_kernel<6>, dim3(grid), dim3(64), 0, s, h->dc, w);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_ric64_kernel<10>, dim3(grid), dim3(64), 0, s, h->dc, w);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[13], s));
-            h->ev_used[6] = true;
-            h->ev_valid = true;
-        }
-        return FTMPC_OK;
-    }
-    if (h->use_f64 && h->use_ws64) {
-        SolveWs64Params w;
+    if (h->use_f64) {      // one float64 kernel takes the whole batch: no work lists
         sp.hscratch = nullptr;
         sp.tile_words = 0;
         sp.qlist = nullptr;
         sp.qcount = nullptr;
         sp.qhead = nullptr;
-        sp.dbg_H = reinterpret_cast<float*>(h->d_dbgH64);     // (diagnostic build: phase stamps)
-        w.base = sp;
-        w.slot = h->ws64_slot;
-        w.slot_doubles = h->ws64_slot_doubles;
-        const int grid = (int)std::min<int64_t>(B, h->grid_ws64);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[12], s));
-        if (h->ws64_nvt == 1) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ws64_kernel<1>, dim3(grid), dim3(ftmpc::ws64k::WG), 0, s, h->dc, w);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_ws64_kernel<3>, dim3(grid), dim3(ftmpc::ws64k::WG), 0, s, h->dc, w);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[13], s));
-            h->ev_used[6] = true;
-            h->ev_valid = true;
+        if (h->use_ric64) {
+            ftmpc::SolveRicParams w;
+            HIP_TRY(h, hipMemsetAsync(h->d_qctl + 4, 0, sizeof(int32_t), s));
+            sp.qhead = h->d_qctl + 4;       // shared instance cursor
+            sp.dbg_H = reinterpret_cast<float*>(h->d_dbgH64.p);     // (diagnostic build: phase stamps)
+            w.base = sp;
+            w.slot = h->ric_slot;
+            w.slot_doubles = h->ric_slot_doubles;
+            fill_state_bounds(h, w);
+            // with state bounds the iteration stops at mu 1e-10 unless the caller asked otherwise, as the other general-constraint
+            // modes do: the barrier weight of an active state row enters the Riccati recursion's state weight (see the kernel)
+            DeviceConsts dcr = h->dc;
+            if (h->sbounds && !(h->cfg.mu_stop > 0)) dcr.mu_stop = 1e-10;
+            const int grid = (int)std::min<int64_t>(B, h->grid_ric);
+            rc = profiled(h, 6, s, [&] { hipLaunchKernelGGL(pick_ric64(h), dim3(grid), dim3(64), 0, s, dcr, w); });
+        } else if (h->use_ws64) {
+            SolveWs64Params w;
+            sp.dbg_H = reinterpret_cast<float*>(h->d_dbgH64.p);     // (diagnostic build: phase stamps)
+            w.base = sp;
+            w.slot = h->ws64_slot;
+            w.slot_doubles = h->ws64_slot_doubles;
+            const int grid = (int)std::min<int64_t>(B, h->grid_ws64);
+            rc = profiled(h, 6, s, [&] { hipLaunchKernelGGL(pick_ws64(h), dim3(grid), dim3(ftmpc::ws64k::WG), 0, s, h->dc, w); });
+        } else {
+            Solve64Params q;
+            q.base = sp;
+            q.Hs = h->Hs; q.Ls = h->Ls; q.Eall = h->Eall;
+            q.tile_doubles = h->tile_doubles;
+            q.e_doubles = h->e_doubles;
+            q.npad_max = h->npad_max;
+            q.nb_lo = 0;
+            q.dbg_H = h->d_dbgH64;
+            q.dbg_vec = h->d_dbgv64;
+            q.warmG = nullptr; q.hullA = nullptr; q.hull_set = nullptr; q.hullb = nullptr; q.out_tau0 = nullptr; q.out_G = nullptr;
+            q.hull_rows = 0;
+            fill_term(h, q);
+            q.eN = h->d_eN;
+            const int grid = (int)std::min<int64_t>(B, h->grid64);
+            rc = profiled(h, 4, s, [&] { hipLaunchKernelGGL(pick_f64(h, false), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, h->dc, q); });
         }
-        return FTMPC_OK;
-    }
-    if (h->use_f64) {
-        Solve64Params q;
-        sp.hscratch = nullptr;
-        sp.tile_words = 0;
-        sp.qlist = nullptr;
-        sp.qcount = nullptr;
-        sp.qhead = nullptr;
-        q.base = sp;
-        q.Hs = h->Hs; q.Ls = h->Ls; q.Eall = h->Eall;
-        q.tile_doubles = h->tile_doubles;
-        q.e_doubles = h->e_doubles;
-        q.npad_max = h->npad_max;
-        q.nb_lo = 0;
-        q.dbg_H = h->d_dbgH64;
-        q.dbg_vec = h->d_dbgv64;
-        q.warmG = nullptr; q.hullA = nullptr; q.hull_set = nullptr; q.hullb = nullptr; q.out_tau0 = nullptr; q.out_G = nullptr;
-        q.hull_rows = 0;
-        q.termA = h->tset ? h->d_term : nullptr;
-        q.termb = h->tset ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
-        q.term_rows = h->tset ? h->cfg.term_rows : 0;
-        q.eN = h->d_eN;
-        const int grid = (int)std::min<int64_t>(B, h->grid64);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[8], s));
-        if (h->tset)
-            hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<4, 1, 2>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, h->dc, q);
-        else if (h->npad_max <= 256)
-            hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<4, 1>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, h->dc, q);
-        else if (h->npad_max <= 640)
-            hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, 3>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, h->dc, q);
-        else
-            hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, ftmpc::f64k::NVT_MAX>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, h->dc, q);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[9], s));
-            h->ev_used[4] = true;
-            h->ev_valid = true;
-        }
-        return FTMPC_OK;
+        if (rc == FTMPC_OK && h->profiling) h->ev_valid = true;
+        return rc;
     }
     // fp32 instantiations NB = 8, 9, 10: each pulls the instances with ceil(n/16) <= NB (the first also the empty
     // ones, the last also shapes beyond every instantiation, which it reports) from the list the linearise kernel
     // wrote for it; a launch whose list is empty returns at once
-    auto launch_ws = [&](int v, int ev_slot) -> int {   // kernel 8 on work list v
-        SolveWgParams w;
-        w.base = sp;
-        w.base.hscratch = nullptr;
-        w.base.tile_words = 0;
-        w.base.qlist = h->d_qlist + (int64_t)v * B;
-        w.base.qcount = h->d_qctl + v;
-        w.base.qhead = h->d_qctl + 4 + v;
-        w.slot = h->ws_slot;
-        w.slot_words = h->ws_slot_words;
-        const int grid = grid_for(v, h->grid_ws);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[2 * ev_slot], s));
-        if (h->ws_nb == 6) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ws32_kernel<6>, dim3(grid), dim3(ftmpc::wsk::WG), 0, s, h->dc, w);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_ws32_kernel<8>, dim3(grid), dim3(ftmpc::wsk::WG), 0, s, h->dc, w);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[2 * ev_slot + 1], s));
-            h->ev_used[ev_slot] = true;
-        }
-        return FTMPC_OK;
-    };
-    for (int v = 0; v < nvar; ++v) {
-        const int NBv = 8 + v;
-        sp.hscratch = h->hs[v];
-        sp.tile_words = slot_words(NBv, h->dc.N);
+    auto on_list = [&](int v) {
         sp.qlist = h->d_qlist + (int64_t)v * B;
         sp.qcount = h->d_qctl + v;
         sp.qhead = h->d_qctl + 4 + v;
+    };
+    for (int v = 0; v < nvar; ++v) {
+        sp.hscratch = h->hs[v];
+        sp.tile_words = slot_words(8 + v, h->dc.N);
+        on_list(v);
         const int grid = grid_for(v, h->grid[v]);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[2 + 2 * v], s));
-        if (v == 0) hipLaunchKernelGGL(ftmpc::ftmpc_solve_f32_kernel<8>, dim3(grid), dim3(64), 0, s, h->dc, sp);
-        else if (v == 1) hipLaunchKernelGGL(ftmpc::ftmpc_solve_f32_kernel<9>, dim3(grid), dim3(64), 0, s, h->dc, sp);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_f32_kernel<10>, dim3(grid), dim3(64), 0, s, h->dc, sp);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[3 + 2 * v], s));
-            h->ev_used[1 + v] = true;
-        }
-    }
-    if (h->use_wg && h->use_wsw) {     // kernel 10 on work list 3
-        sp.hscratch = h->wsw_slot;
-        sp.tile_words = h->wsw_slot_words;
-        sp.qlist = h->d_qlist + (int64_t)3 * B;
-        sp.qcount = h->d_qctl + 3;
-        sp.qhead = h->d_qctl + 7;
-        const int grid = grid_for(3, h->grid_wsw);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[10], s));
-        if (h->ws_nb == 6) hipLaunchKernelGGL(ftmpc::ftmpc_solve_wsw32_kernel<6>, dim3(grid), dim3(64), 0, s, h->dc, sp);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_wsw32_kernel<8>, dim3(grid), dim3(64), 0, s, h->dc, sp);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[11], s));
-            h->ev_used[5] = true;
-        }
-    } else if (h->use_wg && h->use_ws) {
-        const int rc = launch_ws(3, 5);
+        rc = profiled(h, 1 + v, s, [&] { hipLaunchKernelGGL(pick_f32(v), dim3(grid), dim3(64), 0, s, h->dc, sp); });
         if (rc != FTMPC_OK) return rc;
-    } else if (h->use_wg) {
-        SolveWgParams w;
-        w.base = sp;
-        w.base.hscratch = nullptr;
-        w.base.tile_words = 0;
-        w.base.qlist = h->d_qlist + (int64_t)3 * B;
-        w.base.qcount = h->d_qctl + 3;
-        w.base.qhead = h->d_qctl + 7;
-        w.slot = h->wg_slot;
-        w.slot_words = h->wg_slot_words;
-        const int grid = grid_for(3, h->grid_wg);
-        if (h->profiling) HIP_TRY(h, hipEventRecord(h->ev[10], s));
-        hipLaunchKernelGGL(ftmpc::ftmpc_solve_wg32_kernel<15>, dim3(grid), dim3(ftmpc::wgk::WG), 0, s, h->dc, w);
-        HIP_TRY(h, hipGetLastError());
-        if (h->profiling) {
-            HIP_TRY(h, hipEventRecord(h->ev[11], s));
-            h->ev_used[5] = true;
+    }
+    if (h->use_wg) {      // work list 3 (ceil(n / 16) >= 11): kernel 10, kernel 8 or the workgroup kernel with the factor in LDS
+        on_list(3);
+        if (h->use_wsw) {
+            sp.hscratch = h->wsw_slot;
+            sp.tile_words = h->wsw_slot_words;
+            const int grid = grid_for(3, h->grid_wsw);
+            rc = profiled(h, 5, s, [&] { hipLaunchKernelGGL(pick_wsw32(h), dim3(grid), dim3(64), 0, s, h->dc, sp); });
+        } else {
+            SolveWgParams w;
+            sp.hscratch = nullptr;
+            sp.tile_words = 0;
+            w.base = sp;
+            w.slot = h->use_ws ? h->ws_slot.p : h->wg_slot.p;
+            w.slot_words = h->use_ws ? h->ws_slot_words : h->wg_slot_words;
+            const int grid = grid_for(3, h->use_ws ? h->grid_ws : h->grid_wg);
+            rc = profiled(h, 5, s, [&] {
+                if (h->use_ws) hipLaunchKernelGGL(pick_ws32(h), dim3(grid), dim3(ftmpc::wsk::WG), 0, s, h->dc, w);
+                else hipLaunchKernelGGL(ftmpc::ftmpc_solve_wg32_kernel<15>, dim3(grid), dim3(ftmpc::wgk::WG), 0, s, h->dc, w);
+            });
         }
+        if (rc != FTMPC_OK) return rc;
     }
     if (h->profiling) h->ev_valid = true;
     if (h->h_qcnt && !capturing && !h->qcnt_pending) {     // this step's list lengths, for the next one
@@ -696,14 +754,12 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
     if (h->use_ric64) h->use_ws64 = false;
     h->tset = cfg->terminal_set != 0;
     if (h->tset) {
-        const char* why = nullptr;
-        if (cfg->term_rows < 1 || cfg->term_rows > FTMPC_MAX_TERM_ROWS) why = "term_rows out of range 1..80";
+        if (cfg->term_rows < 1 || cfg->term_rows > FTMPC_MAX_TERM_ROWS) {
+            delete h;
+            return fail(nullptr, FTMPC_ERR_ARG, "term_rows out of range 1..80");
+        }
         h->tset_thruster = 16 * h->nb_max <= 256;      // (the THRUSTER form with terminal rows lives on the dense float64 kernel's n <= 256 mode; the
                                                        //  two-stage form -- ftmpc_solve_wrench_batch -- has no such limit: kernel 13)
-        if (why) {
-            delete h;
-            return fail(nullptr, FTMPC_ERR_ARG, why);
-        }
     }
     h->npad_max = 16 * h->nb_max;
     h->device = cfg->device_id;
@@ -737,7 +793,7 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
         h->stream2 = nullptr;      // (no overlap: the two-stage step allocates after kernel 13, on the one stream)
         (void)hipGetLastError();
     }
-    if (sbad || grow(h, &h->d_qctl, 8) != FTMPC_OK) {
+    if (sbad || h->d_qctl.ensure(h, 8) != FTMPC_OK) {
         g_create_error = "stream / event / work-list allocation failed";
         ftmpc_destroy(h);
         return FTMPC_ERR_HIP;
@@ -745,83 +801,48 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
     if (cfg->lin_split_max != 0) h->lin_split_max = cfg->lin_split_max < 0 ? 0 : cfg->lin_split_max;
     if (cfg->stage_chunks >= 1 && cfg->stage_chunks <= ftmpc_handle::MAX_CHUNKS) h->stage_chunks = cfg->stage_chunks;
     // persistent grids: resident workgroups per CU from the occupancy query (LDS-bound)
-    int per[3] = {0, 0, 0};
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[0], ftmpc::ftmpc_solve_f32_kernel<8>, 64, 0);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[1], ftmpc::ftmpc_solve_f32_kernel<9>, 64, 0);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[2], ftmpc::ftmpc_solve_f32_kernel<10>, 64, 0);
-    for (int v = 0; v < 3; ++v) h->grid[v] = h->num_cu * (per[v] < 1 ? 1 : per[v]);
-    int per64 = 0;
-    if (16 * h->nb_max <= 256)
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per64, ftmpc::ftmpc_solve_f64_kernel<4, 1>, ftmpc::f64k::WG, 0);
-    else if (16 * h->nb_max <= 640)
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per64, ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, 3>, ftmpc::f64k::WG, 0);
-    else
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per64, ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, ftmpc::f64k::NVT_MAX>, ftmpc::f64k::WG, 0);
-    if (per64 < 1) per64 = 1;
-    if (per64 > 2) per64 = 2;
-    if (h->tset) per64 = 1;     // the general-constraint instantiations hold ~50 KiB of LDS and one workgroup per CU
+    for (int v = 0; v < 3; ++v) h->grid[v] = h->num_cu * std::max(1, blocks_per_cu(pick_f32(v), 64));
+    // (the general-constraint instantiations hold ~50 KiB of LDS and one workgroup per CU)
+    const int per64 = h->tset ? 1 : std::min(2, std::max(1, blocks_per_cu(pick_f64(h, false), ftmpc::f64k::WG)));
     h->grid64 = h->num_cu * per64;
     h->tile_doubles = (int64_t)tiles_of(h->nb_max) * 256;
     h->e_doubles = (int64_t)(cfg->N + 2) * 9 * h->npad_max;     // + raw terminal rows GN and the terminal-set panel
     bool bad = false;
     if (h->use_f64) {
-        bad = grow(h, &h->Hs, h->grid64 * h->tile_doubles) != FTMPC_OK || grow(h, &h->Ls, h->grid64 * h->tile_doubles) != FTMPC_OK ||
-              grow(h, &h->Eall, h->grid64 * h->e_doubles) != FTMPC_OK ||
-              grow(h, &h->d_dbgH64, (int64_t)h->npad_max * h->npad_max) != FTMPC_OK ||
-              grow(h, &h->d_dbgv64, 3 * (int64_t)h->npad_max + 4) != FTMPC_OK;
+        bad = h->Hs.ensure(h, h->grid64 * h->tile_doubles) != FTMPC_OK || h->Ls.ensure(h, h->grid64 * h->tile_doubles) != FTMPC_OK ||
+              h->Eall.ensure(h, h->grid64 * h->e_doubles) != FTMPC_OK ||
+              h->d_dbgH64.ensure(h, (int64_t)h->npad_max * h->npad_max) != FTMPC_OK ||
+              h->d_dbgv64.ensure(h, 3 * (int64_t)h->npad_max + 4) != FTMPC_OK;
         if (!bad && h->use_ric64) {
-            int per = 0;
-            if (h->sbounds && h->ric_nv == 6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ric64_kernel<6, true>, 64, 0);
-            else if (h->sbounds) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ric64_kernel<10, true>, 64, 0);
-            else if (h->ric_nv == 4) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ric64_kernel<4>, 64, 0);
-            else if (h->ric_nv == 6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ric64_kernel<6>, 64, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ric64_kernel<10>, 64, 0);
-            h->grid_ric = h->num_cu * std::max(1, per);
+            h->grid_ric = h->num_cu * std::max(1, blocks_per_cu(pick_ric64(h), 64));
             h->ric_slot_doubles = ftmpc::rick::slot_doubles(cfg->N);
-            bad = grow(h, &h->ric_slot, (int64_t)h->grid_ric * h->ric_slot_doubles) != FTMPC_OK;
+            bad = h->ric_slot.ensure(h, (int64_t)h->grid_ric * h->ric_slot_doubles) != FTMPC_OK;
         }
         if (!bad && h->use_ws64) {
-            int per = 0;
-            if (h->ws64_nvt == 1) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ws64_kernel<1>, ftmpc::ws64k::WG, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ws64_kernel<3>, ftmpc::ws64k::WG, 0);
-            h->grid_ws64 = h->num_cu * std::max(1, std::min(per, FTMPC_WS64_WPC));
+            h->grid_ws64 = h->num_cu * std::max(1, std::min(blocks_per_cu(pick_ws64(h), ftmpc::ws64k::WG), FTMPC_WS64_WPC));
             h->ws64_slot_doubles = ftmpc::ws64k::slot_doubles(cfg->N);
-            bad = grow(h, &h->ws64_slot, (int64_t)h->grid_ws64 * h->ws64_slot_doubles) != FTMPC_OK;
+            bad = h->ws64_slot.ensure(h, (int64_t)h->grid_ws64 * h->ws64_slot_doubles) != FTMPC_OK;
         }
-        if (!bad && h->tset) {
-            bad = grow(h, &h->d_term, (int64_t)cfg->term_rows * 10) != FTMPC_OK;
-            if (!bad) {
-                std::vector<double> t((size_t)cfg->term_rows * 10);
-                std::memcpy(t.data(), cfg->term_A, (size_t)cfg->term_rows * 9 * sizeof(double));
-                std::memcpy(t.data() + (size_t)cfg->term_rows * 9, cfg->term_b, (size_t)cfg->term_rows * sizeof(double));
-                bad = hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess;
-            }
-        }
+        if (!bad && h->tset) bad = term_upload(h) != FTMPC_OK;
     } else {
-        bad = grow(h, &h->hs[0], (int64_t)h->grid[0] * slot_words(8, cfg->N)) != FTMPC_OK ||
-              (h->nb_max > 8 && grow(h, &h->hs[1], (int64_t)h->grid[1] * slot_words(9, cfg->N)) != FTMPC_OK) ||
-              (h->nb_max > 9 && grow(h, &h->hs[2], (int64_t)h->grid[2] * slot_words(10, cfg->N)) != FTMPC_OK) ||
-              grow(h, &h->d_dbgH, 4096 * 24 + 256 * 256) != FTMPC_OK || grow(h, &h->d_dbgv, 3 * 256 + 4) != FTMPC_OK;
+        bad = h->hs[0].ensure(h, (int64_t)h->grid[0] * slot_words(8, cfg->N)) != FTMPC_OK ||
+              (h->nb_max > 8 && h->hs[1].ensure(h, (int64_t)h->grid[1] * slot_words(9, cfg->N)) != FTMPC_OK) ||
+              (h->nb_max > 9 && h->hs[2].ensure(h, (int64_t)h->grid[2] * slot_words(10, cfg->N)) != FTMPC_OK) ||
+              h->d_dbgH.ensure(h, 4096 * 24 + 256 * 256) != FTMPC_OK || h->d_dbgv.ensure(h, 3 * 256 + 4) != FTMPC_OK;
         if (!bad && h->use_ws) {
-            int per = 0;
-            if (h->ws_nb == 6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ws32_kernel<6>, ftmpc::wsk::WG, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ws32_kernel<8>, ftmpc::wsk::WG, 0);
-            h->grid_ws = h->num_cu * (per > 0 ? per : 1);
+            h->grid_ws = h->num_cu * std::max(1, blocks_per_cu(pick_ws32(h), ftmpc::wsk::WG));
             h->ws_slot_words = ftmpc::wsk::slot_words(h->ws_nb, cfg->N);
-            bad = grow(h, &h->ws_slot, (int64_t)h->grid_ws * h->ws_slot_words) != FTMPC_OK;
+            bad = h->ws_slot.ensure(h, (int64_t)h->grid_ws * h->ws_slot_words) != FTMPC_OK;
         }
         if (!bad && h->use_wsw) {
-            int per = 0;
-            if (h->ws_nb == 6) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_wsw32_kernel<6>, 64, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_wsw32_kernel<8>, 64, 0);
-            h->grid_wsw = h->num_cu * (per > 0 ? per : 1);
+            h->grid_wsw = h->num_cu * std::max(1, blocks_per_cu(pick_wsw32(h), 64));
             h->wsw_slot_words = ftmpc::wswk::slot_words(h->ws_nb, cfg->N);
-            bad = grow(h, &h->wsw_slot, (int64_t)h->grid_wsw * h->wsw_slot_words) != FTMPC_OK;
+            bad = h->wsw_slot.ensure(h, (int64_t)h->grid_wsw * h->wsw_slot_words) != FTMPC_OK;
         }
         if (!bad && h->use_wg) {
             h->grid_wg = h->num_cu;      // ~150 KiB of LDS: one workgroup per CU
             h->wg_slot_words = ftmpc::wgk::slot_words(15, cfg->N);
-            bad = grow(h, &h->wg_slot, (int64_t)h->grid_wg * h->wg_slot_words) != FTMPC_OK;
+            bad = h->wg_slot.ensure(h, (int64_t)h->grid_wg * h->wg_slot_words) != FTMPC_OK;
         }
     }
     if (!bad && cfg->terminal_cost_terms) {
@@ -843,9 +864,7 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
             if (t.poly_exp[i] < 0 || t.poly_exp[i] > 16 || t.root_exp[i] < 0 || t.root_exp[i] > 16) bad = true;
         }
         t.cconst = cfg->tc_const;
-        void* p = nullptr;
-        bad = bad || hipMalloc(&p, sizeof(TermCost)) != hipSuccess;
-        h->d_tcost = static_cast<TermCost*>(p);
+        bad = bad || h->d_tcost.ensure(h, 1) != FTMPC_OK;
         bad = bad || hipMemcpy(h->d_tcost, &t, sizeof(TermCost), hipMemcpyHostToDevice) != hipSuccess;
         if (bad) h->err = "terminal-cost tables: bad exponent or allocation failure";
     }
@@ -861,13 +880,6 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
 int ftmpc_destroy(ftmpc_handle* h) {
     if (!h) return FTMPC_OK;
     (void)hipSetDevice(h->device);
-    void* ptrs[] = {h->rec, h->d_x0, h->d_ub, h->d_stuck, h->d_xref, h->d_uref, h->d_warm, h->d_u0, h->d_U,
-                    h->d_status, h->d_iters, h->hs[0], h->hs[1], h->hs[2], h->d_dbgH, h->d_dbgv, h->Hs, h->Ls, h->Eall, h->d_dbgH64, h->d_dbgv64,
-                    h->d_atau, h->d_aub, h->d_au, h->d_ast, h->d_ait, h->d_qlist, h->d_qctl, h->d_term, h->d_eN, h->gHs, h->gLs,
-                    h->gEall, h->wg_slot, h->ws_slot, h->ws64_slot, h->ric_slot, h->ricw_slot, h->d_cbar, h->wsw_slot, h->hull_slot, h->d_tcost, h->d_cost, h->d_sqU, h->d_sqQ, h->d_sqT, h->d_sqJ, h->d_sqJall, h->d_sqF, h->d_hullA, h->d_hullb, h->d_warmG, h->d_tau0, h->d_G, h->d_taud, h->d_hullset, h->d_ast2,
-                    h->d_swG, h->d_swT, h->d_swJ, h->d_swJall, h->d_swF, h->d_swX};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     if (h->sqp_exec) (void)hipGraphExecDestroy(h->sqp_exec);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_alloc) (void)hipEventDestroy(h->ev_alloc);
@@ -886,7 +898,7 @@ int ftmpc_destroy(ftmpc_handle* h) {
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
-    delete h;
+    delete h;      // (the device buffers go with it)
     return FTMPC_OK;
 }
 
@@ -898,50 +910,35 @@ int ftmpc_reserve(ftmpc_handle* h, int64_t max_batch) {
     HIP_TRY(h, hipSetDevice(h->device));
     const int N = h->cfg.N, NT = h->cfg.NT;
     const int64_t B = max_batch;
-    float* recf = nullptr;
-    // every buffer below is freed before it is re-allocated: until all of them exist again the handle holds NO batch
-    // capacity, so a failure part-way (out of memory) makes the next call grow everything again instead of launching on
-    // freed pointers
-    h->cap_batch = 0;
-    if (h->rec) (void)hipFree(h->rec);
-    h->rec = nullptr;
-    int rc = grow(h, &recf, B * N * ftmpc::REC_STRIDE * 2);   // float64 records
-    if (rc != FTMPC_OK) return rc;
-    h->rec = recf;
-    if ((rc = grow(h, &h->d_x0, B * 13)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_ub, B * NT)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_stuck, B * NT)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_warm, B * N * NT)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_u0, B * NT)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_U, B * N * NT)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_status, B)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_iters, B)) != FTMPC_OK) return rc;
-    if (!h->use_f64 && (rc = grow(h, &h->d_qlist, 4 * B)) != FTMPC_OK) return rc;
-    if ((rc = grow(h, &h->d_eN, B * 9)) != FTMPC_OK) return rc;
-    if (h->sbounds && (rc = grow(h, &h->d_cbar, B * h->cfg.N * 13)) != FTMPC_OK) return rc;
-    h->cap_batch = B;
-    return FTMPC_OK;
+    // each buffer is freed before it is re-allocated; until all of them exist again the handle holds NO batch capacity
+    return ensure_group(h->cap_batch, B, [&] {
+        int rc;
+        if ((rc = h->rec.ensure(h, B * N * ftmpc::REC_STRIDE * 2)) != FTMPC_OK) return rc;   // float64 records
+        if ((rc = h->d_x0.ensure(h, B * 13)) != FTMPC_OK) return rc;
+        if ((rc = h->d_ub.ensure(h, B * NT)) != FTMPC_OK) return rc;
+        if ((rc = h->d_stuck.ensure(h, B * NT)) != FTMPC_OK) return rc;
+        if ((rc = h->d_warm.ensure(h, B * N * NT)) != FTMPC_OK) return rc;
+        if ((rc = h->d_u0.ensure(h, B * NT)) != FTMPC_OK) return rc;
+        if ((rc = h->d_U.ensure(h, B * N * NT)) != FTMPC_OK) return rc;
+        if ((rc = h->d_status.ensure(h, B)) != FTMPC_OK) return rc;
+        if ((rc = h->d_iters.ensure(h, B)) != FTMPC_OK) return rc;
+        if (!h->use_f64 && (rc = h->d_qlist.ensure(h, 4 * B)) != FTMPC_OK) return rc;
+        if ((rc = h->d_eN.ensure(h, B * 9)) != FTMPC_OK) return rc;
+        if (h->sbounds && (rc = h->d_cbar.ensure(h, B * h->cfg.N * 13)) != FTMPC_OK) return rc;
+        return rc;
+    });
 }
 
 static int stage_refs(ftmpc_handle* h, int64_t B, const double* xref, int64_t xref_stride, const double* uref,
                       int64_t uref_stride) {
     const int N = h->cfg.N;
     const int64_t nx = xref_stride == 0 ? 9 * (N + 1) : B * xref_stride;
-    if (nx > h->cap_xref) {
-        h->cap_xref = 0;   // (a failed growth must not leave a stale capacity)
-        int rc = grow(h, &h->d_xref, nx);
-        if (rc != FTMPC_OK) return rc;
-        h->cap_xref = nx;
-    }
+    int rc = h->d_xref.ensure(h, nx);
+    if (rc != FTMPC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->d_xref, xref, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (uref) {
         const int64_t nu = uref_stride == 0 ? 6 * (N + 1) : B * uref_stride;
-        if (nu > h->cap_uref) {
-            h->cap_uref = 0;   // (a failed growth must not leave a stale capacity)
-            int rc = grow(h, &h->d_uref, nu);
-            if (rc != FTMPC_OK) return rc;
-            h->cap_uref = nu;
-        }
+        if ((rc = h->d_uref.ensure(h, nu)) != FTMPC_OK) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->d_uref, uref, nu * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     return FTMPC_OK;
@@ -951,6 +948,16 @@ static int check_strides(ftmpc_handle* h, int64_t xref_stride, int64_t uref_stri
     const int N = h->cfg.N;
     if (xref_stride != 0 && xref_stride < 9 * (N + 1)) return fail(h, FTMPC_ERR_ARG, "xref_stride must be 0 or >= 9*(N+1)");
     if (uref && uref_stride != 0 && uref_stride < 6 * (N + 1)) return fail(h, FTMPC_ERR_ARG, "uref_stride must be 0 or >= 6*(N+1)");
+    return FTMPC_OK;
+}
+
+// the state, bounds and stuck thrusts of a batch into the handle's mirrors (ftmpc_reserve'd by the caller), on the handle's stream
+static int stage_inputs(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck) {
+    const int NT = h->cfg.NT;
+    hipStream_t s = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
     return FTMPC_OK;
 }
 
@@ -989,16 +996,7 @@ int ftmpc_solve_batch(ftmpc_handle* h, int64_t B, const double* x0, const double
     // reference windows on the device (shared: once; per instance: with the ranges below)
     const int64_t nxr = xref_stride == 0 ? 9 * (N + 1) : B * xref_stride;
     const int64_t nur = !uref ? 0 : (uref_stride == 0 ? 6 * (N + 1) : B * uref_stride);
-    if (nxr > h->cap_xref) {
-        h->cap_xref = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_xref, nxr)) != FTMPC_OK) return rc;
-        h->cap_xref = nxr;
-    }
-    if (nur > h->cap_uref) {
-        h->cap_uref = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_uref, nur)) != FTMPC_OK) return rc;
-        h->cap_uref = nur;
-    }
+    if ((rc = h->d_xref.ensure(h, nxr)) != FTMPC_OK || (rc = h->d_uref.ensure(h, nur)) != FTMPC_OK) return rc;
     // pinned mirrors: inputs [x0 | ub | stuck | warm | xref | uref], outputs [u0 | U | status | iters]
     const int64_t o_x0 = 0, o_ub = o_x0 + B * 13, o_st = o_ub + B * NT, o_wm = o_st + B * NT, o_xr = o_wm + (warmU ? B * nw : 0),
                   o_ur = o_xr + nxr, in_words = o_ur + nur;
@@ -1072,16 +1070,10 @@ int ftmpc_eval_cost_batch(ftmpc_handle* h, int64_t B, const double* x0, const do
     if (rc != FTMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
-    if (B > h->cap_cost) {
-        h->cap_cost = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_cost, B)) != FTMPC_OK) return rc;
-        h->cap_cost = B;
-    }
+    if ((rc = h->d_cost.ensure(h, B)) != FTMPC_OK) return rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->d_U, U, B * N * NT * sizeof(double), hipMemcpyHostToDevice, s));
     ftmpc::CostParams cp;
@@ -1184,19 +1176,14 @@ static int sqp_enqueue(ftmpc_handle* h, int64_t B, const double* d_xref, int64_t
                        const double* d_warm, int32_t sqp_iters, int32_t backtracks, double tol, ftmpc::SqpState& S, double** J0_out) {
     const int64_t nw = (int64_t)h->cfg.N * h->cfg.NT;
     int rc;
-    if (B > h->cap_sqp) {
-        h->cap_sqp = 0;
-        if ((rc = grow(h, &h->d_sqU, B * nw)) != FTMPC_OK || (rc = grow(h, &h->d_sqQ, B * nw)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_sqT, B * nw)) != FTMPC_OK || (rc = grow(h, &h->d_sqJ, 4 * B)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_sqF, 6 * B)) != FTMPC_OK)
-            return rc;
-        h->cap_sqp = B;
-    }
-    if (B * backtracks > h->cap_sqJall) {
-        h->cap_sqJall = 0;
-        if ((rc = grow(h, &h->d_sqJall, B * backtracks)) != FTMPC_OK) return rc;
-        h->cap_sqJall = B * backtracks;
-    }
+    rc = ensure_group(h->cap_sqp, B, [&] {
+        int r;
+        if ((r = h->d_sqU.ensure(h, B * nw)) != FTMPC_OK || (r = h->d_sqQ.ensure(h, B * nw)) != FTMPC_OK ||
+            (r = h->d_sqT.ensure(h, B * nw)) != FTMPC_OK || (r = h->d_sqJ.ensure(h, 4 * B)) != FTMPC_OK)
+            return r;
+        return h->d_sqF.ensure(h, 6 * B);
+    });
+    if (rc != FTMPC_OK || (rc = h->d_sqJall.ensure(h, B * backtracks)) != FTMPC_OK) return rc;
     // FTMPC_SQP_GRAPH: 0 never, 1 always; unset: batches up to 512 (measured, ten major iterations: 7.0 -> 6.2 ms at B = 256; at
     // B = 1 024 the replay is SLOWER than the direct launches, 10.0 against 7.6 ms -- a captured step always launches the full
     // persistent grids, the direct path shrinks those whose work list was empty the step before)
@@ -1285,9 +1272,7 @@ int ftmpc_solve_sqp_batch(ftmpc_handle* h, int64_t B, const double* x0, const do
     const int N = h->cfg.N, NT = h->cfg.NT;
     const int64_t nw = (int64_t)N * NT;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmU) HIP_TRY(h, hipMemcpyAsync(h->d_warm, warmU, B * nw * sizeof(double), hipMemcpyHostToDevice, s));
     ftmpc::SqpState S;
@@ -1319,11 +1304,8 @@ int ftmpc_solve_batch_device(ftmpc_handle* h, int64_t B, const double* x0, const
     int rc = check_strides(h, xref_stride, uref_stride, uref);
     if (rc != FTMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (B > h->cap_batch) {
-        h->cap_batch = 0;   // (a failed growth must not leave a stale capacity)
-        // growing the workspace allocates: callers that time or graph-capture must ftmpc_reserve first
-        if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
-    }
+    // growing the workspace allocates: callers that time or graph-capture must ftmpc_reserve first
+    if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return enqueue(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, warmU, out_u0, out_U, status, iters,
                    reinterpret_cast<hipStream_t>(stream), -1);
 }
@@ -1365,77 +1347,67 @@ static int wrench_prepare(ftmpc_handle* h, int64_t B, const double* hull_A, int3
     int rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
-    if (hull_fp32(h, hull_rows)) {     // kernel 11: one wave per instance, H_w tiles in LDS; only the float64 gradient scratch is global
-        if (!h->hull_slot) {
-            int per = 0;
-            if (h->cfg.terminal_set) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_hull32_kernel<6, true>, 64, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_hull32_kernel<6, false>, 64, 0);
-            h->grid_hull = h->num_cu * (per > 0 ? per : 1);
-            h->hull_slot_words = ftmpc::wswk::slot_words(6, N);
-            if ((rc = grow(h, &h->hull_slot, (int64_t)h->grid_hull * h->hull_slot_words)) != FTMPC_OK) return rc;
-        }
+    if (hull_fp32(h, hull_rows) && !h->hull_slot) {     // kernel 11: one wave per instance, H_w tiles in LDS; only the float64 gradient scratch is global
+        h->grid_hull = h->num_cu * std::max(1, blocks_per_cu(pick_hull32(h, hull_rows), 64));
+        h->hull_slot_words = ftmpc::wswk::slot_words(6, N);
+        if ((rc = h->hull_slot.ensure(h, (int64_t)h->grid_hull * h->hull_slot_words)) != FTMPC_OK) return rc;
     }
     if (hull_ricw(h, hull_rows)) {     // kernel 13's per-wave slots (sized by the row count)
         const int64_t need = ftmpc::rickw::slot_doubles(N, hull_rows, h->sbounds);
         if (!h->ricw_slot || need > h->ricw_slot_doubles) {
-            int per = 0;
-            if (h->sbounds && N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6, false, true>, 64, 0);
-            else if (h->sbounds) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10, false, true>, 64, 0);
-            else if (h->cfg.terminal_set && N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6, true>, 64, 0);
-            else if (h->cfg.terminal_set) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10, true>, 64, 0);
-            else if (N <= 24) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<6>, 64, 0);
-            else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ftmpc::ftmpc_solve_ricw64_kernel<10>, 64, 0);
-            h->grid_ricw = h->num_cu * std::max(1, per);
-            h->ricw_slot_doubles = 0;
-            if ((rc = grow(h, &h->ricw_slot, (int64_t)h->grid_ricw * need)) != FTMPC_OK) return rc;
+            h->grid_ricw = h->num_cu * std::max(1, blocks_per_cu(pick_ricw64(h, hull_rows), 64));
+            if ((rc = h->ricw_slot.ensure(h, (int64_t)h->grid_ricw * need)) != FTMPC_OK) return rc;
             h->ricw_slot_doubles = need;
         }
     }
-    // the dense float64 kernel's slots: the terminal-set forms, kernel_select = FTMPC_KERNEL_DENSE, N > 40 -- the whole batch, or what
-    // kernel 11 hands over (hull and terminal rows active together, a polish that did not settle: SolveHullParams::fb_list)
-    if (h->cfg.terminal_set && !h->d_term) {      // the rows of the terminal set on the device: term_A | term_b
-        if ((rc = grow(h, &h->d_term, (int64_t)h->cfg.term_rows * 10)) != FTMPC_OK) return rc;
-        std::vector<double> t((size_t)h->cfg.term_rows * 10);
-        std::memcpy(t.data(), h->cfg.term_A, (size_t)h->cfg.term_rows * 9 * sizeof(double));
-        std::memcpy(t.data() + (size_t)h->cfg.term_rows * 9, h->cfg.term_b, (size_t)h->cfg.term_rows * sizeof(double));
-        HIP_TRY(h, hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if ((rc = term_upload(h)) != FTMPC_OK) return rc;
+    // the dense float64 kernel's slots: kernel_select = FTMPC_KERNEL_DENSE, N > 40 -- the whole batch, or what kernel 11 hands over
+    // (hull and terminal rows active together, a polish that did not settle: SolveHullParams::fb_list)
     if (!hull_ricw(h, hull_rows) && !h->gHs) {   // per-workgroup slots of the 6N-variable problem (separate from the thruster-space slots of this handle)
         const int nbg = (6 * N + 15) / 16;
         h->npad_gen = 16 * nbg;
         h->grid_gen = h->num_cu;
         h->tile_doubles_gen = (int64_t)tiles_of(nbg) * 256;
         h->e_doubles_gen = (int64_t)(N + 2) * 9 * h->npad_gen;
-        if ((rc = grow(h, &h->gHs, h->grid_gen * h->tile_doubles_gen)) != FTMPC_OK || (rc = grow(h, &h->gLs, h->grid_gen * h->tile_doubles_gen)) != FTMPC_OK ||
-            (rc = grow(h, &h->gEall, h->grid_gen * h->e_doubles_gen)) != FTMPC_OK)
+        if ((rc = h->gHs.ensure(h, h->grid_gen * h->tile_doubles_gen)) != FTMPC_OK || (rc = h->gLs.ensure(h, h->grid_gen * h->tile_doubles_gen)) != FTMPC_OK ||
+            (rc = h->gEall.ensure(h, h->grid_gen * h->e_doubles_gen)) != FTMPC_OK)
             return rc;
-        if (h->cfg.terminal_set && !h->d_term) {
-            if ((rc = grow(h, &h->d_term, (int64_t)h->cfg.term_rows * 10)) != FTMPC_OK) return rc;
-            std::vector<double> t((size_t)h->cfg.term_rows * 10);
-            std::memcpy(t.data(), h->cfg.term_A, (size_t)h->cfg.term_rows * 9 * sizeof(double));
-            std::memcpy(t.data() + (size_t)h->cfg.term_rows * 9, h->cfg.term_b, (size_t)h->cfg.term_rows * sizeof(double));
-            HIP_TRY(h, hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
     }
     const int64_t nA = (int64_t)n_sets * hull_rows * 6;
-    if (nA > h->cap_hullA) {
-        h->cap_hullA = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_hullA, nA)) != FTMPC_OK) return rc;
-        h->cap_hullA = nA;
-    }
-    if (B > h->cap_wrench) {
-        h->cap_wrench = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_hullb, B * FTMPC_MAX_HULL_ROWS)) != FTMPC_OK || (rc = grow(h, &h->d_hullset, B)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_warmG, B * N * 6)) != FTMPC_OK || (rc = grow(h, &h->d_tau0, B * 6)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_G, B * N * 6)) != FTMPC_OK || (rc = grow(h, &h->d_taud, B * 6)) != FTMPC_OK || (rc = grow(h, &h->d_ast2, 3 * B)) != FTMPC_OK)      // allocation status | iterations | kernel 11's hand-over list
-            return rc;
-        h->cap_wrench = B;
-    }
+    if ((rc = h->d_hullA.ensure(h, nA)) != FTMPC_OK) return rc;
+    rc = ensure_group(h->cap_wrench, B, [&] {
+        int r;
+        if ((r = h->d_hullb.ensure(h, B * FTMPC_MAX_HULL_ROWS)) != FTMPC_OK || (r = h->d_hullset.ensure(h, B)) != FTMPC_OK ||
+            (r = h->d_warmG.ensure(h, B * N * 6)) != FTMPC_OK || (r = h->d_tau0.ensure(h, B * 6)) != FTMPC_OK ||
+            (r = h->d_G.ensure(h, B * N * 6)) != FTMPC_OK || (r = h->d_taud.ensure(h, B * 6)) != FTMPC_OK)
+            return r;
+        return h->d_ast2.ensure(h, 3 * B);      // allocation status | iterations | kernel 11's hand-over list
+    });
+    if (rc != FTMPC_OK) return rc;
     hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_hullA, hull_A, nA * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(h->d_hullb, hull_b, B * hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
     if (hull_set) HIP_TRY(h, hipMemcpyAsync(h->d_hullset, hull_set, B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     return FTMPC_OK;
+}
+
+// The allocation half of a two-stage step on stream st: u0 in h->d_u0 = min-norm allocation of h->d_tau0 - D stuck, status /
+// iterations in h->d_ast2; of every instance, or (list mode) of the *count instances in list.
+static void wrench_allocate(ftmpc_handle* h, int64_t B, hipStream_t st, const int32_t* list, const int32_t* count) {
+    hipLaunchKernelGGL(ftmpc::ftmpc_healthy_wrench_kernel, dim3((unsigned)((B * 6 + 255) / 256)), dim3(256), 0, st, h->dc, B,
+                       (const double*)h->d_tau0, (const double*)h->d_stuck, h->d_taud.p, list, count);
+    ftmpc::AllocParams a;
+    a.B = B;
+    a.tau = h->d_taud;
+    a.ub = h->d_ub;
+    a.out_u = h->d_u0;
+    a.status = h->d_ast2;
+    a.iters = h->d_ast2 + B;
+    a.max_iters = 50;
+    a.tol = 1e-8;
+    a.list = list;
+    a.count = count;
+    hipLaunchKernelGGL(ftmpc::ftmpc_allocate_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, h->dc, a);
 }
 
 // The QP half of a two-stage step over DEVICE buffers (h->d_x0 / d_ub / d_stuck, the staged hull tables, the given reference
@@ -1458,50 +1430,33 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
     lp.warmG = d_warmG;
     lp.out_eN = h->d_eN;
     lp.tcost = h->d_tcost;
-    lp.out_cbar = h->sbounds ? h->d_cbar : nullptr;      // the linearisation trajectory (about warmG, or D stuck) for the state rows
+    lp.out_cbar = h->sbounds ? h->d_cbar.p : nullptr;      // the linearisation trajectory (about warmG, or D stuck) for the state rows
     launch_linearize(h, B, (int)((B + 63) / 64), s, lp);
     HIP_TRY(h, hipGetLastError());
     // the wrench problem stops at mu 1e-10 unless the caller asked otherwise (general rows: see ftmpc_config.mu_stop)
     DeviceConsts dcg = h->dc;
     if (!(h->cfg.mu_stop > 0)) dcg.mu_stop = 1e-10;
-    if (hull_fp32(h, hull_rows)) {
+    const bool handed = hull_fp32(h, hull_rows);
+    if (handed) {
         HIP_TRY(h, hipMemsetAsync(h->d_qctl, 0, 8 * sizeof(int32_t), s));
         ftmpc::SolveHullParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.base.B = B;
-        q.base.rec = h->rec;
-        q.base.ub = h->d_ub; q.base.stuck = h->d_stuck;
+        fill_wrench(h, q, B, hull_rows, has_set, d_warmG);
         q.base.out_u0 = h->d_u0;
-        q.base.status = h->d_status; q.base.iters = h->d_iters;
         q.base.hscratch = h->hull_slot;
         q.base.tile_words = h->hull_slot_words;
         q.base.qhead = h->d_qctl + 7;
-        q.base.dbg_inst = -1;
-        q.base.dbg_H = h->use_f64 ? reinterpret_cast<float*>(h->d_dbgH64) : h->d_dbgH;     // (diagnostic build: phase stamps)
-        q.warmG = d_warmG;
-        q.hullA = h->d_hullA;
-        q.hull_set = has_set ? h->d_hullset : nullptr;
-        q.hullb = h->d_hullb;
-        q.hull_rows = hull_rows;
-        q.out_tau0 = h->d_tau0;
-        q.out_G = h->d_G;
-        q.termA = h->cfg.terminal_set ? h->d_term : nullptr;
-        q.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
-        q.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
-        q.eN = h->d_eN;
+        q.base.dbg_H = h->use_f64 ? reinterpret_cast<float*>(h->d_dbgH64.p) : h->d_dbgH.p;     // (diagnostic build: phase stamps)
         const int grid = (int)std::min<int64_t>(B, h->grid_hull);
-        q.fb_list = h->d_ast2 + 2 * h->cap_wrench;
+        q.fb_list = handover_list(h);
         q.fb_count = h->d_qctl;      // (the generalized-force path builds no work lists: the counter of list 0 is free)
         // kernel 11 leaves the interior-point iteration at mu 1e-7 for its polish: below that the fp32 slacks and duals of the
         // active rows are noise that spoils the active set they are read for (measured on 16 384 instances: 253 polishes do not
         // settle from mu 1e-10, 66 from 1e-7, same 1.9e-6 f_max worst error; from 1e-6 a wrong set is "verified")
         DeviceConsts dch = dcg;
         if (!(h->cfg.mu_stop > 0)) dch.mu_stop = 1e-7;
-        if (h->cfg.terminal_set) hipLaunchKernelGGL((ftmpc::ftmpc_solve_hull32_kernel<6, true>), dim3(grid), dim3(64), 0, s, dch, q);
-        else hipLaunchKernelGGL((ftmpc::ftmpc_solve_hull32_kernel<6, false>), dim3(grid), dim3(64), 0, s, dch, q);
+        hipLaunchKernelGGL(pick_hull32(h, hull_rows), dim3(grid), dim3(64), 0, s, dch, q);
         HIP_TRY(h, hipGetLastError());
     }
-    const bool handed = hull_fp32(h, hull_rows);
     h->wrench_handed = handed;
     // allocation of the batch on a second stream, beside kernel 13's pass over the hand-over list (not while profiling: the
     // event pairs of ftmpc_last_kernel_ms sit on one stream)
@@ -1510,92 +1465,35 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
     if (overlap) {
         HIP_TRY(h, hipEventRecord(h->ev_fork, s));
         HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-        hipLaunchKernelGGL(ftmpc::ftmpc_healthy_wrench_kernel, dim3((unsigned)((B * 6 + 255) / 256)), dim3(256), 0, h->stream2, h->dc, B,
-                           (const double*)h->d_tau0, (const double*)h->d_stuck, h->d_taud, (const int32_t*)nullptr, (const int32_t*)nullptr);
-        ftmpc::AllocParams a0;
-        a0.B = B;
-        a0.tau = h->d_taud;
-        a0.ub = h->d_ub;
-        a0.out_u = h->d_u0;
-        a0.status = h->d_ast2;
-        a0.iters = h->d_ast2 + B;
-        a0.max_iters = 50;
-        a0.tol = 1e-8;
-        hipLaunchKernelGGL(ftmpc::ftmpc_allocate_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream2, h->dc, a0);
+        wrench_allocate(h, B, h->stream2, nullptr, nullptr);
         HIP_TRY(h, hipEventRecord(h->ev_alloc, h->stream2));
     }
     if (hull_ricw(h, hull_rows)) {      // kernel 13: the whole batch, or what kernel 11 handed over
         ftmpc::SolveRicwParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.base.B = B;
-        q.base.rec = h->rec;
-        q.base.ub = h->d_ub; q.base.stuck = h->d_stuck;
-        q.base.status = h->d_status; q.base.iters = h->d_iters;
-        q.base.dbg_inst = -1;
-        q.base.qlist = handed ? h->d_ast2 + 2 * h->cap_wrench : nullptr;
-        q.base.qcount = handed ? h->d_qctl : nullptr;
+        fill_wrench(h, q, B, hull_rows, has_set, d_warmG);
+        q.base.qlist = handed ? handover_list(h) : nullptr;
+        q.base.qcount = handed ? h->d_qctl.p : nullptr;
         HIP_TRY(h, hipMemsetAsync(h->d_qctl + 4, 0, sizeof(int32_t), s));
         q.base.qhead = h->d_qctl + 4;
         q.slot = h->ricw_slot;
         q.slot_doubles = h->ricw_slot_doubles;
-        q.warmG = d_warmG;
-        q.hullA = h->d_hullA;
-        q.hull_set = has_set ? h->d_hullset : nullptr;
-        q.hullb = h->d_hullb;
-        q.hull_rows = hull_rows;
-        q.out_tau0 = h->d_tau0;
-        q.out_G = h->d_G;
-        q.termA = h->cfg.terminal_set ? h->d_term : nullptr;
-        q.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
-        q.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
-        q.eN = h->d_eN;
-        for (int i = 0; i < FTMPC_NX; ++i) {
-            q.xlb[i] = h->cfg.xlb[i];
-            q.xub[i] = h->cfg.xub[i];
-        }
-        q.cbar = h->sbounds ? h->d_cbar : nullptr;
+        fill_state_bounds(h, q);
         const int grid = (int)std::min<int64_t>(B, h->grid_ricw);
-        if (h->sbounds && h->cfg.N <= 24) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<6, false, true>), dim3(grid), dim3(64), 0, s, dcg, q);
-        else if (h->sbounds) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<10, false, true>), dim3(grid), dim3(64), 0, s, dcg, q);
-        else if (h->cfg.terminal_set && h->cfg.N <= 24) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<6, true>), dim3(grid), dim3(64), 0, s, dcg, q);
-        else if (h->cfg.terminal_set) hipLaunchKernelGGL((ftmpc::ftmpc_solve_ricw64_kernel<10, true>), dim3(grid), dim3(64), 0, s, dcg, q);
-        else if (h->cfg.N <= 24) hipLaunchKernelGGL(ftmpc::ftmpc_solve_ricw64_kernel<6>, dim3(grid), dim3(64), 0, s, dcg, q);
-        else hipLaunchKernelGGL(ftmpc::ftmpc_solve_ricw64_kernel<10>, dim3(grid), dim3(64), 0, s, dcg, q);
-        HIP_TRY(h, hipGetLastError());
-    } else {
-    // the dense float64 kernel: the whole batch, or what kernel 11 handed over
-    Solve64Params q;
-    std::memset(&q, 0, sizeof(q));
-    q.base.B = B;
-    q.base.rec = h->rec;
-    q.base.ub = h->d_ub; q.base.stuck = h->d_stuck;
-    q.base.out_u0 = h->d_u0;
-    q.base.status = h->d_status; q.base.iters = h->d_iters;
-    q.base.dbg_inst = -1;
-    q.base.qlist = handed ? h->d_ast2 + 2 * h->cap_wrench : nullptr;
-    q.base.qcount = handed ? h->d_qctl : nullptr;
-    q.Hs = h->gHs; q.Ls = h->gLs; q.Eall = h->gEall;
-    q.tile_doubles = h->tile_doubles_gen;
-    q.e_doubles = h->e_doubles_gen;
-    q.npad_max = h->npad_gen;
-    q.warmG = d_warmG;
-    q.hullA = h->d_hullA;
-    q.hull_set = has_set ? h->d_hullset : nullptr;
-    q.hullb = h->d_hullb;
-    q.hull_rows = hull_rows;
-    q.termA = h->cfg.terminal_set ? h->d_term : nullptr;
-    q.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
-    q.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
-    q.eN = h->d_eN;
-    q.out_tau0 = h->d_tau0;
-    q.out_G = h->d_G;
-    const int grid = (int)std::min<int64_t>(B, h->grid_gen);
-    if (h->cfg.terminal_set)
-        hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<4, 1, 3>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, dcg, q);
-    else
-        hipLaunchKernelGGL((ftmpc::ftmpc_solve_f64_kernel<4, 1, 1>), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, dcg, q);
-    HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(pick_ricw64(h, hull_rows), dim3(grid), dim3(64), 0, s, dcg, q);
+    } else {      // the dense float64 kernel: the whole batch, or what kernel 11 handed over
+        Solve64Params q;
+        fill_wrench(h, q, B, hull_rows, has_set, d_warmG);
+        q.base.out_u0 = h->d_u0;
+        q.base.qlist = handed ? handover_list(h) : nullptr;
+        q.base.qcount = handed ? h->d_qctl.p : nullptr;
+        q.Hs = h->gHs; q.Ls = h->gLs; q.Eall = h->gEall;
+        q.tile_doubles = h->tile_doubles_gen;
+        q.e_doubles = h->e_doubles_gen;
+        q.npad_max = h->npad_gen;
+        const int grid = (int)std::min<int64_t>(B, h->grid_gen);
+        hipLaunchKernelGGL(pick_f64(h, true), dim3(grid), dim3(ftmpc::f64k::WG), 0, s, dcg, q);
     }
+    HIP_TRY(h, hipGetLastError());
     return FTMPC_OK;
 }
 
@@ -1603,31 +1501,13 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
 // QP half started it on the second stream; only the instances kernel 11 handed over remain (list mode).
 static int wrench_alloc_enqueue(ftmpc_handle* h, int64_t B, bool forked) {
     hipStream_t s = h->stream;
-    // second stage: min-norm allocation of the wrench the healthy thrusters have to produce
-    ftmpc::AllocParams ap;
-    ap.B = B;
-    ap.tau = h->d_taud;
-    ap.ub = h->d_ub;
-    ap.out_u = h->d_u0;
-    ap.status = h->d_ast2;
-    ap.iters = h->d_ast2 + B;
-    ap.max_iters = 50;
-    ap.tol = 1e-8;
-    auto allocate = [&](hipStream_t st, const int32_t* list, const int32_t* count) {
-        hipLaunchKernelGGL(ftmpc::ftmpc_healthy_wrench_kernel, dim3((unsigned)((B * 6 + 255) / 256)), dim3(256), 0, st, h->dc, B,
-                           (const double*)h->d_tau0, (const double*)h->d_stuck, h->d_taud, list, count);
-        ftmpc::AllocParams a = ap;
-        a.list = list;
-        a.count = count;
-        hipLaunchKernelGGL(ftmpc::ftmpc_allocate_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, h->dc, a);
-    };
     if (forked) {
         // the handed-over instances (a few dozen of a regular batch, one wave each: ~2 ms of latency, the device nearly idle) run
         // on kernel 13 while the second stream allocates everything kernel 11 certified; their own allocation follows in list mode
         HIP_TRY(h, hipStreamWaitEvent(s, h->ev_alloc, 0));
-        allocate(s, h->d_ast2 + 2 * h->cap_wrench, h->d_qctl);
+        wrench_allocate(h, B, s, handover_list(h), h->d_qctl);
     } else {
-        allocate(s, nullptr, nullptr);
+        wrench_allocate(h, B, s, nullptr, nullptr);
     }
     HIP_TRY(h, hipGetLastError());
     return FTMPC_OK;
@@ -1655,9 +1535,7 @@ int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const
     if (rc != FTMPC_OK) return rc;
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmG) HIP_TRY(h, hipMemcpyAsync(h->d_warmG, warmG, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
     if ((rc = wrench_enqueue(h, B, hull_rows, hull_set != nullptr, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride,
@@ -1692,42 +1570,20 @@ int ftmpc_last_handed_over(ftmpc_handle* h, int64_t* count) {
 // tests/test_gpu_wrench_sqp.py is 9.4e3; the default is ten times that, rounded.
 #define FTMPC_SQPW_PENALTY 1.0e5
 
-// the rows of the terminal set on the device (term_A | term_b), once per handle
-static int term_upload(ftmpc_handle* h) {
-    if (!h->cfg.terminal_set || h->d_term) return FTMPC_OK;
-    if (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS) return fail(h, FTMPC_ERR_ARG, "term_rows out of range");
-    int rc = grow(h, &h->d_term, (int64_t)h->cfg.term_rows * 10);
-    if (rc != FTMPC_OK) return rc;
-    std::vector<double> t((size_t)h->cfg.term_rows * 10);
-    std::memcpy(t.data(), h->cfg.term_A, (size_t)h->cfg.term_rows * 9 * sizeof(double));
-    std::memcpy(t.data() + (size_t)h->cfg.term_rows * 9, h->cfg.term_b, (size_t)h->cfg.term_rows * sizeof(double));
-    HIP_TRY(h, hipMemcpy(h->d_term, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-    return FTMPC_OK;
-}
-
 // workspace of the wrench SQP: iterates [B*N*6] x 2, per-instance doubles [6B] (merit | alpha | cost0 | cost | violation | spare),
 // flags [6B] (the layout of d_sqF), trial merits [B*backtracks], centre states [B*(N+1)*13] when wanted
 static int sqpw_grow(ftmpc_handle* h, int64_t B, int32_t backtracks, bool want_X) {
     const int N = h->cfg.N;
     int rc;
-    if (B > h->cap_swsqp) {
-        h->cap_swsqp = 0;   // (a failed growth must not leave a stale capacity)
-        if ((rc = grow(h, &h->d_swG, B * N * 6)) != FTMPC_OK || (rc = grow(h, &h->d_swT, B * N * 6)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_swJ, 6 * B)) != FTMPC_OK || (rc = grow(h, &h->d_swF, 6 * B)) != FTMPC_OK)
-            return rc;
-        h->cap_swsqp = B;
-    }
-    if (B * backtracks > h->cap_swJall) {
-        h->cap_swJall = 0;
-        if ((rc = grow(h, &h->d_swJall, B * backtracks)) != FTMPC_OK) return rc;
-        h->cap_swJall = B * backtracks;
-    }
-    if (want_X && B > h->cap_swX) {
-        h->cap_swX = 0;
-        if ((rc = grow(h, &h->d_swX, B * (N + 1) * 13)) != FTMPC_OK) return rc;
-        h->cap_swX = B;
-    }
-    return FTMPC_OK;
+    rc = ensure_group(h->cap_swsqp, B, [&] {
+        int r;
+        if ((r = h->d_swG.ensure(h, B * N * 6)) != FTMPC_OK || (r = h->d_swT.ensure(h, B * N * 6)) != FTMPC_OK ||
+            (r = h->d_swJ.ensure(h, 6 * B)) != FTMPC_OK)
+            return r;
+        return h->d_swF.ensure(h, 6 * B);
+    });
+    if (rc != FTMPC_OK || (rc = h->d_swJall.ensure(h, B * backtracks)) != FTMPC_OK) return rc;
+    return want_X ? h->d_swX.ensure(h, B * (N + 1) * 13) : FTMPC_OK;
 }
 
 static ftmpc::CostWrenchParams cost_wrench_params(const ftmpc_handle* h, int64_t B, const double* d_xref, int64_t xref_stride,
@@ -1739,9 +1595,7 @@ static ftmpc::CostWrenchParams cost_wrench_params(const ftmpc_handle* h, int64_t
     cw.uref = d_uref; cw.uref_stride = uref_stride;
     cw.G = nullptr;
     cw.tcost = h->d_tcost;
-    cw.termA = h->cfg.terminal_set ? h->d_term : nullptr;
-    cw.termb = h->cfg.terminal_set ? h->d_term + (int64_t)h->cfg.term_rows * 9 : nullptr;
-    cw.term_rows = h->cfg.terminal_set ? h->cfg.term_rows : 0;
+    fill_term(h, cw);
     cw.sigma = sigma;
     cw.out_merit = cw.out_cost = cw.out_tviol = cw.out_X = nullptr;
     return cw;
@@ -1756,9 +1610,8 @@ static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_
                         const double* d_uref, int64_t uref_stride, const double* d_warm, int32_t sqp_iters, int32_t backtracks, double tol,
                         double sigma, bool want_X, ftmpc::SqpState& S) {
     const int N = h->cfg.N;
-    int rc = sqpw_grow(h, B, backtracks, want_X);
+    int rc = sqpw_grow(h, B, backtracks, want_X);      // (the terminal rows: wrench_prepare)
     if (rc != FTMPC_OK) return rc;
-    if ((rc = term_upload(h)) != FTMPC_OK) return rc;
     hipStream_t s = h->stream;
     S.B = B; S.N = N; S.NT = 6;
     S.ub = nullptr;
@@ -1879,9 +1732,7 @@ int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, c
     if ((rc = check_strides(h, xref_stride, uref_stride, uref)) != FTMPC_OK) return rc;
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmG) HIP_TRY(h, hipMemcpyAsync(h->d_warmG, warmG, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
     ftmpc::SqpState S;
@@ -1911,15 +1762,14 @@ int ftmpc_allocate_batch(ftmpc_handle* h, int64_t B, const double* tau, const do
     if (B == 0) return FTMPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const int NT = h->cfg.NT;
-    if (B > h->cap_alloc) {
-        h->cap_alloc = 0;   // (a failed growth must not leave a stale capacity)
-        int rc;
-        if ((rc = grow(h, &h->d_atau, B * 6)) != FTMPC_OK || (rc = grow(h, &h->d_aub, B * NT)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_au, B * NT)) != FTMPC_OK || (rc = grow(h, &h->d_ast, B)) != FTMPC_OK ||
-            (rc = grow(h, &h->d_ait, B)) != FTMPC_OK)
-            return rc;
-        h->cap_alloc = B;
-    }
+    const int rc = ensure_group(h->cap_alloc, B, [&] {
+        int r;
+        if ((r = h->d_atau.ensure(h, B * 6)) != FTMPC_OK || (r = h->d_aub.ensure(h, B * NT)) != FTMPC_OK ||
+            (r = h->d_au.ensure(h, B * NT)) != FTMPC_OK || (r = h->d_ast.ensure(h, B)) != FTMPC_OK)
+            return r;
+        return h->d_ait.ensure(h, B);
+    });
+    if (rc != FTMPC_OK) return rc;
     hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_atau, tau, B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(h->d_aub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1993,9 +1843,7 @@ int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B, const double* x0, const dou
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ub, ub, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->d_stuck, stuck, B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmU) HIP_TRY(h, hipMemcpyAsync(h->d_warm, warmU, B * N * NT * sizeof(double), hipMemcpyHostToDevice, s));
     if (!h->use_f64) HIP_TRY(h, hipMemsetAsync(h->d_dbgv, 0, (3 * 256 + 4) * sizeof(float), s));
@@ -2198,48 +2046,26 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
     const int64_t ncol = (int64_t)T + N;   // windows t .. t+N for t < T
-    double *d_xr = nullptr, *d_ur = nullptr, *d_warmB = nullptr, *d_hist = nullptr, *d_xhist = nullptr;
-    int32_t *d_bad = nullptr, *d_abad = nullptr;
+    // (this call's own buffers: freed on every way out)
+    DevBuf<double> d_xr, d_ur, d_warmB, d_hist, d_xhist;
+    DevBuf<int32_t> d_bad, d_abad;
     // fault schedule (E > 0): events [on | de | hull_set], patterns [ub | stuck], hull offsets, the plant's own pattern [ub | stuck]
     const int E = fs ? fs->n_events : 0;
-    int32_t* d_fev = nullptr;
-    double *d_fpat = nullptr, *d_fhb = nullptr, *d_plant = nullptr;
-    auto cleanup = [&]() {
-        if (d_fev) (void)hipFree(d_fev);
-        if (d_fpat) (void)hipFree(d_fpat);
-        if (d_fhb) (void)hipFree(d_fhb);
-        if (d_plant) (void)hipFree(d_plant);
-        if (d_xhist) (void)hipFree(d_xhist);
-        if (d_abad) (void)hipFree(d_abad);
-        if (d_xr) (void)hipFree(d_xr);
-        if (d_ur) (void)hipFree(d_ur);
-        if (d_warmB) (void)hipFree(d_warmB);
-        if (d_hist) (void)hipFree(d_hist);
-        if (d_bad) (void)hipFree(d_bad);
-    };
-#define SIM_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e__ = (expr);                                                           \
-        if (e__ != hipSuccess) {                                                           \
-            cleanup();                                                                     \
-            return fail(h, FTMPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-        }                                                                                  \
-    } while (0)
-    SIM_TRY(hipMalloc(&d_xr, (size_t)ncol * 9 * sizeof(double)));
-    if (uref_traj) SIM_TRY(hipMalloc(&d_ur, (size_t)ncol * 6 * sizeof(double)));
-    if (!wl) SIM_TRY(hipMalloc(&d_warmB, (size_t)B * N * NT * sizeof(double)));
+    DevBuf<int32_t> d_fev;
+    DevBuf<double> d_fpat, d_fhb, d_plant;
+    HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
+    if (uref_traj) HIP_TRY(h, hipMalloc(&d_ur.p, (size_t)ncol * 6 * sizeof(double)));
+    if (!wl) HIP_TRY(h, hipMalloc(&d_warmB.p, (size_t)B * N * NT * sizeof(double)));
     if (wl && wl->alloc_failed) {
-        SIM_TRY(hipMalloc(&d_abad, (size_t)T * sizeof(int32_t)));
-        SIM_TRY(hipMemsetAsync(d_abad, 0, (size_t)T * sizeof(int32_t), s));
+        HIP_TRY(h, hipMalloc(&d_abad.p, (size_t)T * sizeof(int32_t)));
+        HIP_TRY(h, hipMemsetAsync(d_abad, 0, (size_t)T * sizeof(int32_t), s));
     }
-    if (u_hist) SIM_TRY(hipMalloc(&d_hist, (size_t)T * B * NT * sizeof(double)));
-    SIM_TRY(hipMalloc(&d_bad, (size_t)T * sizeof(int32_t)));
-    SIM_TRY(hipMemsetAsync(d_bad, 0, (size_t)T * sizeof(int32_t), s));
-    SIM_TRY(hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (uref_traj) SIM_TRY(hipMemcpyAsync(d_ur, uref_traj, (size_t)ncol * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-    SIM_TRY(hipMemcpyAsync(h->d_x0, x, (size_t)B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-    SIM_TRY(hipMemcpyAsync(h->d_ub, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-    SIM_TRY(hipMemcpyAsync(h->d_stuck, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    if (u_hist) HIP_TRY(h, hipMalloc(&d_hist.p, (size_t)T * B * NT * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&d_bad.p, (size_t)T * sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetAsync(d_bad, 0, (size_t)T * sizeof(int32_t), s));
+    HIP_TRY(h, hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (uref_traj) HIP_TRY(h, hipMemcpyAsync(d_ur, uref_traj, (size_t)ncol * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = stage_inputs(h, B, x, ub, stuck)) != FTMPC_OK) return rc;
     ftmpc::SimParams sp;
     sp.B = B;
     sp.x = h->d_x0;
@@ -2252,7 +2078,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     sp.status = h->d_status;
     sp.bad_count = d_bad;
     if (x_hist) {
-        SIM_TRY(hipMalloc(&d_xhist, (size_t)T * B * 13 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_xhist.p, (size_t)T * B * 13 * sizeof(double)));
         sp.x_hist = d_xhist;
     }
     const int64_t nw = B * (int64_t)N * NT;
@@ -2269,17 +2095,17 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             if (ev[i] >= 0 && ev[i] < T) ev_step[ev[i]] = 1;
             if (ev[i] >= 0 && ev[BE + i] < T) ev_step[ev[BE + i]] = 1;
         }
-        SIM_TRY(hipMalloc(&d_fev, ev.size() * sizeof(int32_t)));
-        SIM_TRY(hipMalloc(&d_fpat, (size_t)BE * NT * 2 * sizeof(double)));
-        SIM_TRY(hipMalloc(&d_plant, (size_t)B * NT * 2 * sizeof(double)));
-        SIM_TRY(hipMemcpyAsync(d_fev, ev.data(), ev.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        SIM_TRY(hipMemcpyAsync(d_fpat, fs->ub, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        SIM_TRY(hipMemcpyAsync(d_fpat + BE * NT, fs->stuck, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        SIM_TRY(hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        SIM_TRY(hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMalloc(&d_fev.p, ev.size() * sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc(&d_fpat.p, (size_t)BE * NT * 2 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_plant.p, (size_t)B * NT * 2 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_fev, ev.data(), ev.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_fpat, fs->ub, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_fpat + BE * NT, fs->stuck, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
         if (wl) {
-            SIM_TRY(hipMalloc(&d_fhb, (size_t)BE * wl->hull_rows * sizeof(double)));
-            SIM_TRY(hipMemcpyAsync(d_fhb, fs->hull_b, (size_t)BE * wl->hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMalloc(&d_fhb.p, (size_t)BE * wl->hull_rows * sizeof(double)));
+            HIP_TRY(h, hipMemcpyAsync(d_fhb, fs->hull_b, (size_t)BE * wl->hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
         }
         fe.B = B;
         fe.E = E;
@@ -2291,13 +2117,13 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         fe.plant_stuck = d_plant + B * NT;
         fe.ub = h->d_ub;
         fe.stuck = h->d_stuck;
-        fe.warmU = wl ? nullptr : d_warmB;
+        fe.warmU = wl ? nullptr : d_warmB.p;
         if (wl) {
             fe.warmG = h->d_warmG;
             fe.hullA = h->d_hullA;
             fe.ev_hullset = fs->hull_set ? d_fev + 2 * BE : nullptr;
             fe.ev_hullb = d_fhb;
-            fe.hullset = wl->has_set ? h->d_hullset : nullptr;
+            fe.hullset = wl->has_set ? h->d_hullset.p : nullptr;
             fe.hullb = h->d_hullb;
             fe.hull_rows = wl->hull_rows;
         }
@@ -2309,7 +2135,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             fe.t = t;
             fe.repair = t > 0;
             hipLaunchKernelGGL(ftmpc::ftmpc_fault_event_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, fe);
-            SIM_TRY(hipGetLastError());
+            HIP_TRY(h, hipGetLastError());
             // the work lists follow the new patterns: no small grid for a list that was empty the step before
             h->qcnt_valid = false;
             h->qcnt_pending = false;
@@ -2320,7 +2146,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
             ftmpc::SqpState S;
             rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
-                              t > 0 ? h->d_warmG : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
+                              t > 0 ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
             if (rc == FTMPC_OK) {
                 Gfin = S.U;
                 sp.status = S.status;
@@ -2331,28 +2157,25 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         } else if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
             ftmpc::SqpState S;
             double* J0 = nullptr;
-            rc = sqp_enqueue(h, B, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0, t > 0 ? d_warmB : nullptr, sqp_iters,
+            rc = sqp_enqueue(h, B, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0, t > 0 ? d_warmB.p : nullptr, sqp_iters,
                              backtracks, tol, S, &J0);
             if (rc == FTMPC_OK) {
                 Ufin = S.U;
                 sp.status = S.status;
-                SIM_TRY(hipMemcpy2DAsync(h->d_u0, NT * sizeof(double), S.U, (size_t)N * NT * sizeof(double), NT * sizeof(double), (size_t)B,
+                HIP_TRY(h, hipMemcpy2DAsync(h->d_u0, NT * sizeof(double), S.U, (size_t)N * NT * sizeof(double), NT * sizeof(double), (size_t)B,
                                          hipMemcpyDeviceToDevice, s));
             }
         } else if (wl) {         // the reference's two-stage structure: wrench MPC with the hull rows, then allocation
             rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
-                                t > 0 ? h->d_warmG : nullptr);
+                                t > 0 ? h->d_warmG.p : nullptr);
             if (rc == FTMPC_OK && d_abad)
                 hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
                                    d_abad + t);
         } else {
             rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
-                         t > 0 ? d_warmB : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
+                         t > 0 ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
         }
-        if (rc != FTMPC_OK) {
-            cleanup();
-            return rc;
-        }
+        if (rc != FTMPC_OK) return rc;
         sp.step = t;
         hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
         if (wl)     // wrench warm start: shifted by one stage, the last stage repeats
@@ -2360,16 +2183,14 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                                Gfin, h->d_warmG, 1);
         else
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, B, N, NT, Ufin, d_warmB, 0);
-        SIM_TRY(hipGetLastError());
+        HIP_TRY(h, hipGetLastError());
     }
-    SIM_TRY(hipMemcpyAsync(x, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (u_hist) SIM_TRY(hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (x_hist) SIM_TRY(hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (not_converged) SIM_TRY(hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (d_abad) SIM_TRY(hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SIM_TRY(hipStreamSynchronize(s));
-#undef SIM_TRY
-    cleanup();
+    HIP_TRY(h, hipMemcpyAsync(x, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (d_abad) HIP_TRY(h, hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return FTMPC_OK;
 }
 
@@ -2377,7 +2198,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
 /* diagnostic build only: copies the per-instance phase cycle totals (12 u64 per instance, first
  * `count` <= 4096 instances) of the last fp32 solve */
 int ftmpc_debug_read_stamps(ftmpc_handle* h, int64_t count, unsigned long long* out) {
-    const void* src = h ? (h->use_f64 ? (const void*)h->d_dbgH64 : (const void*)h->d_dbgH) : nullptr;
+    const void* src = h ? (h->use_f64 ? (const void*)h->d_dbgH64.p : (const void*)h->d_dbgH.p) : nullptr;
     if (!h || !out || count < 0 || count > 4096 || !src || (h->use_f64 && count > 512)) return FTMPC_ERR_ARG;
     HIP_TRY(h, hipDeviceSynchronize());
     HIP_TRY(h, hipMemcpy(out, src, (size_t)count * 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -4,7 +4,9 @@
   * ftmpc_solve_wrench_batch refuses a hull table number outside [0, n_sets) instead of reading past the tables on the device;
   * the shipped code object is hipcc's assembly with the asm-side wait states LOWERED by scripts/check_hazards.py
     (csrc/Makefile); `make plain` keeps them as written.  Both builds must give the same bits on every kernel family: a
-    wrong entry of the wait-state table would show as slightly different numbers, nowhere else.
+    wrong entry of the wait-state table would show as slightly different numbers, nowhere else;
+  * device buffers whose layout depends on their CAPACITY (kernel 11's hand-over list behind the allocation status, the per-wave
+    slots of kernel 13) give the bits of a fresh handle when the handle is reused at a smaller batch and through other entries.
 """
 import ctypes as C
 import os
@@ -56,6 +58,67 @@ def test_wrench_entry_refuses_a_hull_table_number_out_of_range(gpu_mpc_factory):
         assert e.value.code == -1 and "hull_set[3]" in str(e.value)
     again = mpc.solve_wrench(x0, ub, stuck, xr, hull=hull)
     assert np.array_equal(good["u0"], again["u0"])
+
+
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        if a[k] is not None:
+            assert np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"), k
+
+
+def test_reused_handle_gives_the_bits_of_a_fresh_one_two_stage_fp32(gpu_mpc_factory):
+    """One fp32 handle with the terminal set (kernel 11 hands over to kernel 13: the list sits at 2 * capacity of the status
+    buffer, the producer and both consumers must agree on it) through 512 instances, a 64-instance slice, the thruster form, the
+    wrench SQP and 512 again: every result is bitwise the one a fresh handle gives for that call (for the two 512-instance calls
+    the first IS the fresh handle's).  Vehicles with the tracking error on the boundary of the set: hull and terminal rows active
+    together, which is what kernel 11 hands over -- asserted for the slice."""
+    sys.path.insert(0, str(Path(__file__).parent))
+    from test_gpu_wrench import _near_terminal_set
+    from ft_mpc_amd.controllers.tools.terminal_ingredients import load_terminal
+    N, NT, B, lo = 15, 16, 512, 128
+    term = load_terminal().term_set
+    x0, ub, stuck, xref = _near_terminal_set(B, N, NT, 2, 9100, term.A, term.b.reshape(-1), scale=1.0)
+    xr = np.ascontiguousarray(xref.reshape(-1, order="F"))
+    sl = slice(lo, lo + 64)
+    kw = dict(N=N, NT=NT, dtype="f32", max_iters=60, terminal_set=term)
+    calls = [
+        lambda m: m.solve_wrench(x0, ub, stuck, xr, return_G=True),
+        lambda m: m.solve_wrench(x0[sl], ub[sl], stuck[sl], xr, return_G=True),
+        lambda m: m.solve(x0[sl], ub[sl], stuck[sl], xr, return_U=True),
+        lambda m: m.solve_sqp_wrench(x0[sl], ub[sl], stuck[sl], xr, sqp_iters=2),
+        lambda m: m.solve_wrench(x0, ub, stuck, xr, return_G=True),
+    ]
+    mpc = gpu_mpc_factory(**kw)
+    got, handed = [], []
+    for call in calls:
+        got.append(call(mpc))
+        handed.append(mpc.last_handed_over())
+    print("handed over:", handed)
+    assert handed[1] >= 1 and handed[0] >= handed[1]      # (the slice is part of the batch)
+    assert (got[1]["status"] == 0).any()
+    _same(got[4], got[0])
+    for i in (1, 2, 3):
+        _same(got[i], calls[i](gpu_mpc_factory(**kw)))
+
+
+def test_reused_handle_gives_the_bits_of_a_fresh_one_state_bounds_f64(gpu_mpc_factory):
+    """Kernel 13's state-bound instantiation (<6, false, true>: its per-wave slot has a tail of its own) at 128 instances, then 32."""
+    sys.path.insert(0, str(Path(__file__).parent))
+    import wrench_state_rows as ws
+    from oracle import qp_oracle as qo
+    N, NT, B = 15, 16, 128
+    xlb, xub = ws.bounds()
+    kw = dict(N=N, NT=NT, dtype="f64", max_iters=60, xlb=xlb, xub=xub)
+    x0, ub, stuck, xref = qo.make_batch(B, N, NT, 2, 5115)
+    xr = np.ascontiguousarray(xref.reshape(-1, order="F"))
+    mpc = gpu_mpc_factory(**kw)
+    big = mpc.solve_wrench(x0, ub, stuck, xr, return_G=True)
+    small = mpc.solve_wrench(x0[96:], ub[96:], stuck[96:], xr, return_G=True)
+    assert (small["status"] == 0).any()
+    _same(small, gpu_mpc_factory(**kw).solve_wrench(x0[96:], ub[96:], stuck[96:], xr, return_G=True))
+    for k in big:
+        assert np.array_equal(big[k][96:], small[k], equal_nan=big[k].dtype.kind == "f"), k
 
 
 _AB_CASES = [  # (name, N, NT, faults, B, dtype, kernel_select): one batch per kernel family of the library
