@@ -122,7 +122,8 @@ struct ftmpc_handle {
     int grid_wg = 0;
     int64_t wg_slot_words = 0;
     // float64 through the wrench-space form (kernel 9): 6 N <= 256, N * NT <= 768, ten or more thrusters
-    bool tset_thruster = true;         // the thruster form with the terminal set fits the dense float64 kernel's general-constraint mode
+    bool tset_thruster = true;         // the thruster form with the terminal set is served: dense float64 kernel (n <= 256) or kernel 12 (N <= 40)
+    bool tset_ric = false;             // ... by kernel 12's terminal-set instantiation (n > 256, or kernel_select = FTMPC_KERNEL_RICCATI)
     bool sbounds = false;              // state bounds: the thruster-space solve runs on kernel 12's state-bound instantiation
     DevBuf<double> d_cbar;             // [B*N*13] linearisation trajectory (state bounds only)
     bool use_ric64 = false;            // kernel 12: float64, Newton systems by the Riccati recursion, one wave per instance
@@ -358,6 +359,9 @@ WgKernel pick_ws32(const ftmpc_handle* h) { return h->ws_nb == 6 ? ftmpc::ftmpc_
 F32Kernel pick_wsw32(const ftmpc_handle* h) { return h->ws_nb == 6 ? ftmpc::ftmpc_solve_wsw32_kernel<6> : ftmpc::ftmpc_solve_wsw32_kernel<8>; }
 Ws64Kernel pick_ws64(const ftmpc_handle* h) { return h->ws64_nvt == 1 ? ftmpc::ftmpc_solve_ws64_kernel<1> : ftmpc::ftmpc_solve_ws64_kernel<3>; }
 Ric64Kernel pick_ric64(const ftmpc_handle* h) {
+    if (h->tset_ric && h->ric_nv == 4) return ftmpc::ftmpc_solve_ric64_kernel<4, false, true>;
+    if (h->tset_ric && h->ric_nv == 6) return ftmpc::ftmpc_solve_ric64_kernel<6, false, true>;
+    if (h->tset_ric) return ftmpc::ftmpc_solve_ric64_kernel<10, false, true>;
     if (h->sbounds && h->ric_nv == 6) return ftmpc::ftmpc_solve_ric64_kernel<6, true>;
     if (h->sbounds) return ftmpc::ftmpc_solve_ric64_kernel<10, true>;
     if (h->ric_nv == 4) return ftmpc::ftmpc_solve_ric64_kernel<4>;
@@ -367,7 +371,7 @@ Ric64Kernel pick_ric64(const ftmpc_handle* h) {
 // the dense float64 kernel; wrench: the generalized-force formulation (6 N variables, hull rows) instead of the thruster form
 F64Kernel pick_f64(const ftmpc_handle* h, bool wrench) {
     if (wrench) return h->cfg.terminal_set ? ftmpc::ftmpc_solve_f64_kernel<4, 1, 3> : ftmpc::ftmpc_solve_f64_kernel<4, 1, 1>;
-    if (h->tset) return ftmpc::ftmpc_solve_f64_kernel<4, 1, 2>;
+    if (h->tset && !h->tset_ric) return ftmpc::ftmpc_solve_f64_kernel<4, 1, 2>;      // (tset_ric: the dense kernel only dumps the box QP)
     if (h->npad_max <= 256) return ftmpc::ftmpc_solve_f64_kernel<4, 1>;
     if (h->npad_max <= 640) return ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, 3>;
     return ftmpc::ftmpc_solve_f64_kernel<ftmpc::f64k::RPF, ftmpc::f64k::NVT_MAX>;
@@ -444,6 +448,12 @@ void fill_wrench(const ftmpc_handle* h, P& q, int64_t B, int32_t hull_rows, bool
 }
 
 int tiles_of(int nb) { return nb * (nb + 1) / 2; }
+// per-workgroup slots of the dense float64 kernel (thruster form)
+int dense_ensure(ftmpc_handle* h) {
+    int rc;
+    if ((rc = h->Hs.ensure(h, h->grid64 * h->tile_doubles)) != FTMPC_OK || (rc = h->Ls.ensure(h, h->grid64 * h->tile_doubles)) != FTMPC_OK) return rc;
+    return h->Eall.ensure(h, h->grid64 * h->e_doubles);
+}
 // per-workgroup global slot of the fp32 kernels (layout: ftmpc_common.h): sweep scratch, then the Hessian tiles
 // Linearisation: full records per wave for large batches; below `lin_split_max` instances the direction-split grid
 // (13 blocks per 64 instances, ftmpc_linearize.hip), which fills the device from a few hundred instances on.
@@ -465,7 +475,8 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
             const double* warmU, double* out_u0, double* out_U, int32_t* status, int32_t* iters,
             hipStream_t s, int64_t dbg_inst) {
     if (h->tset && !h->tset_thruster)
-        return fail(h, FTMPC_ERR_ARG, "the thruster form with the terminal set needs N * NT <= 256 (ftmpc_solve_wrench_batch, the reference's two-stage form, has no such limit)");
+        return fail(h, FTMPC_ERR_ARG, "the thruster form with the terminal set needs N <= 40 (the Riccati kernel), and N * NT <= 256 with kernel_select = FTMPC_KERNEL_DENSE "
+                                      "(ftmpc_solve_wrench_batch, the reference's two-stage form, also serves N > 40)");
     if (B <= 0) return FTMPC_OK;
     LinParams lp;
     lp.B = B;
@@ -525,10 +536,12 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
             w.slot = h->ric_slot;
             w.slot_doubles = h->ric_slot_doubles;
             fill_state_bounds(h, w);
+            fill_term(h, w);
+            w.eN = h->d_eN;
             // with state bounds the iteration stops at mu 1e-10 unless the caller asked otherwise, as the other general-constraint
             // modes do: the barrier weight of an active state row enters the Riccati recursion's state weight (see the kernel)
             DeviceConsts dcr = h->dc;
-            if (h->sbounds && !(h->cfg.mu_stop > 0)) dcr.mu_stop = 1e-10;
+            if (h->sbounds && !(h->cfg.mu_stop > 0)) dcr.mu_stop = 1e-10;      // (terminal set: build_consts has done the same)
             const int grid = (int)std::min<int64_t>(B, h->grid_ric);
             rc = profiled(h, 6, s, [&] { hipLaunchKernelGGL(pick_ric64(h), dim3(grid), dim3(64), 0, s, dcr, w); });
         } else if (h->use_ws64) {
@@ -610,7 +623,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 450; }
+int32_t ftmpc_version(void) { return 451; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -693,13 +706,18 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
         return fail(nullptr, FTMPC_ERR_NODEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
     if (cfg->dtype != FTMPC_DTYPE_F32 && cfg->dtype != FTMPC_DTYPE_F64)
         return fail(nullptr, FTMPC_ERR_ARG, "dtype must be FTMPC_DTYPE_F32 or FTMPC_DTYPE_F64");
-    if (cfg->kernel_select != FTMPC_KERNEL_AUTO && cfg->kernel_select != FTMPC_KERNEL_DENSE && cfg->kernel_select != FTMPC_KERNEL_WORKGROUP)
-        return fail(nullptr, FTMPC_ERR_ARG, "kernel_select must be FTMPC_KERNEL_AUTO, FTMPC_KERNEL_DENSE or FTMPC_KERNEL_WORKGROUP");
+    if (cfg->kernel_select != FTMPC_KERNEL_AUTO && cfg->kernel_select != FTMPC_KERNEL_DENSE && cfg->kernel_select != FTMPC_KERNEL_WORKGROUP &&
+        cfg->kernel_select != FTMPC_KERNEL_RICCATI)
+        return fail(nullptr, FTMPC_ERR_ARG, "kernel_select must be FTMPC_KERNEL_AUTO, FTMPC_KERNEL_DENSE, FTMPC_KERNEL_WORKGROUP or FTMPC_KERNEL_RICCATI");
     if (cfg->stage_chunks < 0 || cfg->stage_chunks > ftmpc_handle::MAX_CHUNKS)
         return fail(nullptr, FTMPC_ERR_ARG, "stage_chunks out of range 0..8");
     ftmpc_handle* h = new (std::nothrow) ftmpc_handle();
     if (!h) return fail(nullptr, FTMPC_ERR_ALLOC, "out of host memory");
     h->cfg = *cfg;
+    // FTMPC_KERNEL_RICCATI: the Riccati kernel where the terminal-set thruster form would take the dense one (N <= 40); routed as AUTO
+    // everywhere else (every other test of kernel_select asks "is it DENSE" or "is it WORKGROUP")
+    const bool ask_ric = cfg->kernel_select == FTMPC_KERNEL_RICCATI;
+    const bool sel_auto = cfg->kernel_select == FTMPC_KERNEL_AUTO || ask_ric;
     std::string why;
     int rc = build_consts(*cfg, h->dc, why);
     if (rc != FTMPC_OK) {
@@ -749,7 +767,7 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
                 delete h;
                 return fail(nullptr, FTMPC_ERR_ARG, "state_bounds: xlb[i] < xub[i] is required for every component (use +-FTMPC_NO_BOUND for none)");
             }
-    h->use_ric64 = h->use_f64 && cfg->terminal_set == 0 && (cfg->kernel_select == FTMPC_KERNEL_AUTO || h->sbounds) && cfg->N <= 40;
+    h->use_ric64 = h->use_f64 && cfg->terminal_set == 0 && (sel_auto || h->sbounds) && cfg->N <= 40;
     h->ric_nv = (cfg->N <= 16 && !h->sbounds) ? 4 : (cfg->N <= 24 ? 6 : 10);
     if (h->use_ric64) h->use_ws64 = false;
     h->tset = cfg->terminal_set != 0;
@@ -758,8 +776,16 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
             delete h;
             return fail(nullptr, FTMPC_ERR_ARG, "term_rows out of range 1..80");
         }
-        h->tset_thruster = 16 * h->nb_max <= 256;      // (the THRUSTER form with terminal rows lives on the dense float64 kernel's n <= 256 mode; the
-                                                       //  two-stage form -- ftmpc_solve_wrench_batch -- has no such limit: kernel 13)
+        // the THRUSTER form with terminal rows: the dense float64 kernel's n <= 256 mode where it fits (and kernel_select does not ask for
+        // the Riccati kernel), kernel 12's terminal-set instantiation beyond that up to N = 40; FTMPC_KERNEL_DENSE keeps the dense kernel
+        // and its limit.  (The two-stage form -- ftmpc_solve_wrench_batch -- has no such limit: kernel 13.)
+        const bool dense_fits = 16 * h->nb_max <= 256;
+        h->tset_ric = cfg->N <= 40 && sel_auto && (ask_ric || !dense_fits);
+        h->tset_thruster = dense_fits || h->tset_ric;
+        if (h->tset_ric) {
+            h->use_ric64 = true;
+            h->ric_nv = cfg->N <= 16 ? 4 : (cfg->N <= 24 ? 6 : 10);
+        }
     }
     h->npad_max = 16 * h->nb_max;
     h->device = cfg->device_id;
@@ -803,19 +829,21 @@ int ftmpc_create(const ftmpc_config* cfg, ftmpc_handle** out) {
     // persistent grids: resident workgroups per CU from the occupancy query (LDS-bound)
     for (int v = 0; v < 3; ++v) h->grid[v] = h->num_cu * std::max(1, blocks_per_cu(pick_f32(v), 64));
     // (the general-constraint instantiations hold ~50 KiB of LDS and one workgroup per CU)
-    const int per64 = h->tset ? 1 : std::min(2, std::max(1, blocks_per_cu(pick_f64(h, false), ftmpc::f64k::WG)));
+    const int per64 = (h->tset && !h->tset_ric) ? 1 : std::min(2, std::max(1, blocks_per_cu(pick_f64(h, false), ftmpc::f64k::WG)));
     h->grid64 = h->num_cu * per64;
     h->tile_doubles = (int64_t)tiles_of(h->nb_max) * 256;
     h->e_doubles = (int64_t)(cfg->N + 2) * 9 * h->npad_max;     // + raw terminal rows GN and the terminal-set panel
     bool bad = false;
     if (h->use_f64) {
-        bad = h->Hs.ensure(h, h->grid64 * h->tile_doubles) != FTMPC_OK || h->Ls.ensure(h, h->grid64 * h->tile_doubles) != FTMPC_OK ||
-              h->Eall.ensure(h, h->grid64 * h->e_doubles) != FTMPC_OK ||
+        // (a terminal-set handle beyond the dense kernel's n <= 256 -- served by kernel 12 or not at all -- never solves on the dense
+        // slots: ftmpc_debug_build_qp allocates them when it is first called)
+        const bool dense_slots = !h->tset || 16 * h->nb_max <= 256;
+        bad = (dense_slots && dense_ensure(h) != FTMPC_OK) ||
               h->d_dbgH64.ensure(h, (int64_t)h->npad_max * h->npad_max) != FTMPC_OK ||
               h->d_dbgv64.ensure(h, 3 * (int64_t)h->npad_max + 4) != FTMPC_OK;
         if (!bad && h->use_ric64) {
             h->grid_ric = h->num_cu * std::max(1, blocks_per_cu(pick_ric64(h), 64));
-            h->ric_slot_doubles = ftmpc::rick::slot_doubles(cfg->N);
+            h->ric_slot_doubles = h->tset_ric ? ftmpc::rick::slot_doubles_ts(cfg->N) : ftmpc::rick::slot_doubles(cfg->N);
             bad = h->ric_slot.ensure(h, (int64_t)h->grid_ric * h->ric_slot_doubles) != FTMPC_OK;
         }
         if (!bad && h->use_ws64) {
@@ -1211,7 +1239,7 @@ static int sqp_enqueue(ftmpc_handle* h, int64_t B, const double* d_xref, int64_t
         mix(&h->dc, sizeof(h->dc));
         const void* ptrs[2] = {h->d_tcost, h->rec};
         mix(ptrs, sizeof(ptrs));
-        const int sw[8] = {h->use_f64, h->use_wg, h->use_ric64, h->nb_max, h->tset, h->sbounds, h->cfg.kernel_select, (int)h->lin_split_max};
+        const int sw[9] = {h->use_f64, h->use_wg, h->use_ric64, h->nb_max, h->tset, h->sbounds, h->cfg.kernel_select, (int)h->lin_split_max, h->tset_ric};
         mix(sw, sizeof(sw));
         key.consts = f;
     }
@@ -1827,7 +1855,7 @@ static const char* const k_kernel_names[FTMPC_KERNEL_SLOTS] = {"ftmpc_linearize_
 const char* ftmpc_kernel_name(int32_t slot) { return (slot >= 0 && slot < FTMPC_KERNEL_SLOTS) ? k_kernel_names[slot] : ""; }
 
 const char* ftmpc_routed_kernel_name(const ftmpc_handle* h, int32_t slot) {
-    if (h && slot == 6) return h->use_ric64 ? "ftmpc_solve_ric64_kernel" : "ftmpc_solve_ws64_kernel";
+    if (h && slot == 6) return h->use_ric64 ? "ftmpc_solve_ric64_kernel" : "ftmpc_solve_ws64_kernel";      // (kernel 12 also with the terminal set: tset_ric)
     if (h && slot == 5) return h->use_wsw ? "ftmpc_solve_wsw32_kernel" : (h->use_ws ? "ftmpc_solve_ws32_kernel" : "ftmpc_solve_wg32_kernel<15>");
     return ftmpc_kernel_name(slot);
 }
@@ -1850,6 +1878,7 @@ int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B, const double* x0, const dou
     if (h->use_ws && h->nb_max > 15)
         return fail(h, FTMPC_ERR_ARG, "the QP dump needs N * NT <= 240 on the fp32 path (create the handle with dtype FTMPC_DTYPE_F64 for larger shapes)");
     const bool ws64_was = h->use_ws64, ric_was = h->use_ric64;      // (the dump comes from the dense float64 kernel: the only one that forms H)
+    if (h->use_f64 && (rc = dense_ensure(h)) != FTMPC_OK) return rc;     // (not allocated by ftmpc_create where no solve uses them)
     h->use_ws64 = false;
     h->use_ric64 = false;
     const bool wsw_was = h->use_wsw;

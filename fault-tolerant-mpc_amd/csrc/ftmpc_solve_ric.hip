@@ -90,6 +90,12 @@ __device__ __forceinline__ double mvt_part(const f64x4& M, const f64x4& xr) { re
 constexpr int NSTATE = 20;      // (+ six: the interior-point iterate kept while the early polish runs)
 __host__ __device__ constexpr int64_t state_off(int N) { return (int64_t)N * 2 * 256; }
 __host__ __device__ constexpr int64_t slot_doubles(int N) { return state_off(N) + (int64_t)NSTATE * ((N + 3) / 4) * 64; }
+// terminal-set rows (template TS; row i = lane + 64 j, j < 2), a tail after everything else so that the layout above does not move:
+// s | z | carried primal residual | ds_a | dz_a | active | penalty, then s | z | residual of the iterate kept while the polish runs
+constexpr int NTROW = 10;
+constexpr int MTP = 80;         // FTMPC_MAX_TERM_ROWS
+__host__ __device__ constexpr int64_t trow_off(int N) { return slot_doubles(N); }
+__host__ __device__ constexpr int64_t slot_doubles_ts(int N) { return trow_off(N) + (int64_t)NTROW * 2 * 64; }
 }  // namespace rick
 
 struct SolveRicParams {
@@ -100,6 +106,11 @@ struct SolveRicParams {
     // stages j = 1 .. N-1; |bound| >= 1e299 = no row.  cbar: [B*N*13] the linearisation trajectory c_1 .. c_N (ftmpc_linearize.hip)
     double xlb[13], xub[13];
     const double* cbar;
+    // terminal set (template TS): rows term_A (e_N + dx_N) <= term_b on the terminal tracking error (spiraling_mpc.py:198-202)
+    const double* termA;       // [term_rows*9]
+    const double* termb;       // [term_rows]
+    const double* eN;          // [B*9] terminal tracking error at the linearisation point (ftmpc_linearize.hip)
+    int32_t term_rows;         // <= rick::MTP
 };
 
 #ifndef FTMPC_RIC_WAVES
@@ -115,10 +126,22 @@ struct SolveRicParams {
 // work.  The objective gradient is carried as  grad + Gbar' psi  (grad per thruster variable as before, psi_j per state of stage
 // j, never condensed: the sweeps apply Gbar' implicitly), and both parts follow the step through the Newton identity:
 //     grad += alpha (rhs_u - Sigma dd),     psi_j += alpha (-q_j - Sx_j dx_j).
-template <int NV, bool SB = false>
+// TS: the TERMINAL SET  term_A (e_N + dx_N) <= term_b  (kernel 13's treatment in this formulation).  Its rows act on the terminal
+// state only: the 9 x 9 block m9 = A_T' diag(z / s) A_T on the terminal weight S_N = 2 P of the factor sweep -- one tile built once
+// per iteration -- and a 9-vector q_N on the terminal state-linear term, routed as SB routes q_j; psi_N (nine entries) carries the
+// state-space part of the objective gradient.  The rows need not hold at the start point: s = max(residual, 0.1) and a carried primal
+// residual that every step shrinks by (1 - alpha_p).  The polish takes the terminal rows with z > s into its active set beside the
+// bounds, with the penalty 1e6 hs / |A_T,i GN|^2 (GN GN' from X_{k+1} = A X_k A' + Bt Bt' in the start point's forward sweep).
+template <int NV, bool SB = false, bool TS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_RIC_WAVES, FTMPC_RIC_WAVES))) ftmpc_solve_ric64_kernel(const DeviceConsts C, const SolveRicParams Q) {
     using namespace rick;
+    static_assert(!(TS && SB), "state bounds together with the terminal set are not built");
     constexpr int NS = 4 * NV;
+    __shared__ double s_tA[TS ? MTP * 9 : 2];                            // rows of term_A
+    __shared__ __attribute__((aligned(32))) double m9[TS ? 81 : 2];      // A_T' W A_T
+    __shared__ __attribute__((aligned(32))) double qT[TS ? 16 : 4];      // terminal state-linear term q_N (position 4 q + rr = element q + 4 rr)
+    __shared__ double x9[TS ? 81 : 2];                                   // (GN GN')[0:9, 0:9]: the norms |A_T,i GN|^2 of the polish's penalties
+    __shared__ double psN[TS ? 32 : 2];                                  // psi_N | the one of the iterate kept while the polish runs (at 16)
     __shared__ __attribute__((aligned(32))) double qxv[SB ? NS * 16 : 4];   // per stage the state-linear term q_j of the Newton problem (position 4 q + rr = element q + 4 rr)
     const SolveParams& P = Q.base;
     __shared__ __attribute__((aligned(32))) double recbuf[2][REC_STRIDE];
@@ -238,6 +261,93 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         // state-bound rows of this lane: (stage 4 v + lq in 1 .. N-1, component li < 13), upper and lower
         const bool xhu = SB && li < 13 && Q.xub[li < 13 ? li : 0] < 1e299, xhl = SB && li < 13 && Q.xlb[li < 13 ? li : 0] > -1e299;
         auto xrow = [&](int v) { return li < 13 && 4 * v + lq >= 1 && 4 * v + lq <= N - 1; };
+        // ---- terminal-set rows (TS): row lane + 64 j, its state in the tail of the slot ----
+        const int MT = TS ? Q.term_rows : 0;
+        [[maybe_unused]] double* const tst = slot + trow_off(N);
+        [[maybe_unused]] auto tref = [&](int arr, int j) -> double& { return tst[(int64_t)(arr * 2 + j) * 64 + lane]; };
+        enum { T_S = 0, T_Z = 1, T_RP = 2, T_DSA = 3, T_DZA = 4, T_ACT = 5, T_W = 6, T_KS = 7, T_KZ = 8, T_KRP = 9 };
+        [[maybe_unused]] auto trv = [&](int j) { return TS && lane + 64 * j < MT; };
+        if constexpr (TS) {
+            for (int i = lane; i < MTP * 9; i += 64) s_tA[i] = (i < MT * 9) ? Q.termA[i] : 0.0;
+            if (lane < 16) {
+                qT[lane] = 0.0;
+                psN[lane] = 0.0;
+            }
+            wave_lds_fence();
+        }
+        // A_T,i . x for a 9-vector in LDS (natural order)
+        [[maybe_unused]] auto term_dot = [&](int j, const double* x) -> double {
+            const double* a = s_tA + 9 * (trv(j) ? lane + 64 * j : 0);
+            double t = 0.0;
+#pragma unroll
+            for (int r = 0; r < 9; ++r) t += a[r] * x[r];
+            return t;
+        };
+        // m9 = A_T' diag(w) A_T for per-row weights
+        [[maybe_unused]] auto term_blocks = [&](auto wof) {
+            if constexpr (TS) {
+                double acc[45];
+#pragma unroll
+                for (int p = 0; p < 45; ++p) acc[p] = 0.0;
+                for (int j = 0; j < 2; ++j) {
+                    const double w = trv(j) ? wof(j) : 0.0;
+                    const double* a = s_tA + 9 * (trv(j) ? lane + 64 * j : 0);
+                    int p = 0;
+#pragma unroll
+                    for (int r1 = 0; r1 < 9; ++r1) {
+                        const double wa = w * a[r1];
+#pragma unroll
+                        for (int r2 = 0; r2 <= r1; ++r2) acc[p++] += wa * a[r2];
+                    }
+                }
+                wave_lds_fence();
+                int p = 0;
+#pragma unroll
+                for (int r1 = 0; r1 < 9; ++r1)
+#pragma unroll
+                    for (int r2 = 0; r2 <= r1; ++r2) {
+                        const double t = wave_red<DAdd>(acc[p++]);
+                        if (lane == 0) {
+                            m9[9 * r1 + r2] = t;
+                            m9[9 * r2 + r1] = t;
+                        }
+                    }
+                wave_lds_fence();
+            }
+        };
+        // q_N = psi_N + A_T' t for per-row values t (the Newton problem's convention: + q'x)
+        [[maybe_unused]] auto term_linear = [&](auto tof) {
+            if constexpr (TS) {
+                double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int j = 0; j < 2; ++j) {
+                    const double t = trv(j) ? tof(j) : 0.0;
+                    const double* a = s_tA + 9 * (trv(j) ? lane + 64 * j : 0);
+#pragma unroll
+                    for (int r = 0; r < 9; ++r) acc[r] += a[r] * t;
+                }
+                wave_lds_fence();
+#pragma unroll
+                for (int r = 0; r < 9; ++r) {
+                    const double t = wave_red<DAdd>(acc[r]);
+                    if (lane == 0) qT[v64pos(r)] = psN[r] + t;
+                }
+                wave_lds_fence();
+            }
+        };
+        // psi_N += alpha (-q_N - m9 dx_N) after a solve (dx_N: wst, stage N - 1): the terminal part of the Newton identity
+        [[maybe_unused]] auto psi_step = [&](double alpha) {
+            if constexpr (TS) {
+                wave_lds_fence();
+                if (lane < 9) {
+                    const double* x = wst + (N - 1) * 16;
+                    double t = qT[v64pos(lane)];
+#pragma unroll
+                    for (int c = 0; c < 9; ++c) t += m9[9 * lane + c] * x[c];
+                    psN[lane] -= alpha * t;
+                }
+                wave_lds_fence();
+            }
+        };
         // ---- stage record k (three 8-byte loads per lane) and, in the vector sweeps, the factors W_k, Y_k: requested TWO stages
         // ahead of their use into one of two register sets (a stage of a vector sweep is ~1.5 k cycles, a round trip to the
         // Infinity Cache / HBM under load more), committed to the LDS record buffer when their stage begins ----
@@ -312,6 +422,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 if constexpr (SB) {      // s = p_{k+1} + q_{k+1}
                     if (k + 1 <= N - 1) s += *reinterpret_cast<const f64x4*>(&qxv[(k + 1) * 16 + 4 * lq]);
                 }
+                if constexpr (TS) {      // s = q_N
+                    if (k + 1 == N) s += *reinterpret_cast<const f64x4*>(&qT[4 * lq]);
+                }
                 const double ru = quad_red<DAdd>(mvt_part(Bt, s)) - rvec[k * 16 + li];
                 const f64x4 w = mv(Wk, ru);
                 if (li == 0) *reinterpret_cast<f64x4*>(&wst[k * 16 + 4 * lq]) = w;
@@ -339,7 +452,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 if (lq == 0) rvec[k * 16 + li] = uc;
                 const f64x4 xn = mv2(A, xc, Bt, uc);
                 xc = row2col(xn, k & 1);
-                if constexpr (SB) {
+                if constexpr (SB || TS) {
                     if (lq == 0) wst[k * 16 + li] = xc;      // x_{k+1} of the solution, natural order (w_k has been consumed)
                 }
             };
@@ -365,11 +478,28 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             Pre p0, p1;
             // forward: dx_{k+1} = A dx_k + Bt d_k, kept in natural order in wst (stage k + 1 at slot k)
             double xc = 0.0;
+            [[maybe_unused]] f64x4 Xg = zero4;      // (TS) GN GN' by X_{k+1} = A X_k A' + Bt Bt'
+            [[maybe_unused]] auto transpose = [&](const f64x4& M) -> f64x4 {
+                wave_lds_fence();
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) tsc[(lq + 4 * rr) * 17 + li] = M[rr];
+                wave_lds_fence();
+                f64x4 T;
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr) T[rr] = tsc[li * 17 + lq + 4 * rr];
+                wave_lds_fence();
+                return T;
+            };
             auto gf = [&](int k, Pre& p) {
                 commit(p, k & 1);
                 if (k + 2 < N) request(p, k + 2, false);
                 f64x4 A, Bt;
                 stage_tiles(recbuf[k & 1], A, Bt);
+                if constexpr (TS) {
+                    const f64x4 At = transpose(A), Btr = transpose(Bt);
+                    const f64x4 T1 = hullk::mm_tn64(Xg, At, zero4);          // X A'   (X symmetric)
+                    Xg = hullk::mm_tn64(At, T1, hullk::mm_tn64(Btr, Btr, zero4));      // A X A' + Bt Bt'
+                }
                 const f64x4 xn = mv2(A, xc, Bt, rvec[k * 16 + li]);
                 xc = row2col(xn, k & 1);
                 if (lq == 0) wst[k * 16 + li] = xc;
@@ -379,6 +509,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             for (int k = 0; k < N; k += 2) {
                 gf(k, p0);
                 if (k + 1 < N) gf(k + 1, p1);
+            }
+            if constexpr (TS) {
+                wave_lds_fence();
+#pragma unroll
+                for (int rr = 0; rr < 4; ++rr)
+                    if (lq + 4 * rr < 9 && li < 9) x9[9 * (lq + 4 * rr) + li] = Xg[rr];
+                wave_lds_fence();
             }
             // backward (alongside: the open-loop weight S_j = Qt_j + A_j' S_{j+1} A_j, whose diag(Rt + Bt' S Bt) is the diagonal of the
             // condensed Hessian -- the scale of the polish's penalty)
@@ -475,6 +612,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
                 mrows += wave_red<DAdd>(cnt);
             }
+            if constexpr (TS) {      // terminal rows: residual at the start point (wst: dx of the start point), slack max(residual, 0.1), carried residual
+                double cnt = 0.0;
+                for (int j = 0; j < 2; ++j) {
+                    double s0 = 1.0, rp = 0.0;
+                    if (trv(j)) {
+                        const int i = lane + 64 * j;
+                        double res = Q.termb[i] - term_dot(j, wst + (N - 1) * 16);
+#pragma unroll
+                        for (int r = 0; r < 9; ++r) res -= s_tA[9 * i + r] * Q.eN[inst * 9 + r];
+                        s0 = fmax(res, 0.1);
+                        rp = s0 - res;
+                        wm = fmax(wm, s0);
+                        cnt += 1.0;
+                    }
+                    tref(T_S, j) = s0;
+                    tref(T_RP, j) = rp;
+                }
+                mrows += wave_red<DAdd>(cnt);
+            }
             wm = wave_red<DMax>(wm);
             const double mu0 = fmax(0.02 * gm * wm, 1e-3);
             for (int v = 0; v < nv; ++v) {
@@ -486,6 +642,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                     sref(X_ZL, v) = (xrow(v) && xhl) ? mu0 / sref(X_SL, v) : 0.0;
                 }
             }
+            if constexpr (TS)
+                for (int j = 0; j < 2; ++j) tref(T_Z, j) = trv(j) ? mu0 / tref(T_S, j) : 0.0;
         }
         // ---- backward Riccati sweep with Sigma in rvec [Sx in wst]: the factors W_k, Y_k of every stage -> global slot ----
         auto ric_factor = [&]() -> bool {
@@ -507,6 +665,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
 #pragma unroll
                             for (int rr = 0; rr < 4; ++rr)
                                 if (lq + 4 * rr == li) S[rr] += sx;
+                        }
+                    }
+                    if constexpr (TS) {      // the terminal rows' barrier term on the terminal weight
+                        if (k + 1 == N) {
+#pragma unroll
+                            for (int rr = 0; rr < 4; ++rr)
+                                if (lq + 4 * rr < 9 && li < 9) S[rr] += m9[9 * (lq + 4 * rr) + li];
                         }
                     }
                     const f64x4 SA = hullk::mm_tn64(S, A, zero4), SBt = hullk::mm_tn64(S, Bt, zero4);      // (S is symmetric)
@@ -570,15 +735,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
             }
             wave_lds_fence();
+            if constexpr (TS) {
+                for (int j = 0; j < 2; ++j)
+                    if (trv(j)) {
+                        csum += tref(T_S, j) * tref(T_Z, j);
+                        rpn = fmax(rpn, fabs(tref(T_RP, j)));
+                    }
+            }
             const double mu = wave_red<DAdd>(csum) * inv2n;
-            if constexpr (SB) rpn = wave_red<DMax>(rpn);
+            if constexpr (SB || TS) rpn = wave_red<DMax>(rpn);
             if (!(mu == mu) || !(rpn == rpn)) {
                 status = 2;
                 break;
             }
-            if (!(mu >= C.mu_stop) && !(rpn >= 1e-9)) {
-                status = 0;
-                break;
+            const bool conv = !(mu >= C.mu_stop) && !(rpn >= 1e-9);
+            if constexpr (!TS) {
+                if (conv) {
+                    status = 0;
+                    break;
+                }
             }
             if constexpr (!SB) {
                 // ---- EARLY ACTIVE-SET POLISH (box rows): once mu < 1e-7 the bounds with z > s are taken as active and the problem on that
@@ -586,7 +761,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 // Sigma = penalty on the active variables, 0 elsewhere), signs verified, at most three rounds -- as polish_general does for
                 // the general rows.  Verified: done, with the exact solution and 3-4 interior-point iterations saved (12.9 -> 9.4 on
                 // config 5).  Not verified: the iterate kept aside is restored and the iteration runs on to mu_stop as before.
-                if (!polish_tried && mu < 1e-7) {
+                // TS: tried once the carried residual has closed as well, and once more at mu_stop (as kernel 13 does)
+                if ((!polish_tried && mu < 1e-7 && (!TS || rpn < 1e-9)) || (TS && conv)) {
                     polish_tried = true;
                     const double pw = 1e6 * hs;
                     unsigned actl = 0u, actu = 0u;
@@ -603,6 +779,27 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                         sref(S_ZL, v) = al ? zl : 0.0;      // multipliers of the inactive bounds: 0
                         sref(S_ZU, v) = au ? zu : 0.0;
                     }
+                    if constexpr (TS) {      // terminal rows: active set, true slack (the carried residual has closed), penalty pw / |A_T,i GN|^2
+                        for (int j = 0; j < 2; ++j) {
+                            const double s_ = tref(T_S, j), z = tref(T_Z, j), rp = tref(T_RP, j);
+                            tref(T_KS, j) = s_;
+                            tref(T_KZ, j) = z;
+                            tref(T_KRP, j) = rp;
+                            const bool act = trv(j) && z > s_;
+                            tref(T_ACT, j) = act ? 1.0 : 0.0;
+                            if (!act) tref(T_Z, j) = 0.0;
+                            tref(T_S, j) = s_ - rp;
+                            tref(T_RP, j) = 0.0;
+                            double c2 = 0.0;
+                            const double* a = s_tA + 9 * (trv(j) ? lane + 64 * j : 0);
+                            for (int r1 = 0; r1 < 9; ++r1)
+                                for (int r2 = 0; r2 < 9; ++r2) c2 += a[r1] * x9[9 * r1 + r2] * a[r2];
+                            tref(T_W, j) = pw / fmax(c2, 1e-300);
+                        }
+                        wave_lds_fence();
+                        if (lane < 9) psN[16 + lane] = psN[lane];
+                        wave_lds_fence();
+                    }
                     bool verified = false;
                     int rounds = 0;
                     for (int rd = 0; rd < 3 && !verified; ++rd) {
@@ -610,6 +807,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                         for (int v = 0; v < nv; ++v)
                             rvec[(4 * v + lq) * 16 + li] = ((actl >> v & 1u) ? pw : 0.0) + ((actu >> v & 1u) ? pw : 0.0);
                         wave_lds_fence();
+                        term_blocks([&](int j) { return tref(T_ACT, j) != 0.0 ? tref(T_W, j) : 0.0; });
                         if (__builtin_amdgcn_readfirstlane(!ric_factor())) break;
                         ++rounds;
                         for (int in = 0; in < 2; ++in) {
@@ -626,7 +824,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                                 sref(K_DD, v) = r;
                             }
                             wave_lds_fence();
+                            // terminal rows: q_N = psi_N - A_T' (W s_A - lam)
+                            term_linear([&](int j) { return tref(T_ACT, j) != 0.0 ? tref(T_Z, j) - tref(T_W, j) * tref(T_S, j) : 0.0; });
                             ric_solve();
+                            if constexpr (TS) {
+                                psi_step(1.0);
+                                for (int j = 0; j < 2; ++j)
+                                    if (trv(j)) {
+                                        const double s_ = tref(T_S, j), ch = term_dot(j, wst + (N - 1) * 16);
+                                        if (tref(T_ACT, j) != 0.0) tref(T_Z, j) += tref(T_W, j) * (ch - s_);
+                                        tref(T_S, j) = s_ - ch;
+                                    }
+                            }
                             for (int v = 0; v < nv; ++v)
                                 if (tvalid(v)) {
                                     const bool al = actl >> v & 1u, au = actu >> v & 1u;
@@ -650,6 +859,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                                     if (sref(S_ZU, v) < 0.0) { sref(S_ZU, v) = 0.0; actu &= ~(1u << v); changed = true; }
                                 } else if (sref(S_SU, v) < -1e-10) { actu |= 1u << v; changed = true; }
                             }
+                        if constexpr (TS) {
+                            for (int j = 0; j < 2; ++j)
+                                if (trv(j)) {
+                                    const bool act = tref(T_ACT, j) != 0.0;
+                                    if (act && tref(T_Z, j) < 0.0) {
+                                        tref(T_ACT, j) = 0.0;
+                                        tref(T_Z, j) = 0.0;
+                                        changed = true;
+                                    } else if (!act && tref(T_S, j) < -1e-10) {
+                                        tref(T_ACT, j) = 1.0;
+                                        changed = true;
+                                    }
+                                }
+                        }
                         verified = !__any(changed);
                     }
                     nit += rounds;
@@ -664,6 +887,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                         sref(S_ZU, v) = sref(K_ZU, v);
                         sref(S_GRAD, v) = sref(K_GRAD, v);
                     }
+                    if constexpr (TS) {
+                        for (int j = 0; j < 2; ++j) {
+                            tref(T_S, j) = tref(T_KS, j);
+                            tref(T_Z, j) = tref(T_KZ, j);
+                            tref(T_RP, j) = tref(T_KRP, j);
+                        }
+                        if (lane < 9) psN[lane] = psN[16 + lane];
+                    }
                     wave_lds_fence();
                     for (int v = 0; v < nv; ++v) {
                         const double sl = sref(S_SL, v), su = sref(S_SU, v), zl = sref(S_ZL, v), zu = sref(S_ZU, v);
@@ -672,16 +903,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                     wave_lds_fence();
                 }
             }
+            if constexpr (TS) {
+                if (conv) {      // (the polish at mu_stop did not settle either: the interior-point iterate is the result)
+                    status = 0;
+                    break;
+                }
+            }
             if (it == C.max_iters) break;
             ++nit;
             S64(4);
+            term_blocks([&](int j) { return tref(T_Z, j) / tref(T_S, j); });
             const bool fok = ric_factor();
             S64(1);
             if (__builtin_amdgcn_readfirstlane(!fok)) {
                 // (state bounds: Sx ~ 1 / mu on an active row enters S, and P_k = A'SA - Y'Y is then a difference of numbers of that
                 // size: the recursion runs out of digits near mu ~ 1e-11.  As kernel 3's general-constraint modes: a breakdown
-                // once mu < 1e-7 with the primal residual closed ends the iteration as converged)
-                status = (SB && mu < 1e-7 && rpn < 1e-9) ? 0 : 2;
+                // once mu < 1e-7 with the primal residual closed ends the iteration as converged.  TS: the same rule, which is
+                // oracle/qp_oracle.py:ipm_general's, so that the statuses agree; the polish has been tried by then -- in this very
+                // iteration or an earlier one -- and the result is the unpolished iterate of this mu)
+                status = ((SB || TS) && mu < 1e-7 && rpn < 1e-9) ? 0 : 2;
                 --nit;
                 break;
             }
@@ -700,8 +940,23 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
             }
             wave_lds_fence();
+            term_linear([&](int j) { return tref(T_Z, j) / tref(T_S, j) * tref(T_RP, j); });      // (predictor: no second-order term)
             ric_solve();
             double ap = 1.0, ad = 1.0;
+            if constexpr (TS) {      // ds = -rp - A_T dx_N,  dz = -z - z ds / s
+                for (int j = 0; j < 2; ++j) {
+                    double ds = 0.0, dz = 0.0;
+                    if (trv(j)) {
+                        const double s_ = tref(T_S, j), z = tref(T_Z, j);
+                        ds = -tref(T_RP, j) - term_dot(j, wst + (N - 1) * 16);
+                        dz = -z - z * ds / s_;
+                        if (ds < 0.0) ap = fmin(ap, -s_ / ds);
+                        if (dz < 0.0) ad = fmin(ad, -z / dz);
+                    }
+                    tref(T_DSA, j) = ds;
+                    tref(T_DZA, j) = dz;
+                }
+            }
             for (int v = 0; v < nv; ++v) {
                 const bool okv = tvalid(v);
                 const double da = okv ? rvec[(4 * v + lq) * 16 + li] : 0.0;
@@ -757,6 +1012,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                     }
                 }
             }
+            if constexpr (TS)
+                for (int j = 0; j < 2; ++j)
+                    if (trv(j)) csum += (tref(T_S, j) + ap * tref(T_DSA, j)) * (tref(T_Z, j) + ad * tref(T_DZA, j));
             const double mu_aff = wave_red<DAdd>(csum) * inv2n;
             double sigma = mu_aff / mu;
             sigma = fmin(fmax(sigma * sigma * sigma, 0.0), 1.0);
@@ -792,9 +1050,22 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
             }
             wave_lds_fence();
+            // terminal rows: t = z rp / s - kappa,  kappa = (ds_a dz_a - sigma mu) / s
+            term_linear([&](int j) { return (tref(T_Z, j) * tref(T_RP, j) - (tref(T_DSA, j) * tref(T_DZA, j) - sm)) / tref(T_S, j); });
             ric_solve();
             ap = 1e300;
             ad = 1e300;
+            [[maybe_unused]] double tds[2] = {0.0, 0.0}, tdz[2] = {0.0, 0.0};
+            if constexpr (TS) {
+                for (int j = 0; j < 2; ++j)
+                    if (trv(j)) {
+                        const double s_ = tref(T_S, j), z = tref(T_Z, j), rp = tref(T_RP, j);
+                        tds[j] = -rp - term_dot(j, wst + (N - 1) * 16);
+                        tdz[j] = (-(s_ * z + tref(T_DSA, j) * tref(T_DZA, j) - sm) - z * tds[j]) / s_;
+                        if (tds[j] < 0.0) ap = fmin(ap, -s_ / tds[j]);
+                        if (tdz[j] < 0.0) ad = fmin(ad, -z / tdz[j]);
+                    }
+            }
             for (int v = 0; v < nv; ++v)
                 if (tvalid(v)) {
                     const double sl = sref(S_SL, v), su = sref(S_SU, v), zl = sref(S_ZL, v), zu = sref(S_ZU, v), da = sref(S_DA, v);
@@ -830,6 +1101,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
             }
             ap = fmin(1.0, 0.9995 * wave_red<DMin>(ap));
             ad = fmin(1.0, 0.9995 * wave_red<DMin>(ad));
+            if constexpr (TS) {      // rows and psi_N follow the step
+                psi_step(ap);
+                for (int j = 0; j < 2; ++j)
+                    if (trv(j)) {
+                        tref(T_S, j) += ap * tds[j];
+                        tref(T_Z, j) += ad * tdz[j];
+                        tref(T_RP, j) *= (1.0 - ap);
+                    }
+            }
             if constexpr (SB) {      // rows and psi follow the step: psi += alpha (-q - Sx dx)
                 for (int v = 0; v < nv; ++v)
                     if (xrow(v)) {
@@ -910,5 +1190,8 @@ template __global__ void ftmpc_solve_ric64_kernel<6>(const DeviceConsts, const S
 template __global__ void ftmpc_solve_ric64_kernel<10>(const DeviceConsts, const SolveRicParams);   // N <= 40 (BASELINE config 5)
 template __global__ void ftmpc_solve_ric64_kernel<6, true>(const DeviceConsts, const SolveRicParams);    // with state bounds (N <= 24)
 template __global__ void ftmpc_solve_ric64_kernel<10, true>(const DeviceConsts, const SolveRicParams);   // with state bounds (N <= 40)
+template __global__ void ftmpc_solve_ric64_kernel<4, false, true>(const DeviceConsts, const SolveRicParams);     // with the terminal set (N <= 16)
+template __global__ void ftmpc_solve_ric64_kernel<6, false, true>(const DeviceConsts, const SolveRicParams);     // (N <= 24)
+template __global__ void ftmpc_solve_ric64_kernel<10, false, true>(const DeviceConsts, const SolveRicParams);    // (N <= 40)
 
 }  // namespace ftmpc

@@ -21,7 +21,7 @@ MAX_HULL_ROWS = 128
 MAX_TCOST = 24
 MAX_FAULT_EVENTS = 8
 KERNEL_SLOTS = 7
-KERNEL_AUTO, KERNEL_DENSE, KERNEL_WORKGROUP = 0, 1, 2
+KERNEL_AUTO, KERNEL_DENSE, KERNEL_WORKGROUP, KERNEL_RICCATI = 0, 1, 2, 3
 
 # every symbol include/ftmpc.h declares (tests check the list against the header)
 SYMBOLS = (

@@ -83,9 +83,10 @@ class BatchedMPC:
         if cfg.dtype not in ("f32", "f64"):
             raise ValueError("dtype must be 'f32' or 'f64'")
         c.dtype = 1 if cfg.dtype == "f64" else 0
-        if cfg.kernel_select not in ("auto", "dense", "workgroup"):
-            raise ValueError("kernel_select must be 'auto', 'dense' or 'workgroup'")
-        c.kernel_select = {"auto": _lib.KERNEL_AUTO, "dense": _lib.KERNEL_DENSE, "workgroup": _lib.KERNEL_WORKGROUP}[cfg.kernel_select]
+        if cfg.kernel_select not in ("auto", "dense", "workgroup", "riccati"):
+            raise ValueError("kernel_select must be 'auto', 'dense', 'workgroup' or 'riccati'")
+        c.kernel_select = {"auto": _lib.KERNEL_AUTO, "dense": _lib.KERNEL_DENSE, "workgroup": _lib.KERNEL_WORKGROUP,
+                           "riccati": _lib.KERNEL_RICCATI}[cfg.kernel_select]
         c.lin_split_max, c.stage_chunks = int(cfg.lin_split_max), int(cfg.stage_chunks)
         c.J[:] = list(_f64(cfg.J, 9))
         D = cfg.D

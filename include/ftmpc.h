@@ -28,7 +28,8 @@ extern "C" {
 #define FTMPC_MAX_TERM_ROWS 80   /* rows of the terminal set (config/terminal.yaml: 72) */
 #define FTMPC_MAX_TCOST_TERMS 24  /* non-quadratic terms of the terminal cost (config/terminal.yaml: 13 polynomial + 12 root terms) */
 #define FTMPC_MAX_HULL_ROWS 128  /* facets of the generalized-force hull (26 for every fault set of the reference vehicle; 112 for a
-                                    generic 8-thruster allocation matrix).  More than 32: float64 Riccati kernel only (no terminal set) */
+                                    generic 8-thruster allocation matrix).  More than 32: float64 Riccati kernel only (kernel 13, with or without
+                                    the terminal set: see ftmpc_solve_wrench_batch) */
 #define FTMPC_NX 13
 #define FTMPC_NOPT 9
 #define FTMPC_NG 6
@@ -89,9 +90,16 @@ typedef struct ftmpc_config {
     double mu_stop;     /* stop when mean complementarity < mu_stop (<=0: library default) */
     /*
      * Terminal set  term_A (c_N[0:9] - xref_N) <= term_b  (the polytope of config/terminal.yaml, term_set; reference
-     * spiraling_mpc.py:199-202).  terminal_set != 0 adds these rows to the QP; ftmpc_solve_batch then runs on the dense float64
-     * kernel whatever the dtype (needs N * NT <= 256: checked when it is called), ftmpc_solve_wrench_batch as described there
-     * (no such limit).  An instance whose terminal set cannot
+     * spiraling_mpc.py:199-202).  terminal_set != 0 adds these rows to the QP; ftmpc_solve_batch then runs in float64 whatever
+     * the dtype: on the dense float64 kernel where N * NT <= 256 (padded to 16), on the Riccati kernel ftmpc_solve_ric64_kernel
+     * beyond that up to N = 40 (and for every N <= 40 with kernel_select = FTMPC_KERNEL_RICCATI).  N > 40 with N * NT > 256, and
+     * kernel_select = FTMPC_KERNEL_DENSE with N * NT > 256, are refused with FTMPC_ERR_ARG when a solve is called.  As in the dense
+     * kernel's general-row modes, a factorisation that breaks down once mu < 1e-7 with the rows' primal residual below 1e-9 ends the
+     * iteration as converged, as oracle/qp_oracle.py:ipm_general does: FTMPC_STATUS_OK with the interior-point iterate of that mu
+     * (the active-set polish has been tried on it or on an earlier one and did not settle, so the exact-solution accuracy of a
+     * polished result does not hold for such an instance); an earlier breakdown is
+     * FTMPC_STATUS_NUMERIC;
+     * ftmpc_solve_wrench_batch as described there (no such limit).  An instance whose terminal set cannot
      * be reached within the horizon ends with FTMPC_STATUS_MAXITER / _NUMERIC (the reference logs IPOPT's failure
      * and carries on, spiraling_mpc.py:347-352).
      */
@@ -118,9 +126,11 @@ typedef struct ftmpc_config {
     /*
      * Implementation switches (diagnostics and A/B runs; 0 = the library's choice everywhere).  They live here, per handle:
      * the library reads no environment variable and keeps no process-global state.
-     *   kernel_select   FTMPC_KERNEL_AUTO | FTMPC_KERNEL_DENSE | FTMPC_KERNEL_WORKGROUP: with DENSE the Newton systems are always factorised in the
-     *                   thruster variables (kernel 7 / the dense float64 kernel) even where the library would go through
-     *                   the 6N-variable wrench-space form (kernel 8 / its float64 sibling)
+     *   kernel_select   FTMPC_KERNEL_AUTO | FTMPC_KERNEL_DENSE | FTMPC_KERNEL_WORKGROUP | FTMPC_KERNEL_RICCATI: with DENSE the Newton systems
+     *                   are always factorised in the thruster variables (kernel 7 / the dense float64 kernel) even where the
+     *                   library would go through the 6N-variable wrench-space form (kernel 8 / its float64 sibling); with
+     *                   RICCATI the thruster form with the terminal set runs on the Riccati kernel for every N <= 40, also
+     *                   where AUTO keeps the dense float64 kernel (N * NT <= 256) -- everything else is routed as with AUTO
      *   lin_split_max   batch size up to which the linearisation is split by tangent direction (0: library default 8192;
      *                   < 0: never split)
      *   stage_chunks    ranges the host-buffer entry point stages a batch in (0: whole blocks of 65 536 instances; 1..8)
@@ -152,6 +162,8 @@ typedef struct ftmpc_config {
 #define FTMPC_KERNEL_DENSE 1
 #define FTMPC_KERNEL_WORKGROUP 2   /* the wrench-space form on a 4-wave workgroup per instance (kernel 8) where the library would
                                       give the instance one wave (kernel 10) */
+#define FTMPC_KERNEL_RICCATI 3     /* ftmpc_solve_ric64_kernel (Riccati recursion, one wave per instance) where the library would take the
+                                      dense float64 kernel for the thruster form with the terminal set (N <= 40); otherwise as AUTO */
 
 typedef struct ftmpc_handle ftmpc_handle;
 
@@ -458,13 +470,15 @@ int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, do
  * 160 < N*NT: ftmpc_solve_wsw32_kernel (Newton systems through the 6N-variable wrench-space form, one wave per instance:
  * N <= 16 with N*NT <= 256, N <= 21 with N*NT <= 384), ftmpc_solve_ws32_kernel (the same form on a workgroup per instance:
  * kernel_select = FTMPC_KERNEL_WORKGROUP) or, with kernel_select = FTMPC_KERNEL_DENSE and N*NT <= 240, the dense
- * ftmpc_solve_wg32_kernel<15> (the slot reports all three names), 6 condense+IPM fp64 through the wrench-space form (ftmpc_solve_ws64_kernel, 6 N <= 256). */
+ * ftmpc_solve_wg32_kernel<15> (the slot reports all three names), 6 IPM fp64 on one wave per instance by the
+ * Riccati recursion (ftmpc_solve_ric64_kernel, N <= 40: the box QP, the state bounds, and the terminal set where N * NT > 256 or
+ * kernel_select = FTMPC_KERNEL_RICCATI) or condense+IPM fp64 through the wrench-space form (ftmpc_solve_ws64_kernel, 6 N <= 256). */
 #define FTMPC_KERNEL_SLOTS 7
 int ftmpc_set_profiling(ftmpc_handle* h, int32_t enabled);
 int ftmpc_last_kernel_ms(ftmpc_handle* h, float* ms, int32_t n_slots);
 const char* ftmpc_kernel_name(int32_t slot);
-/* the ONE kernel slot `slot` launches on this handle (slot 5 names three kernels above; which of them runs is the handle's routing:
- * its shape and kernel_select) */
+/* the ONE kernel slot `slot` launches on this handle (slot 5 names three kernels above, slot 6 two; which of them runs is the
+ * handle's routing: its shape, terminal_set / state_bounds and kernel_select) */
 const char* ftmpc_routed_kernel_name(const ftmpc_handle* h, int32_t slot);
 
 /*
@@ -472,6 +486,10 @@ const char* ftmpc_routed_kernel_name(const ftmpc_handle* h, int32_t slot);
  * QP the solve kernel sees (active thrusters only):  n = N*na,  H [n*n] row-major,
  * g [n], lo [n], hi [n] (bounds on d = U - Ubar), all as double.  *n_out receives n.
  * H_cap is the capacity of H in elements (>= n*n).
+ * The dump is the BOX QP: the rows of the terminal set are not part of it.  On a terminal-set handle whose thruster form runs on
+ * ftmpc_solve_ric64_kernel (N * NT > 256, or kernel_select = FTMPC_KERNEL_RICCATI) it comes from the dense float64 kernel's box mode --
+ * the same H, g, lo, hi as a handle without the set dumps -- and the first call allocates that kernel's per-workgroup slots, which
+ * ftmpc_create leaves out for such a handle beyond N * NT = 256.
  */
 int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B,
                          const double* x0, const double* ub, const double* stuck,
