@@ -623,7 +623,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 451; }
+int32_t ftmpc_version(void) { return 500; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -1945,7 +1945,33 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
-                         double* x_hist = nullptr);
+                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr);
+
+// An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
+static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
+    if (!oc) return FTMPC_OK;
+    if (oc->struct_size != (int32_t)sizeof(ftmpc_outcomes))
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.struct_size is " + std::to_string(oc->struct_size) + ", this library expects " +
+                                          std::to_string(sizeof(ftmpc_outcomes)));
+    if (oc->index0 < 0) return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index0 is negative");
+    if (oc->index_total == 0 && oc->index0 != 0)
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index_total = 0 (the call is the campaign) needs index0 = 0");
+    if (oc->index_total != 0 && (oc->index_total < 0 || oc->index0 > oc->index_total - B))
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index_total: index0 + B = " + std::to_string(oc->index0) + " + " + std::to_string(B) +
+                                          " exceeds index_total = " + std::to_string(oc->index_total));
+    if (oc->settle_step) {
+        const double tol[3] = {oc->tol_pos, oc->tol_vel, oc->tol_rate};
+        const char* name[3] = {"tol_pos", "tol_vel", "tol_rate"};
+        for (int i = 0; i < 3; ++i)
+            if (!(tol[i] > 0.0) || !std::isfinite(tol[i]))
+                return fail(h, FTMPC_ERR_ARG, std::string("ftmpc_outcomes.") + name[i] + " must be positive and finite when settle_step is asked for");
+    }
+    if (oc->tset_step && (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS))
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.tset_step needs the terminal rows of the handle's config (term_rows in 1..80)");
+    if (oc->alloc_failed && !wrench)
+        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.alloc_failed: the thruster form has no allocation (use ftmpc_simulate_wrench_outcomes_batch)");
+    return FTMPC_OK;
+}
 
 // A fault schedule's layout and values (include/ftmpc.h, ftmpc_fault_schedule).  wrench: the wrench form, whose call has n_sets hull
 // tables of hull_rows rows and its own hull_set (call_set) or not.
@@ -1995,16 +2021,25 @@ int ftmpc_simulate_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
                                 const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                 int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                 double* u_hist, double* x_hist, int32_t* not_converged) {
+    return ftmpc_simulate_outcomes_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                         x_hist, not_converged, nullptr);
+}
+
+int ftmpc_simulate_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     int rc = check_schedule(h, B, faults, false, 0, false);
     if (rc != FTMPC_OK) return rc;
+    if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) return FTMPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist);
+                         faults, x_hist, out);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2012,16 +2047,28 @@ int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed) {
+    return ftmpc_simulate_wrench_outcomes_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                                seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                                nullptr);
+}
+
+int ftmpc_simulate_wrench_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                         const ftmpc_outcomes* out) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
     if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
+    if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) return FTMPC_OK;
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2070,7 +2117,8 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist) {
+                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
+                         const ftmpc_outcomes* oc) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2082,6 +2130,13 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     const int E = fs ? fs->n_events : 0;
     DevBuf<int32_t> d_fev;
     DevBuf<double> d_fpat, d_fhb, d_plant;
+    // outcomes: records [err_int 3 | err_max 3 | impulse 2] x B and [settle | tset | unsolved | first_unsolved | alloc_failed] x B, the
+    // terminal rows of the config, the status history
+    const bool want_rec = oc && (oc->err_int || oc->err_max || oc->impulse || oc->settle_step || oc->tset_step || oc->unsolved ||
+                                 oc->first_unsolved || oc->alloc_failed);
+    const bool want_out = want_rec || (oc && oc->status_hist);
+    DevBuf<double> d_orec, d_oterm;
+    DevBuf<int32_t> d_oint, d_shist;
     HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
     if (uref_traj) HIP_TRY(h, hipMalloc(&d_ur.p, (size_t)ncol * 6 * sizeof(double)));
     if (!wl) HIP_TRY(h, hipMalloc(&d_warmB.p, (size_t)B * N * NT * sizeof(double)));
@@ -2106,9 +2161,49 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     sp.u_hist = d_hist;
     sp.status = h->d_status;
     sp.bad_count = d_bad;
+    sp.index0 = oc ? oc->index0 : 0;
+    sp.index_total = oc && oc->index_total != 0 ? oc->index_total : B;
     if (x_hist) {
         HIP_TRY(h, hipMalloc(&d_xhist.p, (size_t)T * B * 13 * sizeof(double)));
         sp.x_hist = d_xhist;
+    }
+    ftmpc::OutcomeParams op{};
+    if (want_out) {
+        HIP_TRY(h, hipMalloc(&d_orec.p, (size_t)B * 8 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_oint.p, (size_t)B * 5 * sizeof(int32_t)));
+        HIP_TRY(h, hipMemsetAsync(d_orec, 0, (size_t)B * 8 * sizeof(double), s));
+        HIP_TRY(h, hipMemsetAsync(d_oint, 0, (size_t)B * 5 * sizeof(int32_t), s));
+        HIP_TRY(h, hipMemsetAsync(d_oint + B, 0xFF, (size_t)B * sizeof(int32_t), s));          // tset_step = -1
+        HIP_TRY(h, hipMemsetAsync(d_oint + 3 * B, 0xFF, (size_t)B * sizeof(int32_t), s));      // first_unsolved = -1
+        op.B = B;
+        op.x = h->d_x0;
+        op.u0 = h->d_u0;
+        op.astatus = wl ? h->d_ast2.p : nullptr;
+        op.err_int = d_orec;
+        op.err_max = d_orec + 3 * B;
+        op.impulse = d_orec + 6 * B;
+        op.settle = d_oint;
+        op.tset = d_oint + B;
+        op.unsolved = d_oint + 2 * B;
+        op.first_unsolved = d_oint + 3 * B;
+        op.alloc_failed = d_oint + 4 * B;
+        if (oc->settle_step) {
+            op.tol[0] = oc->tol_pos;
+            op.tol[1] = oc->tol_vel;
+            op.tol[2] = oc->tol_rate;
+        }
+        if (oc->tset_step) {
+            const int R = h->cfg.term_rows;
+            HIP_TRY(h, hipMalloc(&d_oterm.p, (size_t)R * 10 * sizeof(double)));
+            HIP_TRY(h, hipMemcpyAsync(d_oterm, h->cfg.term_A, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(d_oterm + R * 9, h->cfg.term_b, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
+            op.term = d_oterm;
+            op.term_rows = R;
+        }
+        if (oc->status_hist) {
+            HIP_TRY(h, hipMalloc(&d_shist.p, (size_t)T * B * sizeof(int32_t)));
+            op.status_hist = d_shist;
+        }
     }
     const int64_t nw = B * (int64_t)N * NT;
     std::vector<char> ev_step;         // steps at which some instance switches its plant or controller pattern
@@ -2207,6 +2302,14 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (rc != FTMPC_OK) return rc;
         sp.step = t;
         hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
+        if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
+            op.step = t;
+            op.ub = sp.ub;
+            op.stuck = sp.stuck;
+            op.status = sp.status;
+            op.xref = d_xr + (int64_t)9 * (t + 1);
+            hipLaunchKernelGGL(ftmpc::ftmpc_outcome_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op);
+        }
         if (wl)     // wrench warm start: shifted by one stage, the last stage repeats
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((B * N * 6 + 255) / 256)), dim3(256), 0, s, B, N, 6,
                                Gfin, h->d_warmG, 1);
@@ -2219,6 +2322,17 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (d_abad) HIP_TRY(h, hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (want_out) {
+        double* const rec[3] = {oc->err_int, oc->err_max, oc->impulse};
+        const int64_t rec_off[3] = {0, 3 * B, 6 * B}, rec_n[3] = {3 * B, 3 * B, 2 * B};
+        for (int i = 0; i < 3; ++i)
+            if (rec[i]) HIP_TRY(h, hipMemcpyAsync(rec[i], d_orec + rec_off[i], (size_t)rec_n[i] * sizeof(double), hipMemcpyDeviceToHost, s));
+        int32_t* const cnt[5] = {oc->settle_step, oc->tset_step, oc->unsolved, oc->first_unsolved, oc->alloc_failed};
+        for (int i = 0; i < 5; ++i)
+            if (cnt[i]) HIP_TRY(h, hipMemcpyAsync(cnt[i], d_oint + i * B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (oc->status_hist)
+            HIP_TRY(h, hipMemcpyAsync(oc->status_hist, d_shist, (size_t)T * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(h, hipStreamSynchronize(s));
     return FTMPC_OK;
 }

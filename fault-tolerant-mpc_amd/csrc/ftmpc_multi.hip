@@ -198,6 +198,117 @@ void shard(int64_t B, int G, int g, int64_t& lo, int64_t& hi) {
     hi = B * (g + 1) / G;
 }
 
+// rows [T][n][w] of a shard's history into the caller's [T][B][w] at vehicle lo
+template <typename V>
+void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_t n, int64_t w) {
+    for (int64_t t = 0; t < T; ++t) std::memcpy(dst + (t * B + lo) * w, src + t * n * w, (size_t)(n * w) * sizeof(V));
+}
+
+// The closed loops over the device slots (ftmpc_multi_simulate_outcomes_batch / _wrench_outcomes_batch; hull_A == nullptr: the thruster
+// form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
+// caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
+// staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
+int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* hull_A,
+                   int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows, const double* xref_traj,
+                   const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                   double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                   int32_t* alloc_failed, const ftmpc_outcomes* out, bool wrench) {
+    if (!m) return FTMPC_ERR_ARG;
+    auto refuse = [m](const std::string& msg) {
+        m->err = msg;
+        return FTMPC_ERR_ARG;
+    };
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || (wrench && (!hull_A || !hull_b || hull_rows < 1)))
+        return refuse("null buffer or negative size");
+    if (out && out->struct_size != (int32_t)sizeof(ftmpc_outcomes))
+        return refuse("ftmpc_outcomes.struct_size is " + std::to_string(out->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_outcomes)));
+    if (out && (out->index0 != 0 || (out->index_total != 0 && out->index_total != B)))
+        return refuse("ftmpc_outcomes.index0 / index_total are set per device slot by the multi-GPU driver: pass 0 / 0 or 0 / B");
+    if (faults && faults->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return refuse("ftmpc_fault_schedule: bad struct_size");
+    if (faults && (faults->n_events < 0 || faults->n_events > FTMPC_MAX_FAULT_EVENTS))
+        return refuse("ftmpc_fault_schedule: n_events outside [0, FTMPC_MAX_FAULT_EVENTS]");
+    if (B == 0 || T == 0) return FTMPC_OK;
+    const int G = (int)m->dev.size();
+    if (G > B) return refuse("more device slots (" + std::to_string(G) + ") than vehicles (B = " + std::to_string(B) + ")");
+    const int NT = m->cfg.NT;
+    std::vector<std::vector<int32_t>> bad((size_t)G), abad((size_t)G);      // per-slot counts per step
+    const int rc = multi_run(m, [&](ftmpc_multi::Dev& d) -> int {
+        const int g = (int)(&d - m->dev.data());
+        int64_t lo, hi;
+        shard(B, G, g, lo, hi);
+        const int64_t n = hi - lo;
+        ftmpc_fault_schedule fs{};
+        if (faults) {
+            fs = *faults;
+            const int64_t E = fs.n_events;
+            if (fs.onset) fs.onset += lo * E;
+            if (fs.detect) fs.detect += lo * E;
+            if (fs.ub) fs.ub += lo * E * NT;
+            if (fs.stuck) fs.stuck += lo * E * NT;
+            if (fs.hull_set) fs.hull_set += lo * E;
+            if (fs.hull_b) fs.hull_b += lo * E * hull_rows;
+        }
+        ftmpc_outcomes oc{};
+        oc.struct_size = (int32_t)sizeof(ftmpc_outcomes);
+        oc.index0 = lo;
+        oc.index_total = B;
+        const bool whole = n == B;      // one slot: no staging
+        std::vector<double> uh, xh;
+        std::vector<int32_t> sh;
+        try {
+            bad[g].assign((size_t)T, 0);
+            abad[g].assign((size_t)T, 0);
+            if (u_hist && !whole) uh.resize((size_t)T * n * NT);
+            if (x_hist && !whole) xh.resize((size_t)T * n * 13);
+            if (out && out->status_hist && !whole) sh.resize((size_t)T * n);
+        } catch (const std::bad_alloc&) {
+            return dev_fail(d, FTMPC_ERR_ALLOC, "out of host memory for the shard's histories");
+        }
+        if (out) {
+            oc.tol_pos = out->tol_pos;
+            oc.tol_vel = out->tol_vel;
+            oc.tol_rate = out->tol_rate;
+            oc.err_int = out->err_int ? out->err_int + lo * 3 : nullptr;
+            oc.err_max = out->err_max ? out->err_max + lo * 3 : nullptr;
+            oc.impulse = out->impulse ? out->impulse + lo * 2 : nullptr;
+            oc.settle_step = out->settle_step ? out->settle_step + lo : nullptr;
+            oc.tset_step = out->tset_step ? out->tset_step + lo : nullptr;
+            oc.unsolved = out->unsolved ? out->unsolved + lo : nullptr;
+            oc.first_unsolved = out->first_unsolved ? out->first_unsolved + lo : nullptr;
+            oc.alloc_failed = out->alloc_failed ? out->alloc_failed + lo : nullptr;
+            oc.status_hist = !out->status_hist ? nullptr : (whole ? out->status_hist : sh.data());
+        }
+        double* const uh_p = !u_hist ? nullptr : (whole ? u_hist : uh.data());
+        double* const xh_p = !x_hist ? nullptr : (whole ? x_hist : xh.data());
+        const int rc2 = wrench ? ftmpc_simulate_wrench_outcomes_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
+                                                                      xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
+                                                                      faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
+                                                                      alloc_failed ? abad[g].data() : nullptr, &oc)
+                               : ftmpc_simulate_outcomes_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                               seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                               bad[g].data(), &oc);
+        if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
+        if (!whole) {
+            if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
+            if (x_hist) scatter_rows(x_hist, xh.data(), T, B, lo, n, 13);
+            if (out && out->status_hist) scatter_rows(out->status_hist, sh.data(), T, B, lo, n, 1);
+        }
+        return FTMPC_OK;
+    });
+    if (rc != FTMPC_OK) return rc;
+    for (int32_t t = 0; t < T; ++t) {
+        int32_t nb = 0, na = 0;
+        for (int g = 0; g < G; ++g) {
+            nb += bad[g][t];
+            na += abad[g][t];
+        }
+        if (not_converged) not_converged[t] = nb;
+        if (alloc_failed) alloc_failed[t] = na;
+    }
+    return FTMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -413,6 +524,24 @@ int ftmpc_multi_download(ftmpc_multi* m, double* out_u0, double* out_U, int32_t*
         DEV_TRY(d, hipStreamSynchronize(d.s));
         return FTMPC_OK;
     });
+}
+
+int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, false);
+}
+
+int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                               const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                               int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                               uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, true);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

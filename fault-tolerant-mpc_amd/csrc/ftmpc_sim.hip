@@ -55,7 +55,7 @@ struct SimParams {
     const double* stuck;
     double noise[4];      // amplitudes: position, velocity, orientation, angular velocity (U(0, a), sim_env.py:25-30)
     unsigned long long seed;
-    int64_t step;
+    int64_t step, index0, index_total;   // noise counter (step * index_total + index0 + b) * 13 + i: vehicles [index0, index0 + B) of a campaign
     double* u_hist;       // nullptr or [T*B*NT]
     const int32_t* status;
     int32_t* bad_count;   // nullptr or [T]
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(64) ftmpc_plant_step_kernel(const DeviceConsts
     // one-sided uniform measurement noise (sim_env.py:88-91), then quaternion renormalisation (:93)
     for (int i = 0; i < 13; ++i) {
         const double a = i < 3 ? S.noise[0] : (i < 6 ? S.noise[1] : (i < 10 ? S.noise[2] : S.noise[3]));
-        if (a > 0.0) x[i] += a * u01(S.seed, (unsigned long long)((S.step * S.B + b) * 13 + i));
+        if (a > 0.0) x[i] += a * u01(S.seed, (unsigned long long)((S.step * S.index_total + S.index0 + b) * 13 + i));
     }
     const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
     for (int i = 6; i < 10; ++i) x[i] *= qn;
@@ -405,6 +405,101 @@ __global__ void __launch_bounds__(64) ftmpc_fault_event_kernel(const DeviceConst
     } else if (F.repair && F.warmU) {
         double* w = F.warmU + (b * N + k) * NT;
         for (int j = 0; j < NT; ++j) w[j] = fmin(fmax(w[j], 0.0), F.ev_ub[src + j]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Per-vehicle outcomes of a fault campaign (ftmpc_simulate_outcomes_batch / ftmpc_simulate_wrench_outcomes_batch): launched after the
+// plant kernel of loop step t, only when the call asks for an outcome or for status_hist.  It reduces what the histories would
+// carry -- x_{t+1} (what the plant kernel just wrote), the command u_t, the PLANT's pattern and the solve / allocation status of the
+// step -- into 84 bytes per vehicle, so that a campaign never needs x_hist / u_hist on the host:
+//   e = robot_to_center(x_{t+1})[0:9] - xref[:, t+1];   ep, ev, ew = |e[0:3]|, |e[3:6]|, |e[6:9]|
+//   err_int  += dt (ep^2, ev^2, ew^2)          err_max = max(err_max, (ep, ev, ew))
+//   impulse  += dt (sum_i a_i, sum_i c_i)      c_i = ub_i > 0 ? u_i : 0 (commanded), a_i = c_i + stuck_i (delivered: sys_model.py:198-208)
+//   settle    = t + 1 where a norm is outside its band (last such step + 1; records start at 0)
+//   tset      = t at the first step with term_A e <= term_b on every row (records start at -1)
+//   unsolved, first_unsolved, alloc_failed: counts / first step of a non-zero status
+// The records always exist as a set (the host copies out what the caller asked for); `term` and `astatus` are null where the caller
+// did not ask for tset_step / the loop has no allocation.  One lane per vehicle; the rows of the terminal set are the same addresses
+// for every lane, and a vehicle stops evaluating them once it has entered the set.
+// ---------------------------------------------------------------------------------------------------------
+struct OutcomeParams {
+    int64_t B;
+    int32_t step, term_rows;
+    const double* x;          // [B*13] the state after this step
+    const double* u0;         // [B*NT] the command of this step
+    const double* ub;         // [B*NT] the plant's pattern
+    const double* stuck;
+    const int32_t* status;    // [B] solve status of this step
+    const int32_t* astatus;   // nullptr or [B] allocation status
+    const double* xref;       // 9 reference values of column step + 1
+    const double* term;       // nullptr or [term_rows*9 | term_rows]
+    double tol[3];            // settle band: position, velocity, angular rate
+    double* err_int;          // [B*3]
+    double* err_max;          // [B*3]
+    double* impulse;          // [B*2]
+    int32_t* settle;          // [B]
+    int32_t* tset;            // [B]
+    int32_t* unsolved;        // [B]
+    int32_t* first_unsolved;  // [B]
+    int32_t* alloc_failed;    // [B]
+    int32_t* status_hist;     // nullptr or [T*B]
+};
+
+__global__ void __launch_bounds__(64) ftmpc_outcome_kernel(const DeviceConsts C, const OutcomeParams O) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= O.B) return;
+    const int NT = C.NT;
+    const int32_t t = O.step;
+    double x[13];
+    for (int i = 0; i < 13; ++i) x[i] = O.x[b * 13 + i];
+    // robot -> orbit-centre state (spiral_model.py:91-109), as kernel 1 forms it
+    double e[9];
+    {
+        double RT[9], wxr[3], a[3], c[3];
+        rotT(x + 6, RT);
+        cross3(x + 10, C.r, wxr);
+        mat3vec(RT, C.r, a);
+        mat3vec(RT, wxr, c);
+        for (int i = 0; i < 3; ++i) {
+            e[i] = x[i] + a[i] - O.xref[i];
+            e[3 + i] = x[3 + i] + c[i] - O.xref[3 + i];
+            e[6 + i] = x[10 + i] - O.xref[6 + i];
+        }
+    }
+    const double dt = C.dt;
+    bool inside = true;
+    for (int j = 0; j < 3; ++j) {
+        const double n2 = e[3 * j] * e[3 * j] + e[3 * j + 1] * e[3 * j + 1] + e[3 * j + 2] * e[3 * j + 2];
+        const double n = sqrt(n2);
+        O.err_int[b * 3 + j] += dt * n2;
+        O.err_max[b * 3 + j] = fmax(O.err_max[b * 3 + j], n);
+        inside = inside && n <= O.tol[j];
+    }
+    if (!inside) O.settle[b] = t + 1;
+    double del = 0.0, cmd = 0.0;
+    for (int i = 0; i < NT; ++i) {
+        const double c = O.ub[b * NT + i] > 0.0 ? O.u0[b * NT + i] : 0.0;
+        cmd += c;
+        del += c + O.stuck[b * NT + i];
+    }
+    O.impulse[b * 2] += dt * del;
+    O.impulse[b * 2 + 1] += dt * cmd;
+    const int32_t st = O.status[b];
+    if (st != 0) {
+        if (O.unsolved[b]++ == 0) O.first_unsolved[b] = t;
+    }
+    if (O.astatus && O.astatus[b] != 0) O.alloc_failed[b] += 1;
+    if (O.status_hist) O.status_hist[(int64_t)t * O.B + b] = st;
+    if (O.term && O.tset[b] < 0) {
+        const double* tb = O.term + (int64_t)O.term_rows * 9;
+        bool in = true;
+        for (int r = 0; r < O.term_rows; ++r) {
+            double s = 0.0;
+            for (int j = 0; j < 9; ++j) s += O.term[r * 9 + j] * e[j];
+            in = in && s <= tb[r];
+        }
+        if (in) O.tset[b] = t;
     }
 }
 

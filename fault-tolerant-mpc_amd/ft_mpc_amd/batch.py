@@ -39,6 +39,8 @@ class MPCConfig:
     # terminal set  term_A (c_N[0:9] - xref_N) <= term_b  (config/terminal.yaml term_set; spiraling_mpc.py:199-202):
     # a TerminalSet / (A, b) pair, or True for the shipped config/terminal.yaml.  Needs dtype "f64".
     terminal_set: object = None
+    # False: the rows above are carried in the config (for the tset_step outcome of `simulate`) but are NOT added to the QP
+    terminal_set_active: bool = True
     # non-quadratic part of the terminal cost (config/terminal.yaml `cost` beyond e'P e; spiraling_mpc.py:196): a
     # TerminalIngredients object, or True for the shipped config/terminal.yaml.  Every QP then carries its exact
     # gradient at the linearisation point and eval_cost includes it (see BatchedMPC.solve_sqp).
@@ -122,7 +124,7 @@ class BatchedMPC:
             b = _f64(b).reshape(-1)
             if A.shape[0] != b.size or A.shape[0] > _lib.MAX_TERM_ROWS:
                 raise ValueError(f"terminal set must have at most {_lib.MAX_TERM_ROWS} rows of 9 coefficients")
-            c.terminal_set, c.term_rows = 1, A.shape[0]
+            c.terminal_set, c.term_rows = (1 if cfg.terminal_set_active else 0), A.shape[0]
             flatA = np.zeros(_lib.MAX_TERM_ROWS * 9)
             flatA[:A.size] = A.reshape(-1)
             flatb = np.zeros(_lib.MAX_TERM_ROWS)
@@ -444,7 +446,7 @@ class BatchedMPC:
     # -- closed loop on the device (SimulationEnvironment.run_simulation, batched) ------------
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
-                 faults=None, detect_delay=0, return_states=False):
+                 faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -456,86 +458,17 @@ class BatchedMPC:
         at the onset step, the controller detect_delay steps later (int, [B] or [B,E]) and repairs its warm start then.  On the wrench
         form the hull tables are built over all patterns together (hull None, or ft_mpc_amd.faults.fault_hull_tables of the same
         schedule built beforehand).  return_states: also x_hist [T,B,13], the state after each step.
-        Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist])."""
-        N, NT = self.cfg.N, self.cfg.NT
-        x = _f64(x0).reshape(-1, 13).copy()
-        B = x.shape[0]
-        ub = _f64(ub, (B, NT))
-        stuck = _f64(stuck, (B, NT))
-        xr = _f64(xref_traj)
-        if xr.shape != (9, T + N):
-            raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}")
-        xr = np.ascontiguousarray(xr.reshape(-1, order="F"))
-        ur = None
-        if uref_traj is not None:
-            ur = _f64(uref_traj)
-            if ur.shape != (6, T + N):
-                raise ValueError("uref_traj must be 6 x (T+N)")
-            ur = np.ascontiguousarray(ur.reshape(-1, order="F"))
-        nz = _f64(noise, 4)
-        uh = np.empty((T, B, NT)) if return_inputs else None
-        xh = np.empty((T, B, 13)) if return_states else None
-        bad = np.zeros(T, np.int32)
-        ext = faults is not None or return_states      # the entries with a fault schedule and x_hist
-        sched, keep, fh = None, None, None
-        if faults is not None:
-            from .faults import fault_hull_tables, normalize_schedule
-            onset, detect, eub, est = normalize_schedule(faults, B, NT, T, detect_delay)
-            keep = [onset, detect, eub, est]
-            sched = _lib.ftmpc_fault_schedule(struct_size=C.sizeof(_lib.ftmpc_fault_schedule), n_events=onset.shape[1],
-                                              onset=_ptr(onset, C.c_int32), detect=_ptr(detect, C.c_int32), ub=_ptr(eub), stuck=_ptr(est))
-            if formulation == "wrench":
-                if hull is not None and ("ev_set" not in hull or np.shape(hull["ev_set"]) != onset.shape):
-                    raise ValueError("with faults `hull` must be None or ft_mpc_amd.faults.fault_hull_tables of the same schedule")
-                fh = fault_hull_tables(self.D, ub, stuck, eub, est, onset) if hull is None else hull
-                hull = fh
-                evs, evb = fh["ev_set"], np.ascontiguousarray(fh["ev_b"], dtype=np.float64)
-                keep += [evs, evb]
-                sched.hull_set, sched.hull_b = _ptr(evs, C.c_int32), _ptr(evb)
-        sp = C.byref(sched) if sched is not None else None
-        if formulation == "wrench":
-            from .controllers.tools.input_bounds import hull_tables
-            if hull is None:
-                hull = hull_tables(self.D, ub, stuck)
-            if np.asarray(hull["degenerate"], bool).any():
-                raise ValueError("a vehicle's healthy thrusters do not span R^6: no input hull (use the thruster formulation)")
-            A = np.ascontiguousarray(hull["A"], dtype=np.float64)
-            hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
-            hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
-            abad = np.zeros(T, np.int32)
-            if ext:
-                self._check(self.lib.ftmpc_simulate_wrench_faults_batch(
-                    self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                    int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                    float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-                out = dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-                if return_states:
-                    out["x_hist"] = xh
-                return out
-            if sqp_iters:
-                self._check(self.lib.ftmpc_simulate_wrench_batch_ex(
-                    self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                    int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                    float(penalty), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-                return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-            self._check(self.lib.ftmpc_simulate_wrench_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0],
-                                                             _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
-                                                             C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-            return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-        if formulation != "thruster":
-            raise ValueError("formulation must be 'thruster' or 'wrench'")
-        if ext:
-            self._check(self.lib.ftmpc_simulate_faults_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
-                                                             _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                                                             sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32)))
-            out = dict(x=x, u=uh, not_converged=bad)
-            if return_states:
-                out["x_hist"] = xh
-            return out
-        self._check(self.lib.ftmpc_simulate_batch_ex(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
-                                                     _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                                                     _ptr(uh), _ptr(bad, C.c_int32)))
-        return dict(x=x, u=uh, not_converged=bad)
+        outcomes: per-vehicle results reduced on the device while the loop runs (include/ftmpc.h, ftmpc_outcomes), so that a campaign
+        needs neither history: True for err_int [B,3], err_max [B,3], impulse [B,2] (delivered, commanded), unsolved [B],
+        first_unsolved [B], tset_step [B] (when the config has terminal rows) and, wrench form, alloc_failed [B]; a
+        dict(tol_pos=, tol_vel=, tol_rate=) adds settle_step [B] for that band (a key fields=[names] asks for exactly those).
+        return_status: also status_hist [T,B], the solve status of every vehicle at every step.  index0 / index_total: the call's
+        vehicles are [index0, index0 + B) of a campaign of index_total; the noise is then what the same vehicles draw in one call over
+        the whole campaign (default: the call is the campaign).
+        Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
+        [, status_hist])."""
+        return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
+                         formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -601,6 +534,152 @@ class BatchedMPC:
                                                   _ptr(g), _ptr(lo), _ptr(hi), C.byref(n)))
         n = n.value
         return H[:n * n].reshape(n, n).copy(), g[:n].copy(), lo[:n].copy(), hi[:n].copy()
+
+
+OUTCOME_FIELDS = (("err_int", 3, np.float64), ("err_max", 3, np.float64), ("impulse", 2, np.float64), ("settle_step", 0, np.int32),
+                  ("tset_step", 0, np.int32), ("unsolved", 0, np.int32), ("first_unsolved", 0, np.int32), ("alloc_failed", 0, np.int32))
+
+
+def _outcome_request(obj, B, T, wrench, outcomes, return_status, index0, index_total):
+    """The ftmpc_outcomes struct of a simulate call and the arrays it points into: (struct, dict of outcome arrays | None,
+    status_hist | None)."""
+    oc = _lib.ftmpc_outcomes(struct_size=C.sizeof(_lib.ftmpc_outcomes), index0=int(index0),
+                             index_total=0 if index_total is None else int(index_total))
+    arrays = None
+    if outcomes is not None and outcomes is not False:
+        spec = {} if outcomes is True else dict(outcomes)
+        names = spec.pop("fields", None)
+        tols = [spec.pop(k, None) for k in ("tol_pos", "tol_vel", "tol_rate")]
+        if spec:
+            raise ValueError(f"outcomes: unknown keys {sorted(spec)}")
+        if any(t is not None for t in tols) and not all(t is not None for t in tols):
+            raise ValueError("outcomes: tol_pos, tol_vel and tol_rate come together")
+        if tols[0] is not None:
+            oc.tol_pos, oc.tol_vel, oc.tol_rate = (float(t) for t in tols)
+        if names is None:
+            names = [n for n, _, _ in OUTCOME_FIELDS
+                     if not (n == "settle_step" and tols[0] is None) and not (n == "tset_step" and obj._c.term_rows == 0)
+                     and not (n == "alloc_failed" and not wrench)]
+        arrays = {}
+        for n, w, dt in OUTCOME_FIELDS:
+            if n in names:
+                arrays[n] = np.zeros((B, w) if w else (B,), dt)
+                setattr(oc, n, _ptr(arrays[n], C.c_double if dt is np.float64 else C.c_int32))
+        if len(arrays) != len(names):
+            raise ValueError(f"outcomes: fields must be among {[n for n, _, _ in OUTCOME_FIELDS]}")
+    sh = None
+    if return_status:
+        sh = np.zeros((T, B), np.int32)
+        oc.status_hist = _ptr(sh, C.c_int32)
+    return oc, arrays, sh
+
+
+def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
+              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total):
+    """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
+    N, NT = self.cfg.N, self.cfg.NT
+    x = _f64(x0).reshape(-1, 13).copy()
+    B = x.shape[0]
+    ub = _f64(ub, (B, NT))
+    stuck = _f64(stuck, (B, NT))
+    xr = _f64(xref_traj)
+    if xr.shape != (9, T + N):
+        raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}")
+    xr = np.ascontiguousarray(xr.reshape(-1, order="F"))
+    ur = None
+    if uref_traj is not None:
+        ur = _f64(uref_traj)
+        if ur.shape != (6, T + N):
+            raise ValueError("uref_traj must be 6 x (T+N)")
+        ur = np.ascontiguousarray(ur.reshape(-1, order="F"))
+    nz = _f64(noise, 4)
+    uh = np.empty((T, B, NT)) if return_inputs else None
+    xh = np.empty((T, B, 13)) if return_states else None
+    bad = np.zeros(T, np.int32)
+    ext = faults is not None or return_states      # the entries with a fault schedule and x_hist
+    sched, keep, fh = None, None, None
+    if faults is not None:
+        from .faults import fault_hull_tables, normalize_schedule
+        onset, detect, eub, est = normalize_schedule(faults, B, NT, T, detect_delay)
+        keep = [onset, detect, eub, est]
+        sched = _lib.ftmpc_fault_schedule(struct_size=C.sizeof(_lib.ftmpc_fault_schedule), n_events=onset.shape[1],
+                                          onset=_ptr(onset, C.c_int32), detect=_ptr(detect, C.c_int32), ub=_ptr(eub), stuck=_ptr(est))
+        if formulation == "wrench":
+            if hull is not None and ("ev_set" not in hull or np.shape(hull["ev_set"]) != onset.shape):
+                raise ValueError("with faults `hull` must be None or ft_mpc_amd.faults.fault_hull_tables of the same schedule")
+            fh = fault_hull_tables(self.D, ub, stuck, eub, est, onset) if hull is None else hull
+            hull = fh
+            evs, evb = fh["ev_set"], np.ascontiguousarray(fh["ev_b"], dtype=np.float64)
+            keep += [evs, evb]
+            sched.hull_set, sched.hull_b = _ptr(evs, C.c_int32), _ptr(evb)
+    sp = C.byref(sched) if sched is not None else None
+    if formulation not in ("thruster", "wrench"):
+        raise ValueError("formulation must be 'thruster' or 'wrench'")
+    # the entries with outcomes: asked for, a slice of a campaign, or the multi-GPU driver (which has no others)
+    new = multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
+    oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
+
+    def result(out):
+        if return_states:
+            out["x_hist"] = xh
+        if orec is not None:
+            out["outcomes"] = orec
+        if sh is not None:
+            out["status_hist"] = sh
+        return out
+    pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
+    if formulation == "wrench":
+        from .controllers.tools.input_bounds import hull_tables
+        if hull is None:
+            hull = hull_tables(self.D, ub, stuck)
+        if np.asarray(hull["degenerate"], bool).any():
+            raise ValueError("a vehicle's healthy thrusters do not span R^6: no input hull (use the thruster formulation)")
+        A = np.ascontiguousarray(hull["A"], dtype=np.float64)
+        hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
+        hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
+        abad = np.zeros(T, np.int32)
+        if new:
+            self._check(getattr(self.lib, pre + "wrench_outcomes_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
+        if ext:
+            self._check(self.lib.ftmpc_simulate_wrench_faults_batch(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
+            out = dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+            if return_states:
+                out["x_hist"] = xh
+            return out
+        if sqp_iters:
+            self._check(self.lib.ftmpc_simulate_wrench_batch_ex(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
+            return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+        self._check(self.lib.ftmpc_simulate_wrench_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0],
+                                                         _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
+                                                         C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
+        return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if new:
+        self._check(getattr(self.lib, pre + "outcomes_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc)))
+        return result(dict(x=x, u=uh, not_converged=bad))
+    if ext:
+        self._check(self.lib.ftmpc_simulate_faults_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
+                                                         _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                                                         sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32)))
+        out = dict(x=x, u=uh, not_converged=bad)
+        if return_states:
+            out["x_hist"] = xh
+        return out
+    self._check(self.lib.ftmpc_simulate_batch_ex(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
+                                                 _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                                                 _ptr(uh), _ptr(bad, C.c_int32)))
+    return dict(x=x, u=uh, not_converged=bad)
 
 
 def make_synthetic_batch(B, N, NT, nfault, seed, f_max=F_MAX, omega_des=(0.0, 0.0, 0.6)):

@@ -53,6 +53,8 @@ class MultiGPUMPC:
         self.lib = _lib.load_library()
         self._C = C
         c = BatchedMPC.make_c_config(self.lib, self.cfg)
+        self._c = c
+        self.D = np.array(list(c.D))[:6 * self.cfg.NT].reshape(6, self.cfg.NT)
         if devices is None:
             ids, n = None, 0
         elif isinstance(devices, int):
@@ -120,6 +122,16 @@ class MultiGPUMPC:
         self._check(self.lib.ftmpc_multi_solve_batch(self._h, B, _ptr(x0), _ptr(ub), _ptr(stuck), _ptr(xref), xs, _ptr(uref), us,
                                                      _ptr(warmU), _ptr(u0), _ptr(U), _ptr(status, C.c_int32), _ptr(iters, C.c_int32)))
         return dict(u0=u0, U=U, status=status, iters=iters)
+
+    def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0, return_inputs=False,
+                 sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0, faults=None, detect_delay=0,
+                 return_states=False, outcomes=None, return_status=False):
+        """BatchedMPC.simulate over the device slots (ftmpc_multi_simulate_outcomes_batch / _wrench_outcomes_batch): slot g runs its
+        shard as the slice [lo, hi) of the campaign, so the noise -- and wherever a vehicle's solve does not depend on its batch, every
+        output -- is what one handle computes for the whole batch.  Same arguments and result, without index0 / index_total."""
+        from .batch import _simulate
+        return _simulate(self, True, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
+                         formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, 0, None)
 
     # -- shards resident in HBM between steps ---------------------------------------------------
     def upload(self, x0, ub, stuck, xref, uref=None, warmU=None):

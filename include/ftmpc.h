@@ -462,6 +462,63 @@ int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed);
 
+/*
+ * Per-vehicle outcomes of a fault campaign, reduced on the device while the closed loop runs, so that a caller who wants to know
+ * which vehicles recovered, when, and at what cost needs neither x_hist nor u_hist (3.3 GB at B = 65 536, T = 300, NT = 8; the
+ * records below are 84 bytes per vehicle).  Per loop step t, with x_{t+1} the state after the step (after noise and
+ * renormalisation), e = robot_to_center(x_{t+1})[0:9] - xref_traj[:, t+1] (spiral_model.py:91-109) and ep, ev, ew the Euclidean
+ * norms of e[0:3], e[3:6], e[6:9]:
+ *   err_int        [B*3]  sum_t dt ep^2, sum_t dt ev^2, sum_t dt ew^2, added in step order
+ *   err_max        [B*3]  max_t ep, ev, ew
+ *   impulse        [B*2]  sum_t dt sum_i a_i  and  sum_t dt sum_i c_i, with c_i = ub_i > 0 ? u_i : 0 what was commanded of a live
+ *                         thruster and a_i = c_i + stuck_i what the plant applied (sys_model.py:198-208); ub / stuck are the PLANT's
+ *                         pattern of step t (under a fault schedule: of the last event with onset <= t)
+ *   settle_step    [B]    smallest s in [0, T] with ep <= tol_pos, ev <= tol_vel and ew <= tol_rate at every step t >= s (the last
+ *                         step outside the band + 1): 0 inside throughout, T not settled at the end
+ *   tset_step      [B]    first step t with term_A e <= term_b on all term_rows rows of the handle's config, -1 never.  The rows of
+ *                         the config whether or not terminal_set is on; asked for with term_rows = 0: FTMPC_ERR_ARG
+ *   unsolved       [B]    number of steps whose solve status (the SQP's last QP where an SQP ran) was not 0
+ *   first_unsolved [B]    the first such step, -1 none
+ *   alloc_failed   [B]    wrench form: number of steps whose allocation status was not 0.  Thruster form: FTMPC_ERR_ARG if non-NULL
+ *   status_hist    [T*B]  a history, not a record: the solve status of every instance at every step
+ * Each output is NULL (not wanted) or a HOST buffer of that size.  With every output NULL nothing is added to the loop's launches.
+ * index0 / index_total: this call's vehicles are [index0, index0 + B) of a campaign of index_total vehicles.  The measurement noise
+ * of vehicle b at step t, component i is drawn at counter (t * index_total + index0 + b) * 13 + i, so slices of a campaign run as
+ * separate calls (on other handles, devices or processes) draw exactly what the same vehicles draw in one call over the whole
+ * campaign.  0 / 0 means 0 / B: the call is the campaign, the counter of the entries without this struct.
+ * FTMPC_ERR_ARG, the message naming the field: a struct_size other than sizeof(ftmpc_outcomes); index0 < 0; index_total != 0 with
+ * index0 + B > index_total; settle_step with a tolerance that is not positive and finite.
+ */
+typedef struct ftmpc_outcomes {
+    int32_t struct_size;      /* sizeof(ftmpc_outcomes) */
+    int32_t reserved;
+    int64_t index0, index_total;
+    double tol_pos, tol_vel, tol_rate;   /* settle band; read only when settle_step is asked for */
+    double* err_int;
+    double* err_max;
+    double* impulse;
+    int32_t* settle_step;
+    int32_t* tset_step;
+    int32_t* unsolved;
+    int32_t* first_unsolved;
+    int32_t* alloc_failed;
+    int32_t* status_hist;
+} ftmpc_outcomes;
+
+/* ftmpc_simulate_faults_batch with the outcomes `out` (NULL: exactly ftmpc_simulate_faults_batch). */
+int ftmpc_simulate_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out);
+
+/* ftmpc_simulate_wrench_faults_batch with the outcomes `out` (NULL: exactly ftmpc_simulate_wrench_faults_batch). */
+int ftmpc_simulate_wrench_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                         const ftmpc_outcomes* out);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -536,6 +593,24 @@ int ftmpc_multi_upload(ftmpc_multi* m, int64_t B,
                        const double* warmU);
 int ftmpc_multi_step(ftmpc_multi* m, int32_t steps, int32_t keep_U);
 int ftmpc_multi_download(ftmpc_multi* m, double* out_u0, double* out_U, int32_t* status, int32_t* iters);
+/* The closed loops on the multi-GPU driver: ftmpc_simulate_outcomes_batch / ftmpc_simulate_wrench_outcomes_batch with device slot g
+ * running the vehicles [lo, hi) of ftmpc_multi_shard_bounds as the slice index0 = lo of a campaign of index_total = B, so the result is
+ * what one handle computes for the whole batch wherever a vehicle's solve does not depend on its batch.  Every per-vehicle input
+ * (x, ub, stuck, the call's hull_set / hull_b, the schedule's arrays) is read at the shard's offset; hull_A, the reference
+ * trajectories, the noise amplitudes and the seed are shared.  Per-vehicle outputs land at the shard's offset, the [T, B, ..]
+ * histories row by row, not_converged [T] / alloc_failed [T] are summed over the slots.  `out` may be NULL; its index0 / index_total
+ * must be 0 / 0 or 0 / B (the driver sets them per slot).  More slots than vehicles (B > 0): FTMPC_ERR_ARG.  A failing slot fails the
+ * call with its message. */
+int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out);
+int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                               const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                               int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                               uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

@@ -3,7 +3,9 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
 
     python scripts/fault_campaign_perf.py [--case thruster|wrench64|wrench32|all] [--reps 3] [--json out.json]
     python scripts/fault_campaign_perf.py --once            # one call per case with the schedule (under rocprofv3)
-    python scripts/fault_campaign_perf.py --stats kernel_stats.csv   # the event kernel's share of the kernel time
+    python scripts/fault_campaign_perf.py --stats kernel_stats.csv   # the event and outcome kernels' share of the kernel time
+    python scripts/fault_campaign_perf.py --outcomes        # also the loop with the schedule and every per-vehicle outcome
+    python scripts/fault_campaign_perf.py --slots 2         # every loop on the multi-GPU driver with 2 slots on device 0
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -47,10 +49,15 @@ def batch(c, seed=4040):
     return x0, ub, stuck, dict(onset=onset, ub=eub[:, None], stuck=est[:, None])
 
 
-def run(name, reps, once=False):
+def run(name, reps, once=False, outcomes=False, slots=0):
     import ft_mpc_amd
     c = CASES[name]
-    mpc = ft_mpc_amd.BatchedMPC(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
+    cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
+    if slots > 0:
+        from ft_mpc_amd.sharding import MultiGPUMPC
+        mpc = MultiGPUMPC(cfg, devices=[0] * slots)
+    else:
+        mpc = ft_mpc_amd.BatchedMPC(cfg)
     x0, ub, stuck, f = batch(c)
     B = x0.shape[0]
     xr = np.zeros((9, T + c["N"]))
@@ -62,8 +69,10 @@ def run(name, reps, once=False):
         from ft_mpc_amd.controllers.tools.input_bounds import hull_tables
         plain["hull"] = hull_tables(mpc.D, ub, stuck)
         withf["hull"] = fl.fault_hull_tables(mpc.D, ub, stuck, f["ub"], f["stuck"], f["onset"])
+    # every outcome, the settle band included: 84 bytes per vehicle instead of x_hist + u_hist
+    witho = dict(withf, outcomes=dict(tol_pos=0.5, tol_vel=0.1, tol_rate=0.05))
     if once:
-        mpc.simulate(x0, ub, stuck, xr, T, **withf, **kw)
+        mpc.simulate(x0, ub, stuck, xr, T, **(witho if outcomes else withf), **kw)
         mpc.close()
         return None
     res = {}
@@ -72,8 +81,10 @@ def run(name, reps, once=False):
         h = withf["hull"]
         after["hull"] = dict(A=h["A"], set=h["ev_set"][:, 0], b=np.ascontiguousarray(h["ev_b"][:, 0]), rows=h["rows"],
                              degenerate=np.zeros(B, bool))
-    for label, extra, u, s in (("without", plain, ub, stuck), ("with", withf, ub, stuck),
-                               ("without_after_pattern", after, f["ub"][:, 0], f["stuck"][:, 0])):
+    runs = [("without", plain, ub, stuck), ("with", withf, ub, stuck), ("without_after_pattern", after, f["ub"][:, 0], f["stuck"][:, 0])]
+    if outcomes:
+        runs.append(("with_outcomes", witho, ub, stuck))
+    for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
         mpc.simulate(x0, u, s, xr, T, **extra, **kw)          # warm-up: workspaces, code objects, grid hints
         ts = []
@@ -86,7 +97,11 @@ def run(name, reps, once=False):
                           alloc_failed=int(out.get("alloc_failed", np.zeros(1)).sum()))
     mpc.close()
     res["ratio_with_over_without"] = res["with"]["steps_per_s"] / res["without"]["steps_per_s"]
-    res.update(case=name, B=B, T=T, **{k: c[k] for k in ("N", "NT", "dtype", "formulation")})
+    if outcomes:
+        res["ratio_outcomes_over_with"] = res["with_outcomes"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["history_bytes"] = T * B * (13 + c["NT"]) * 8
+        res["outcome_bytes"] = B * (8 * 8 + 5 * 4)
+    res.update(case=name, B=B, T=T, slots=slots, **{k: c[k] for k in ("N", "NT", "dtype", "formulation")})
     return res
 
 
@@ -97,8 +112,13 @@ def stats(path):
     ev = [r for r in rows if "ftmpc_fault_event_kernel" in r["Name"]]
     evt = sum(float(r["TotalDurationNs"]) for r in ev)
     calls = sum(int(r["Calls"]) for r in ev)
+    oc = [r for r in rows if "ftmpc_outcome_kernel" in r["Name"]]
+    oct_ = sum(float(r["TotalDurationNs"]) for r in oc)
+    ocalls = sum(int(r["Calls"]) for r in oc)
     return dict(total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
-                event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0)
+                event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0,
+                outcome_kernel_ms=oct_ * 1e-6, outcome_kernel_calls=ocalls, outcome_kernel_avg_us=(oct_ / ocalls * 1e-3) if ocalls else 0.0,
+                outcome_kernel_share=oct_ / tot if tot else 0.0)
 
 
 def main():
@@ -108,6 +128,8 @@ def main():
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--stats", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--outcomes", action="store_true")
+    ap.add_argument("--slots", type=int, default=0)
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -115,7 +137,7 @@ def main():
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
