@@ -623,7 +623,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 500; }
+int32_t ftmpc_version(void) { return 510; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -1945,7 +1945,49 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
-                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr);
+                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr);
+
+// A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
+// message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string plant_model_problem(const ftmpc_plant_model* pm, int64_t B, int NT, int64_t first = 0) {
+    if (!pm) return "";
+    if (pm->struct_size != (int32_t)sizeof(ftmpc_plant_model))
+        return "ftmpc_plant_model.struct_size is " + std::to_string(pm->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_plant_model));
+    auto at = [first](const char* field, int64_t b, const std::string& what) {
+        return std::string("ftmpc_plant_model.") + field + ": vehicle " + std::to_string(first + b) + " " + what;
+    };
+    if (pm->mass)
+        for (int64_t b = 0; b < B; ++b)
+            if (!std::isfinite(pm->mass[b]) || !(pm->mass[b] > 0.0)) return at("mass", b, "is not finite and positive");
+    if (pm->J)
+        for (int64_t b = 0; b < B; ++b) {
+            const double* J = pm->J + b * 9;
+            double big = 0.0;
+            for (int k = 0; k < 9; ++k) {
+                if (!std::isfinite(J[k])) return at("J", b, "has a non-finite entry");
+                big = std::max(big, std::fabs(J[k]));
+            }
+            for (int i = 0; i < 3; ++i)
+                for (int j = i + 1; j < 3; ++j)
+                    if (std::fabs(J[3 * i + j] - J[3 * j + i]) > 1e-12 * big) return at("J", b, "is not symmetric");
+            const double m2 = J[0] * J[4] - J[1] * J[3];
+            const double m3 = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
+            if (!(J[0] > 0.0) || !(m2 > 0.0) || !(m3 > 0.0)) return at("J", b, "is not positive definite");
+        }
+    const double* const arr[3] = {pm->D, pm->force, pm->torque};
+    const char* const name[3] = {"D", "force", "torque"};
+    const int64_t per[3] = {6 * (int64_t)NT, 3, 3};
+    for (int a = 0; a < 3; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < B * per[a]; ++i)
+                if (!std::isfinite(arr[a][i])) return at(name[a], i / per[a], "has a non-finite entry");
+    return "";
+}
+static int check_plant(ftmpc_handle* h, int64_t B, const ftmpc_plant_model* pm) {
+    const std::string msg = plant_model_problem(pm, B, h->cfg.NT);
+    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
 
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
 static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
@@ -2029,17 +2071,27 @@ int ftmpc_simulate_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double*
                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
+    return ftmpc_simulate_plant_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                      x_hist, not_converged, out, nullptr);
+}
+
+int ftmpc_simulate_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                               const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                               int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                               double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                               const ftmpc_plant_model* plant) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     int rc = check_schedule(h, B, faults, false, 0, false);
     if (rc != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
+    if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) return FTMPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out);
+                         faults, x_hist, out, plant);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2058,17 +2110,29 @@ int ftmpc_simulate_wrench_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, 
                                          int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                          double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                          const ftmpc_outcomes* out) {
+    return ftmpc_simulate_wrench_plant_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                             seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                             out, nullptr);
+}
+
+int ftmpc_simulate_wrench_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                      int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                      double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                      const ftmpc_outcomes* out, const ftmpc_plant_model* plant) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
     if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
+    if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) return FTMPC_OK;
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2118,7 +2182,7 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
-                         const ftmpc_outcomes* oc) {
+                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2137,6 +2201,72 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     const bool want_out = want_rec || (oc && oc->status_hist);
     DevBuf<double> d_orec, d_oterm;
     DevBuf<int32_t> d_oint, d_shist;
+    // plant model (checked by the entry): the arrays that are given, transposed to component-major [k][B] on the host (the layout of
+    // ftmpc::PlantVar), 1 / m_b and J_b^-1 computed here, once per call; the host copies live until the stream is drained
+    const bool var_plant = pm && (pm->mass || pm->J || pm->D || pm->force || pm->torque);
+    DevBuf<double> d_pim, d_pJ, d_pD, d_pf, d_pt;
+    std::vector<double> h_pim, h_pJ, h_pD, h_pf, h_pt;
+    ftmpc::PlantVar pv{};
+    if (var_plant) {
+        // dst [K][B] = src [B][K]^T, 64 vehicles at a time so that each of the K write streams fills whole cache lines
+        auto transpose = [B](const double* src, int64_t K, double* dst) {
+            for (int64_t b0 = 0; b0 < B; b0 += 64) {
+                const int64_t b1 = std::min(B, b0 + 64);
+                for (int64_t k = 0; k < K; ++k)
+                    for (int64_t b = b0; b < b1; ++b) dst[k * B + b] = src[b * K + k];
+            }
+        };
+        auto upload = [&](DevBuf<double>& d, const std::vector<double>& v) -> int {
+            HIP_TRY(h, hipMalloc(&d.p, v.size() * sizeof(double)));
+            HIP_TRY(h, hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            return FTMPC_OK;
+        };
+        try {
+            if (pm->mass) {
+                h_pim.resize((size_t)B);
+                for (int64_t b = 0; b < B; ++b) h_pim[b] = 1.0 / pm->mass[b];
+            }
+            if (pm->J) {
+                h_pJ.resize((size_t)B * 18);
+                for (int64_t b = 0; b < B; ++b) {
+                    const double* J = pm->J + b * 9;
+                    const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
+                    const double idet = 1.0 / (J[0] * c00 + J[1] * c01 + J[2] * c02);
+                    const double inv[9] = {c00 * idet, (J[2] * J[7] - J[1] * J[8]) * idet, (J[1] * J[5] - J[2] * J[4]) * idet,
+                                           c01 * idet, (J[0] * J[8] - J[2] * J[6]) * idet, (J[2] * J[3] - J[0] * J[5]) * idet,
+                                           c02 * idet, (J[1] * J[6] - J[0] * J[7]) * idet, (J[0] * J[4] - J[1] * J[3]) * idet};
+                    for (int k = 0; k < 9; ++k) {
+                        h_pJ[(size_t)k * B + b] = J[k];
+                        h_pJ[(size_t)(9 + k) * B + b] = inv[k];
+                    }
+                }
+            }
+            if (pm->D) {
+                h_pD.resize((size_t)B * 6 * NT);
+                transpose(pm->D, 6 * (int64_t)NT, h_pD.data());
+            }
+            if (pm->force) {
+                h_pf.resize((size_t)B * 3);
+                transpose(pm->force, 3, h_pf.data());
+            }
+            if (pm->torque) {
+                h_pt.resize((size_t)B * 3);
+                transpose(pm->torque, 3, h_pt.data());
+            }
+        } catch (const std::bad_alloc&) {
+            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the plant model's staging arrays");
+        }
+        if (pm->mass && (rc = upload(d_pim, h_pim)) != FTMPC_OK) return rc;
+        if (pm->J && (rc = upload(d_pJ, h_pJ)) != FTMPC_OK) return rc;
+        if (pm->D && (rc = upload(d_pD, h_pD)) != FTMPC_OK) return rc;
+        if (pm->force && (rc = upload(d_pf, h_pf)) != FTMPC_OK) return rc;
+        if (pm->torque && (rc = upload(d_pt, h_pt)) != FTMPC_OK) return rc;
+        pv.inv_mass = d_pim;
+        pv.J = d_pJ;
+        pv.D = d_pD;
+        pv.force = d_pf;
+        pv.torque = d_pt;
+    }
     HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
     if (uref_traj) HIP_TRY(h, hipMalloc(&d_ur.p, (size_t)ncol * 6 * sizeof(double)));
     if (!wl) HIP_TRY(h, hipMalloc(&d_warmB.p, (size_t)B * N * NT * sizeof(double)));
@@ -2301,7 +2431,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         }
         if (rc != FTMPC_OK) return rc;
         sp.step = t;
-        hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
+        if (var_plant)
+            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_var_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv);
+        else
+            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
         if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
             op.step = t;
             op.ub = sp.ub;

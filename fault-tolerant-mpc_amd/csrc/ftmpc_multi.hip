@@ -204,7 +204,7 @@ void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_
     for (int64_t t = 0; t < T; ++t) std::memcpy(dst + (t * B + lo) * w, src + t * n * w, (size_t)(n * w) * sizeof(V));
 }
 
-// The closed loops over the device slots (ftmpc_multi_simulate_outcomes_batch / _wrench_outcomes_batch; hull_A == nullptr: the thruster
+// The closed loops over the device slots (ftmpc_multi_simulate_plant_batch / _wrench_plant_batch; hull_A == nullptr: the thruster
 // form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
 // caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
 // staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
@@ -212,7 +212,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows, const double* xref_traj,
                    const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                   int32_t* alloc_failed, const ftmpc_outcomes* out, bool wrench) {
+                   int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, bool wrench) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -227,6 +227,10 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
     if (faults && faults->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return refuse("ftmpc_fault_schedule: bad struct_size");
     if (faults && (faults->n_events < 0 || faults->n_events > FTMPC_MAX_FAULT_EVENTS))
         return refuse("ftmpc_fault_schedule: n_events outside [0, FTMPC_MAX_FAULT_EVENTS]");
+    {     // the plant model over the whole batch, so that a refusal names the vehicle by its number in the caller's arrays
+        const std::string msg = plant_model_problem(plant, B, m->cfg.NT);
+        if (!msg.empty()) return refuse(msg);
+    }
     if (B == 0 || T == 0) return FTMPC_OK;
     const int G = (int)m->dev.size();
     if (G > B) return refuse("more device slots (" + std::to_string(G) + ") than vehicles (B = " + std::to_string(B) + ")");
@@ -247,6 +251,15 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (fs.stuck) fs.stuck += lo * E * NT;
             if (fs.hull_set) fs.hull_set += lo * E;
             if (fs.hull_b) fs.hull_b += lo * E * hull_rows;
+        }
+        ftmpc_plant_model pl{};
+        if (plant) {
+            pl = *plant;
+            if (pl.mass) pl.mass += lo;
+            if (pl.J) pl.J += lo * 9;
+            if (pl.D) pl.D += lo * 6 * NT;
+            if (pl.force) pl.force += lo * 3;
+            if (pl.torque) pl.torque += lo * 3;
         }
         ftmpc_outcomes oc{};
         oc.struct_size = (int32_t)sizeof(ftmpc_outcomes);
@@ -280,14 +293,14 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         }
         double* const uh_p = !u_hist ? nullptr : (whole ? u_hist : uh.data());
         double* const xh_p = !x_hist ? nullptr : (whole ? x_hist : xh.data());
-        const int rc2 = wrench ? ftmpc_simulate_wrench_outcomes_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
-                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
-                                                                      xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
-                                                                      faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
-                                                                      alloc_failed ? abad[g].data() : nullptr, &oc)
-                               : ftmpc_simulate_outcomes_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
-                                                               seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                               bad[g].data(), &oc);
+        const int rc2 = wrench ? ftmpc_simulate_wrench_plant_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+                                                                   hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
+                                                                   xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
+                                                                   faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
+                                                                   alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr)
+                               : ftmpc_simulate_plant_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                            seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                            bad[g].data(), &oc, plant ? &pl : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -531,7 +544,16 @@ int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, false);
+}
+
+int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, false);
 }
 
 int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -541,7 +563,18 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, true);
+}
+
+int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                            uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                            const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                            int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                            const ftmpc_plant_model* plant) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, true);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

@@ -503,4 +503,109 @@ __global__ void __launch_bounds__(64) ftmpc_outcome_kernel(const DeviceConsts C,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Plant dispersion (ftmpc_simulate_plant_batch / ftmpc_simulate_wrench_plant_batch; include/ftmpc.h, ftmpc_plant_model): vehicle b's
+// plant has its own mass m_b, inertia J_b, allocation matrix D_b, a constant disturbance force f_b (inertial frame) and torque t_b
+// (body frame), while the controller keeps the model of DeviceConsts:
+//   [F; tau] = D_b a      v' = (Rot(q)^T F + f_b) / m_b      w' = J_b^-1 (tau + t_b - w x J_b w)      p', q' as plant_f
+// ftmpc_plant_step_var_kernel is ftmpc_plant_step_kernel with that right-hand side (same noise, counter, renormalisation, histories
+// and bad_count); it is launched in its place only when the call's plant model has at least one array.  (It stands at the end of the
+// file, not beside the kernel it generalises, so that the build logs keep the source lines of every kernel above.)
+// The arrays are component-major, [k][B]: lane b reads base + k * B + b, so a wave's load covers 512 contiguous bytes (the C ABI is
+// vehicle-major; the host transposes once per call while staging, and inverts m_b and J_b there).  A null array is a wave-uniform
+// branch to the DeviceConsts value.
+// ---------------------------------------------------------------------------------------------------------
+struct PlantVar {
+    const double* inv_mass;   // nullptr or [B]       1 / m_b
+    const double* J;          // nullptr or [18][B]   J_b row-major, then J_b^-1 row-major
+    const double* D;          // nullptr or [6*NT][B] k = g * NT + i
+    const double* force;      // nullptr or [3][B]
+    const double* torque;     // nullptr or [3][B]
+};
+
+namespace {
+// plant_f with the vehicle's own 1 / m, J, J^-1 and the acceleration fm = f_b / m_b of the disturbance force; the disturbance torque
+// is constant over the step in the body frame, so the caller has added it to gen[3..5]
+__device__ __forceinline__ void plant_f_var(const double inv_mass, const double* J, const double* Jinv, const double* fm, const double* x,
+                                            const double* gen, double* dx) {
+    const double *v = x + 3, *q = x + 6, *w = x + 10;
+    dx[0] = v[0]; dx[1] = v[1]; dx[2] = v[2];
+    const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
+    const double R00 = qx * qx - qy * qy - qz * qz + qw * qw, R01 = 2 * (qx * qy + qz * qw), R02 = 2 * (qx * qz - qy * qw);
+    const double R10 = 2 * (qx * qy - qz * qw), R11 = -qx * qx + qy * qy - qz * qz + qw * qw, R12 = 2 * (qy * qz + qx * qw);
+    const double R20 = 2 * (qx * qz + qy * qw), R21 = 2 * (qy * qz - qx * qw), R22 = -qx * qx - qy * qy + qz * qz + qw * qw;
+    const double f0 = gen[0] * inv_mass, f1 = gen[1] * inv_mass, f2 = gen[2] * inv_mass;
+    dx[3] = R00 * f0 + R10 * f1 + R20 * f2 + fm[0];
+    dx[4] = R01 * f0 + R11 * f1 + R21 * f2 + fm[1];
+    dx[5] = R02 * f0 + R12 * f1 + R22 * f2 + fm[2];
+    dx[6] = 0.5 * (w[2] * qy - w[1] * qz + w[0] * qw);
+    dx[7] = 0.5 * (-w[2] * qx + w[0] * qz + w[1] * qw);
+    dx[8] = 0.5 * (w[1] * qx - w[0] * qy + w[2] * qw);
+    dx[9] = 0.5 * (-w[0] * qx - w[1] * qy - w[2] * qz);
+    double Jw[3], t[3];
+    for (int i = 0; i < 3; ++i) Jw[i] = J[3 * i] * w[0] + J[3 * i + 1] * w[1] + J[3 * i + 2] * w[2];
+    t[0] = gen[3] - (w[1] * Jw[2] - w[2] * Jw[1]);
+    t[1] = gen[4] - (w[2] * Jw[0] - w[0] * Jw[2]);
+    t[2] = gen[5] - (w[0] * Jw[1] - w[1] * Jw[0]);
+    for (int i = 0; i < 3; ++i) dx[10 + i] = Jinv[3 * i] * t[0] + Jinv[3 * i + 1] * t[1] + Jinv[3 * i + 2] * t[2];
+}
+}  // namespace
+
+__global__ void __launch_bounds__(64) ftmpc_plant_step_var_kernel(const DeviceConsts C, const SimParams S, const PlantVar V) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t B = S.B;
+    if (b >= B) return;
+    const int NT = C.NT;
+    double gen[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < NT; ++i) {
+        const double u = S.u0[b * NT + i];
+        if (S.u_hist) S.u_hist[(S.step * B + b) * NT + i] = u;
+        const double t = (S.ub[b * NT + i] > 0.0 ? u : 0.0) + S.stuck[b * NT + i];   // sys_model.py:198-208
+        if (V.D) {
+            for (int g = 0; g < 6; ++g) gen[g] += V.D[(int64_t)(g * NT + i) * B + b] * t;
+        } else {
+            for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * t;
+        }
+    }
+    double J[9], Jinv[9], fm[3] = {0, 0, 0};
+    const double inv_mass = V.inv_mass ? V.inv_mass[b] : C.inv_mass;
+    if (V.J) {
+        for (int k = 0; k < 9; ++k) {
+            J[k] = V.J[k * B + b];
+            Jinv[k] = V.J[(9 + k) * B + b];
+        }
+    } else {
+        for (int k = 0; k < 9; ++k) {
+            J[k] = C.J[k];
+            Jinv[k] = C.Jinv[k];
+        }
+    }
+    if (V.force)
+        for (int k = 0; k < 3; ++k) fm[k] = V.force[k * B + b] * inv_mass;
+    if (V.torque)
+        for (int k = 0; k < 3; ++k) gen[3 + k] += V.torque[k * B + b];
+    double x[13], k1[13], k2[13], k3[13], k4[13], s[13];
+    for (int i = 0; i < 13; ++i) x[i] = S.x[b * 13 + i];
+    const double dt = C.dt;
+    plant_f_var(inv_mass, J, Jinv, fm, x, gen, k1);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k1[i];
+    plant_f_var(inv_mass, J, Jinv, fm, s, gen, k2);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k2[i];
+    plant_f_var(inv_mass, J, Jinv, fm, s, gen, k3);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + dt * k3[i];
+    plant_f_var(inv_mass, J, Jinv, fm, s, gen, k4);
+    for (int i = 0; i < 13; ++i) x[i] += dt / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    // noise, renormalisation, histories and bad_count exactly as ftmpc_plant_step_kernel
+    for (int i = 0; i < 13; ++i) {
+        const double a = i < 3 ? S.noise[0] : (i < 6 ? S.noise[1] : (i < 10 ? S.noise[2] : S.noise[3]));
+        if (a > 0.0) x[i] += a * u01(S.seed, (unsigned long long)((S.step * S.index_total + S.index0 + b) * 13 + i));
+    }
+    const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
+    for (int i = 6; i < 10; ++i) x[i] *= qn;
+    for (int i = 0; i < 13; ++i) S.x[b * 13 + i] = x[i];
+    if (S.x_hist)
+        for (int i = 0; i < 13; ++i) S.x_hist[(S.step * B + b) * 13 + i] = x[i];
+    if (S.bad_count && S.status && S.status[b] != 0) atomicAdd(&S.bad_count[S.step], 1);
+}
+
 }  // namespace ftmpc

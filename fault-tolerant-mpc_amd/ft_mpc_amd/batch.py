@@ -446,7 +446,8 @@ class BatchedMPC:
     # -- closed loop on the device (SimulationEnvironment.run_simulation, batched) ------------
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
-                 faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None):
+                 faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
+                 plant=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -465,10 +466,14 @@ class BatchedMPC:
         return_status: also status_hist [T,B], the solve status of every vehicle at every step.  index0 / index_total: the call's
         vehicles are [index0, index0 + B) of a campaign of index_total; the noise is then what the same vehicles draw in one call over
         the whole campaign (default: the call is the campaign).
+        plant: the plant the loop integrates, per vehicle (include/ftmpc.h, ftmpc_plant_model; ft_mpc_amd.dispersion.sample draws one):
+        a dict with any of mass [B], J [B,3,3], D [B,6,NT], force [B,3] (inertial frame), torque [B,3] (body frame); a key that is
+        missing takes the config's value (zero for the disturbances).  The controller keeps the nominal model.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
         [, status_hist])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
-                         formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total)
+                         formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
+                         plant)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -574,8 +579,31 @@ def _outcome_request(obj, B, T, wrench, outcomes, return_status, index0, index_t
     return oc, arrays, sh
 
 
+PLANT_FIELDS = (("mass", ()), ("J", (3, 3)), ("D", (6, None)), ("force", (3,)), ("torque", (3,)))      # None: NT
+
+
+def _plant_request(plant, B, NT):
+    """The ftmpc_plant_model struct of a simulate call and the arrays it points into (kept alive by the caller)."""
+    spec = dict(plant)
+    pm = _lib.ftmpc_plant_model(struct_size=C.sizeof(_lib.ftmpc_plant_model))
+    keep = []
+    for name, tail in PLANT_FIELDS:
+        a = spec.pop(name, None)
+        if a is None:
+            continue
+        shape = (B,) + tuple(NT if d is None else d for d in tail)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"plant[{name!r}] must have shape {shape}, not {a.shape}")
+        keep.append(a)
+        setattr(pm, name, _ptr(a))
+    if spec:
+        raise ValueError(f"plant: unknown keys {sorted(spec)}")
+    return pm, keep
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
-              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total):
+              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -615,8 +643,10 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     sp = C.byref(sched) if sched is not None else None
     if formulation not in ("thruster", "wrench"):
         raise ValueError("formulation must be 'thruster' or 'wrench'")
-    # the entries with outcomes: asked for, a slice of a campaign, or the multi-GPU driver (which has no others)
-    new = multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
+    # the entries with outcomes: asked for, a slice of a campaign, the multi-GPU driver (which has no others), or a plant model (whose
+    # entries take the outcomes struct too)
+    pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
+    new = multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None or pm is not None
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     def result(out):
@@ -638,6 +668,12 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if pm is not None:
+            self._check(getattr(self.lib, pre + "wrench_plant_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), C.byref(pm)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if new:
             self._check(getattr(self.lib, pre + "wrench_outcomes_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -663,6 +699,11 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if pm is not None:
+        self._check(getattr(self.lib, pre + "plant_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), C.byref(pm)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if new:
         self._check(getattr(self.lib, pre + "outcomes_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

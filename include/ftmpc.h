@@ -519,6 +519,52 @@ int ftmpc_simulate_wrench_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, 
                                          double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                          const ftmpc_outcomes* out);
 
+/*
+ * Plant dispersion: the plant that the closed loop integrates, per vehicle, while the CONTROLLER keeps the nominal model of the
+ * handle's config everywhere (linearisation, cost, hulls, allocation, robot_to_center, the reference of the outcomes).  Vehicle b has
+ * a plant mass m_b, a plant inertia J_b (3 x 3, symmetric positive definite), a plant allocation matrix D_b (6 x NT), a constant
+ * disturbance force f_b in the inertial frame and a constant disturbance torque t_b in the body frame.  With
+ * a_i = (ub_i > 0 ? u_i : 0) + stuck_i, exactly as without this struct and taken from the plant's pattern of that step under a fault
+ * schedule:
+ *   [F; tau] = D_b a
+ *   p' = v
+ *   v' = (Rot(q)^T F + f_b) / m_b
+ *   q' = 1/2 Omega(w) q
+ *   w' = J_b^-1 (tau + t_b - w x J_b w)
+ * RK4 over dt holds a, f_b and t_b constant.  The noise, its counter, the renormalisation, u_hist, x_hist and not_converged are those
+ * of the entries without this struct.  An array that is NULL takes the handle's value for every vehicle: cfg.mass, cfg.J, cfg.D,
+ * zero force, zero torque.  `impulse` of ftmpc_outcomes keeps its meaning of thruster force a_i: a gain error of a thruster lives in
+ * D_b (a scaled column), not in a.  All arrays are HOST buffers, vehicle-major, so a shard of a campaign is a pointer offset.
+ * plant = NULL, or a struct whose five arrays are all NULL, launches exactly the kernels of the _outcomes_ entries.
+ * FTMPC_ERR_ARG, the message naming the field and the first offending vehicle: a struct_size other than sizeof(ftmpc_plant_model); a
+ * mass that is not finite or not positive; a J that is not finite, not symmetric to 1e-12 of its largest entry or not positive
+ * definite (leading minors); a non-finite entry of D, force or torque.
+ */
+typedef struct ftmpc_plant_model {
+    int32_t struct_size;   /* sizeof(ftmpc_plant_model) */
+    int32_t reserved;
+    const double* mass;    /* NULL or [B]        > 0, finite */
+    const double* J;       /* NULL or [B*9]      row-major, symmetric positive definite */
+    const double* D;       /* NULL or [B*6*NT]   row-major 6 x NT per vehicle, row stride NT */
+    const double* force;   /* NULL or [B*3]      inertial frame */
+    const double* torque;  /* NULL or [B*3]      body frame */
+} ftmpc_plant_model;
+
+/* ftmpc_simulate_outcomes_batch with the plant model `plant` (NULL: exactly ftmpc_simulate_outcomes_batch). */
+int ftmpc_simulate_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                               const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                               int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                               double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                               const ftmpc_plant_model* plant);
+
+/* ftmpc_simulate_wrench_outcomes_batch with the plant model `plant` (NULL: exactly ftmpc_simulate_wrench_outcomes_batch). */
+int ftmpc_simulate_wrench_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                      int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                      double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                      const ftmpc_outcomes* out, const ftmpc_plant_model* plant);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -611,6 +657,21 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out);
+/* The two entries above with the plant model `plant` (ftmpc_plant_model; NULL: exactly the entries above).  Every array of the struct
+ * is read at the shard's offset: mass + lo, J + 9 lo, D + 6 NT lo, force + 3 lo, torque + 3 lo.  A refusal names the vehicle by its
+ * number in the whole batch. */
+int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant);
+int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                            uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                            const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                            int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                            const ftmpc_plant_model* plant);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

@@ -6,11 +6,16 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --stats kernel_stats.csv   # the event and outcome kernels' share of the kernel time
     python scripts/fault_campaign_perf.py --outcomes        # also the loop with the schedule and every per-vehicle outcome
     python scripts/fault_campaign_perf.py --slots 2         # every loop on the multi-GPU driver with 2 slots on device 0
+    python scripts/fault_campaign_perf.py --dispersion      # also the loops with a dispersed plant (BatchedMPC.simulate(plant=...))
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
 Cases: thruster form N = 20, NT = 8, B = 65 536, fp32, T = 20; wrench form N = 15, NT = 16, B = 16 384, T = 20 on an fp32 and a
-float64 handle (vehicles whose hull would be flat in either pattern are dropped from both runs)."""
+float64 handle (vehicles whose hull would be flat in either pattern are dropped from both runs).
+--dispersion: the loops without and with the schedule once more with ft_mpc_amd.dispersion.sample at mass 10 %, inertia 10 %, gain 5 %,
+centre of mass 1 cm, force 0.05 N, torque 0.005 N m (ftmpc_plant_step_var_kernel in place of ftmpc_plant_step_kernel); with --once it
+makes one call with the dispersed plant and one without, so that a kernel_stats.csv of that run holds both plant kernels, and --stats
+reports the time per launch of each."""
 import argparse
 import csv
 import json
@@ -49,7 +54,10 @@ def batch(c, seed=4040):
     return x0, ub, stuck, dict(onset=onset, ub=eub[:, None], stuck=est[:, None])
 
 
-def run(name, reps, once=False, outcomes=False, slots=0):
+DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
+
+
+def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -71,7 +79,13 @@ def run(name, reps, once=False, outcomes=False, slots=0):
         withf["hull"] = fl.fault_hull_tables(mpc.D, ub, stuck, f["ub"], f["stuck"], f["onset"])
     # every outcome, the settle band included: 84 bytes per vehicle instead of x_hist + u_hist
     witho = dict(withf, outcomes=dict(tol_pos=0.5, tol_vel=0.1, tol_rate=0.05))
+    plant = None
+    if dispersion:
+        from ft_mpc_amd.dispersion import sample
+        plant = sample(B, c["NT"], mpc.D, cfg.J, cfg.mass, seed=17, **DISPERSION)
     if once:
+        if dispersion:
+            mpc.simulate(x0, ub, stuck, xr, T, plant=plant, **(witho if outcomes else withf), **kw)
         mpc.simulate(x0, ub, stuck, xr, T, **(witho if outcomes else withf), **kw)
         mpc.close()
         return None
@@ -84,6 +98,8 @@ def run(name, reps, once=False, outcomes=False, slots=0):
     runs = [("without", plain, ub, stuck), ("with", withf, ub, stuck), ("without_after_pattern", after, f["ub"][:, 0], f["stuck"][:, 0])]
     if outcomes:
         runs.append(("with_outcomes", witho, ub, stuck))
+    if dispersion:
+        runs += [("without_dispersed", dict(plain, plant=plant), ub, stuck), ("with_dispersed", dict(withf, plant=plant), ub, stuck)]
     for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
         mpc.simulate(x0, u, s, xr, T, **extra, **kw)          # warm-up: workspaces, code objects, grid hints
@@ -101,6 +117,10 @@ def run(name, reps, once=False, outcomes=False, slots=0):
         res["ratio_outcomes_over_with"] = res["with_outcomes"]["steps_per_s"] / res["with"]["steps_per_s"]
         res["history_bytes"] = T * B * (13 + c["NT"]) * 8
         res["outcome_bytes"] = B * (8 * 8 + 5 * 4)
+    if dispersion:
+        res["ratio_dispersed_over_without"] = res["without_dispersed"]["steps_per_s"] / res["without"]["steps_per_s"]
+        res["ratio_dispersed_over_with"] = res["with_dispersed"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["plant_model_bytes"] = int(sum(a.nbytes for a in plant.values()))
     res.update(case=name, B=B, T=T, slots=slots, **{k: c[k] for k in ("N", "NT", "dtype", "formulation")})
     return res
 
@@ -115,7 +135,14 @@ def stats(path):
     oc = [r for r in rows if "ftmpc_outcome_kernel" in r["Name"]]
     oct_ = sum(float(r["TotalDurationNs"]) for r in oc)
     ocalls = sum(int(r["Calls"]) for r in oc)
-    return dict(total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
+    def per_launch(kernel):      # "name(" so that ftmpc_plant_step_kernel does not also count ftmpc_plant_step_var_kernel
+        k = [r for r in rows if kernel + "(" in r["Name"]]
+        n = sum(int(r["Calls"]) for r in k)
+        return n, (sum(float(r["TotalDurationNs"]) for r in k) / n * 1e-3) if n else 0.0
+    pn, pus = per_launch("ftmpc_plant_step_kernel")
+    vn, vus = per_launch("ftmpc_plant_step_var_kernel")
+    return dict(plant_kernel_calls=pn, plant_kernel_avg_us=pus, plant_var_kernel_calls=vn, plant_var_kernel_avg_us=vus,
+                total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
                 event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0,
                 outcome_kernel_ms=oct_ * 1e-6, outcome_kernel_calls=ocalls, outcome_kernel_avg_us=(oct_ / ocalls * 1e-3) if ocalls else 0.0,
                 outcome_kernel_share=oct_ / tot if tot else 0.0)
@@ -130,6 +157,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--outcomes", action="store_true")
     ap.add_argument("--slots", type=int, default=0)
+    ap.add_argument("--dispersion", action="store_true")
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -137,7 +165,7 @@ def main():
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once, a.outcomes, a.slots)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
