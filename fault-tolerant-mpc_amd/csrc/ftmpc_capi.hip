@@ -623,7 +623,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 510; }
+int32_t ftmpc_version(void) { return 520; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -1199,7 +1199,11 @@ static int sqp_record(ftmpc_handle* h, int64_t B, const double* d_xref, int64_t 
 // close, count): ~300 launches of mostly tiny kernels for ten major iterations, launch-bound on small batches.  A call that repeats
 // the previous call's shape (batch, buffers, strides, counts, constants; no reallocation in between) is recorded into a hipGraph and
 // every further one replays it with ONE launch (small batches; see FTMPC_SQP_GRAPH below).  Profiling or a failed capture leave the
-// direct launches.  (The closed loop of ftmpc_simulate_batch_ex moves its reference pointer every step: direct launches.)
+// direct launches.  A closed loop with the shared reference moves its reference pointer every step: direct launches.  Under a mission
+// with tables (simulate_core) the reference is the call's window buffer, the same pointer at every step, so such a loop replays its
+// graph from the third step on.  The recorded graph then holds pointers to buffers of that CALL (windows, warm start), which are
+// freed when it returns; it is replayed only on a key match, and the key holds those pointers, the batch and the strides: a later call
+// matches only if its own live buffers sit at the same addresses, and their sizes follow from B and the config, so they are the same.
 static int sqp_enqueue(ftmpc_handle* h, int64_t B, const double* d_xref, int64_t xref_stride, const double* d_uref, int64_t uref_stride,
                        const double* d_warm, int32_t sqp_iters, int32_t backtracks, double tol, ftmpc::SqpState& S, double** J0_out) {
     const int64_t nw = (int64_t)h->cfg.N * h->cfg.NT;
@@ -1945,7 +1949,8 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
-                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr);
+                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
+                         const ftmpc_mission* ms = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -1987,6 +1992,62 @@ static std::string plant_model_problem(const ftmpc_plant_model* pm, int64_t B, i
 static int check_plant(ftmpc_handle* h, int64_t B, const ftmpc_plant_model* pm) {
     const std::string msg = plant_model_problem(pm, B, h->cfg.NT);
     return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
+
+// A mission's layout and values (include/ftmpc.h, ftmpc_mission) over the vehicles [0, B) of a loop of T steps with horizon N, together
+// with the call's own xref_traj / uref_traj: empty when acceptable, else the message, which names the field and, where there is one,
+// the first offending vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T, int N, const double* xref_traj, const double* uref_traj,
+                                   int64_t first = 0) {
+    if (!ms) return xref_traj ? "" : "null buffer or negative size";
+    if (ms->struct_size != (int32_t)sizeof(ftmpc_mission))
+        return "ftmpc_mission.struct_size is " + std::to_string(ms->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_mission));
+    if (ms->n_tables < 0) return "ftmpc_mission.n_tables is negative";
+    if (ms->n_tables == 0) {
+        if (!xref_traj) return "ftmpc_mission.n_tables = 0: every vehicle tracks the call's xref_traj, which is NULL";
+        if (ms->table) return "ftmpc_mission.table is given, but n_tables = 0 (no table to choose from)";
+        if (ms->offset) return "ftmpc_mission.offset is given, but n_tables = 0 (the call's xref_traj has no start column)";
+        return "";
+    }
+    const int64_t K = ms->n_tables, C = ms->n_cols, need = (int64_t)T + N;
+    if (!ms->xref) return "ftmpc_mission.xref is NULL with n_tables = " + std::to_string(K);
+    if (C < need)
+        return "ftmpc_mission.n_cols = " + std::to_string(C) + " is below T + N = " + std::to_string(need);
+    if (xref_traj) return "ftmpc_mission.n_tables > 0: the call's xref_traj must be NULL (the tables are the reference)";
+    if (uref_traj) return "ftmpc_mission.n_tables > 0: the call's uref_traj must be NULL (ftmpc_mission.uref holds the tables' uref)";
+    auto at = [first](const char* field, int64_t b, const std::string& what) {
+        return std::string("ftmpc_mission.") + field + ": vehicle " + std::to_string(first + b) + " " + what;
+    };
+    if (ms->table)
+        for (int64_t b = 0; b < B; ++b)
+            if (ms->table[b] < 0 || ms->table[b] >= K)
+                return at("table", b, "has table " + std::to_string(ms->table[b]) + ", outside [0, " + std::to_string(K) + ")");
+    if (ms->offset)
+        for (int64_t b = 0; b < B; ++b) {
+            if (ms->offset[b] < 0) return at("offset", b, "has a negative start column");
+            if ((int64_t)ms->offset[b] + need > C)
+                return at("offset", b, "has offset + T + N = " + std::to_string((int64_t)ms->offset[b] + need) + " beyond n_cols = " +
+                                           std::to_string(C));
+        }
+    const double* const arr[2] = {ms->xref, ms->uref};
+    const char* const name[2] = {"xref", "uref"};
+    const int64_t rows[2] = {9, 6};
+    for (int a = 0; a < 2; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < K * rows[a] * C; ++i)
+                if (!std::isfinite(arr[a][i]))
+                    return std::string("ftmpc_mission.") + name[a] + ": table " + std::to_string(i / (rows[a] * C)) +
+                           " has a non-finite entry in column " + std::to_string(i % (rows[a] * C) / rows[a]);
+    return "";
+}
+static int check_mission(ftmpc_handle* h, int64_t B, int32_t T, const ftmpc_mission* ms, const double* xref_traj, const double* uref_traj) {
+    const std::string msg = mission_problem(ms, B, T, h->cfg.N, xref_traj, uref_traj);
+    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
+// cost of a loop without steps: zero
+static void zero_mission_cost(const ftmpc_mission* ms, int64_t B) {
+    if (ms && ms->cost && B > 0) std::fill(ms->cost, ms->cost + 3 * B, 0.0);
 }
 
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
@@ -2080,18 +2141,31 @@ int ftmpc_simulate_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x,
                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                const ftmpc_plant_model* plant) {
+    return ftmpc_simulate_mission_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                        x_hist, not_converged, out, plant, nullptr);
+}
+
+int ftmpc_simulate_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                 const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                 int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                 double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     int rc = check_schedule(h, B, faults, false, 0, false);
     if (rc != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if (B == 0 || T == 0) return FTMPC_OK;
+    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if (B == 0 || T == 0) {
+        zero_mission_cost(mission, B);
+        return FTMPC_OK;
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant);
+                         faults, x_hist, out, plant, mission);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2121,18 +2195,33 @@ int ftmpc_simulate_wrench_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, dou
                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                       const ftmpc_outcomes* out, const ftmpc_plant_model* plant) {
+    return ftmpc_simulate_wrench_mission_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                               seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                               out, plant, nullptr);
+}
+
+int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                        const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
     if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if (B == 0 || T == 0) return FTMPC_OK;
+    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if (B == 0 || T == 0) {
+        zero_mission_cost(mission, B);
+        return FTMPC_OK;
+    }
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2182,7 +2271,7 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
-                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm) {
+                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2198,7 +2287,15 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     // terminal rows of the config, the status history
     const bool want_rec = oc && (oc->err_int || oc->err_max || oc->impulse || oc->settle_step || oc->tset_step || oc->unsolved ||
                                  oc->first_unsolved || oc->alloc_failed);
-    const bool want_out = want_rec || (oc && oc->status_hist);
+    // mission (checked by the entry): reference tables with a table number and a start column per vehicle, gathered into per-vehicle
+    // windows before every solve (ftmpc::RefWindow), and / or the closed-loop cost.  Without tables and without cost nothing below
+    // differs from a call without the struct.
+    const bool windows = ms && ms->n_tables > 0;
+    const bool want_cost = ms && ms->cost;
+    const bool has_uref = windows ? ms->uref != nullptr : uref_traj != nullptr;
+    DevBuf<double> d_mtab, d_mutab, d_xwin, d_uwin, d_qprev, d_cost;
+    DevBuf<int32_t> d_mtbl, d_moff;
+    const bool want_out = want_rec || (oc && oc->status_hist) || want_cost;
     DevBuf<double> d_orec, d_oterm;
     DevBuf<int32_t> d_oint, d_shist;
     // plant model (checked by the entry): the arrays that are given, transposed to component-major [k][B] on the host (the layout of
@@ -2267,7 +2364,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         pv.force = d_pf;
         pv.torque = d_pt;
     }
-    HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
+    if (!windows) HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
     if (uref_traj) HIP_TRY(h, hipMalloc(&d_ur.p, (size_t)ncol * 6 * sizeof(double)));
     if (!wl) HIP_TRY(h, hipMalloc(&d_warmB.p, (size_t)B * N * NT * sizeof(double)));
     if (wl && wl->alloc_failed) {
@@ -2277,9 +2374,50 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (u_hist) HIP_TRY(h, hipMalloc(&d_hist.p, (size_t)T * B * NT * sizeof(double)));
     HIP_TRY(h, hipMalloc(&d_bad.p, (size_t)T * sizeof(int32_t)));
     HIP_TRY(h, hipMemsetAsync(d_bad, 0, (size_t)T * sizeof(int32_t), s));
-    HIP_TRY(h, hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (!windows) HIP_TRY(h, hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
     if (uref_traj) HIP_TRY(h, hipMemcpyAsync(d_ur, uref_traj, (size_t)ncol * 6 * sizeof(double), hipMemcpyHostToDevice, s));
     if ((rc = stage_inputs(h, B, x, ub, stuck)) != FTMPC_OK) return rc;
+    const int64_t xw = 9 * (int64_t)(N + 1), uw = 6 * (int64_t)(N + 1);     // doubles per window
+    ftmpc::RefWindow rw{};
+    if (windows) {
+        const size_t KC = (size_t)ms->n_tables * (size_t)ms->n_cols;
+        HIP_TRY(h, hipMalloc(&d_mtab.p, KC * 9 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_mtab, ms->xref, KC * 9 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMalloc(&d_xwin.p, (size_t)(B * xw) * sizeof(double)));
+        if (ms->uref) {
+            HIP_TRY(h, hipMalloc(&d_mutab.p, KC * 6 * sizeof(double)));
+            HIP_TRY(h, hipMemcpyAsync(d_mutab, ms->uref, KC * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMalloc(&d_uwin.p, (size_t)(B * uw) * sizeof(double)));
+        }
+        if (ms->table) {
+            HIP_TRY(h, hipMalloc(&d_mtbl.p, (size_t)B * sizeof(int32_t)));
+            HIP_TRY(h, hipMemcpyAsync(d_mtbl, ms->table, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        if (ms->offset) {
+            HIP_TRY(h, hipMalloc(&d_moff.p, (size_t)B * sizeof(int32_t)));
+            HIP_TRY(h, hipMemcpyAsync(d_moff, ms->offset, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        rw.B = B;
+        rw.C = ms->n_cols;
+        rw.N1 = N + 1;
+        rw.xtab = d_mtab;
+        rw.utab = d_mutab;
+        rw.table = d_mtbl;
+        rw.offset = d_moff;
+        rw.xwin = d_xwin;
+        rw.uwin = d_uwin;
+    }
+    ftmpc::MissionOut mo{};
+    if (want_cost) {     // the three sums, and q_0 of every vehicle from the staged x (pitch 13 -> 4 doubles)
+        HIP_TRY(h, hipMalloc(&d_cost.p, (size_t)B * 3 * sizeof(double)));
+        HIP_TRY(h, hipMemsetAsync(d_cost, 0, (size_t)B * 3 * sizeof(double), s));
+        HIP_TRY(h, hipMalloc(&d_qprev.p, (size_t)B * 4 * sizeof(double)));
+        HIP_TRY(h, hipMemcpy2DAsync(d_qprev, 4 * sizeof(double), h->d_x0 + 6, 13 * sizeof(double), 4 * sizeof(double), (size_t)B,
+                                 hipMemcpyDeviceToDevice, s));
+        mo.cost = d_cost;
+        mo.qprev = d_qprev;
+        mo.tcost = h->d_tcost;
+    }
     ftmpc::SimParams sp;
     sp.B = B;
     sp.x = h->d_x0;
@@ -2317,12 +2455,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         op.unsolved = d_oint + 2 * B;
         op.first_unsolved = d_oint + 3 * B;
         op.alloc_failed = d_oint + 4 * B;
-        if (oc->settle_step) {
+        if (oc && oc->settle_step) {
             op.tol[0] = oc->tol_pos;
             op.tol[1] = oc->tol_vel;
             op.tol[2] = oc->tol_rate;
         }
-        if (oc->tset_step) {
+        if (oc && oc->tset_step) {
             const int R = h->cfg.term_rows;
             HIP_TRY(h, hipMalloc(&d_oterm.p, (size_t)R * 10 * sizeof(double)));
             HIP_TRY(h, hipMemcpyAsync(d_oterm, h->cfg.term_A, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -2330,7 +2468,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             op.term = d_oterm;
             op.term_rows = R;
         }
-        if (oc->status_hist) {
+        if (oc && oc->status_hist) {
             HIP_TRY(h, hipMalloc(&d_shist.p, (size_t)T * B * sizeof(int32_t)));
             op.status_hist = d_shist;
         }
@@ -2394,12 +2532,22 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             h->qcnt_valid = false;
             h->qcnt_pending = false;
         }
-        // window t..t+N of the reference (column-major, so a plain pointer offset); warm start from step 1 on
+        // window t..t+N of the reference (column-major, so a plain pointer offset; under a mission with tables: every vehicle's own
+        // window, gathered here); warm start from step 1 on
+        if (windows) {
+            rw.t = t;
+            const int64_t nwin = B * (xw + (rw.utab ? uw : 0));
+            hipLaunchKernelGGL(ftmpc::ftmpc_ref_window_kernel, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, s, rw);
+            HIP_TRY(h, hipGetLastError());
+        }
+        const double* const xr_t = windows ? d_xwin.p : d_xr + (int64_t)9 * t;
+        const double* const ur_t = !has_uref ? nullptr : (windows ? d_uwin.p : d_ur + (int64_t)6 * t);
+        const int64_t xr_s = windows ? xw : 0, ur_s = windows ? uw : 0;
         const double* Ufin = h->d_U;
         const double* Gfin = h->d_G;
         if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
             ftmpc::SqpState S;
-            rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
+            rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
                               t > 0 ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
             if (rc == FTMPC_OK) {
                 Gfin = S.U;
@@ -2411,8 +2559,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         } else if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
             ftmpc::SqpState S;
             double* J0 = nullptr;
-            rc = sqp_enqueue(h, B, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0, t > 0 ? d_warmB.p : nullptr, sqp_iters,
-                             backtracks, tol, S, &J0);
+            rc = sqp_enqueue(h, B, xr_t, xr_s, ur_t, ur_s, t > 0 ? d_warmB.p : nullptr, sqp_iters, backtracks, tol, S, &J0);
             if (rc == FTMPC_OK) {
                 Ufin = S.U;
                 sp.status = S.status;
@@ -2420,13 +2567,13 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                                          hipMemcpyDeviceToDevice, s));
             }
         } else if (wl) {         // the reference's two-stage structure: wrench MPC with the hull rows, then allocation
-            rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
+            rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
                                 t > 0 ? h->d_warmG.p : nullptr);
             if (rc == FTMPC_OK && d_abad)
                 hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
                                    d_abad + t);
         } else {
-            rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, d_xr + (int64_t)9 * t, 0, uref_traj ? d_ur + (int64_t)6 * t : nullptr, 0,
+            rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, xr_t, xr_s, ur_t, ur_s,
                          t > 0 ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
         }
         if (rc != FTMPC_OK) return rc;
@@ -2440,8 +2587,16 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             op.ub = sp.ub;
             op.stuck = sp.stuck;
             op.status = sp.status;
-            op.xref = d_xr + (int64_t)9 * (t + 1);
-            hipLaunchKernelGGL(ftmpc::ftmpc_outcome_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op);
+            if (windows || want_cost) {     // a column per vehicle (column 1 of its window, column 0 of its uref window) and / or the cost
+                mo.xref = xr_t + 9;
+                mo.xref_stride = xr_s;
+                mo.uref = ur_t;
+                mo.uref_stride = ur_s;
+                hipLaunchKernelGGL(ftmpc::ftmpc_outcome_mission_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op, mo);
+            } else {
+                op.xref = d_xr + (int64_t)9 * (t + 1);
+                hipLaunchKernelGGL(ftmpc::ftmpc_outcome_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op);
+            }
         }
         if (wl)     // wrench warm start: shifted by one stage, the last stage repeats
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((B * N * 6 + 255) / 256)), dim3(256), 0, s, B, N, 6,
@@ -2455,7 +2610,8 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (d_abad) HIP_TRY(h, hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (want_out) {
+    if (want_cost) HIP_TRY(h, hipMemcpyAsync(ms->cost, d_cost, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (want_out && oc) {
         double* const rec[3] = {oc->err_int, oc->err_max, oc->impulse};
         const int64_t rec_off[3] = {0, 3 * B, 6 * B}, rec_n[3] = {3 * B, 3 * B, 2 * B};
         for (int i = 0; i < 3; ++i)

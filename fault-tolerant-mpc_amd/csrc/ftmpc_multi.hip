@@ -204,7 +204,7 @@ void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_
     for (int64_t t = 0; t < T; ++t) std::memcpy(dst + (t * B + lo) * w, src + t * n * w, (size_t)(n * w) * sizeof(V));
 }
 
-// The closed loops over the device slots (ftmpc_multi_simulate_plant_batch / _wrench_plant_batch; hull_A == nullptr: the thruster
+// The closed loops over the device slots (ftmpc_multi_simulate_mission_batch / _wrench_mission_batch; hull_A == nullptr: the thruster
 // form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
 // caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
 // staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
@@ -212,13 +212,14 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows, const double* xref_traj,
                    const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                   int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, bool wrench) {
+                   int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                   bool wrench) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
         return FTMPC_ERR_ARG;
     };
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || (wrench && (!hull_A || !hull_b || hull_rows < 1)))
+    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise || (wrench && (!hull_A || !hull_b || hull_rows < 1)))
         return refuse("null buffer or negative size");
     if (out && out->struct_size != (int32_t)sizeof(ftmpc_outcomes))
         return refuse("ftmpc_outcomes.struct_size is " + std::to_string(out->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_outcomes)));
@@ -231,7 +232,14 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         const std::string msg = plant_model_problem(plant, B, m->cfg.NT);
         if (!msg.empty()) return refuse(msg);
     }
-    if (B == 0 || T == 0) return FTMPC_OK;
+    {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
+        const std::string msg = mission_problem(mission, B, T, m->cfg.N, xref_traj, uref_traj);
+        if (!msg.empty()) return refuse(msg);
+    }
+    if (B == 0 || T == 0) {
+        zero_mission_cost(mission, B);
+        return FTMPC_OK;
+    }
     const int G = (int)m->dev.size();
     if (G > B) return refuse("more device slots (" + std::to_string(G) + ") than vehicles (B = " + std::to_string(B) + ")");
     const int NT = m->cfg.NT;
@@ -260,6 +268,13 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (pl.D) pl.D += lo * 6 * NT;
             if (pl.force) pl.force += lo * 3;
             if (pl.torque) pl.torque += lo * 3;
+        }
+        ftmpc_mission mi{};
+        if (mission) {
+            mi = *mission;
+            if (mi.table) mi.table += lo;
+            if (mi.offset) mi.offset += lo;
+            if (mi.cost) mi.cost += lo * 3;
         }
         ftmpc_outcomes oc{};
         oc.struct_size = (int32_t)sizeof(ftmpc_outcomes);
@@ -293,14 +308,15 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         }
         double* const uh_p = !u_hist ? nullptr : (whole ? u_hist : uh.data());
         double* const xh_p = !x_hist ? nullptr : (whole ? x_hist : xh.data());
-        const int rc2 = wrench ? ftmpc_simulate_wrench_plant_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
-                                                                   hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
-                                                                   xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
-                                                                   faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
-                                                                   alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr)
-                               : ftmpc_simulate_plant_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
-                                                            seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                            bad[g].data(), &oc, plant ? &pl : nullptr);
+        const int rc2 = wrench ? ftmpc_simulate_wrench_mission_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+                                                                     hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
+                                                                     xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
+                                                                     faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
+                                                                     alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
+                                                                     mission ? &mi : nullptr)
+                               : ftmpc_simulate_mission_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                              seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                              bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -544,7 +560,7 @@ int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -553,7 +569,16 @@ int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, doubl
                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                      const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, false);
+}
+
+int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                       const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, false);
 }
 
 int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -563,7 +588,7 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -574,7 +599,18 @@ int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T
                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                             const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, true);
+}
+
+int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                              const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                              int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                              uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                              const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                              int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                              const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, true);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

@@ -608,4 +608,155 @@ __global__ void __launch_bounds__(64) ftmpc_plant_step_var_kernel(const DeviceCo
     if (S.bad_count && S.status && S.status[b] != 0) atomicAdd(&S.bad_count[S.step], 1);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Reference missions (ftmpc_simulate_mission_batch / ftmpc_simulate_wrench_mission_batch; include/ftmpc.h, ftmpc_mission): K reference
+// tables of C columns, and per vehicle a table number and a start column.  At loop step t vehicle b tracks the columns
+// offset[b] + t .. offset[b] + t + N of its table.  ftmpc_ref_window_kernel gathers those columns into per-vehicle windows
+//   xwin [B][9 (N+1)]   and, when the mission has uref tables,   uwin [B][6 (N+1)]
+// once per step before the solve; every consumer of the reference (linearise, cost, outcome kernels) then reads (base, stride) as the
+// one-step entries always could.  One lane per double of the output: the writes are contiguous over the launch, the reads contiguous
+// within a vehicle (a window is 9 (N+1) consecutive doubles of a column-major table).  The host has checked
+// offset[b] + T + N <= C and table[b] in [0, K), so no read leaves a table.  (Both kernels stand at the end of the file so that the
+// build logs keep the source lines of every kernel above.)
+// ---------------------------------------------------------------------------------------------------------
+struct RefWindow {
+    int64_t B, C;             // vehicles, columns per table
+    int32_t N1, t;            // N + 1 columns per window, loop step
+    const double* xtab;       // [K][9*C]
+    const double* utab;       // nullptr or [K][6*C]
+    const int32_t* table;     // nullptr (table 0) or [B]
+    const int32_t* offset;    // nullptr (0) or [B]
+    double* xwin;             // [B][9*N1]
+    double* uwin;             // nullptr or [B][6*N1]
+};
+
+__global__ void __launch_bounds__(256) ftmpc_ref_window_kernel(const RefWindow W) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nx = W.B * 9 * W.N1;
+    int rows = 9;
+    const double* tab = W.xtab;
+    double* win = W.xwin;
+    if (i >= nx) {
+        if (!W.utab) return;
+        i -= nx;
+        rows = 6;
+        tab = W.utab;
+        win = W.uwin;
+    }
+    const int64_t per = (int64_t)rows * W.N1;
+    if (i >= W.B * per) return;
+    const int64_t b = i / per, j = i - b * per;
+    const int64_t k = W.table ? W.table[b] : 0;
+    const int64_t c0 = (W.offset ? W.offset[b] : 0) + W.t;
+    win[i] = tab[(k * W.C + c0) * rows + j];
+}
+
+// ftmpc_outcome_kernel with a reference column per vehicle and the closed-loop cost (include/ftmpc.h, ftmpc_mission.cost); launched
+// in its place when the mission has tables or asks for cost.  The records of OutcomeParams are formed by the same expressions in the
+// same order, so with a shared reference (xref_stride = 0) they are the bits ftmpc_outcome_kernel writes.  cost, in step order:
+//   cost[0] += e' diag(Q) e                      e = robot_to_center(x_{t+1})[0:9] - (the vehicle's column t + 1)
+//   cost[1] += w' diag(R) w                      w = D a - [Rot(q_t)^T uref_t[0:3]; uref_t[3:6]] - [f_virt; 0], a_i as `impulse`
+//   cost[2]  = e' P e (+ V_nq(e))                the terminal cost of the last step's error, rewritten each step
+// with the rotation ftmpc_cost_kernel applies to ur (mat3vec(rotT(q), .)), D, Q, R, P, f_virt of DeviceConsts, and q_t the
+// quaternion of the state step t started from: qprev [B*4], staged from x by the host before the loop and rewritten here with
+// x_{t+1}'s (each lane reads and writes its own four values).
+struct MissionOut {
+    const double* xref;       // column t + 1: per vehicle at xref + b * xref_stride (0: shared)
+    int64_t xref_stride;
+    const double* uref;       // nullptr (zero) or column t: per vehicle at uref + b * uref_stride
+    int64_t uref_stride;
+    double* qprev;            // nullptr (no cost) or [B*4]
+    double* cost;             // nullptr or [B*3]
+    const TermCost* tcost;    // nullptr or the non-quadratic terminal-cost terms
+};
+
+__global__ void __launch_bounds__(64) ftmpc_outcome_mission_kernel(const DeviceConsts C, const OutcomeParams O, const MissionOut M) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= O.B) return;
+    const int NT = C.NT;
+    const int32_t t = O.step;
+    const double* xref = M.xref + b * M.xref_stride;
+    double x[13];
+    for (int i = 0; i < 13; ++i) x[i] = O.x[b * 13 + i];
+    double e[9];
+    {
+        double RT[9], wxr[3], a[3], c[3];
+        rotT(x + 6, RT);
+        cross3(x + 10, C.r, wxr);
+        mat3vec(RT, C.r, a);
+        mat3vec(RT, wxr, c);
+        for (int i = 0; i < 3; ++i) {
+            e[i] = x[i] + a[i] - xref[i];
+            e[3 + i] = x[3 + i] + c[i] - xref[3 + i];
+            e[6 + i] = x[10 + i] - xref[6 + i];
+        }
+    }
+    const double dt = C.dt;
+    bool inside = true;
+    for (int j = 0; j < 3; ++j) {
+        const double n2 = e[3 * j] * e[3 * j] + e[3 * j + 1] * e[3 * j + 1] + e[3 * j + 2] * e[3 * j + 2];
+        const double n = sqrt(n2);
+        O.err_int[b * 3 + j] += dt * n2;
+        O.err_max[b * 3 + j] = fmax(O.err_max[b * 3 + j], n);
+        inside = inside && n <= O.tol[j];
+    }
+    if (!inside) O.settle[b] = t + 1;
+    double del = 0.0, cmd = 0.0;
+    double gen[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < NT; ++i) {
+        const double c = O.ub[b * NT + i] > 0.0 ? O.u0[b * NT + i] : 0.0;
+        cmd += c;
+        del += c + O.stuck[b * NT + i];
+        if (M.cost) {
+            const double a = c + O.stuck[b * NT + i];
+            for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * a;
+        }
+    }
+    O.impulse[b * 2] += dt * del;
+    O.impulse[b * 2 + 1] += dt * cmd;
+    const int32_t st = O.status[b];
+    if (st != 0) {
+        if (O.unsolved[b]++ == 0) O.first_unsolved[b] = t;
+    }
+    if (O.astatus && O.astatus[b] != 0) O.alloc_failed[b] += 1;
+    if (O.status_hist) O.status_hist[(int64_t)t * O.B + b] = st;
+    if (O.term && O.tset[b] < 0) {
+        const double* tb = O.term + (int64_t)O.term_rows * 9;
+        bool in = true;
+        for (int r = 0; r < O.term_rows; ++r) {
+            double s = 0.0;
+            for (int j = 0; j < 9; ++j) s += O.term[r * 9 + j] * e[j];
+            in = in && s <= tb[r];
+        }
+        if (in) O.tset[b] = t;
+    }
+    if (M.cost) {
+        double cq = 0.0;
+        for (int a = 0; a < 9; ++a) cq += C.Q[a] * e[a] * e[a];
+        double ur[6] = {0, 0, 0, 0, 0, 0};
+        if (M.uref) {
+            const double* uref = M.uref + b * M.uref_stride;
+            double q[4], RT[9], f3[3] = {uref[0], uref[1], uref[2]}, o[3];
+            for (int i = 0; i < 4; ++i) q[i] = M.qprev[b * 4 + i];
+            rotT(q, RT);
+            mat3vec(RT, f3, o);
+            ur[0] = o[0]; ur[1] = o[1]; ur[2] = o[2];
+            ur[3] = uref[3]; ur[4] = uref[4]; ur[5] = uref[5];
+        }
+        double cr = 0.0;
+        for (int g = 0; g < 6; ++g) {
+            const double w = gen[g] - ur[g] - (g < 3 ? C.fvirt[g] : 0.0);
+            cr += C.R[g] * w * w;
+        }
+        double v = 0.0;
+        for (int a = 0; a < 9; ++a)
+            for (int c = 0; c < 9; ++c) v += e[a] * C.P[9 * a + c] * e[c];
+        if (M.tcost) v += term_cost_nq(*M.tcost, e, nullptr);
+        M.cost[b * 3] += cq;
+        M.cost[b * 3 + 1] += cr;
+        M.cost[b * 3 + 2] = v;
+        for (int i = 0; i < 4; ++i) M.qprev[b * 4 + i] = x[6 + i];
+    }
+}
+
 }  // namespace ftmpc

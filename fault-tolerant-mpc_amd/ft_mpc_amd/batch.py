@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None):
+                 plant=None, mission=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -469,11 +469,16 @@ class BatchedMPC:
         plant: the plant the loop integrates, per vehicle (include/ftmpc.h, ftmpc_plant_model; ft_mpc_amd.dispersion.sample draws one):
         a dict with any of mass [B], J [B,3,3], D [B,6,NT], force [B,3] (inertial frame), torque [B,3] (body frame); a key that is
         missing takes the config's value (zero for the disturbances).  The controller keeps the nominal model.
+        mission: what each vehicle is asked to fly (include/ftmpc.h, ftmpc_mission; ft_mpc_amd.missions builds one): a dict with
+        tables [K,9,C], optionally utables [K,6,C], table [B] int (default 0) and offset [B] int (default 0); at step t vehicle b tracks
+        the columns offset[b] + t .. offset[b] + t + N of its table (offset[b] + T + N <= C), and its outcomes are measured against
+        them.  xref_traj (and uref_traj) must then be None.  outcomes=dict(cost=True, ..), or "cost" among its fields, adds
+        outcomes["cost"] [B,3]: the realised sum of e'Qe, of ut'R ut and the terminal cost of the last error; outcomes=True does not.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
         [, status_hist])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant)
+                         plant, mission)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -602,18 +607,77 @@ def _plant_request(plant, B, NT):
     return pm, keep
 
 
+def _mission_request(mission, B, T, N, want_cost):
+    """The ftmpc_mission struct of a simulate call, the arrays it points into (kept alive by the caller) and the cost array | None.
+    mission None: the struct only asks for cost (n_tables = 0)."""
+    ms = _lib.ftmpc_mission(struct_size=C.sizeof(_lib.ftmpc_mission))
+    keep = []
+    if mission is not None:
+        spec = dict(mission)
+        tables = spec.pop("tables", None)
+        if tables is None:
+            raise ValueError("mission: needs tables [K,9,C]")
+        tables = _f64(tables)
+        if tables.ndim != 3 or tables.shape[0] < 1 or tables.shape[1] != 9:
+            raise ValueError(f"mission['tables'] must have shape [K,9,C] with K >= 1, not {tables.shape}")
+        K, _, Cn = tables.shape
+        xt = np.ascontiguousarray(tables.transpose(0, 2, 1))      # [K][C][9]: every table column-major
+        keep.append(xt)
+        ms.n_tables, ms.n_cols, ms.xref = K, Cn, _ptr(xt)
+        ut = spec.pop("utables", None)
+        if ut is not None:
+            ut = _f64(ut)
+            if ut.shape != (K, 6, Cn):
+                raise ValueError(f"mission['utables'] must have shape {(K, 6, Cn)}, not {ut.shape}")
+            ut = np.ascontiguousarray(ut.transpose(0, 2, 1))
+            keep.append(ut)
+            ms.uref = _ptr(ut)
+        for name in ("table", "offset"):
+            a = spec.pop(name, None)
+            if a is None:
+                continue
+            a = np.asarray(a)
+            if a.shape != (B,) or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"mission[{name!r}] must be {B} integers, not {a.dtype} {a.shape}")
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            keep.append(a)
+            setattr(ms, name, _ptr(a, C.c_int32))
+        if spec:
+            raise ValueError(f"mission: unknown keys {sorted(spec)}")
+    cost = None
+    if want_cost:
+        cost = np.zeros((B, 3))
+        ms.cost = _ptr(cost)
+    return ms, keep, cost
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
-              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None):
+              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
     B = x.shape[0]
     ub = _f64(ub, (B, NT))
     stuck = _f64(stuck, (B, NT))
-    xr = _f64(xref_traj)
-    if xr.shape != (9, T + N):
-        raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}")
-    xr = np.ascontiguousarray(xr.reshape(-1, order="F"))
+    # `cost` is an outcome by name, but lives in the mission struct (ftmpc_outcomes is full): taken out of the request here
+    want_cost = False
+    if isinstance(outcomes, dict):
+        outcomes = dict(outcomes)
+        want_cost = bool(outcomes.pop("cost", False))
+        if outcomes.get("fields") is not None and "cost" in outcomes["fields"]:
+            want_cost = True
+            outcomes["fields"] = [n for n in outcomes["fields"] if n != "cost"]
+    ms, mkeep, cost = None, None, None
+    if mission is not None and (xref_traj is not None or uref_traj is not None):
+        raise ValueError("with a mission xref_traj and uref_traj must be None (the mission's tables are the reference)")
+    if mission is not None or want_cost:
+        ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
+    xr = None
+    if mission is None:
+        xr = _f64(xref_traj)
+        if xr.shape != (9, T + N):
+            raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}")
+        xr = np.ascontiguousarray(xr.reshape(-1, order="F"))
     ur = None
     if uref_traj is not None:
         ur = _f64(uref_traj)
@@ -646,8 +710,14 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     # the entries with outcomes: asked for, a slice of a campaign, the multi-GPU driver (which has no others), or a plant model (whose
     # entries take the outcomes struct too)
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
-    new = multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None or pm is not None
+    new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
+           or pm is not None or ms is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
+
+    if cost is not None:
+        orec = {} if orec is None else orec
+        orec["cost"] = cost
+    pmp = C.byref(pm) if pm is not None else None
 
     def result(out):
         if return_states:
@@ -668,6 +738,12 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if ms is not None:
+            self._check(getattr(self.lib, pre + "wrench_mission_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, C.byref(ms)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if pm is not None:
             self._check(getattr(self.lib, pre + "wrench_plant_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -699,6 +775,11 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if ms is not None:
+        self._check(getattr(self.lib, pre + "mission_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, C.byref(ms)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if pm is not None:
         self._check(getattr(self.lib, pre + "plant_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

@@ -21,6 +21,9 @@ _M = (1 << 64) - 1
 # draw of vehicle v, component c: counter v * STRIDE + c (the same for every B and NT, so a slice draws the whole campaign's values)
 STRIDE = 32
 C_MASS, C_INERTIA, C_COM, C_FORCE, C_TORQUE, C_GAIN = 0, 1, 4, 7, 10, 16       # 1, 3, 3, 3, 3, NT <= 16 components
+# component 13 is reserved for missions.phase_offsets (a vehicle's start column); 14 and 15 are free.  Nothing else may draw from a
+# component that is taken: two quantities drawn from one counter with one seed are the same number.
+C_PHASE = 13
 
 
 def u01(seed, idx):

@@ -22,21 +22,75 @@ def plant_patterns(ub, stuck, faults, T, detect_delay=0):
     return pu, ps
 
 
-def centre_error(x_hist, xref_traj, r):
-    """e [T,B,9] = robot_to_center(x_hist[t])[0:9] - xref_traj[:, t+1]."""
-    x = np.asarray(x_hist, float)
-    T = x.shape[0]
+def _rot(x):
+    """World -> body rotation matrices [..., 3, 3] of the states x [..., 13] (util/utils.py:4-19)."""
     qx, qy, qz, qw = (x[..., 6 + i] for i in range(4))
-    R = np.empty(x.shape[:2] + (3, 3))       # world -> body (util/utils.py:4-19); robot_to_center applies its transpose
+    R = np.empty(x.shape[:-1] + (3, 3))
     R[..., 0, 0], R[..., 0, 1], R[..., 0, 2] = qx * qx - qy * qy - qz * qz + qw * qw, 2 * (qx * qy + qz * qw), 2 * (qx * qz - qy * qw)
     R[..., 1, 0], R[..., 1, 1], R[..., 1, 2] = 2 * (qx * qy - qz * qw), -qx * qx + qy * qy - qz * qz + qw * qw, 2 * (qy * qz + qx * qw)
     R[..., 2, 0], R[..., 2, 1], R[..., 2, 2] = 2 * (qx * qz + qy * qw), 2 * (qy * qz - qx * qw), -qx * qx - qy * qy + qz * qz + qw * qw
+    return R
+
+
+def centre_state(x_hist, r):
+    """robot_to_center(x_hist[t])[0:9], [T,B,9]: the orbit-centre [p, v, omega] of every state."""
+    x = np.asarray(x_hist, float)
+    R = _rot(x)                              # robot_to_center applies the transpose
     r = np.asarray(r, float).reshape(3)
     w = x[..., 10:13]
     pos = x[..., 0:3] + np.einsum("tbji,j->tbi", R, r)
     vel = x[..., 3:6] + np.einsum("tbji,tbj->tbi", R, np.cross(w, r))
-    c = np.concatenate([pos, vel, w], axis=-1)
-    return c - np.asarray(xref_traj, float)[:, 1:T + 1].T[:, None, :]
+    return np.concatenate([pos, vel, w], axis=-1)
+
+
+def centre_error(x_hist, xref_traj, r):
+    """e [T,B,9] = robot_to_center(x_hist[t])[0:9] - xref_traj[:, t+1]."""
+    T = np.shape(x_hist)[0]
+    return centre_state(x_hist, r) - np.asarray(xref_traj, float)[:, 1:T + 1].T[:, None, :]
+
+
+def closed_loop_cost(Q, R, P, D, f_virt, r, x0, x_hist, u_hist, plant_ub, plant_stuck, xref, uref=None, v_nq=None):
+    """The device's `cost` outcome [B,3] from histories (include/ftmpc.h, ftmpc_mission.cost), summed in step order:
+      cost[:, 0] = sum_t e_{t+1}' diag(Q) e_{t+1}
+      cost[:, 1] = sum_t w_t' diag(R) w_t,   w_t = D a_t - [Rot(q_t)^T uref_t[0:3]; uref_t[3:6]] - [f_virt; 0]
+      cost[:, 2] = e_T' P e_T (+ v_nq(e_T))
+    Q [9], R [6], P [9,9], D [6,NT], f_virt [3], r [3]: the handle's (BatchedMPC.cfg.Q / .R / .f_virt, BatchedMPC.P / .D / .r).
+    x0 [B,13] the states the loop started from, x_hist [T,B,13], u_hist [T,B,NT] (commanded), plant_ub / plant_stuck [B,NT] or
+    [T,B,NT] (plant_patterns).  xref: what x_hist[t] is measured against -- [T,B,9] per vehicle (missions.error_columns), or a shared
+    trajectory 9 x (>= T+1), whose column t + 1 it is; uref: [T,B,6] per vehicle (the column of step t), a shared 6 x (>= T), or None
+    (zero).  v_nq: the non-quadratic terminal-cost terms as a function of e [B,9] -> [B], or None."""
+    x_hist = np.asarray(x_hist, float)
+    T, B = x_hist.shape[:2]
+    u = np.asarray(u_hist, float)
+    pu = np.broadcast_to(np.asarray(plant_ub, float), u.shape)
+    ps = np.broadcast_to(np.asarray(plant_stuck, float), u.shape)
+    Q, R, P = np.asarray(Q, float).reshape(9), np.asarray(R, float).reshape(6), np.asarray(P, float).reshape(9, 9)
+    D = np.asarray(D, float).reshape(6, -1)
+    fv = np.concatenate([np.asarray(f_virt, float).reshape(3), np.zeros(3)])
+    xref = np.asarray(xref, float)
+    if xref.ndim == 2:
+        xref = np.broadcast_to(xref[:, 1:T + 1].T[:, None, :], (T, B, 9))
+    if uref is not None:
+        uref = np.asarray(uref, float)
+        if uref.ndim == 2:
+            uref = np.broadcast_to(uref[:, :T].T[:, None, :], (T, B, 6))
+    e = centre_state(x_hist, r) - xref
+    start = np.concatenate([np.asarray(x0, float).reshape(1, B, 13), x_hist[:-1]], axis=0) if T else x_hist      # the state step t started from
+    Rq = _rot(start)
+    a = np.where(pu > 0.0, u, 0.0) + ps
+    cost = np.zeros((B, 3))
+    for t in range(T):
+        cost[:, 0] += (Q * e[t] * e[t]).sum(axis=-1)
+        w = a[t] @ D.T - fv
+        if uref is not None:
+            w[:, 0:3] -= np.einsum("bji,bj->bi", Rq[t], uref[t, :, 0:3])
+            w[:, 3:6] -= uref[t, :, 3:6]
+        cost[:, 1] += (R * w * w).sum(axis=-1)
+    if T:
+        cost[:, 2] = np.einsum("bi,ij,bj->b", e[-1], P, e[-1])
+        if v_nq is not None:
+            cost[:, 2] += v_nq(e[-1])
+    return cost
 
 
 def outcomes_from_history(cfg, x_hist, u_hist, status_hist, xref_traj, plant_ub, plant_stuck, tol=None, term=None,

@@ -565,6 +565,59 @@ int ftmpc_simulate_wrench_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, dou
                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                       const ftmpc_outcomes* out, const ftmpc_plant_model* plant);
 
+/*
+ * Reference missions and the closed-loop cost.  A mission is K reference tables and, per vehicle, a table number and a start column:
+ * table k is xref [9 x C] column-major (orbit-centre [p, v, omega], exactly the columns of xref_traj) and optionally uref [6 x C].
+ * Vehicle b has table[b] in [0, K) and offset[b] >= 0; at loop step t its solve tracks the columns offset[b] + t .. offset[b] + t + N
+ * of its table, for xref and uref alike, and every outcome and tset_step take
+ *   e = robot_to_center(x_{t+1})[0:9] - column offset[b] + t + 1   of its table.
+ * offset[b] + T + N <= C is required: a table does not wrap around.  Everything else in the loop (warm-start shift, fault events and
+ * warm-start repair, plant or dispersed plant, noise counter, histories) is as without the struct.  The tables are shared by the
+ * vehicles and uploaded once per call; a kernel gathers every vehicle's window [9 (N+1)] (and [6 (N+1)] with uref) before each solve
+ * into buffers of the call: 120 (N+1) bytes per vehicle, 2.5 KB at N = 20, 165 MB at B = 65 536.
+ * cost [B*3], accumulated in step order and not multiplied by dt (the controller's stage cost is not), with Q, R, P, D and f_virt of
+ * the handle's config (a dispersed plant's D_b stays on the plant side):
+ *   cost[b][0] = sum_t e_{t+1}' diag(Q) e_{t+1}
+ *   cost[b][1] = sum_t w_t' diag(R) w_t,   w_t = D a_t - [Rot(q_t)^T uref_t[0:3]; uref_t[3:6]] - [f_virt; 0]
+ *                a_i = (ub_i > 0 ? u_i : 0) + stuck_i from the PLANT's pattern of step t (the a_i of `impulse`), q_t the quaternion of
+ *                the state step t started from (the call's x for t = 0, else the state after step t-1's noise and renormalisation),
+ *                uref_t column offset[b] + t (zero without uref), rotated as ftmpc_eval_cost_batch rotates ur
+ *   cost[b][2] = V(e_T), the terminal cost of the last step's error as ftmpc_eval_cost_batch defines V for the handle: e' P e, plus
+ *                V_nq(e) when terminal_cost_terms != 0.  Zero for T = 0.
+ * n_tables = 0: every vehicle tracks the call's xref_traj / uref_traj and the struct only asks for cost.  mission = NULL, or
+ * n_tables = 0 with cost = NULL, launches exactly the kernels of the _plant_ entries and returns their bits.
+ * FTMPC_ERR_ARG, the message naming the field and, where there is one, the first offending vehicle: a struct_size other than
+ * sizeof(ftmpc_mission); n_tables < 0; with n_tables > 0: xref NULL, n_cols < T + N, the call's xref_traj or uref_traj not NULL, a
+ * table[b] outside [0, K), an offset[b] < 0 or with offset[b] + T + N > n_cols, a non-finite table entry; with n_tables = 0: the
+ * call's xref_traj NULL, table or offset not NULL.
+ */
+typedef struct ftmpc_mission {
+    int32_t struct_size;      /* sizeof(ftmpc_mission) */
+    int32_t n_tables;         /* K >= 0.  0: every vehicle tracks the call's xref_traj / uref_traj (the struct then only asks for cost) */
+    int64_t n_cols;           /* C, columns of every table */
+    const double* xref;       /* [K][9*C] */
+    const double* uref;       /* NULL (hover on every table) or [K][6*C] */
+    const int32_t* table;     /* NULL (table 0) or [B] */
+    const int32_t* offset;    /* NULL (0) or [B] */
+    double* cost;             /* NULL or [B*3], output */
+} ftmpc_mission;
+
+/* ftmpc_simulate_plant_batch with the mission `mission` (NULL: exactly ftmpc_simulate_plant_batch).  With n_tables > 0 xref_traj and
+ * uref_traj must be NULL. */
+int ftmpc_simulate_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                 const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                 int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                 double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission);
+
+/* ftmpc_simulate_wrench_plant_batch with the mission `mission` (NULL: exactly ftmpc_simulate_wrench_plant_batch). */
+int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                        const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -672,6 +725,21 @@ int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T
                                             const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                             const ftmpc_plant_model* plant);
+/* The two entries above with the mission `mission` (ftmpc_mission; NULL: exactly the entries above).  The mission is checked once over
+ * the whole batch, so a refusal names the vehicle by its number in the caller's arrays; the tables are shared, table + lo, offset + lo
+ * and cost + 3 lo are read or written per shard. */
+int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                       const ftmpc_plant_model* plant, const ftmpc_mission* mission);
+int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                              const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                              int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                              uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                              const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                              int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                              const ftmpc_plant_model* plant, const ftmpc_mission* mission);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

@@ -7,6 +7,8 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --outcomes        # also the loop with the schedule and every per-vehicle outcome
     python scripts/fault_campaign_perf.py --slots 2         # every loop on the multi-GPU driver with 2 slots on device 0
     python scripts/fault_campaign_perf.py --dispersion      # also the loops with a dispersed plant (BatchedMPC.simulate(plant=...))
+    python scripts/fault_campaign_perf.py --mission         # also the loops under a three-table mission with random phases, and with cost
+    python scripts/fault_campaign_perf.py --trace kernel_trace.csv   # per-launch times of the mission kernels and of the linearise kernel
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -15,7 +17,16 @@ float64 handle (vehicles whose hull would be flat in either pattern are dropped 
 --dispersion: the loops without and with the schedule once more with ft_mpc_amd.dispersion.sample at mass 10 %, inertia 10 %, gain 5 %,
 centre of mass 1 cm, force 0.05 N, torque 0.005 N m (ftmpc_plant_step_var_kernel in place of ftmpc_plant_step_kernel); with --once it
 makes one call with the dispersed plant and one without, so that a kernel_stats.csv of that run holds both plant kernels, and --stats
-reports the time per launch of each."""
+reports the time per launch of each.
+--mission: the loops without and with the schedule once more under BatchedMPC.simulate(mission=...): three tables (hover, a circle of
+radius 0.5 m and period 40 s with its uref, a line at 0.05 m/s), the table number b mod 3 and a start column from
+ft_mpc_amd.missions.phase_offsets per vehicle (ftmpc_ref_window_kernel before every solve, per-vehicle windows in the linearise kernel),
+and the loop with the schedule, the mission and the cost outcome (ftmpc_outcome_mission_kernel); before them the same two loops under
+a mission of the hover table alone, whose QPs are those of the shared loop, so that the difference is the mission's own overhead and
+not other work in the solves.  With --once it makes one call with
+the mission and the cost and then one with the shared reference; --trace reads the kernel_trace.csv of such a run (rocprofv3
+--kernel-trace) and reports the time per launch of the two mission kernels and of the linearise kernel in either call: the launches
+of the linearise kernel are split at the first launch of ftmpc_plant_step_kernel that follows the last ftmpc_ref_window_kernel."""
 import argparse
 import csv
 import json
@@ -54,10 +65,29 @@ def batch(c, seed=4040):
     return x0, ub, stuck, dict(onset=onset, ub=eub[:, None], stuck=est[:, None])
 
 
+PHASES = 200      # start columns of a mission are drawn from [0, PHASES)
+
+
+def mission(B, N, mass):
+    """Three tables of PHASES + T + N columns and a (table, offset) per vehicle; mass: the config's, for the circle's uref."""
+    from ft_mpc_amd.missions import mission_tables, phase_offsets
+    cols = PHASES + T + N
+    t = 0.1 * np.arange(cols)
+    hover, circle, line, ucirc = np.zeros((9, cols)), np.zeros((9, cols)), np.zeros((9, cols)), np.zeros((6, cols))
+    for x in (hover, circle, line):
+        x[8] = 0.6
+    R, om = 0.5, 2 * np.pi / 40.0
+    circle[0], circle[1], circle[3], circle[4] = R * np.cos(om * t) - R, R * np.sin(om * t), -R * om * np.sin(om * t), R * om * np.cos(om * t)
+    ucirc[0], ucirc[1] = -mass * R * om * om * np.cos(om * t), -mass * R * om * om * np.sin(om * t)
+    line[0], line[3] = 0.05 * t, 0.05
+    return dict(tables=mission_tables([hover, circle, line]), utables=mission_tables([np.zeros((6, 1)), ucirc, np.zeros((6, 1))], rows=6),
+                table=(np.arange(B) % 3).astype(np.int32), offset=phase_offsets(B, PHASES, seed=23))
+
+
 DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
 
 
-def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False):
+def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -83,7 +113,10 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False):
     if dispersion:
         from ft_mpc_amd.dispersion import sample
         plant = sample(B, c["NT"], mpc.D, cfg.J, cfg.mass, seed=17, **DISPERSION)
+    msn = mission(B, c["N"], cfg.mass) if with_mission else None
     if once:
+        if with_mission:
+            mpc.simulate(x0, ub, stuck, None, T, mission=msn, **dict(withf, outcomes=dict(fields=["cost"])), **kw)
         if dispersion:
             mpc.simulate(x0, ub, stuck, xr, T, plant=plant, **(witho if outcomes else withf), **kw)
         mpc.simulate(x0, ub, stuck, xr, T, **(witho if outcomes else withf), **kw)
@@ -100,13 +133,21 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False):
         runs.append(("with_outcomes", witho, ub, stuck))
     if dispersion:
         runs += [("without_dispersed", dict(plain, plant=plant), ub, stuck), ("with_dispersed", dict(withf, plant=plant), ub, stuck)]
+    if with_mission:
+        # the hover table alone at the same start columns: the QPs of the shared loop bit for bit, so what differs is the gather, the
+        # per-vehicle loads of the linearise kernel and the call's staging -- not the work of the solves
+        hov = dict(tables=msn["tables"][:1], offset=msn["offset"])
+        runs += [("without_mission_hover", dict(plain, mission=hov), ub, stuck), ("with_mission_hover", dict(withf, mission=hov), ub, stuck),
+                 ("without_mission", dict(plain, mission=msn), ub, stuck), ("with_mission", dict(withf, mission=msn), ub, stuck),
+                 ("with_mission_cost", dict(withf, mission=msn, outcomes=dict(fields=["cost"])), ub, stuck)]
     for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
-        mpc.simulate(x0, u, s, xr, T, **extra, **kw)          # warm-up: workspaces, code objects, grid hints
+        ref = None if "mission" in extra else xr              # a mission's tables are the reference
+        mpc.simulate(x0, u, s, ref, T, **extra, **kw)         # warm-up: workspaces, code objects, grid hints
         ts = []
         for _ in range(reps):
             t0 = time.perf_counter()
-            out = mpc.simulate(x0, u, s, xr, T, **extra, **kw)
+            out = mpc.simulate(x0, u, s, ref, T, **extra, **kw)
             ts.append(time.perf_counter() - t0)
         ms = float(np.median(ts)) * 1e3
         res[label] = dict(ms=ms, steps_per_s=B * T / (ms * 1e-3), not_converged=int(out["not_converged"].sum()),
@@ -121,6 +162,13 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False):
         res["ratio_dispersed_over_without"] = res["without_dispersed"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_dispersed_over_with"] = res["with_dispersed"]["steps_per_s"] / res["with"]["steps_per_s"]
         res["plant_model_bytes"] = int(sum(a.nbytes for a in plant.values()))
+    if with_mission:
+        res["ratio_mission_hover_over_without"] = res["without_mission_hover"]["steps_per_s"] / res["without"]["steps_per_s"]
+        res["ratio_mission_hover_over_with"] = res["with_mission_hover"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["ratio_mission_over_without"] = res["without_mission"]["steps_per_s"] / res["without"]["steps_per_s"]
+        res["ratio_mission_over_with"] = res["with_mission"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["ratio_mission_cost_over_with"] = res["with_mission_cost"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["window_bytes"] = B * 15 * (c["N"] + 1) * 8
     res.update(case=name, B=B, T=T, slots=slots, **{k: c[k] for k in ("N", "NT", "dtype", "formulation")})
     return res
 
@@ -148,6 +196,23 @@ def stats(path):
                 outcome_kernel_share=oct_ / tot if tot else 0.0)
 
 
+def trace(path):
+    """Time per launch of the mission kernels and of the linearise kernel with and without windows, from the kernel_trace.csv of a
+    `--once --mission` run (the call with the mission comes first)."""
+    rows = list(csv.DictReader(open(path)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3
+    last_win = max((i for i, r in enumerate(rows) if "ftmpc_ref_window_kernel" in r["Kernel_Name"]), default=-1)
+    split = next((i for i in range(last_win + 1, len(rows)) if "ftmpc_plant_step_kernel" in rows[i]["Kernel_Name"]), len(rows))
+    out = {}
+    for key, name, sel in (("ref_window", "ftmpc_ref_window_kernel", rows), ("outcome_mission", "ftmpc_outcome_mission_kernel", rows),
+                           ("linearize_windows", "ftmpc_linearize_kernel", rows[:split + 1]),
+                           ("linearize_shared", "ftmpc_linearize_kernel", rows[split + 1:])):
+        d = [dur(r) for r in sel if name in r["Kernel_Name"]]
+        out[key + "_calls"], out[key + "_avg_us"] = len(d), float(np.mean(d)) if d else 0.0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="all", choices=["all"] + list(CASES))
@@ -158,14 +223,19 @@ def main():
     ap.add_argument("--outcomes", action="store_true")
     ap.add_argument("--slots", type=int, default=0)
     ap.add_argument("--dispersion", action="store_true")
+    ap.add_argument("--mission", action="store_true")
+    ap.add_argument("--trace", default=None)
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
         return
+    if a.trace:
+        print(json.dumps(trace(a.trace)))
+        return
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
