@@ -674,12 +674,35 @@ typedef __attribute__((address_space(3))) double lds_f64;
 typedef __attribute__((address_space(3))) const float lds_cf32;
 typedef __attribute__((address_space(1))) double glb_f64;
 typedef __attribute__((address_space(1))) const double glb_cf64;
-// GOFF: offset (doubles) of the wrench scratch behind the gradient in the global slot (>= n)
-template <class SPtr, int GOFF = 160>   // stage storage: lds_f64* when it fits behind the vectors, else glb_f64* (long horizons)
-__device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, lds_f64* recd, lds_cf32* s_Da,
-                                            lds_cf32* dnat, SPtr sS, glb_f64* gout, int na, int lane) {
+// The handle constants that the kernel indexes per lane: the run D | Q | R | P | LPt | sq2Q of DeviceConsts (282 doubles), read
+// through a pointer -- the LDS copy a wave makes once at kernel start (NB = 8), or the kernel-argument segment itself (NB = 9, 10:
+// no LDS to spare).  Indexed per lane in the by-value struct, the whole struct was copied to scratch at kernel entry and every
+// such read was a scratch round trip, per instance.
+typedef __attribute__((address_space(3))) const double lds_cf64;
+typedef __attribute__((address_space(4))) const double karg_cf64;
+constexpr int CT_D = 0, CT_Q = CT_D + 6 * MAX_NT, CT_R = CT_Q + 9, CT_P = CT_R + 6, CT_LPT = CT_P + 81, CT_SQ2Q = CT_LPT + 81, CT_WORDS = CT_SQ2Q + 9;
+static_assert(offsetof(DeviceConsts, Q) == offsetof(DeviceConsts, D) + 8 * CT_Q && offsetof(DeviceConsts, R) == offsetof(DeviceConsts, D) + 8 * CT_R &&
+              offsetof(DeviceConsts, P) == offsetof(DeviceConsts, D) + 8 * CT_P && offsetof(DeviceConsts, LPt) == offsetof(DeviceConsts, D) + 8 * CT_LPT &&
+              offsetof(DeviceConsts, sq2Q) == offsetof(DeviceConsts, D) + 8 * CT_SQ2Q && offsetof(DeviceConsts, rho) == offsetof(DeviceConsts, D) + 8 * CT_WORDS,
+              "the constant table is the run D .. sq2Q of DeviceConsts");
+// GOFF: offset (doubles) of the wrench scratch behind the gradient (>= n)
+// SPtr: stage storage, lds_f64* when it fits behind the vectors, else glb_f64* (long horizons).  GPtr: the gradient and the wrench
+// perturbations, lds_f64* (the tile area of the build, dead during the iteration) or glb_f64* (the global slot).  CPtr: see above.
+template <class SPtr, class GPtr, class CPtr, int GOFF = 160>
+__device__ __noinline__ void struct_grad_at(int N, double dt, CPtr ctab, glb_cf64* recg, lds_f64* recd, lds_cf32* s_Da,
+                                            lds_cf32* dnat, SPtr sS, GPtr gout, int na, int lane) {
     constexpr int ZERO = REC_STRIDE;
-    const int N = C.N;
+    // lanes exchange the wrench perturbations, the stage storage and the gradient: through LDS a compiler barrier orders them
+    // (one wave, in-order LDS), through the global slot the stores must have landed
+    constexpr bool GLOBAL_XCHG = std::is_same<SPtr, glb_f64*>::value || std::is_same<GPtr, glb_f64*>::value;
+    auto xchg_fence = [&]() {
+        if constexpr (GLOBAL_XCHG) {
+            __threadfence_block();
+            wave_global_fence();
+        } else {
+            wave_lds_fence();
+        }
+    };
     const int m = lane & 15, q = lane >> 4;
     int offX[4], offG[2], offAT[4], offBT[4];
 #pragma unroll
@@ -694,37 +717,27 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
     if (lane == 0) {
         recd[REC_STRIDE] = 0.0;
         recd[REC_STRIDE + 1] = 1.0;
-        recd[REC_STRIDE + 2] = C.dt;
+        recd[REC_STRIDE + 2] = dt;
     }
     // per-lane rows of this lane's column tile: r_i = q + 4 i
     double qrow[4], rrow[2], da_op[2];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) qrow[i] = (q + 4 * i < 9) ? C.Q[q + 4 * i] : 0.0;
+    for (int i = 0; i < 4; ++i) qrow[i] = (q + 4 * i < 9) ? ctab[CT_Q + q + 4 * i] : 0.0;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        rrow[i] = (q + 4 * i < 6) ? C.R[q + 4 * i] : 0.0;
+        rrow[i] = (q + 4 * i < 6) ? ctab[CT_R + q + 4 * i] : 0.0;
         da_op[i] = (q + 4 * i < 6) ? (double)s_Da[(q + 4 * i) * MAX_NT + m] : 0.0;   // Da[g][a=m]: A operand of Da' z
     }
-    // terminal weight as an A operand, P[m][4s+q] (9x9, zero padded).  Read HERE: `C` is a generic
-    // reference, and a flat load inside the sweeps would force every later wait to vmcnt(0).
+    // terminal weight as an A operand, P[m][4s+q] (9x9, zero padded)
     double pa[4];
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) pa[s4] = (m < 9 && 4 * s4 + q < 9) ? C.P[9 * m + 4 * s4 + q] : 0.0;
+    for (int s4 = 0; s4 < 4; ++s4) pa[s4] = (m < 9 && 4 * s4 + q < 9) ? ctab[CT_P + 9 * m + 4 * s4 + q] : 0.0;
     const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
-    // wrench perturbations gen_k = Da d_k of ALL stages up front, one (stage, component) pair per lane,
-    // parked behind the gradient in the global scratch (N x 8 doubles) and prefetched with the records
-    glb_f64* genS = gout + GOFF;
-    for (int t = lane; t < N * 8; t += 64) {
-        const int k = t >> 3, g = t & 7;
-        double acc = 0.0;
-        if (g < 6)
-            for (int a = 0; a < na; ++a) acc += (double)s_Da[g * MAX_NT + a] * (double)dnat[k * na + a];
-        genS[t] = acc;
-    }
-    __threadfence_block();
-    wave_global_fence();   // lanes exchange through the global slot here
     // this lane's two wrench rows (g = q and q+4) of stage k
     const int g1 = (q + 4 < 6) ? q + 4 : 7;      // slot 7 of every stage is zero
+    // wrench perturbations gen_k = Da d_k of ALL stages up front, one (stage, component) pair per lane,
+    // parked behind the gradient (N x 8 doubles) and fetched with the records
+    GPtr genS = gout + GOFF;
     // The float64 records come from HBM (they were last touched by the condensing, a few hundred
     // thousand cycles ago) and one stage of a sweep is only ~500 cycles of work: the loads run FOUR
     // stages ahead, in four statically named register sets (a rotating copy would wait for the load).
@@ -733,14 +746,21 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
     // conditional around a load turns into a phi whose copy waits for the load just issued
     const int w2 = (lane + 128 < REC_STRIDE) ? lane + 128 : REC_STRIDE - 1;     // third word of this lane (152 = 2*64 + 24)
     const int d2 = (lane + 128 < REC_STRIDE) ? lane + 128 : REC_STRIDE + 3;     // LDS dump word behind {0, 1, dt}
-    auto issue = [&](auto SL, int kk) {
+    auto issue_rec = [&](auto SL, int kk) {
         constexpr int sl = decltype(SL)::value;
         glb_cf64* r = recg + (int64_t)kk * REC_STRIDE;
         pf[sl][0] = r[lane];
         pf[sl][1] = r[lane + 64];
         pf[sl][2] = r[w2];
+    };
+    auto issue_gen = [&](auto SL, int kk) {
+        constexpr int sl = decltype(SL)::value;
         pg[sl][0] = genS[kk * 8 + q];
         pg[sl][1] = genS[kk * 8 + g1];
+    };
+    auto issue = [&](auto SL, int kk) {
+        issue_rec(SL, kk);
+        issue_gen(SL, kk);
     };
     auto stage_to_lds = [&](auto SL) {
         constexpr int sl = decltype(SL)::value;
@@ -752,14 +772,31 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
     using S1 = std::integral_constant<int, 1>;
     using S2 = std::integral_constant<int, 2>;
     using S3 = std::integral_constant<int, 3>;
+    const int N4 = N & ~3;
+    // the first four records are requested before the products below, which cover their trip
+    issue_rec(S0{}, 0);
+    issue_rec(S1{}, (1 < N) ? 1 : 0);
+    issue_rec(S2{}, (2 < N) ? 2 : 0);
+    issue_rec(S3{}, (3 < N) ? 3 : 0);
+    for (int t = lane; t < N * 8; t += 64) {
+        const int k = t >> 3, g = t & 7;
+        double acc = 0.0;
+        if (g < 6)
+            for (int a = 0; a < na; ++a) acc += (double)s_Da[g * MAX_NT + a] * (double)dnat[k * na + a];
+        genS[t] = acc;
+    }
+    xchg_fence();
     // ---- forward sweep: dc_{k+1} = A_k dc_k + B_k gen_k ----
+    // With N a multiple of four the last four stages request, in place of a record past the end, what the adjoint sweep
+    // starts with: records N-1 .. N-4 into register sets 0 .. 3.
+    const bool hand_on = N4 == N;
     f64x4 dc = zero;
     auto fwd = [&](auto SL, int k) {
         constexpr int sl = decltype(SL)::value;
         wave_lds_fence();
         stage_to_lds(SL);
         const double g0 = pg[sl][0], g1v = pg[sl][1];
-        issue(SL, (k + 4 < N) ? k + 4 : N - 1);
+        issue(SL, (k + 4 < N) ? k + 4 : (hand_on ? 2 * N - 5 - k : N - 1));
         wave_lds_fence();
         // two accumulators: a dependent float64 MFMA costs its full 16 passes, so halve the chain
         f64x4 nx = zero, ny = zero;
@@ -779,18 +816,21 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
 #pragma unroll
             for (int i = 0; i < 3; ++i) t[i] = qrow[i] * dc[i];
         }
+        // (the sums in every lane, not under the lane mask: past a skipped masked block the terminal products above would reach
+        // the loop's back edge unread, and the registers they are still writing are the first the next stage reuses)
+        double s0 = recd[REC_WE + q] + t.x, s1 = recd[REC_WE + q + 4] + t.y, s2 = recd[REC_WE + 8] + t.z;
+        asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2));      // (keeps them here: the optimiser sinks them back under the mask)
         if (m == 0) {
             SPtr srow = sS + (k + 1) * 9;
-            srow[q] = recd[REC_WE + q] + t.x;
-            srow[q + 4] = recd[REC_WE + q + 4] + t.y;
-            if (q == 0) srow[8] = recd[REC_WE + 8] + t.z;
+            srow[q] = s0;
+            srow[q + 4] = s1;
+            if (q == 0) srow[8] = s2;
         }
     };
-    const int N4 = N & ~3;
-    issue(S0{}, 0);
-    issue(S1{}, (1 < N) ? 1 : 0);
-    issue(S2{}, (2 < N) ? 2 : 0);
-    issue(S3{}, (3 < N) ? 3 : 0);
+    issue_gen(S0{}, 0);
+    issue_gen(S1{}, (1 < N) ? 1 : 0);
+    issue_gen(S2{}, (2 < N) ? 2 : 0);
+    issue_gen(S3{}, (3 < N) ? 3 : 0);
     for (int k = 0; k < N4; k += 4) {
         fwd(S0{}, k);
         fwd(S1{}, k + 1);
@@ -801,7 +841,8 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
         issue(S0{}, k);
         fwd(S0{}, k);
     }
-    wave_global_fence();   // the stage storage may be the global slot (long horizons)
+    if constexpr (std::is_same<SPtr, glb_f64*>::value) wave_global_fence();   // the stage storage is the global slot (long horizons)
+    else wave_lds_fence();
     // ---- adjoint sweep (stage N-1-i uses register set i & 3) ----
     f64x4 lam = zero;
     auto adj = [&](auto SL, int k) {
@@ -849,10 +890,12 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
             lam.w = nl.w;
         }
     };
-    issue(S0{}, N - 1);
-    issue(S1{}, (N - 2 >= 0) ? N - 2 : 0);
-    issue(S2{}, (N - 3 >= 0) ? N - 3 : 0);
-    issue(S3{}, (N - 4 >= 0) ? N - 4 : 0);
+    if (!hand_on) {
+        issue(S0{}, N - 1);
+        issue(S1{}, (N - 2 >= 0) ? N - 2 : 0);
+        issue(S2{}, (N - 3 >= 0) ? N - 3 : 0);
+        issue(S3{}, (N - 4 >= 0) ? N - 4 : 0);
+    }
     int ka = N - 1;
     for (; ka >= 3; ka -= 4) {
         adj(S0{}, ka);
@@ -864,8 +907,15 @@ __device__ __noinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, 
         issue(S0{}, ka);
         adj(S0{}, ka);
     }
-    __threadfence_block();
-    wave_global_fence();   // lanes exchange through the global slot here
+    xchg_fence();
+}
+
+// the same with the constants in the by-value struct and everything exchanged through the global slot: the other solve kernels
+// that take their reference gradient here
+template <class SPtr, int GOFF = 160>
+__device__ __forceinline__ void struct_grad(const DeviceConsts& C, glb_cf64* recg, lds_f64* recd, lds_cf32* s_Da,
+                                            lds_cf32* dnat, SPtr sS, glb_f64* gout, int na, int lane) {
+    struct_grad_at<SPtr, glb_f64*, const double*, GOFF>(C.N, C.dt, &C.D[0], recg, recd, s_Da, dnat, sS, gout, na, lane);
 }
 
 // ---- dense operand images of the stage matrices ------------------------------------------------
@@ -976,6 +1026,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
     __shared__ __attribute__((aligned(16))) float s_Da[6 * MAX_NT];
     __shared__ unsigned char s_stg[NPAD], s_thr[NPAD];
     __shared__ int s_act[MAX_NT];
+    // the per-lane constants of the handle (see CT_D ..): a copy in LDS where there is room (NB = 8: 18.8 of 20 KiB per wave), else
+    // read where they lie, in the kernel-argument segment (DeviceConsts is the first argument: offset 0)
+    constexpr bool CLDS = OCC2;
+    karg_cf64* const kctab = (karg_cf64*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(DeviceConsts, D));
+    using CPtr = typename std::conditional<CLDS, lds_cf64*, karg_cf64*>::type;
+    CPtr ctab;
+    if constexpr (CLDS) {
+        __shared__ double s_ctab[CT_WORDS];
+        for (int i = threadIdx.x; i < CT_WORDS; i += 64) s_ctab[i] = kctab[i];
+        wave_lds_fence();
+        ctab = (lds_cf64*)s_ctab;
+    } else {
+        ctab = kctab;
+    }
     __shared__ __attribute__((aligned(16))) float wlds[OCC2 ? NB * 256 : 4];   // W_J of the current factorisation (OCC2)
     float* const dense = tiles;      // build phase only: 2 x (A 16x16 | B 16x8 | dump word), then LPt 16x16
     float* const xvp = work;         // rhs / solution of the KKT solves
@@ -1011,6 +1075,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         STAMP_START();
         wave_lds_fence();
         // ---------------- prologue: active thrusters, index tables ----------------
+        // (the lane number taken anew: what the prologue derives from the kernel-long one -- the addresses of its loads among it -- is
+        // hoisted out of the instance loop, spilled, and reloaded from scratch in front of every such load)
+        const int lane = lane_now();
+        const int li = lane & 15, lq = lane >> 4;
         double ub_l = 0.0;
         if (lane < NT) ub_l = P.ub[inst * NT + lane];
         const unsigned long long amask = __ballot(lane < NT && ub_l > 0.0);
@@ -1038,7 +1106,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         wave_lds_fence();
         if (lane < na) {
 #pragma unroll
-            for (int g = 0; g < 6; ++g) s_Da[g * MAX_NT + lane] = (float)C.D[g * MAX_NT + s_act[lane]];
+            for (int g = 0; g < 6; ++g) s_Da[g * MAX_NT + lane] = (float)ctab[CT_D + g * MAX_NT + s_act[lane]];
         }
         for (int e = lane; e < npadr; e += 64) {
             const int s = e / na;
@@ -1083,7 +1151,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         }
         for (int i = lane; i < 81; i += 64) {
             const int r = i / 9, c = i - 9 * r;
-            if (c >= r) dense[2 * DENSE_WORDS + 16 * tile_row(r) + tile_row(c)] = (float)C.LPt[i];
+            if (c >= r) dense[2 * DENSE_WORDS + 16 * tile_row(r) + tile_row(c)] = (float)ctab[CT_LPT + i];
         }
         wave_lds_fence();
         const f32x4 lp4 = lds4(dense + 2 * DENSE_WORDS + 16 * li + 4 * lq);   // A operand of E_N = LPt G9
@@ -1127,7 +1195,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         }
         float esc[3];               // sqrt(2 Q) of this lane's costed rows (row-group 3 holds the quaternion: 0); OCC2: 2 Q
 #pragma unroll
-        for (int s3 = 0; s3 < 3; ++s3) esc[s3] = (lq < 3) ? (OCC2 ? 2.f * (float)C.Q[3 * s3 + lq] : (float)C.sq2Q[3 * s3 + lq]) : 0.f;
+        for (int s3 = 0; s3 < 3; ++s3) esc[s3] = (lq < 3) ? (OCC2 ? 2.f * (float)ctab[CT_Q + 3 * s3 + lq] : (float)ctab[CT_SQ2Q + 3 * s3 + lq]) : 0.f;
         f32x4 acc[NTILES];
 #pragma unroll
         for (int t = 0; t < NTILES; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1136,6 +1204,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
         // each tile exactly as its lanes hold it (one b128 per lane, conflict free): the factorisation loads a tile STRAIGHT
         // INTO the MFMA accumulator that collects the Schur terms (sum T'T - H), so no VALU instruction touches it.
         float* const mtab = work;     // MAX_NT x MAX_NT words; the vector workspace is idle until the interior-point iterations
+        float hdmax = 0.f;            // running max of this lane's real diagonal entries of H (the polish penalty's scale)
         auto finish_tile = [&](int I, int J) {     // I, J are constants after unrolling
             // the lane's table addresses recomputed here (lane_now): taken from the kernel-long li / lq, they were reloaded
             // from scratch before every table read and every tile store of the peeled last stage
@@ -1155,6 +1224,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
                     if (s1 == 255 && e1 == e2) add = 1.f;
                     h[rr] += add;
                 }
+            }
+            if (I == J) {      // lane (q, col) of a diagonal tile holds H[16 I + col][16 I + 4 q + r]: its diagonal entry is r = col - 4 q
+                const int r = li - 4 * lq;
+                const float dg = (r == 0) ? h.x : (r == 1) ? h.y : (r == 2) ? h.z : h.w;
+                if (r >= 0 && r < 4 && 16 * I + li < n) hdmax = fmaxf(hdmax, dg);
             }
             htiles.st((I * (I + 1)) / 2 + J, lane, -h);
         };
@@ -1300,6 +1374,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
             }
         }
         wave_lds_fence();   // the dense images in the tile area are dead from here
+        // the penalty of the polish, FTMPC_F32_PW0 max diag(H): wave-uniform, so it waits in a scalar register for the polish
+        const float pw_diag = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, FTMPC_F32_PW0 * wave_max(hdmax))));
 
         // g, bounds, start point
         float gv[NV], lo[NV], hi[NV], sl[NV], su[NV], zl[NV], zu[NV], grad[NV];
@@ -1390,7 +1466,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
                 for (int v = 0; v < NV; ++v) dcur[v] = valid[v] ? ((sl[v] < su[v]) ? lo[v] + sl[v] : hi[v] - su[v]) : 0.f;
             }
             // one accurate (float64, structured) gradient at the current iterate
-            auto refresh = [&]() {
+            // (between: run after the sweeps and before their result is read -- the polish requests its parked factor there)
+            auto refresh = [&](auto between) {
                 float dnow[NV];
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
@@ -1401,16 +1478,30 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
                 wave_lds_fence();
                 constexpr int SAVAIL = (NPAD + SH::SEXTRA) * 4;       // bytes of LDS behind dvp
                 double* const gout = sbuf;                               // global, n doubles
-                if ((N + 1) * 72 <= SAVAIL)
-                    struct_grad(C, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
-                                (lds_f64*)reinterpret_cast<double*>(dvp), (glb_f64*)gout, na, lane);
-                else
-                    struct_grad(C, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
+                // The gradient (n <= 160 doubles) and the wrench perturbations (8 N doubles behind it) go through the tile area of the
+                // build where that is free during the iteration (NB = 8 at two waves: the Hessian lives in the global slot) and the
+                // stage storage is in LDS as well (NB = 8: N <= 21); every other case exchanges through the global slot as before.
+                constexpr bool GLDS = OCC2;
+                static_assert(!GLDS || (160 + 8 * (SAVAIL / 72 - 1)) * 2 <= BUILD_WORDS, "gradient and wrench perturbations beyond the tile area");
+                lds_f64* const gout_l = (lds_f64*)reinterpret_cast<double*>(tiles);
+                const bool s_in_lds = (N + 1) * 72 <= SAVAIL;
+                if (s_in_lds) {
+                    if constexpr (GLDS)
+                        struct_grad_at(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
+                                    (lds_f64*)reinterpret_cast<double*>(dvp), gout_l, na, lane);
+                    else
+                        struct_grad_at(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
+                                    (lds_f64*)reinterpret_cast<double*>(dvp), (glb_f64*)gout, na, lane);
+                } else
+                    struct_grad_at(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
                                 (glb_f64*)(sbuf + slot_stage_off(N)), (glb_f64*)gout, na, lane);
+                between();
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
                     const int e = v * 64 + lane;
-                    gref[v] = (valid[v] && e < n) ? gout[e] + 2.0 * C.rho * ((double)ubar[v] + (double)dnow[v]) : 0.0;
+                    double ge = 0.0;
+                    if (valid[v] && e < n) ge = (GLDS && s_in_lds) ? (double)gout_l[e] : gout[e];
+                    gref[v] = (valid[v] && e < n) ? ge + 2.0 * C.rho * ((double)ubar[v] + (double)dnow[v]) : 0.0;
                     dref[v] = dnow[v];
                     grad[v] = valid[v] ? (float)gref[v] : 0.f;
                 }
@@ -1418,7 +1509,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
                 STAMP(8);
             };
             if (do_ref) {
-                refresh();
+                refresh([] {});
             } else if (it == 0) {
             // gradient at the start point, gref + H (d - dref).  Later iterates do not need the product
             // again: the Newton system just solved gives  H dd = rhs - Sigma dd,  so the gradient follows
@@ -1517,15 +1608,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
             if (__builtin_amdgcn_readfirstlane(!pol && !pol_tried && mu < FTMPC_F32_MU_POLISH)) {
                 pol_tried = true;
                 pol = 1;
-                float hs = 0.f;
-#pragma unroll
-                for (int I = 0; I < NB; ++I) {      // max diag(H): lane (q, col) of the diagonal tile holds -H[16 I + col][16 I + 4 q + r]
-                    const f32x4 t4 = htiles.ld((I * (I + 1)) / 2 + I, lane);
-                    const int r = li - 4 * lq;
-                    const float dg = (r == 0) ? t4.x : (r == 1) ? t4.y : (r == 2) ? t4.z : t4.w;
-                    if (r >= 0 && r < 4 && 16 * I + li < n) hs = fmaxf(hs, -dg);
-                }
-                pw = FTMPC_F32_PW0 * wave_max(hs);
+                pw = pw_diag;
                 pact = 0u;
 #pragma unroll
                 for (int v = 0; v < NV; ++v) {
@@ -1688,16 +1771,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
 #pragma unroll
                     for (int J = 0; J < NB; ++J) fpark[(slotn++) * 64 + lane] = Wd[J];
                 }
-                refresh();
-                slotn = 0;
+                // the parked tiles are requested before the gradient is read back: the two trips overlap
+                auto unpark = [&]() {
+                    int slotr = 0;
 #pragma unroll
-                for (int I = 1; I < NB; ++I)
+                    for (int I = 1; I < NB; ++I)
 #pragma unroll
-                    for (int J = 0; J < I; ++J) Tt[tidx(I, J)] = fpark[(slotn++) * 64 + lane];
-                if constexpr (!OCC2) {
+                        for (int J = 0; J < I; ++J) Tt[tidx(I, J)] = fpark[(slotr++) * 64 + lane];
+                    if constexpr (!OCC2) {
 #pragma unroll
-                    for (int J = 0; J < NB; ++J) Wd[J] = fpark[(slotn++) * 64 + lane];
-                }
+                        for (int J = 0; J < NB; ++J) Wd[J] = fpark[(slotr++) * 64 + lane];
+                    }
+                };
+                refresh(unpark);
             }
             ap = wave_min(ap);
             ad = wave_min(ad);
