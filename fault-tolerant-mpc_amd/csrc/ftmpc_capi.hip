@@ -623,7 +623,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 520; }
+int32_t ftmpc_version(void) { return 530; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -1950,7 +1950,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
-                         const ftmpc_mission* ms = nullptr);
+                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -2048,6 +2048,49 @@ static int check_mission(ftmpc_handle* h, int64_t B, int32_t T, const ftmpc_miss
 // cost of a loop without steps: zero
 static void zero_mission_cost(const ftmpc_mission* ms, int64_t B) {
     if (ms && ms->cost && B > 0) std::fill(ms->cost, ms->cost + 3 * B, 0.0);
+}
+
+// An actuator's layout and values (include/ftmpc.h, ftmpc_actuator) over the vehicles [0, B): empty when acceptable, else the message,
+// which names the field and, where there is one, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string actuator_problem(const ftmpc_actuator* ac, int64_t B, int NT, int64_t first = 0) {
+    if (!ac) return "";
+    if (ac->struct_size != (int32_t)sizeof(ftmpc_actuator))
+        return "ftmpc_actuator.struct_size is " + std::to_string(ac->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_actuator));
+    if (ac->mode != 0 && ac->mode != 1) return "ftmpc_actuator.mode is " + std::to_string(ac->mode) + ", outside {0, 1}";
+    if (ac->substeps < 0 || ac->substeps > 64) return "ftmpc_actuator.substeps is " + std::to_string(ac->substeps) + ", outside [0, 64]";
+    const int S = ac->substeps > 0 ? ac->substeps : 1;
+    if (ac->min_on < 0 || ac->min_on > S)
+        return "ftmpc_actuator.min_on is " + std::to_string(ac->min_on) + ", outside [0, S = " + std::to_string(S) + "]";
+    if (ac->align < 0 || ac->align > 2) return "ftmpc_actuator.align is " + std::to_string(ac->align) + ", outside {0, 1, 2}";
+    if (!std::isfinite(ac->tau_on) || ac->tau_on < 0) return "ftmpc_actuator.tau_on is negative or not finite";
+    if (!std::isfinite(ac->tau_off) || ac->tau_off < 0) return "ftmpc_actuator.tau_off is negative or not finite";
+    if (ac->mode == 0) {
+        if (ac->min_on != 0) return "ftmpc_actuator.min_on is given, but mode = 0 (a proportional valve has no dead band)";
+        if (ac->align != 0) return "ftmpc_actuator.align is given, but mode = 0 (a proportional valve has no pulse to align)";
+        if (ac->pulses) return "ftmpc_actuator.pulses is given, but mode = 0 (a proportional valve has no pulses)";
+        if (ac->ticks_hist) return "ftmpc_actuator.ticks_hist is given, but mode = 0 (a proportional valve has no ticks)";
+    }
+    if (ac->state)
+        for (int64_t i = 0; i < B * NT; ++i)
+            if (!std::isfinite(ac->state[i]) || ac->state[i] < 0)
+                return "ftmpc_actuator.state: vehicle " + std::to_string(first + i / NT) + " has a negative or non-finite valve state (thruster " +
+                       std::to_string(i % NT) + ")";
+    return "";
+}
+static int check_actuator(ftmpc_handle* h, int64_t B, const ftmpc_actuator* ac) {
+    const std::string msg = actuator_problem(ac, B, h->cfg.NT);
+    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
+// trivial: the loop launches the plant kernels it launches without the struct
+static bool actuator_trivial(const ftmpc_actuator* ac) {
+    return !ac || (ac->mode == 0 && ac->substeps <= 1 && ac->tau_on == 0 && ac->tau_off == 0 && !ac->delivered && !ac->pulses &&
+                   !ac->applied_hist && !ac->ticks_hist && !ac->state);
+}
+// the sums of a loop without steps: zero (the valve states stay as they are)
+static void zero_actuator_sums(const ftmpc_actuator* ac, int64_t B) {
+    if (ac && ac->delivered && B > 0) std::fill(ac->delivered, ac->delivered + B, 0.0);
+    if (ac && ac->pulses && B > 0) std::fill(ac->pulses, ac->pulses + B, 0);
 }
 
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
@@ -2150,6 +2193,15 @@ int ftmpc_simulate_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* 
                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
+    return ftmpc_simulate_actuator_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                         x_hist, not_converged, out, plant, mission, nullptr);
+}
+
+int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2158,14 +2210,16 @@ int ftmpc_simulate_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* 
     if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
+        zero_actuator_sums(actuator, B);
         return FTMPC_OK;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission);
+                         faults, x_hist, out, plant, mission, actuator);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2206,6 +2260,18 @@ int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, d
                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                         const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
+    return ftmpc_simulate_wrench_actuator_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                                seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                                out, plant, mission, nullptr);
+}
+
+int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                         const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                         const ftmpc_actuator* actuator) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
@@ -2214,14 +2280,16 @@ int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, d
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
+        zero_actuator_sums(actuator, B);
         return FTMPC_OK;
     }
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2271,7 +2339,7 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
-                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms) {
+                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2377,6 +2445,55 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (!windows) HIP_TRY(h, hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
     if (uref_traj) HIP_TRY(h, hipMemcpyAsync(d_ur, uref_traj, (size_t)ncol * 6 * sizeof(double), hipMemcpyHostToDevice, s));
     if ((rc = stage_inputs(h, B, x, ub, stuck)) != FTMPC_OK) return rc;
+    // actuator (checked by the entry): not trivial, the plant's step is ftmpc_plant_step_act_kernel's.  The four lag constants are
+    // computed here, once per call; the valve states are staged component-major [NT][B] (the caller's are vehicle-major), delivered and
+    // pulses start at zero
+    const bool act = !actuator_trivial(ac);
+    DevBuf<double> d_aval, d_adel, d_aapp;
+    DevBuf<int32_t> d_apul, d_atick;
+    std::vector<double> h_aval;
+    ftmpc::ActParams ap{};
+    if (act) {
+        const int S = ac->substeps > 0 ? ac->substeps : 1;
+        const double hs = h->cfg.dt / S;
+        ap.pwm = ac->mode == 1;
+        ap.substeps = S;
+        ap.min_on = ac->min_on;
+        ap.align = ac->align;
+        if (ac->tau_on > 0) {
+            ap.E_on = std::exp(-hs / ac->tau_on);
+            ap.K_on = -std::expm1(-hs / ac->tau_on) * ac->tau_on / hs;
+        }
+        if (ac->tau_off > 0) {
+            ap.E_off = std::exp(-hs / ac->tau_off);
+            ap.K_off = -std::expm1(-hs / ac->tau_off) * ac->tau_off / hs;
+        }
+        const size_t nv = (size_t)B * NT;
+        HIP_TRY(h, hipMalloc(&d_aval.p, nv * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_adel.p, (size_t)B * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_apul.p, (size_t)B * sizeof(int32_t)));
+        HIP_TRY(h, hipMemsetAsync(d_adel, 0, (size_t)B * sizeof(double), s));
+        HIP_TRY(h, hipMemsetAsync(d_apul, 0, (size_t)B * sizeof(int32_t), s));
+        if (ac->state) {
+            try {
+                h_aval.resize(nv);
+            } catch (const std::bad_alloc&) {
+                return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the actuator's staging array");
+            }
+            for (int64_t b = 0; b < B; ++b)
+                for (int i = 0; i < NT; ++i) h_aval[(size_t)i * B + b] = ac->state[b * NT + i];
+            HIP_TRY(h, hipMemcpyAsync(d_aval, h_aval.data(), nv * sizeof(double), hipMemcpyHostToDevice, s));
+        } else {
+            HIP_TRY(h, hipMemsetAsync(d_aval, 0, nv * sizeof(double), s));
+        }
+        if (ac->applied_hist) HIP_TRY(h, hipMalloc(&d_aapp.p, (size_t)T * nv * sizeof(double)));
+        if (ac->ticks_hist) HIP_TRY(h, hipMalloc(&d_atick.p, (size_t)T * nv * sizeof(int32_t)));
+        ap.state = d_aval;
+        ap.delivered = d_adel;
+        ap.pulses = d_apul;
+        ap.applied_hist = d_aapp;
+        ap.ticks_hist = d_atick;
+    }
     const int64_t xw = 9 * (int64_t)(N + 1), uw = 6 * (int64_t)(N + 1);     // doubles per window
     ftmpc::RefWindow rw{};
     if (windows) {
@@ -2578,7 +2695,9 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         }
         if (rc != FTMPC_OK) return rc;
         sp.step = t;
-        if (var_plant)
+        if (act)
+            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_act_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv, ap);
+        else if (var_plant)
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_var_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv);
         else
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
@@ -2622,7 +2741,18 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (oc->status_hist)
             HIP_TRY(h, hipMemcpyAsync(oc->status_hist, d_shist, (size_t)T * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
+    if (act) {
+        const size_t nv = (size_t)B * NT;
+        if (ac->delivered) HIP_TRY(h, hipMemcpyAsync(ac->delivered, d_adel, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (ac->pulses) HIP_TRY(h, hipMemcpyAsync(ac->pulses, d_apul, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (ac->applied_hist) HIP_TRY(h, hipMemcpyAsync(ac->applied_hist, d_aapp, (size_t)T * nv * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (ac->ticks_hist) HIP_TRY(h, hipMemcpyAsync(ac->ticks_hist, d_atick, (size_t)T * nv * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (ac->state) HIP_TRY(h, hipMemcpyAsync(h_aval.data(), d_aval, nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(h, hipStreamSynchronize(s));
+    if (act && ac->state)
+        for (int64_t b = 0; b < B; ++b)
+            for (int i = 0; i < NT; ++i) ac->state[b * NT + i] = h_aval[(size_t)i * B + b];
     return FTMPC_OK;
 }
 

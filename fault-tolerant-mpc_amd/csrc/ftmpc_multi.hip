@@ -204,7 +204,7 @@ void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_
     for (int64_t t = 0; t < T; ++t) std::memcpy(dst + (t * B + lo) * w, src + t * n * w, (size_t)(n * w) * sizeof(V));
 }
 
-// The closed loops over the device slots (ftmpc_multi_simulate_mission_batch / _wrench_mission_batch; hull_A == nullptr: the thruster
+// The closed loops over the device slots (ftmpc_multi_simulate_actuator_batch / _wrench_actuator_batch; hull_A == nullptr: the thruster
 // form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
 // caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
 // staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
@@ -213,7 +213,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                   bool wrench) {
+                   const ftmpc_actuator* actuator, bool wrench) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -236,8 +236,14 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         const std::string msg = mission_problem(mission, B, T, m->cfg.N, xref_traj, uref_traj);
         if (!msg.empty()) return refuse(msg);
     }
+    {     // the actuator likewise: the parameters are uniform, delivered / pulses / state and the two histories are per vehicle.  (The
+          // handle entry checks each shard's struct again, state included: what passed here cannot fail there.)
+        const std::string msg = actuator_problem(actuator, B, m->cfg.NT);
+        if (!msg.empty()) return refuse(msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
+        zero_actuator_sums(actuator, B);
         return FTMPC_OK;
     }
     const int G = (int)m->dev.size();
@@ -281,14 +287,23 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         oc.index0 = lo;
         oc.index_total = B;
         const bool whole = n == B;      // one slot: no staging
-        std::vector<double> uh, xh;
-        std::vector<int32_t> sh;
+        std::vector<double> uh, xh, ah;
+        std::vector<int32_t> sh, kh;
+        ftmpc_actuator at{};
+        if (actuator) {
+            at = *actuator;
+            if (at.delivered) at.delivered += lo;
+            if (at.pulses) at.pulses += lo;
+            if (at.state) at.state += lo * NT;
+        }
         try {
             bad[g].assign((size_t)T, 0);
             abad[g].assign((size_t)T, 0);
             if (u_hist && !whole) uh.resize((size_t)T * n * NT);
             if (x_hist && !whole) xh.resize((size_t)T * n * 13);
             if (out && out->status_hist && !whole) sh.resize((size_t)T * n);
+            if (at.applied_hist && !whole) ah.resize((size_t)T * n * NT);
+            if (at.ticks_hist && !whole) kh.resize((size_t)T * n * NT);
         } catch (const std::bad_alloc&) {
             return dev_fail(d, FTMPC_ERR_ALLOC, "out of host memory for the shard's histories");
         }
@@ -308,20 +323,27 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         }
         double* const uh_p = !u_hist ? nullptr : (whole ? u_hist : uh.data());
         double* const xh_p = !x_hist ? nullptr : (whole ? x_hist : xh.data());
-        const int rc2 = wrench ? ftmpc_simulate_wrench_mission_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+        if (!whole) {
+            if (at.applied_hist) at.applied_hist = ah.data();
+            if (at.ticks_hist) at.ticks_hist = kh.data();
+        }
+        const int rc2 = wrench ? ftmpc_simulate_wrench_actuator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
                                                                      xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
                                                                      faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
                                                                      alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
-                                                                     mission ? &mi : nullptr)
-                               : ftmpc_simulate_mission_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
-                                                              seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                              bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr);
+                                                                     mission ? &mi : nullptr, actuator ? &at : nullptr)
+                               : ftmpc_simulate_actuator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                               seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                               bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
+                                                               actuator ? &at : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
             if (x_hist) scatter_rows(x_hist, xh.data(), T, B, lo, n, 13);
             if (out && out->status_hist) scatter_rows(out->status_hist, sh.data(), T, B, lo, n, 1);
+            if (actuator && actuator->applied_hist) scatter_rows(actuator->applied_hist, ah.data(), T, B, lo, n, NT);
+            if (actuator && actuator->ticks_hist) scatter_rows(actuator->ticks_hist, kh.data(), T, B, lo, n, NT);
         }
         return FTMPC_OK;
     });
@@ -560,7 +582,7 @@ int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -569,7 +591,7 @@ int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, doubl
                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                      const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -578,7 +600,7 @@ int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, dou
                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                        const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, nullptr, false);
 }
 
 int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -588,7 +610,7 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -599,7 +621,7 @@ int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T
                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                             const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -610,7 +632,28 @@ int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t
                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, nullptr, true);
+}
+
+int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                        const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, false);
+}
+
+int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                               const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                               int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                               uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                               const ftmpc_actuator* actuator) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, true);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

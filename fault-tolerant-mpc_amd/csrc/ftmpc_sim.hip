@@ -759,4 +759,132 @@ __global__ void __launch_bounds__(64) ftmpc_outcome_mission_kernel(const DeviceC
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Pulsed (PWM) thrusters and valve lag in the plant (ftmpc_simulate_actuator_batch / ftmpc_simulate_wrench_actuator_batch;
+// include/ftmpc.h, ftmpc_actuator).  ftmpc_plant_step_act_kernel is ftmpc_plant_step_var_kernel with the step cut into S sub-steps of
+// h = dt / S, each one RK4 step under the force the valves deliver in it; launched in place of the plant kernel only when the call's
+// actuator is not trivial.  Per thruster i the step has a level L_i and an on-window [s_i, s_i + k_i) of sub-steps:
+//   proportional   L_i = ub_i > 0 ? u_i : 0                 k_i = S, s_i = 0
+//   PWM            L_i = ub_i, d_i = clamp(u_i / ub_i, 0, 1)   k_i = floor(d_i S + 0.5), 0 where below min_on; s_i by the alignment
+// (a dead thruster has L_i = 0, k_i = 0).  In sub-step j the target is g = L_i inside the window, else 0; the valve state a_i moves
+// towards it with the on-pair (E, K) where g > a_i, else the off-pair: mean force m = g + (a_i - g) K, then a_i = g + (a_i - g) E.
+// The four constants come from the host (no transcendental here); E = K = 0 is a valve without lag.  The sub-step's generalised force
+// is D_b (m + stuck) (+ t_b); noise, renormalisation, histories and bad_count come once per step, exactly as the plant kernels'.
+// The per-thruster rows (level, stuck, valve state, the step's force sum, ticks) are indexed by a loop whose bound is a run-time
+// value; as per-lane arrays they would live in scratch, so they are LDS rows [MAX_NT][64], lane-consecutive (no bank conflict).  The
+// nominal D is read at a wave-uniform index (scalar loads), a dispersed D_b in PlantVar's [k][B] layout.  The valve states of the
+// call are component-major [NT][B]; delivered [B] and pulses [B] are buffers of the call, zeroed by the host.  (The kernel stands at
+// the end of the file so that the build logs keep the source lines of every kernel above.)
+// ---------------------------------------------------------------------------------------------------------
+struct ActParams {
+    int32_t pwm, substeps, min_on, align;   // align: 0 leading, 1 centred, 2 trailing
+    double E_on, K_on, E_off, K_off;
+    double* state;            // [NT][B] in/out
+    double* delivered;        // [B]    += h sum_j sum_i (m_ij + stuck_i)
+    int32_t* pulses;          // [B]    += #{i: k_i > 0} (PWM)
+    double* applied_hist;     // nullptr or [T*B*NT]: (1/S) sum_j (m_ij + stuck_i)
+    int32_t* ticks_hist;      // nullptr or [T*B*NT]: k_i (PWM)
+};
+
+__global__ void __launch_bounds__(64) ftmpc_plant_step_act_kernel(const DeviceConsts C, const SimParams S, const PlantVar V,
+                                                                  const ActParams A) {
+    __shared__ double s_lvl[MAX_NT][64], s_stk[MAX_NT][64], s_val[MAX_NT][64], s_sum[MAX_NT][64];
+    __shared__ int32_t s_k[MAX_NT][64];
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t B = S.B;
+    if (b >= B) return;      // (no barrier below: every lane touches its own column of the rows only)
+    const int l = threadIdx.x;
+    const int NT = C.NT, NS = A.substeps;
+    int32_t npulse = 0;
+    for (int i = 0; i < NT; ++i) {
+        const double u = S.u0[b * NT + i];
+        if (S.u_hist) S.u_hist[(S.step * B + b) * NT + i] = u;
+        const double ub = S.ub[b * NT + i];
+        double lvl = ub > 0.0 ? u : 0.0;
+        int32_t k = NS;
+        if (A.pwm) {
+            const double d = ub > 0.0 ? fmin(fmax(u / ub, 0.0), 1.0) : 0.0;
+            k = (int32_t)floor(d * NS + 0.5);
+            if (k < A.min_on) k = 0;
+            lvl = ub > 0.0 ? ub : 0.0;
+            npulse += k > 0;
+            if (A.ticks_hist) A.ticks_hist[(S.step * B + b) * NT + i] = k;
+        }
+        s_lvl[i][l] = lvl;
+        s_stk[i][l] = S.stuck[b * NT + i];
+        s_val[i][l] = A.state[(int64_t)i * B + b];
+        s_sum[i][l] = 0.0;
+        s_k[i][l] = k;
+    }
+    double J[9], Jinv[9], fm[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
+    const double inv_mass = V.inv_mass ? V.inv_mass[b] : C.inv_mass;
+    if (V.J) {
+        for (int k = 0; k < 9; ++k) {
+            J[k] = V.J[k * B + b];
+            Jinv[k] = V.J[(9 + k) * B + b];
+        }
+    } else {
+        for (int k = 0; k < 9; ++k) {
+            J[k] = C.J[k];
+            Jinv[k] = C.Jinv[k];
+        }
+    }
+    if (V.force)
+        for (int k = 0; k < 3; ++k) fm[k] = V.force[k * B + b] * inv_mass;
+    if (V.torque)
+        for (int k = 0; k < 3; ++k) tq[k] = V.torque[k * B + b];
+    double x[13], k1[13], k2[13], k3[13], k4[13], s[13];
+    for (int i = 0; i < 13; ++i) x[i] = S.x[b * 13 + i];
+    const double h = C.dt / NS;
+    double deliv = A.delivered[b];
+#pragma unroll 1
+    for (int j = 0; j < NS; ++j) {
+        double gen[6] = {0, 0, 0, tq[0], tq[1], tq[2]};
+        double tot = 0.0;
+        for (int i = 0; i < NT; ++i) {
+            const int32_t k = s_k[i][l];
+            const int32_t s0 = A.align == 0 ? 0 : (A.align == 1 ? (NS - k) / 2 : NS - k);
+            const double g = (j >= s0 && j < s0 + k) ? s_lvl[i][l] : 0.0;
+            const double a = s_val[i][l];
+            const bool on = g > a;
+            const double m = g + (a - g) * (on ? A.K_on : A.K_off);
+            s_val[i][l] = g + (a - g) * (on ? A.E_on : A.E_off);
+            const double f = m + s_stk[i][l];
+            s_sum[i][l] += f;
+            tot += f;
+            if (V.D) {
+                for (int c = 0; c < 6; ++c) gen[c] += V.D[(int64_t)(c * NT + i) * B + b] * f;
+            } else {
+                for (int c = 0; c < 6; ++c) gen[c] += C.D[c * MAX_NT + i] * f;
+            }
+        }
+        deliv += h * tot;
+        plant_f_var(inv_mass, J, Jinv, fm, x, gen, k1);
+        for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * h * k1[i];
+        plant_f_var(inv_mass, J, Jinv, fm, s, gen, k2);
+        for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * h * k2[i];
+        plant_f_var(inv_mass, J, Jinv, fm, s, gen, k3);
+        for (int i = 0; i < 13; ++i) s[i] = x[i] + h * k3[i];
+        plant_f_var(inv_mass, J, Jinv, fm, s, gen, k4);
+        for (int i = 0; i < 13; ++i) x[i] += h / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    }
+    A.delivered[b] = deliv;
+    if (A.pwm) A.pulses[b] += npulse;
+    for (int i = 0; i < NT; ++i) {
+        A.state[(int64_t)i * B + b] = s_val[i][l];
+        if (A.applied_hist) A.applied_hist[(S.step * B + b) * NT + i] = s_sum[i][l] / NS;
+    }
+    // noise, renormalisation, histories and bad_count exactly as ftmpc_plant_step_kernel
+    for (int i = 0; i < 13; ++i) {
+        const double a = i < 3 ? S.noise[0] : (i < 6 ? S.noise[1] : (i < 10 ? S.noise[2] : S.noise[3]));
+        if (a > 0.0) x[i] += a * u01(S.seed, (unsigned long long)((S.step * S.index_total + S.index0 + b) * 13 + i));
+    }
+    const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
+    for (int i = 6; i < 10; ++i) x[i] *= qn;
+    for (int i = 0; i < 13; ++i) S.x[b * 13 + i] = x[i];
+    if (S.x_hist)
+        for (int i = 0; i < 13; ++i) S.x_hist[(S.step * B + b) * 13 + i] = x[i];
+    if (S.bad_count && S.status && S.status[b] != 0) atomicAdd(&S.bad_count[S.step], 1);
+}
+
 }  // namespace ftmpc

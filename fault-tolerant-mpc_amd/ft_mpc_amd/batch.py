@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None):
+                 plant=None, mission=None, actuator=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -474,11 +474,18 @@ class BatchedMPC:
         the columns offset[b] + t .. offset[b] + t + N of its table (offset[b] + T + N <= C), and its outcomes are measured against
         them.  xref_traj (and uref_traj) must then be None.  outcomes=dict(cost=True, ..), or "cost" among its fields, adds
         outcomes["cost"] [B,3]: the realised sum of e'Qe, of ut'R ut and the terminal cost of the last error; outcomes=True does not.
+        actuator: how the plant's thrusters turn a command into force (include/ftmpc.h, ftmpc_actuator; ft_mpc_amd.actuators restates it
+        in NumPy): a dict with mode="pwm" | "proportional", substeps (S in [1, 64]: the plant's step becomes S RK4 steps of dt / S, and
+        S is the PWM clock), min_on=0 (ticks; shorter pulses are not produced), align="leading" | "centred" | "trailing", tau_on=0.0,
+        tau_off=0.0 (s; time constants of rising and falling thrust), state=None ([B,NT] valve states to start from, finite and >= 0,
+        e.g. those a previous call returned; in proportional mode a command below 0 leaves a negative state: clamp at 0 before
+        handing it on) and fields=(...) among delivered [B] (N s), pulses [B], applied [T,B,NT], ticks [T,B,NT] and state
+        [B,NT]; they come back as out["actuator"].  The controller is not told, and the impulse and cost outcomes stay command-level.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist])."""
+        [, status_hist][, actuator])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission)
+                         plant, mission, actuator)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -651,8 +658,75 @@ def _mission_request(mission, B, T, N, want_cost):
     return ms, keep, cost
 
 
+ACTUATOR_MODES = {"proportional": 0, "pwm": 1}
+ACTUATOR_ALIGN = {"leading": 0, "centred": 1, "trailing": 2}
+ACTUATOR_FIELDS = ("delivered", "pulses", "applied", "ticks", "state")
+
+
+def _actuator_request(actuator, B, T, NT):
+    """The ftmpc_actuator struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    spec = dict(actuator)
+    mode = spec.pop("mode", "proportional")
+    if mode not in ACTUATOR_MODES:
+        raise ValueError(f"actuator['mode'] must be one of {sorted(ACTUATOR_MODES)}, not {mode!r}")
+    align = spec.pop("align", "leading")
+    if align not in ACTUATOR_ALIGN:
+        raise ValueError(f"actuator['align'] must be one of {sorted(ACTUATOR_ALIGN)}, not {align!r}")
+    S = int(spec.pop("substeps", 1))
+    if not 1 <= S <= 64:
+        raise ValueError(f"actuator['substeps'] must be in [1, 64], not {S}")
+    min_on = int(spec.pop("min_on", 0))
+    if not 0 <= min_on <= S:
+        raise ValueError(f"actuator['min_on'] must be in [0, substeps = {S}], not {min_on}")
+    taus = [float(spec.pop(k, 0.0)) for k in ("tau_on", "tau_off")]
+    if not all(np.isfinite(t) and t >= 0 for t in taus):
+        raise ValueError("actuator: tau_on and tau_off must be finite and >= 0")
+    fields = tuple(spec.pop("fields", ()))
+    if any(f not in ACTUATOR_FIELDS for f in fields):
+        raise ValueError(f"actuator['fields'] must be among {list(ACTUATOR_FIELDS)}")
+    if mode == "proportional":
+        if min_on != 0 or align != "leading":
+            raise ValueError("actuator: min_on and align belong to mode='pwm'")
+        if "pulses" in fields or "ticks" in fields:
+            raise ValueError("actuator: the fields pulses and ticks belong to mode='pwm'")
+    state = spec.pop("state", None)
+    if spec:
+        raise ValueError(f"actuator: unknown keys {sorted(spec)}")
+    ac = _lib.ftmpc_actuator(struct_size=C.sizeof(_lib.ftmpc_actuator), mode=ACTUATOR_MODES[mode], substeps=S, min_on=min_on,
+                             align=ACTUATOR_ALIGN[align], tau_on=taus[0], tau_off=taus[1])
+    out = {}
+    if state is not None or "state" in fields:
+        st = np.zeros((B, NT)) if state is None else np.array(state, dtype=np.float64)      # a copy: the call writes into it
+        if st.shape != (B, NT):
+            raise ValueError(f"actuator['state'] must have shape {(B, NT)}, not {st.shape}")
+        if not (np.isfinite(st).all() and (st >= 0).all()):
+            raise ValueError("actuator['state'] must be finite and >= 0")
+        st = np.ascontiguousarray(st)
+        ac.state = _ptr(st)
+        if "state" in fields:
+            out["state"] = st
+        else:
+            out["_state"] = st
+    if "delivered" in fields:
+        out["delivered"] = np.zeros(B)
+        ac.delivered = _ptr(out["delivered"])
+    if "pulses" in fields:
+        out["pulses"] = np.zeros(B, np.int32)
+        ac.pulses = _ptr(out["pulses"], C.c_int32)
+    if "applied" in fields:
+        out["applied"] = np.zeros((T, B, NT))
+        ac.applied_hist = _ptr(out["applied"])
+    if "ticks" in fields:
+        out["ticks"] = np.zeros((T, B, NT), np.int32)
+        ac.ticks_hist = _ptr(out["ticks"], C.c_int32)
+    keep = list(out.values())
+    out.pop("_state", None)
+    return ac, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
-              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None):
+              hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
+              actuator=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -710,8 +784,9 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     # the entries with outcomes: asked for, a slice of a campaign, the multi-GPU driver (which has no others), or a plant model (whose
     # entries take the outcomes struct too)
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
+    ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
-           or pm is not None or ms is not None)
+           or pm is not None or ms is not None or ac is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -726,7 +801,10 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["outcomes"] = orec
         if sh is not None:
             out["status_hist"] = sh
+        if aout is not None:
+            out["actuator"] = aout
         return out
+    msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
     if formulation == "wrench":
         from .controllers.tools.input_bounds import hull_tables
@@ -738,6 +816,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if ac is not None:
+            self._check(getattr(self.lib, pre + "wrench_actuator_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if ms is not None:
             self._check(getattr(self.lib, pre + "wrench_mission_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -775,6 +860,11 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if ac is not None:
+        self._check(getattr(self.lib, pre + "actuator_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp, C.byref(ac)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if ms is not None:
         self._check(getattr(self.lib, pre + "mission_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

@@ -618,6 +618,74 @@ int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, d
                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                         const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission);
 
+/*
+ * Pulsed (PWM) thrusters and valve lag in the plant.  Without the struct every loop applies a_i = (ub_i > 0 ? u_i : 0) + stuck_i as a
+ * force held constant over dt: an ideal proportional thruster.  With it the plant's step of loop step t is cut into S = substeps
+ * sub-steps of h = dt / S (substeps = 0 is read as 1), each one RK4 step of length h of the right-hand side the plant kernels use
+ * (m_b, J_b, D_b, f_b, t_b of the call's ftmpc_plant_model where given, the config's where not), under the force the valves deliver in
+ * that sub-step.  ub_i / stuck_i are the PLANT's pattern of the step (under a fault schedule: of the last event with onset <= t), u_i
+ * the command.  The parameters are uniform over the call.
+ *   mode 0, proportional: the target of every sub-step j is g_ij = ub_i > 0 ? u_i : 0, unclipped as the plant kernels apply it.
+ *   mode 1, PWM: duty d_i = ub_i > 0 ? min(max(u_i / ub_i, 0), 1) : 0, ticks k_i = floor(d_i S + 0.5), then k_i = 0 where k_i < min_on
+ *     (the dead band: nothing rounds up); the on-window starts at tick s_i = 0 (align 0, leading), (S - k_i) / 2 in integer division
+ *     (1, centred) or S - k_i (2, trailing); g_ij = ub_i for s_i <= j < s_i + k_i, else 0.  S is the PWM clock: on-times are whole
+ *     ticks of h, and a pulse does not cross a step boundary.
+ *   valve lag: every thruster has a valve state a_i (N), from `state` or 0 at entry, carried from sub-step to sub-step and from step
+ *     to step.  With E_x = exp(-h / tau_x), K_x = -expm1(-h / tau_x) tau_x / h for x in {on, off} (E = K = 0 for tau_x = 0, no lag),
+ *     computed on the host once per call: in sub-step j the pair (E, K) is the on-pair where g_ij > a_i, else the off-pair; the mean
+ *     force of the sub-step is m_ij = g_ij + (a_i - g_ij) K, then a_i = g_ij + (a_i - g_ij) E.
+ *   A jammed-open valve has no lag and no modulation: the thrust of the sub-step is m_ij + stuck_i, and [F; tau] = D_b (m_j + stuck)
+ *   (plus t_b on the torque) is held over the sub-step.  After the S sub-steps the step ends as without the struct: the noise is added
+ *   once at the same counter, the quaternion renormalised once; u_hist (the command), x_hist and not_converged keep their meaning.
+ * The controller is not told: ftmpc_outcomes.impulse and ftmpc_mission.cost[1] stay command-level a_i = (ub_i > 0 ? u_i : 0) + stuck_i.
+ * What the valves delivered comes back here.  Each output is NULL or a host buffer:
+ *   delivered [B]          sum_t sum_j h sum_i (m_ij + stuck_i), N s, added in step and sub-step order
+ *   pulses [B]             PWM only: the number of (step, thruster) pairs with k_i > 0 (valve wear)
+ *   applied_hist [T*B*NT]  per step (1/S) sum_j (m_ij + stuck_i); summed over thrusters and steps, times dt, it gives delivered
+ *   ticks_hist [T*B*NT]    PWM only: k_i
+ *   state [B*NT]           in/out: the valve states, read at entry (finite, >= 0) and written at exit, so that a campaign continues
+ *                          across calls; NULL starts at 0 and returns nothing.  Under PWM a state stays within [0, ub_i].  In
+ *                          proportional mode the target is the unclipped command, so a command below 0 on a live thruster (solver
+ *                          round-off) leaves a negative state, which the next call would refuse: clamp the returned states at 0
+ *                          before handing them on (a valve does not deliver negative thrust)
+ * actuator = NULL, or mode = 0 with substeps <= 1, both tau 0 and every output (state included) NULL, launches exactly the kernels of
+ * the _mission_ entries and returns their bits.
+ * FTMPC_ERR_ARG, the message naming ftmpc_actuator.<field> and, where there is one, the first offending vehicle, the call's x
+ * untouched: a struct_size other than sizeof(ftmpc_actuator); mode outside {0, 1}; substeps outside [0, 64]; min_on < 0 or > S; align
+ * outside {0, 1, 2}; a tau negative or not finite; mode = 0 with min_on != 0, align != 0, pulses or ticks_hist; a state entry negative
+ * or not finite.
+ */
+typedef struct ftmpc_actuator {
+    int32_t struct_size;      /* sizeof(ftmpc_actuator) */
+    int32_t mode;             /* 0 proportional, 1 PWM */
+    int32_t substeps;         /* S in [1, 64]; 0 is read as 1 */
+    int32_t min_on;           /* ticks, 0 <= min_on <= S (PWM) */
+    int32_t align;            /* 0 leading, 1 centred, 2 trailing (PWM) */
+    int32_t reserved;         /* 0 */
+    double tau_on, tau_off;   /* s, >= 0; 0: no lag */
+    double* delivered;        /* NULL or [B], output */
+    int32_t* pulses;          /* NULL or [B], output (PWM) */
+    double* applied_hist;     /* NULL or [T*B*NT], output */
+    int32_t* ticks_hist;      /* NULL or [T*B*NT], output (PWM) */
+    double* state;            /* NULL or [B*NT], in/out */
+} ftmpc_actuator;
+
+/* ftmpc_simulate_mission_batch with the actuator `actuator` (NULL: exactly ftmpc_simulate_mission_batch). */
+int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator);
+
+/* ftmpc_simulate_wrench_mission_batch with the actuator `actuator` (NULL: exactly ftmpc_simulate_wrench_mission_batch). */
+int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                         const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                         const ftmpc_actuator* actuator);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -740,6 +808,22 @@ int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t
                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission);
+/* The two entries above with the actuator `actuator` (ftmpc_actuator; NULL: exactly the entries above).  The struct is checked once
+ * over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; delivered + lo, pulses + lo and
+ * state + lo NT are read and written per shard, the two histories are copied row by row from the shard's staging as u_hist is. */
+int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                        int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                        const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator);
+int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                               const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                               int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                               uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                               const ftmpc_actuator* actuator);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

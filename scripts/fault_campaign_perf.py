@@ -9,6 +9,7 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --dispersion      # also the loops with a dispersed plant (BatchedMPC.simulate(plant=...))
     python scripts/fault_campaign_perf.py --mission         # also the loops under a three-table mission with random phases, and with cost
     python scripts/fault_campaign_perf.py --trace kernel_trace.csv   # per-launch times of the mission kernels and of the linearise kernel
+    python scripts/fault_campaign_perf.py --actuator        # also the loops with PWM thrusters (S = 16, min_on 1) and valve lag in the plant
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -26,7 +27,12 @@ a mission of the hover table alone, whose QPs are those of the shared loop, so t
 not other work in the solves.  With --once it makes one call with
 the mission and the cost and then one with the shared reference; --trace reads the kernel_trace.csv of such a run (rocprofv3
 --kernel-trace) and reports the time per launch of the two mission kernels and of the linearise kernel in either call: the launches
-of the linearise kernel are split at the first launch of ftmpc_plant_step_kernel that follows the last ftmpc_ref_window_kernel."""
+of the linearise kernel are split at the first launch of ftmpc_plant_step_kernel that follows the last ftmpc_ref_window_kernel.
+--actuator: the loops without and with the schedule once more under BatchedMPC.simulate(actuator=...): PWM on a clock of --substeps
+ticks per step (default 16), min_on 1, centred pulses, tau_on 20 ms, tau_off 10 ms, delivered and pulses returned
+(ftmpc_plant_step_act_kernel in place of ftmpc_plant_step_kernel).  With --once it makes one call with the actuator and one without,
+so that a kernel_stats.csv of that run holds both plant kernels, and --stats reports the time per launch of each and the actuator
+kernel's share of the kernel time."""
 import argparse
 import csv
 import json
@@ -84,10 +90,11 @@ def mission(B, N, mass):
                 table=(np.arange(B) % 3).astype(np.int32), offset=phase_offsets(B, PHASES, seed=23))
 
 
+ACTUATOR = dict(mode="pwm", min_on=1, align="centred", tau_on=0.02, tau_off=0.01, fields=("delivered", "pulses"))
 DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
 
 
-def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False):
+def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False, actuator=False, substeps=16):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -114,7 +121,10 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         from ft_mpc_amd.dispersion import sample
         plant = sample(B, c["NT"], mpc.D, cfg.J, cfg.mass, seed=17, **DISPERSION)
     msn = mission(B, c["N"], cfg.mass) if with_mission else None
+    act = dict(ACTUATOR, substeps=substeps) if actuator else None
     if once:
+        if actuator:
+            mpc.simulate(x0, ub, stuck, xr, T, actuator=act, **(witho if outcomes else withf), **kw)
         if with_mission:
             mpc.simulate(x0, ub, stuck, None, T, mission=msn, **dict(withf, outcomes=dict(fields=["cost"])), **kw)
         if dispersion:
@@ -133,6 +143,8 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         runs.append(("with_outcomes", witho, ub, stuck))
     if dispersion:
         runs += [("without_dispersed", dict(plain, plant=plant), ub, stuck), ("with_dispersed", dict(withf, plant=plant), ub, stuck)]
+    if actuator:
+        runs += [("without_actuator", dict(plain, actuator=act), ub, stuck), ("with_actuator", dict(withf, actuator=act), ub, stuck)]
     if with_mission:
         # the hover table alone at the same start columns: the QPs of the shared loop bit for bit, so what differs is the gather, the
         # per-vehicle loads of the linearise kernel and the call's staging -- not the work of the solves
@@ -152,6 +164,9 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         ms = float(np.median(ts)) * 1e3
         res[label] = dict(ms=ms, steps_per_s=B * T / (ms * 1e-3), not_converged=int(out["not_converged"].sum()),
                           alloc_failed=int(out.get("alloc_failed", np.zeros(1)).sum()))
+        if "actuator" in out:      # what the valves delivered and how often they opened, per vehicle and step
+            res[label].update(delivered_mean_Ns=float(out["actuator"]["delivered"].mean()),
+                              pulses_per_step=float(out["actuator"]["pulses"].mean()) / T)
     mpc.close()
     res["ratio_with_over_without"] = res["with"]["steps_per_s"] / res["without"]["steps_per_s"]
     if outcomes:
@@ -162,6 +177,10 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         res["ratio_dispersed_over_without"] = res["without_dispersed"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_dispersed_over_with"] = res["with_dispersed"]["steps_per_s"] / res["with"]["steps_per_s"]
         res["plant_model_bytes"] = int(sum(a.nbytes for a in plant.values()))
+    if actuator:
+        res["ratio_actuator_over_without"] = res["without_actuator"]["steps_per_s"] / res["without"]["steps_per_s"]
+        res["ratio_actuator_over_with"] = res["with_actuator"]["steps_per_s"] / res["with"]["steps_per_s"]
+        res["substeps"] = substeps
     if with_mission:
         res["ratio_mission_hover_over_without"] = res["without_mission_hover"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_mission_hover_over_with"] = res["with_mission_hover"]["steps_per_s"] / res["with"]["steps_per_s"]
@@ -189,7 +208,9 @@ def stats(path):
         return n, (sum(float(r["TotalDurationNs"]) for r in k) / n * 1e-3) if n else 0.0
     pn, pus = per_launch("ftmpc_plant_step_kernel")
     vn, vus = per_launch("ftmpc_plant_step_var_kernel")
-    return dict(plant_kernel_calls=pn, plant_kernel_avg_us=pus, plant_var_kernel_calls=vn, plant_var_kernel_avg_us=vus,
+    an, aus = per_launch("ftmpc_plant_step_act_kernel")
+    return dict(plant_act_kernel_calls=an, plant_act_kernel_avg_us=aus, plant_act_kernel_share=an * aus * 1e3 / tot if tot else 0.0,
+                plant_kernel_calls=pn, plant_kernel_avg_us=pus, plant_var_kernel_calls=vn, plant_var_kernel_avg_us=vus,
                 total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
                 event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0,
                 outcome_kernel_ms=oct_ * 1e-6, outcome_kernel_calls=ocalls, outcome_kernel_avg_us=(oct_ / ocalls * 1e-3) if ocalls else 0.0,
@@ -225,6 +246,8 @@ def main():
     ap.add_argument("--dispersion", action="store_true")
     ap.add_argument("--mission", action="store_true")
     ap.add_argument("--trace", default=None)
+    ap.add_argument("--actuator", action="store_true")
+    ap.add_argument("--substeps", type=int, default=16)
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -235,7 +258,7 @@ def main():
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
