@@ -74,6 +74,12 @@ struct ftmpc_handle {
     DevBuf<double> d_x0, d_ub, d_stuck, d_xref, d_uref;
     DevBuf<double> d_warm, d_u0, d_U;
     DevBuf<int32_t> d_status, d_iters;
+    // where the last closed loop with a sensor left off (ftmpc_sensor.step0): the warm start its last step shifted, the truth it
+    // returned, the number of the step that would follow.  A call whose step0, batch, form and x are these continues from it.
+    DevBuf<double> d_keep_warm;
+    std::vector<double> keep_x;
+    int64_t keep_B = 0, keep_step = -1;
+    bool keep_wrench = false;
     // allocation operator (ftmpc_allocate_batch)
     DevBuf<double> d_atau, d_aub, d_au;
     DevBuf<int32_t> d_ast, d_ait;
@@ -623,7 +629,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
 
 extern "C" {
 
-int32_t ftmpc_version(void) { return 530; }
+int32_t ftmpc_version(void) { return 540; }
 
 #ifndef FTMPC_BUILD_ID
 #define FTMPC_BUILD_ID "unknown"
@@ -1950,7 +1956,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
-                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr);
+                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -1998,7 +2004,7 @@ static int check_plant(ftmpc_handle* h, int64_t B, const ftmpc_plant_model* pm) 
 // with the call's own xref_traj / uref_traj: empty when acceptable, else the message, which names the field and, where there is one,
 // the first offending vehicle (first: number of vehicle 0 in the caller's batch)
 static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T, int N, const double* xref_traj, const double* uref_traj,
-                                   int64_t first = 0) {
+                                   int64_t first = 0, int L = 0) {
     if (!ms) return xref_traj ? "" : "null buffer or negative size";
     if (ms->struct_size != (int32_t)sizeof(ftmpc_mission))
         return "ftmpc_mission.struct_size is " + std::to_string(ms->struct_size) + ", this library expects " +
@@ -2010,10 +2016,12 @@ static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T
         if (ms->offset) return "ftmpc_mission.offset is given, but n_tables = 0 (the call's xref_traj has no start column)";
         return "";
     }
-    const int64_t K = ms->n_tables, C = ms->n_cols, need = (int64_t)T + N;
+    // (L: the columns a predicting sensor shifts every window by, ftmpc_sensor)
+    const int64_t K = ms->n_tables, C = ms->n_cols, need = (int64_t)T + N + L;
+    const std::string sum = L > 0 ? "T + N + L = " : "T + N = ";
     if (!ms->xref) return "ftmpc_mission.xref is NULL with n_tables = " + std::to_string(K);
     if (C < need)
-        return "ftmpc_mission.n_cols = " + std::to_string(C) + " is below T + N = " + std::to_string(need);
+        return "ftmpc_mission.n_cols = " + std::to_string(C) + " is below " + sum + std::to_string(need);
     if (xref_traj) return "ftmpc_mission.n_tables > 0: the call's xref_traj must be NULL (the tables are the reference)";
     if (uref_traj) return "ftmpc_mission.n_tables > 0: the call's uref_traj must be NULL (ftmpc_mission.uref holds the tables' uref)";
     auto at = [first](const char* field, int64_t b, const std::string& what) {
@@ -2027,7 +2035,7 @@ static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T
         for (int64_t b = 0; b < B; ++b) {
             if (ms->offset[b] < 0) return at("offset", b, "has a negative start column");
             if ((int64_t)ms->offset[b] + need > C)
-                return at("offset", b, "has offset + T + N = " + std::to_string((int64_t)ms->offset[b] + need) + " beyond n_cols = " +
+                return at("offset", b, "has offset + " + sum + std::to_string((int64_t)ms->offset[b] + need) + " beyond n_cols = " +
                                            std::to_string(C));
         }
     const double* const arr[2] = {ms->xref, ms->uref};
@@ -2041,8 +2049,9 @@ static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T
                            " has a non-finite entry in column " + std::to_string(i % (rows[a] * C) / rows[a]);
     return "";
 }
-static int check_mission(ftmpc_handle* h, int64_t B, int32_t T, const ftmpc_mission* ms, const double* xref_traj, const double* uref_traj) {
-    const std::string msg = mission_problem(ms, B, T, h->cfg.N, xref_traj, uref_traj);
+static int check_mission(ftmpc_handle* h, int64_t B, int32_t T, const ftmpc_mission* ms, const double* xref_traj, const double* uref_traj,
+                         int L = 0) {
+    const std::string msg = mission_problem(ms, B, T, h->cfg.N, xref_traj, uref_traj, 0, L);
     return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
 }
 // cost of a loop without steps: zero
@@ -2091,6 +2100,49 @@ static bool actuator_trivial(const ftmpc_actuator* ac) {
 static void zero_actuator_sums(const ftmpc_actuator* ac, int64_t B) {
     if (ac && ac->delivered && B > 0) std::fill(ac->delivered, ac->delivered + B, 0.0);
     if (ac && ac->pulses && B > 0) std::fill(ac->pulses, ac->pulses + B, 0);
+}
+
+// A sensor's layout and values (include/ftmpc.h, ftmpc_sensor) over the vehicles [0, B): empty when acceptable, else the message, which
+// names the field and, for an array, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string sensor_problem(const ftmpc_sensor* se, int64_t B, int NT, int64_t first = 0) {
+    if (!se) return "";
+    if (se->struct_size != (int32_t)sizeof(ftmpc_sensor))
+        return "ftmpc_sensor.struct_size is " + std::to_string(se->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_sensor));
+    if (se->latency < 0 || se->latency > FTMPC_MAX_LATENCY)
+        return "ftmpc_sensor.latency is " + std::to_string(se->latency) + ", outside [0, " + std::to_string(FTMPC_MAX_LATENCY) + "]";
+    if (se->predict != 0 && se->predict != 1) return "ftmpc_sensor.predict is " + std::to_string(se->predict) + ", outside {0, 1}";
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(se->sigma[k]) || se->sigma[k] < 0)
+            return "ftmpc_sensor.sigma[" + std::to_string(k) + "] is negative or not finite";
+    if (se->step0 < 0) return "ftmpc_sensor.step0 is negative";
+    if (se->pending && se->latency == 0) return "ftmpc_sensor.pending is given, but latency = 0 (no command waits)";
+    if (se->pred_hist && se->predict == 0) return "ftmpc_sensor.pred_hist is given, but predict = 0 (nothing is predicted)";
+    if (se->bias)
+        for (int64_t i = 0; i < B * 12; ++i)
+            if (!std::isfinite(se->bias[i]))
+                return "ftmpc_sensor.bias: vehicle " + std::to_string(first + i / 12) + " has a non-finite entry (channel " +
+                       std::to_string(i % 12) + ")";
+    if (se->pending) {
+        const int64_t per = (int64_t)se->latency * NT;
+        for (int64_t i = 0; i < B * per; ++i)
+            if (!std::isfinite(se->pending[i]))
+                return "ftmpc_sensor.pending: vehicle " + std::to_string(first + i / per) + " has a non-finite entry (row " +
+                       std::to_string(i % per / NT) + ")";
+    }
+    return "";
+}
+static int check_sensor(ftmpc_handle* h, int64_t B, const ftmpc_sensor* se) {
+    const std::string msg = sensor_problem(se, B, h->cfg.NT);
+    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
+// trivial: the loop launches the kernels it launches without the struct
+static bool sensor_trivial(const ftmpc_sensor* se) {
+    return !se || (se->latency == 0 && se->predict == 0 && se->sigma[0] == 0 && se->sigma[1] == 0 && se->sigma[2] == 0 && se->sigma[3] == 0 &&
+                   !se->bias && !se->pending && !se->meas_hist && !se->pred_hist);
+}
+// columns a predicting sensor shifts every reference window by (0 for a struct that would be refused)
+static int sensor_shift(const ftmpc_sensor* se) {
+    return se && se->predict == 1 && se->latency > 0 && se->latency <= FTMPC_MAX_LATENCY ? se->latency : 0;
 }
 
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
@@ -2202,6 +2254,16 @@ int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double*
                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
+    return ftmpc_simulate_sensor_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                       x_hist, not_converged, out, plant, mission, actuator, nullptr);
+}
+
+int ftmpc_simulate_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                const ftmpc_sensor* sensor) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2209,7 +2271,8 @@ int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double*
     if (rc != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
+    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
@@ -2219,7 +2282,7 @@ int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double*
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator);
+                         faults, x_hist, out, plant, mission, actuator, sensor);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2272,6 +2335,18 @@ int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, 
                                          double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                          const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                          const ftmpc_actuator* actuator) {
+    return ftmpc_simulate_wrench_sensor_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                              seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                              out, plant, mission, actuator, nullptr);
+}
+
+int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                       const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                       const ftmpc_actuator* actuator, const ftmpc_sensor* sensor) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
@@ -2279,7 +2354,8 @@ int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, 
     if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj)) != FTMPC_OK) return rc;
+    if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
+    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
@@ -2289,7 +2365,7 @@ int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, 
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2339,11 +2415,16 @@ int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
-                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac) {
+                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
+                         const ftmpc_sensor* se) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
-    const int64_t ncol = (int64_t)T + N;   // windows t .. t+N for t < T
+    // sensor (checked by the entry): not trivial, the truth lives in d_xtrue and ftmpc_sense_kernel writes h->d_x0 before every solve;
+    // lat commands wait in the ring d_ring ([lat + 1][B][NT]); a predicting sensor shifts every reference window by L = lat columns
+    const bool sense = !sensor_trivial(se);
+    const int lat = sense ? se->latency : 0, L = sense && se->predict ? lat : 0;
+    const int64_t ncol = (int64_t)T + N + L;   // windows t .. t+N for t < T (t+L .. t+L+N under a predicting sensor)
     // (this call's own buffers: freed on every way out)
     DevBuf<double> d_xr, d_ur, d_warmB, d_hist, d_xhist;
     DevBuf<int32_t> d_bad, d_abad;
@@ -2494,7 +2575,65 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         ap.applied_hist = d_aapp;
         ap.ticks_hist = d_atick;
     }
-    const int64_t xw = 9 * (int64_t)(N + 1), uw = 6 * (int64_t)(N + 1);     // doubles per window
+    DevBuf<double> d_xtrue, d_ring, d_sbias, d_mhist, d_phist;
+    std::vector<double> h_ring;
+    ftmpc::SenseParams sn{};
+    const size_t nu = (size_t)B * NT;       // doubles per ring slot
+    if (sense) {
+        HIP_TRY(h, hipMalloc(&d_xtrue.p, (size_t)B * 13 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_xtrue, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (lat > 0) {      // slots 0 .. lat-1: the pending commands, oldest first (the caller's are vehicle-major [B][lat][NT])
+            HIP_TRY(h, hipMalloc(&d_ring.p, (size_t)(lat + 1) * nu * sizeof(double)));
+            if (se->pending) {
+                try {
+                    h_ring.resize((size_t)lat * nu);
+                } catch (const std::bad_alloc&) {
+                    return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the sensor's staging array");
+                }
+                for (int64_t b = 0; b < B; ++b)
+                    for (int j = 0; j < lat; ++j)
+                        for (int i = 0; i < NT; ++i) h_ring[(size_t)j * nu + b * NT + i] = se->pending[(b * lat + j) * NT + i];
+                HIP_TRY(h, hipMemcpyAsync(d_ring, h_ring.data(), (size_t)lat * nu * sizeof(double), hipMemcpyHostToDevice, s));
+            } else {
+                HIP_TRY(h, hipMemsetAsync(d_ring, 0, (size_t)lat * nu * sizeof(double), s));
+            }
+        }
+        if (se->bias) {
+            HIP_TRY(h, hipMalloc(&d_sbias.p, (size_t)B * 12 * sizeof(double)));
+            HIP_TRY(h, hipMemcpyAsync(d_sbias, se->bias, (size_t)B * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        if (se->meas_hist) HIP_TRY(h, hipMalloc(&d_mhist.p, (size_t)T * B * 13 * sizeof(double)));
+        if (se->pred_hist) HIP_TRY(h, hipMalloc(&d_phist.p, (size_t)T * B * 13 * sizeof(double)));
+        sn.B = B;
+        sn.x = d_xtrue;
+        sn.y = h->d_x0;
+        sn.ub = h->d_ub;
+        sn.stuck = h->d_stuck;
+        sn.ring = d_ring;
+        sn.nslots = lat + 1;
+        sn.latency = lat;
+        sn.predict = se->predict;
+        for (int i = 0; i < 4; ++i) sn.sigma[i] = se->sigma[i];
+        sn.bias = d_sbias;
+        sn.seed = se->seed;
+        sn.index0 = oc ? oc->index0 : 0;
+        sn.index_total = oc && oc->index_total != 0 ? oc->index_total : B;
+        sn.meas_hist = d_mhist;
+        sn.pred_hist = d_phist;
+    }
+    double* const d_truth = sense ? d_xtrue.p : h->d_x0.p;      // what the plant integrates and the outcomes measure
+    // a continued run (step0 > 0, and the handle's last loop with a sensor ended at that step, on this batch and form, in this x):
+    // its first solve is warm-started as the whole run's would be, from what the handle kept; otherwise it starts cold
+    const int64_t nkeep = B * (int64_t)N * (wl ? 6 : NT);
+    bool resume = false;
+    if (sense) {
+        resume = se->step0 > 0 && h->keep_step == se->step0 && h->keep_B == B && h->keep_wrench == (wl != nullptr) &&
+                 h->keep_x.size() == (size_t)B * 13 && std::memcmp(h->keep_x.data(), x, (size_t)B * 13 * sizeof(double)) == 0;
+        h->keep_step = -1;      // valid again only when this call ends well
+        if (resume)
+            HIP_TRY(h, hipMemcpyAsync(wl ? h->d_warmG.p : d_warmB.p, h->d_keep_warm, (size_t)nkeep * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    const int64_t xw = 9 * (int64_t)(N + 1 + L), uw = 6 * (int64_t)(N + 1 + L);     // doubles per window
     ftmpc::RefWindow rw{};
     if (windows) {
         const size_t KC = (size_t)ms->n_tables * (size_t)ms->n_cols;
@@ -2516,7 +2655,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         }
         rw.B = B;
         rw.C = ms->n_cols;
-        rw.N1 = N + 1;
+        rw.N1 = N + 1 + L;
         rw.xtab = d_mtab;
         rw.utab = d_mutab;
         rw.table = d_mtbl;
@@ -2537,7 +2676,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     }
     ftmpc::SimParams sp;
     sp.B = B;
-    sp.x = h->d_x0;
+    sp.x = d_truth;
     sp.u0 = h->d_u0;
     sp.ub = h->d_ub;
     sp.stuck = h->d_stuck;
@@ -2561,7 +2700,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         HIP_TRY(h, hipMemsetAsync(d_oint + B, 0xFF, (size_t)B * sizeof(int32_t), s));          // tset_step = -1
         HIP_TRY(h, hipMemsetAsync(d_oint + 3 * B, 0xFF, (size_t)B * sizeof(int32_t), s));      // first_unsolved = -1
         op.B = B;
-        op.x = h->d_x0;
+        op.x = d_truth;
         op.u0 = h->d_u0;
         op.astatus = wl ? h->d_ast2.p : nullptr;
         op.err_int = d_orec;
@@ -2642,7 +2781,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     for (int t = 0; t < T; ++t) {
         if (E > 0 && ev_step[t]) {     // some instance switches its pattern at this step: before the solve
             fe.t = t;
-            fe.repair = t > 0;
+            fe.repair = t > 0 || resume;
             hipLaunchKernelGGL(ftmpc::ftmpc_fault_event_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, fe);
             HIP_TRY(h, hipGetLastError());
             // the work lists follow the new patterns: no small grid for a list that was empty the step before
@@ -2657,15 +2796,25 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             hipLaunchKernelGGL(ftmpc::ftmpc_ref_window_kernel, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, s, rw);
             HIP_TRY(h, hipGetLastError());
         }
-        const double* const xr_t = windows ? d_xwin.p : d_xr + (int64_t)9 * t;
-        const double* const ur_t = !has_uref ? nullptr : (windows ? d_uwin.p : d_ur + (int64_t)6 * t);
+        // (under a predicting sensor the solve's window starts L columns later; xo_t / uo_t: the step's own columns, for the outcomes)
+        const double* const xo_t = windows ? d_xwin.p : d_xr + (int64_t)9 * t;
+        const double* const uo_t = !has_uref ? nullptr : (windows ? d_uwin.p : d_ur + (int64_t)6 * t);
+        const double* const xr_t = xo_t + (int64_t)9 * L;
+        const double* const ur_t = uo_t ? uo_t + (int64_t)6 * L : nullptr;
+        if (sense) {     // y_t (and its propagation over the queue) into h->d_x0; slot t mod (lat + 1) holds a_t
+            sn.cstep = se->step0 + t;
+            sn.step = t;
+            sn.slot0 = t % (lat + 1);
+            hipLaunchKernelGGL(ftmpc::ftmpc_sense_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sn);
+            HIP_TRY(h, hipGetLastError());
+        }
         const int64_t xr_s = windows ? xw : 0, ur_s = windows ? uw : 0;
         const double* Ufin = h->d_U;
         const double* Gfin = h->d_G;
         if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
             ftmpc::SqpState S;
             rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
-                              t > 0 ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
+                              (t > 0 || resume) ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
             if (rc == FTMPC_OK) {
                 Gfin = S.U;
                 sp.status = S.status;
@@ -2676,7 +2825,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         } else if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
             ftmpc::SqpState S;
             double* J0 = nullptr;
-            rc = sqp_enqueue(h, B, xr_t, xr_s, ur_t, ur_s, t > 0 ? d_warmB.p : nullptr, sqp_iters, backtracks, tol, S, &J0);
+            rc = sqp_enqueue(h, B, xr_t, xr_s, ur_t, ur_s, (t > 0 || resume) ? d_warmB.p : nullptr, sqp_iters, backtracks, tol, S, &J0);
             if (rc == FTMPC_OK) {
                 Ufin = S.U;
                 sp.status = S.status;
@@ -2685,15 +2834,19 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             }
         } else if (wl) {         // the reference's two-stage structure: wrench MPC with the hull rows, then allocation
             rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
-                                t > 0 ? h->d_warmG.p : nullptr);
+                                (t > 0 || resume) ? h->d_warmG.p : nullptr);
             if (rc == FTMPC_OK && d_abad)
                 hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
                                    d_abad + t);
         } else {
             rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, xr_t, xr_s, ur_t, ur_s,
-                         t > 0 ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
+                         (t > 0 || resume) ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
         }
         if (rc != FTMPC_OK) return rc;
+        if (lat > 0) {     // u_t waits lat steps: into the slot behind the newest; the plant and the outcomes get the slot of a_t
+            HIP_TRY(h, hipMemcpyAsync(d_ring + (size_t)((t + lat) % (lat + 1)) * nu, h->d_u0, nu * sizeof(double), hipMemcpyDeviceToDevice, s));
+            sp.u0 = op.u0 = d_ring + (size_t)(t % (lat + 1)) * nu;
+        }
         sp.step = t;
         if (act)
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_act_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv, ap);
@@ -2707,9 +2860,9 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             op.stuck = sp.stuck;
             op.status = sp.status;
             if (windows || want_cost) {     // a column per vehicle (column 1 of its window, column 0 of its uref window) and / or the cost
-                mo.xref = xr_t + 9;
+                mo.xref = xo_t + 9;
                 mo.xref_stride = xr_s;
-                mo.uref = ur_t;
+                mo.uref = uo_t;
                 mo.uref_stride = ur_s;
                 hipLaunchKernelGGL(ftmpc::ftmpc_outcome_mission_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op, mo);
             } else {
@@ -2724,7 +2877,17 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, B, N, NT, Ufin, d_warmB, 0);
         HIP_TRY(h, hipGetLastError());
     }
-    HIP_TRY(h, hipMemcpyAsync(x, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(x, d_truth, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (sense) {
+        if ((rc = h->d_keep_warm.ensure(h, nkeep)) != FTMPC_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_keep_warm, wl ? h->d_warmG.p : d_warmB.p, (size_t)nkeep * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (se->meas_hist) HIP_TRY(h, hipMemcpyAsync(se->meas_hist, d_mhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (se->pred_hist) HIP_TRY(h, hipMemcpyAsync(se->pred_hist, d_phist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (se->pending)      // c_T .. c_{T+lat-1}: the slots from T mod (lat + 1) on, oldest first
+            for (int j = 0; j < lat; ++j)
+                HIP_TRY(h, hipMemcpyAsync(h_ring.data() + (size_t)j * nu, d_ring + (size_t)((T + j) % (lat + 1)) * nu, nu * sizeof(double),
+                                          hipMemcpyDeviceToHost, s));
+    }
     if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -2753,6 +2916,20 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (act && ac->state)
         for (int64_t b = 0; b < B; ++b)
             for (int i = 0; i < NT; ++i) ac->state[b * NT + i] = h_aval[(size_t)i * B + b];
+    if (sense) {
+        try {
+            h->keep_x.assign(x, x + B * 13);
+            h->keep_B = B;
+            h->keep_wrench = wl != nullptr;
+            h->keep_step = se->step0 + T;
+        } catch (const std::bad_alloc&) {
+            h->keep_step = -1;      // nothing kept: the next call starts cold
+        }
+    }
+    if (sense && se->pending)
+        for (int64_t b = 0; b < B; ++b)
+            for (int j = 0; j < lat; ++j)
+                for (int i = 0; i < NT; ++i) se->pending[(b * lat + j) * NT + i] = h_ring[(size_t)j * nu + b * NT + i];
     return FTMPC_OK;
 }
 

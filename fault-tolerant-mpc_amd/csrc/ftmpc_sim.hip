@@ -887,4 +887,104 @@ __global__ void __launch_bounds__(64) ftmpc_plant_step_act_kernel(const DeviceCo
     if (S.bad_count && S.status && S.status[b] != 0) atomicAdd(&S.bad_count[S.step], 1);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Navigation errors and command latency (ftmpc_simulate_sensor_batch / ftmpc_simulate_wrench_sensor_batch; include/ftmpc.h,
+// ftmpc_sensor).  ftmpc_sense_kernel runs before the solve of every step of a loop whose sensor is not trivial: it reads the TRUTH
+// (a buffer of the call, which the plant, outcome and actuator kernels then read and write in place of the handle's x0), forms the
+// measurement y_t, propagates it over the d queued commands when asked to, and writes the handle's x0, which every solver enqueue
+// path reads.  A lane per vehicle.  The queue is a ring of d + 1 slots of [B][NT] (the layout of the handle's u0): slot0 holds a_t,
+// the command the plant applies in this step, the following d - 1 slots a_{t+1} .. a_{t+d-1}.  The prediction is the plant
+// kernel's RK4 step under the CONTROLLER's pattern and the config's model; gen[6] is accumulated inside the thruster loop and D read
+// at wave-uniform indices, so no per-lane array is indexed by the run-time NT.  Gaussian draws by Box-Muller from two counters per
+// channel; a group whose sigma is zero draws nothing.
+// ---------------------------------------------------------------------------------------------------------
+struct SenseParams {
+    int64_t B;
+    const double* x;          // [B*13] the truth
+    double* y;                // [B*13] what the solve reads (the handle's x0)
+    const double* ub;         // [B*NT] the controller's pattern
+    const double* stuck;
+    const double* ring;       // nullptr (d = 0) or [(d+1)][B*NT]
+    int32_t nslots, slot0;    // d + 1, slot of a_t
+    int32_t latency, predict;
+    double sigma[4];
+    const double* bias;       // nullptr or [B*12]
+    unsigned long long seed;
+    int64_t cstep, step, index0, index_total;   // step0 + t (the counter's step), t (the histories' row)
+    double* meas_hist;        // nullptr or [T*B*13]
+    double* pred_hist;        // nullptr or [T*B*13]
+};
+
+namespace {
+__device__ __forceinline__ double gauss01(unsigned long long seed, unsigned long long c) {
+    const double u1 = u01(seed, 2ull * c), u2 = u01(seed, 2ull * c + 1ull);
+    return sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+}
+}  // namespace
+
+__global__ void __launch_bounds__(64) ftmpc_sense_kernel(const DeviceConsts C, const SenseParams P) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int NT = C.NT;
+    double x[13];
+    for (int i = 0; i < 13; ++i) x[i] = P.x[b * 13 + i];
+    const unsigned long long c0 = (unsigned long long)((P.cstep * P.index_total + P.index0 + b) * 12);
+    // e[0:3] position, e[3:6] velocity, e[6:9] the rotation vector theta, e[9:12] rate
+    double e[12];
+    for (int j = 0; j < 12; ++j) {
+        const double sg = P.sigma[j / 3];
+        double v = P.bias ? P.bias[b * 12 + j] : 0.0;
+        if (sg > 0.0) v += sg * gauss01(P.seed, c0 + j);
+        e[j] = v;
+    }
+    for (int i = 0; i < 3; ++i) {
+        x[i] += e[i];
+        x[3 + i] += e[3 + i];
+        x[10 + i] += e[9 + i];
+    }
+    {
+        const double t0 = e[6], t1 = e[7], t2 = e[8];
+        const double n = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+        const double cs = cos(0.5 * n), sn = n < 1e-8 ? 0.5 : sin(0.5 * n) / n;
+        const double qx = x[6], qy = x[7], qz = x[8], qw = x[9];
+        double q[4];
+        q[0] = cs * qx + sn * (t2 * qy - t1 * qz + t0 * qw);
+        q[1] = cs * qy + sn * (-t2 * qx + t0 * qz + t1 * qw);
+        q[2] = cs * qz + sn * (t1 * qx - t0 * qy + t2 * qw);
+        q[3] = cs * qw + sn * (-t0 * qx - t1 * qy - t2 * qz);
+        const double qn = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (int i = 0; i < 4; ++i) x[6 + i] = q[i] * qn;
+    }
+    if (P.meas_hist)
+        for (int i = 0; i < 13; ++i) P.meas_hist[(P.step * P.B + b) * 13 + i] = x[i];
+    if (P.predict) {
+        const double dt = C.dt;
+        int32_t slot = P.slot0;
+#pragma unroll 1
+        for (int j = 0; j < P.latency; ++j) {
+            const double* a = P.ring + (int64_t)slot * P.B * NT;
+            slot = slot + 1 == P.nslots ? 0 : slot + 1;
+            double gen[6] = {0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < NT; ++i) {
+                const double t = (P.ub[b * NT + i] > 0.0 ? a[b * NT + i] : 0.0) + P.stuck[b * NT + i];
+                for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * t;
+            }
+            double k1[13], k2[13], k3[13], k4[13], s[13];
+            plant_f(C, x, gen, k1);
+            for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k1[i];
+            plant_f(C, s, gen, k2);
+            for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k2[i];
+            plant_f(C, s, gen, k3);
+            for (int i = 0; i < 13; ++i) s[i] = x[i] + dt * k3[i];
+            plant_f(C, s, gen, k4);
+            for (int i = 0; i < 13; ++i) x[i] += dt / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+            const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
+            for (int i = 6; i < 10; ++i) x[i] *= qn;
+        }
+        if (P.pred_hist)
+            for (int i = 0; i < 13; ++i) P.pred_hist[(P.step * P.B + b) * 13 + i] = x[i];
+    }
+    for (int i = 0; i < 13; ++i) P.y[b * 13 + i] = x[i];
+}
+
 }  // namespace ftmpc

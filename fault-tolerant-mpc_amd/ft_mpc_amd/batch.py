@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None, actuator=None):
+                 plant=None, mission=None, actuator=None, sensor=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -481,11 +481,19 @@ class BatchedMPC:
         e.g. those a previous call returned; in proportional mode a command below 0 leaves a negative state: clamp at 0 before
         handing it on) and fields=(...) among delivered [B] (N s), pulses [B], applied [T,B,NT], ticks [T,B,NT] and state
         [B,NT]; they come back as out["actuator"].  The controller is not told, and the impulse and cost outcomes stay command-level.
+        sensor: what the controller knows about the state and when its command takes effect (include/ftmpc.h, ftmpc_sensor;
+        ft_mpc_amd.sensors restates it in NumPy): a dict with sigma=(4,) (standard deviations of position, velocity, attitude (rad)
+        and rate), bias=None ([B,12], e.g. sensors.sample_bias), seed=0, step0=0 (number of the call's first step, for a continued
+        run), latency=0 (d in [0, 8]: the command solved at step t acts at t + d), predict=False (propagate the measurement over the
+        d waiting commands and solve for the window d columns later: xref_traj / uref_traj then have T + N + d columns, a mission
+        needs offset + T + N + d <= C), pending=None ([B,d,NT] commands applied in the first d steps; default zeros) and fields=(...)
+        among meas [T,B,13], pred [T,B,13] and pending [B,d,NT] (the commands not yet applied at the end); they come back as
+        out["sensor"].  x, x_hist and the outcomes are the truth; u is the command the plant applied in each step.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator])."""
+        [, status_hist][, actuator][, sensor])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator)
+                         plant, mission, actuator, sensor)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -724,9 +732,37 @@ def _actuator_request(actuator, B, T, NT):
     return ac, keep, out
 
 
+def _sensor_request(sensor, B, T, NT):
+    """The ftmpc_sensor struct of a simulate call, the arrays it points into (kept alive by the caller), the dict of outputs and L, the
+    columns the reference gains (the latency of a predicting sensor)."""
+    from .sensors import request
+    r = request(sensor, B, T, NT)
+    se = _lib.ftmpc_sensor(struct_size=C.sizeof(_lib.ftmpc_sensor), latency=r["latency"], predict=int(r["predict"]),
+                           seed=r["seed"] & ((1 << 64) - 1), step0=r["step0"])
+    for k in range(4):
+        se.sigma[k] = float(r["sigma"][k])
+    keep, out = [], {}
+    if r["bias"] is not None:
+        keep.append(r["bias"])
+        se.bias = _ptr(r["bias"])
+    if r["pending"] is not None or "pending" in r["fields"]:
+        pend = np.ascontiguousarray(r["pending"]) if r["pending"] is not None else np.zeros((B, r["latency"], NT))
+        keep.append(pend)
+        se.pending = _ptr(pend)
+        if "pending" in r["fields"]:
+            out["pending"] = pend
+    if "meas" in r["fields"]:
+        out["meas"] = np.zeros((T, B, 13))
+        se.meas_hist = _ptr(out["meas"])
+    if "pred" in r["fields"]:
+        out["pred"] = np.zeros((T, B, 13))
+        se.pred_hist = _ptr(out["pred"])
+    return se, keep, out, (r["latency"] if r["predict"] else 0)
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None):
+              actuator=None, sensor=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -746,17 +782,24 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         raise ValueError("with a mission xref_traj and uref_traj must be None (the mission's tables are the reference)")
     if mission is not None or want_cost:
         ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
+    se, skeep, sout, L = _sensor_request(sensor, B, T, NT) if sensor is not None else (None, None, None, 0)
+    if L and mission is not None and mission.get("tables") is not None:
+        off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
+        if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
+            raise ValueError(f"mission: offset + T + N + L = {int(off.max()) + T + N + L} is beyond the tables' "
+                             f"{np.shape(mission['tables'])[-1]} columns (L = {L}: the sensor predicts over its latency)")
     xr = None
     if mission is None:
         xr = _f64(xref_traj)
-        if xr.shape != (9, T + N):
-            raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}")
+        if xr.shape != (9, T + N + L):
+            raise ValueError(f"xref_traj must be 9 x (T+N) = 9 x {T + N}" if not L else
+                             f"xref_traj must be 9 x (T+N+L) = 9 x {T + N + L} (L = {L}: the sensor predicts over its latency)")
         xr = np.ascontiguousarray(xr.reshape(-1, order="F"))
     ur = None
     if uref_traj is not None:
         ur = _f64(uref_traj)
-        if ur.shape != (6, T + N):
-            raise ValueError("uref_traj must be 6 x (T+N)")
+        if ur.shape != (6, T + N + L):
+            raise ValueError("uref_traj must be 6 x (T+N)" if not L else f"uref_traj must be 6 x (T+N+L) = 6 x {T + N + L}")
         ur = np.ascontiguousarray(ur.reshape(-1, order="F"))
     nz = _f64(noise, 4)
     uh = np.empty((T, B, NT)) if return_inputs else None
@@ -786,7 +829,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
-           or pm is not None or ms is not None or ac is not None)
+           or pm is not None or ms is not None or ac is not None or se is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -803,6 +846,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["status_hist"] = sh
         if aout is not None:
             out["actuator"] = aout
+        if sout is not None:
+            out["sensor"] = sout
         return out
     msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
@@ -816,6 +861,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if se is not None:
+            self._check(getattr(self.lib, pre + "wrench_sensor_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac) if ac is not None else None, C.byref(se)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if ac is not None:
             self._check(getattr(self.lib, pre + "wrench_actuator_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -860,6 +912,12 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if se is not None:
+        self._check(getattr(self.lib, pre + "sensor_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
+            C.byref(ac) if ac is not None else None, C.byref(se)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if ac is not None:
         self._check(getattr(self.lib, pre + "actuator_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

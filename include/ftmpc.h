@@ -686,6 +686,73 @@ int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, 
                                          const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                          const ftmpc_actuator* actuator);
 
+/* Navigation errors and command latency in the on-device closed loops.  Without this struct one buffer is both the plant's state
+ * and the x0 of every solve, and the command solved from x_t acts over step t.  With it the plant keeps the TRUTH x_t in a buffer of
+ * the call; the call's noise / seed keep acting on the truth (process noise); the outcome, mission-cost and actuator kernels read
+ * the truth; x_hist and the returned x are the truth.  The controller is handed a measurement, and its command acts `latency` steps
+ * later.  The parameters are uniform over the call, bias and pending are per vehicle.
+ *   measurement y_t, formed before the solve of loop step t.  g = index0 + b is the vehicle's campaign number (ftmpc_outcomes), the
+ *     channels are j = 0..11 (position, velocity, attitude, rate: 3 each), c = ((step0 + t) index_total + g) 12 + j the counter:
+ *       u1 = u01(seed, 2c), u2 = u01(seed, 2c + 1) (the splitmix counter function of the process noise),
+ *       z_j = sqrt(-2 log(1 - u1)) cos(2 pi u2)
+ *       y_p = p + bias[b][0:3] + sigma[0] z_{0:3}         y_v = v + bias[b][3:6] + sigma[1] z_{3:6}
+ *       theta = bias[b][6:9] + sigma[2] z_{6:9}, a body-frame rotation vector (rad):  y_q = cos(|theta|/2) q + s Omega(theta) q,
+ *         s = sin(|theta|/2) / |theta| (0.5 below |theta| = 1e-8), Omega the operator of q' = 1/2 Omega(w) q; then y_q / |y_q|
+ *       y_w = w + bias[b][9:12] + sigma[3] z_{9:12}
+ *     bias NULL is zero; sigma[k] == 0 draws nothing for its group.
+ *   latency d in [0, 8]: the plant applies a_t = u_{t-d} at step t; for t < d it applies row t of pending [B][d][NT] (NULL: zeros,
+ *     so only `stuck` acts).  On return pending holds the d commands computed but not yet applied, oldest first.  u_hist[t],
+ *     ftmpc_outcomes.impulse, ftmpc_mission.cost[1] and the actuator all see a_t, the command the plant applied in step t.
+ *   predict = 1: from x^ = y_t, for j = 0..d-1 one RK4 step of dt of the CONTROLLER's model -- the config's mass, J and D, under
+ *     gen = D ((ub_c > 0 ? a_{t+j} : 0) + stuck_c) with the controller's pattern of step t (after a detected fault event) -- and the
+ *     quaternion renormalised after each step.  The solve of step t takes x0 = x^ and the reference window starting at column
+ *     t + d: the trajectory arguments are then [9, T + N + L] and [6, T + N + L], L = predict ? d : 0, and under a mission
+ *     offset + T + N + L <= n_cols.  Outcomes and cost keep column t + 1 of xref and column t of uref.  predict = 0: the solve takes
+ *     y_t and the window at t.
+ *   outputs (NULL or host buffers): meas_hist [T*B*13] the y_t, pred_hist [T*B*13] the x^_t.
+ * sensor = NULL, or latency = 0, predict = 0, all sigma zero and bias, pending and both histories NULL, launches exactly the kernels
+ * of the _actuator_ entries and returns their bits.
+ * Continued runs: a run of T steps equals two runs of T / 2 with pending and step0 handed over, bit for bit where the solves do not
+ * depend on the handle's history.  The queue and the counters travel in the struct; the solver's warm start stays on the handle:
+ * every call with a non-trivial sensor keeps the warm start its last step shifted, the x it returned and step0 + T, and a call
+ * whose step0 (> 0), B, form and x are exactly these warm-starts its first solve from what was kept (and repairs it at a fault
+ * event of its step 0, as a later step would).  Any other call starts cold, as every call without a sensor does.
+ * FTMPC_ERR_ARG, the message naming ftmpc_sensor.<field> and, for an array, the first offending vehicle, the call's x untouched: a
+ * struct_size other than sizeof(ftmpc_sensor); latency outside [0, 8]; predict outside {0, 1}; a sigma negative or not finite; a
+ * bias or pending entry not finite; pending given with latency = 0; pred_hist given with predict = 0; step0 < 0.
+ */
+#define FTMPC_MAX_LATENCY 8
+typedef struct ftmpc_sensor {
+    int32_t struct_size;      /* sizeof(ftmpc_sensor) */
+    int32_t latency;          /* d, control periods, 0..FTMPC_MAX_LATENCY */
+    int32_t predict;          /* 0: the solve takes y_t; 1: y_t propagated over the d queued commands */
+    int32_t reserved;         /* 0 */
+    uint64_t seed;            /* of the sensor noise (the call's seed is the process noise's) */
+    int64_t step0;            /* number of the call's first step in the campaign (>= 0): a continued run draws on */
+    double sigma[4];          /* standard deviations: position (m), velocity (m/s), attitude (rad), rate (rad/s) */
+    const double* bias;       /* NULL (zero) or [B*12] */
+    double* pending;          /* NULL (zeros; nothing returned) or [B*d*NT], in/out */
+    double* meas_hist;        /* NULL or [T*B*13], output */
+    double* pred_hist;        /* NULL or [T*B*13], output (predict = 1) */
+} ftmpc_sensor;
+
+/* ftmpc_simulate_actuator_batch with the sensor `sensor` (NULL: exactly ftmpc_simulate_actuator_batch). */
+int ftmpc_simulate_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                const ftmpc_sensor* sensor);
+
+/* ftmpc_simulate_wrench_actuator_batch with the sensor `sensor` (NULL: exactly ftmpc_simulate_wrench_actuator_batch). */
+int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
+                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
+                                       const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                       const ftmpc_actuator* actuator, const ftmpc_sensor* sensor);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -824,6 +891,24 @@ int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                                const ftmpc_actuator* actuator);
+/* The two entries above with the sensor `sensor` (ftmpc_sensor; NULL: exactly the entries above).  The struct is checked once over
+ * the whole batch, so a refusal names the vehicle by its number in the caller's arrays; bias + 12 lo and pending + lo d NT are read
+ * (and pending written) per shard, the two histories are copied row by row from the shard's staging as u_hist is.
+ * ftmpc_multi_upload / _step take no sensor. */
+int ftmpc_multi_simulate_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                      int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                      const ftmpc_sensor* sensor);
+int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                             const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                             int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                             uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                             const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                             const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                             const ftmpc_actuator* actuator, const ftmpc_sensor* sensor);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

@@ -10,6 +10,7 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --mission         # also the loops under a three-table mission with random phases, and with cost
     python scripts/fault_campaign_perf.py --trace kernel_trace.csv   # per-launch times of the mission kernels and of the linearise kernel
     python scripts/fault_campaign_perf.py --actuator        # also the loops with PWM thrusters (S = 16, min_on 1) and valve lag in the plant
+    python scripts/fault_campaign_perf.py --sensor [--latency 0 2 8] [--predict]   # also the loops with navigation errors and latency
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -32,7 +33,12 @@ of the linearise kernel are split at the first launch of ftmpc_plant_step_kernel
 ticks per step (default 16), min_on 1, centred pulses, tau_on 20 ms, tau_off 10 ms, delivered and pulses returned
 (ftmpc_plant_step_act_kernel in place of ftmpc_plant_step_kernel).  With --once it makes one call with the actuator and one without,
 so that a kernel_stats.csv of that run holds both plant kernels, and --stats reports the time per launch of each and the actuator
-kernel's share of the kernel time."""
+kernel's share of the kernel time.
+--sensor: the loops without and with the schedule once more under BatchedMPC.simulate(sensor=...): noise on every group (1 cm, 5 mm/s,
+0.01 rad, 0.005 rad/s), a bias per vehicle from ft_mpc_amd.sensors.sample_bias, no history returned, once per --latency value (default
+2) and, with --predict, once more with the delay-compensating prediction (ftmpc_sense_kernel before every solve, the plant fed from
+the command ring).  With --once it makes one call with the sensor (the first --latency, --predict as given) and one without, so that
+a kernel_stats.csv of that run holds the sense kernel next to the plant kernel, and --stats reports the time per launch of each."""
 import argparse
 import csv
 import json
@@ -91,10 +97,13 @@ def mission(B, N, mass):
 
 
 ACTUATOR = dict(mode="pwm", min_on=1, align="centred", tau_on=0.02, tau_off=0.01, fields=("delivered", "pulses"))
+SENSOR = dict(sigma=(1e-2, 5e-3, 1e-2, 5e-3), seed=29)
+SENSOR_BIAS = (0.05, 0.01, 0.02, 0.005)
 DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
 
 
-def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False, actuator=False, substeps=16):
+def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False, actuator=False, substeps=16, sensor=False,
+        latencies=(2,), predict=False):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -122,7 +131,19 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         plant = sample(B, c["NT"], mpc.D, cfg.J, cfg.mass, seed=17, **DISPERSION)
     msn = mission(B, c["N"], cfg.mass) if with_mission else None
     act = dict(ACTUATOR, substeps=substeps) if actuator else None
+    sensors = []          # (label suffix, sensor dict, reference with the L more columns a predicting sensor needs)
+    if sensor:
+        from ft_mpc_amd.sensors import sample_bias
+        bias = sample_bias(B, SENSOR_BIAS, seed=31)
+        for d in latencies:
+            for pr in ((False, True) if predict and d > 0 else (False,)):
+                xs = np.zeros((9, T + c["N"] + (d if pr else 0)))
+                xs[8] = 0.6
+                sensors.append((f"sensor_d{d}" + ("_predict" if pr else ""), dict(SENSOR, bias=bias, latency=d, predict=pr), xs))
     if once:
+        if sensor:
+            label, sen, xs = sensors[-1] if predict else sensors[0]
+            mpc.simulate(x0, ub, stuck, xs, T, sensor=sen, **(witho if outcomes else withf), **kw)
         if actuator:
             mpc.simulate(x0, ub, stuck, xr, T, actuator=act, **(witho if outcomes else withf), **kw)
         if with_mission:
@@ -152,9 +173,13 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         runs += [("without_mission_hover", dict(plain, mission=hov), ub, stuck), ("with_mission_hover", dict(withf, mission=hov), ub, stuck),
                  ("without_mission", dict(plain, mission=msn), ub, stuck), ("with_mission", dict(withf, mission=msn), ub, stuck),
                  ("with_mission_cost", dict(withf, mission=msn, outcomes=dict(fields=["cost"])), ub, stuck)]
+    refs = {}
+    for label, sen, xs in sensors:
+        runs += [("without_" + label, dict(plain, sensor=sen), ub, stuck), ("with_" + label, dict(withf, sensor=sen), ub, stuck)]
+        refs["without_" + label] = refs["with_" + label] = xs
     for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
-        ref = None if "mission" in extra else xr              # a mission's tables are the reference
+        ref = None if "mission" in extra else refs.get(label, xr)      # a mission's tables are the reference
         mpc.simulate(x0, u, s, ref, T, **extra, **kw)         # warm-up: workspaces, code objects, grid hints
         ts = []
         for _ in range(reps):
@@ -177,6 +202,9 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         res["ratio_dispersed_over_without"] = res["without_dispersed"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_dispersed_over_with"] = res["with_dispersed"]["steps_per_s"] / res["with"]["steps_per_s"]
         res["plant_model_bytes"] = int(sum(a.nbytes for a in plant.values()))
+    for label, _, _ in sensors:
+        res[f"ratio_{label}_over_without"] = res["without_" + label]["steps_per_s"] / res["without"]["steps_per_s"]
+        res[f"ratio_{label}_over_with"] = res["with_" + label]["steps_per_s"] / res["with"]["steps_per_s"]
     if actuator:
         res["ratio_actuator_over_without"] = res["without_actuator"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_actuator_over_with"] = res["with_actuator"]["steps_per_s"] / res["with"]["steps_per_s"]
@@ -209,7 +237,9 @@ def stats(path):
     pn, pus = per_launch("ftmpc_plant_step_kernel")
     vn, vus = per_launch("ftmpc_plant_step_var_kernel")
     an, aus = per_launch("ftmpc_plant_step_act_kernel")
-    return dict(plant_act_kernel_calls=an, plant_act_kernel_avg_us=aus, plant_act_kernel_share=an * aus * 1e3 / tot if tot else 0.0,
+    sn, sus = per_launch("ftmpc_sense_kernel")
+    return dict(sense_kernel_calls=sn, sense_kernel_avg_us=sus, sense_kernel_share=sn * sus * 1e3 / tot if tot else 0.0,
+                plant_act_kernel_calls=an, plant_act_kernel_avg_us=aus, plant_act_kernel_share=an * aus * 1e3 / tot if tot else 0.0,
                 plant_kernel_calls=pn, plant_kernel_avg_us=pus, plant_var_kernel_calls=vn, plant_var_kernel_avg_us=vus,
                 total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
                 event_kernel_avg_us=(evt / calls * 1e-3) if calls else 0.0, event_kernel_share=evt / tot if tot else 0.0,
@@ -248,6 +278,9 @@ def main():
     ap.add_argument("--trace", default=None)
     ap.add_argument("--actuator", action="store_true")
     ap.add_argument("--substeps", type=int, default=16)
+    ap.add_argument("--sensor", action="store_true")
+    ap.add_argument("--latency", type=int, nargs="+", default=[2])
+    ap.add_argument("--predict", action="store_true")
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -258,7 +291,7 @@ def main():
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps, a.sensor, tuple(a.latency), a.predict)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
