@@ -1939,6 +1939,42 @@ int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B, const double* x0, const dou
     return FTMPC_OK;
 }
 
+int ftmpc_debug_records(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                        const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                        const double* warmU, double* rec_out) {
+    if (!h || !rec_out || B <= 0) return FTMPC_ERR_ARG;
+    int rc = check_strides(h, xref_stride, uref_stride, uref);
+    if (rc != FTMPC_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
+    const int N = h->cfg.N, NT = h->cfg.NT;
+    hipStream_t s = h->stream;
+    if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
+    if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
+    if (warmU) HIP_TRY(h, hipMemcpyAsync(h->d_warm, warmU, B * N * NT * sizeof(double), hipMemcpyHostToDevice, s));
+    LinParams lp;      // as enqueue fills it, work lists included
+    lp.B = B;
+    lp.x0 = h->d_x0; lp.ub = h->d_ub; lp.stuck = h->d_stuck;
+    lp.xref = h->d_xref; lp.xref_stride = xref_stride;
+    lp.uref = uref ? h->d_uref : nullptr; lp.uref_stride = uref_stride;
+    lp.warmU = warmU ? h->d_warm : nullptr;
+    lp.rec = h->rec;
+    lp.warmG = nullptr;
+    lp.out_eN = h->tset ? h->d_eN : nullptr;
+    lp.tcost = h->d_tcost;
+    lp.out_cbar = h->sbounds ? h->d_cbar : nullptr;
+    const int nvar = h->use_f64 ? 0 : (h->nb_max <= 8 ? 1 : (h->nb_max == 9 ? 2 : 3));
+    lp.qlist = h->use_f64 ? nullptr : h->d_qlist;
+    lp.qcount = h->d_qctl;
+    lp.qvmax = h->use_wg ? 3 : nvar - 1;
+    if (!h->use_f64) HIP_TRY(h, hipMemsetAsync(h->d_qctl, 0, 8 * sizeof(int32_t), s));
+    launch_linearize(h, B, (int)((B + 63) / 64), s, lp);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(rec_out, h->rec, (size_t)B * N * ftmpc::REC_STRIDE * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return FTMPC_OK;
+}
+
 int ftmpc_simulate_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                          const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                          double* u_hist, int32_t* not_converged) {

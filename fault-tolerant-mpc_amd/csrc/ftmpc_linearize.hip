@@ -3,8 +3,10 @@
 // One LANE per instance, float64 arithmetic.  A lane's record (152 words per stage) is contiguous per
 // instance because kernel 2 reads it that way, so storing word by word from the lanes would touch 64
 // different cache lines per store instruction (measured: 4.6 GB written + 2.4 GB read-modify-write
-// for a 1.6 GB payload).  The words are therefore staged through LDS ([word][lane], XOR-swizzled so
-// that both sides are bank-conflict free) and written out by the whole wave as contiguous runs.
+// for a 1.6 GB payload).  The words are therefore staged through LDS and written out by the whole wave
+// as contiguous runs.  Full-record kernel: one LDS row per instance at an odd stride (a put is one
+// ds_write_b64 at a constant offset from the lane's row), written out 16 bytes per lane with the
+// addresses stepped by adds and eight LDS reads in flight (flush_half below).
 // For each horizon stage it evaluates the orbit-centre dynamics
 //   (reference: SpiralModel.dx_dt, ft_mpc/models/spiral_model.py:44-76)
 // at the four RK4 stage points (SystemModel.rk4_integrator, ft_mpc/models/sys_model.py:138-162),
@@ -12,8 +14,13 @@
 // (omega0, q0, F, tau) -- the Jacobians the reference obtains from CasADi AD
 // (ft_mpc/controllers/spiraling_mpc.py:217-230).  SURVEY.md Appendix A lists the formulas.
 //
-// Work per instance ~ N * (4 dynamics evaluations + 13 * 4 tangent steps) ~ 0.1 MFLOP: below
-// 1 % of the step, so this kernel is latency/occupancy-trivial and not the roofline kernel.
+// Work per instance ~ N * (4 dynamics evaluations + 13 * 4 tangent steps) ~ 0.1 MFLOP (86 k float64
+// multiply-adds), but the kernel is 7 % of the headline step and not bound by that arithmetic.  It runs
+// one wave per SIMD (256 VGPRs + 256 AGPRs, 40 448 B of LDS), so nothing hides a wait, and the four
+// stage blocks (4 x 67 doubles = 536 registers) do not fit the register file: the tangent loop spends
+// more instructions on copies between the register halves and on spill traffic than on arithmetic.
+// What bounds it is the issue rate of that instruction stream; the write-out is no longer part of it
+// (CHANGELOG, "Linearise kernel: lean record write-out").
 #include <hip/hip_runtime.h>
 
 #include "ftmpc_common.h"
@@ -125,7 +132,53 @@ __device__ inline void stage_eval(const DeviceConsts& C, const double w[3], cons
 
 }  // namespace
 
-constexpr int STG_WORDS = (REC_BPF > REC_STRIDE - REC_BPF) ? REC_BPF : REC_STRIDE - REC_BPF;   // 79: 40 448 B of LDS per wave
+// Staging of the full-record kernel: one LDS row per instance, STG_ROW words apart.  The row stride is odd, so the
+// 32 lanes of one LDS pass hit 32 different bank pairs when every lane stores word `wd` of its own row, and a put is
+// one ds_write_b64 at lane base + constant.  A stage goes out in two halves, split at the even word STG_SPLIT so that
+// both halves start 16-byte aligned in the record: words [0, 78) after direction 6, words [78, 152) at the end of the
+// stage.  Word 78 (AQQ[3][3], direction 6) waits in the row's spare slot 78 over the first flush.
+constexpr int STG_SPLIT = 78;
+constexpr int STG_ROW = 79;                       // 64 * 79 * 8 = 40 448 B of LDS per wave
+static_assert(STG_SPLIT % 2 == 0 && (REC_STRIDE - STG_SPLIT) % 2 == 0 && REC_STRIDE % 2 == 0, "halves are whole 16-byte pairs");
+static_assert(STG_SPLIT == REC_BPF - 1 && REC_AQQ + 15 == STG_SPLIT, "word 78 is the one A word of the second half");
+static_assert(STG_ROW % 2 == 1 && STG_ROW > STG_SPLIT && STG_ROW > REC_STRIDE - STG_SPLIT, "odd row stride that holds either half and the spare slot");
+static_assert(64 * STG_ROW * 8 <= 40960, "four blocks per CU: one wave per SIMD");
+
+// The wave writes words [0, W) of the staged half of its 64 instances to g[inst * rowg + wd]: the same contiguous W-word runs,
+// 16 bytes per lane and store.  Pair p = lane + 64 t of the flattened [inst][W / 2] list belongs to lane `lane`; its instance,
+// LDS index and record offset follow from the previous pair's by adds and compares.  UN LDS reads are issued before the first
+// store; the stores do not wait for each other.  Rows at or past `nreal` are not written.
+template <int W>
+__device__ inline void flush_half(const double* stg, double* g, int rowg, int nreal, int lane) {
+    static_assert(W % 2 == 0 && W / 2 < 64 && W / 2 > 32, "at most two row changes per step of 64 pairs");
+    constexpr int PW = W / 2, UN = 8;
+    int inst = lane >= PW ? 1 : 0;
+    int pw = lane - inst * PW;
+    int la = inst * STG_ROW + 2 * pw;       // LDS word index
+    int ga = inst * rowg + 2 * pw;          // record word offset from g
+    auto group = [&](auto un) {
+        constexpr int U = decltype(un)::value;
+        double v0[U], v1[U];
+        int go[U];
+        bool ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            v0[u] = stg[la];
+            v1[u] = stg[la + 1];
+            go[u] = ga;
+            ok[u] = inst < nreal;
+            // 64 pairs on: PW < 64, so always into the next row, and into the one after it if the rest still overshoots
+            pw += 64 - PW; ++inst; la += 128 + STG_ROW - W; ga += 128 + rowg - W;
+            if (pw >= PW) { pw -= PW; ++inst; la += STG_ROW - W; ga += rowg - W; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (ok[u]) *reinterpret_cast<double2*>(g + go[u]) = make_double2(v0[u], v1[u]);
+    };
+#pragma unroll 1
+    for (int t = 0; t + UN <= PW; t += UN) group(std::integral_constant<int, UN>{});
+    if constexpr (PW % UN != 0) group(std::integral_constant<int, PW % UN>{});
+}
 
 // DIRS = false: the whole record of 64 instances per wave (full batches).  DIRS = true: blockIdx.y picks a contiguous
 // share of the 13 tangent directions (gridDim.y = 13, 4 or 2 shares; y = 0 also writes the words that are not tangents,
@@ -136,7 +189,7 @@ template <typename OutT, int SHARE>   // 0: full records; 1: one direction per b
 __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts C, const LinParams P) {
     static_assert(sizeof(OutT) == 8, "records are float64");
     constexpr bool DIRS = SHARE != 0;
-    __shared__ double stg[DIRS ? 1 : STG_WORDS * 64];
+    __shared__ double stg[DIRS ? 1 : STG_ROW * 64];
     const int lane = threadIdx.x;
     const int64_t b0 = (int64_t)blockIdx.x * 64;
     // lanes past the end of the batch redo the last instance (they take part in the cooperative stores)
@@ -152,19 +205,24 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
         if constexpr (DIRS) {
             if (b0 + lane < P.B) recw[(b * N + pk) * (int64_t)REC_STRIDE + pbase + wd] = (OutT)v;
         } else {
-            stg[wd * 64 + (lane ^ (wd & 63))] = v;
+            // second half: word pbase + wd of the record sits at row slot pbase + wd - STG_SPLIT
+            stg[lane * STG_ROW + wd + (pbase ? REC_BPF - STG_SPLIT : 0)] = v;
         }
     };
-    // the wave writes words [base, base + W) of stage k for its 64 instances: contiguous W-word runs
-    auto flush = [&](int k, int base, int W) {
+    // the wave writes one half of stage k for its 64 instances (flush_half): second = false words [0, STG_SPLIT) and
+    // word STG_SPLIT moves from the spare slot to slot 0 of the lane's own row, second = true words [STG_SPLIT, REC_STRIDE)
+    const int nreal = (int)((P.B - b0 < 64) ? P.B - b0 : 64);
+    auto flush = [&](int k, bool second) {
         if constexpr (!DIRS) {
+            double* const g = recw + (b0 * N + k) * (int64_t)REC_STRIDE;
             __syncthreads();
-            for (int idx = lane; idx < 64 * W; idx += 64) {
-                const int inst = idx / W, wd = idx - inst * W;
-                const double v = stg[wd * 64 + (inst ^ (wd & 63))];
-                if (b0 + inst < P.B) recw[((b0 + inst) * N + k) * (int64_t)REC_STRIDE + base + wd] = (OutT)v;
+            if (!second) {
+                flush_half<STG_SPLIT>(stg, g, N * REC_STRIDE, nreal, lane);
+            } else {
+                flush_half<REC_STRIDE - STG_SPLIT>(stg, g + STG_SPLIT, N * REC_STRIDE, nreal, lane);
             }
             __syncthreads();
+            if (!second) stg[lane * STG_ROW] = stg[lane * STG_ROW + STG_SPLIT];
         }
     };
 
@@ -322,7 +380,7 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
                 }
                 for (int a = 0; a < 4; ++a) put(REC_BQT - REC_BPF + 3 * a + jj, c6 * sq[a]);
             }
-            if (!DIRS && j == 6) flush(k, 0, REC_BPF);   // the A blocks (words 0..78) are complete
+            if (!DIRS && j == 6) flush(k, false);   // the A blocks (words 0..78) are complete
         }
 
         // ---- advance the nonlinear rollout (no quaternion renormalisation, sys_model.py:152-158) ----
@@ -369,7 +427,7 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
             for (int g = 0; g < 6; ++g) put(REC_RUT - REC_BPF + g, rut[g]);
             put(REC_USED - REC_BPF, 0.0);
         }
-        flush(k, REC_BPF, REC_STRIDE - REC_BPF);   // B blocks, W e, R ut (words 79..151)
+        flush(k, true);   // AQQ[3][3], B blocks, W e, R ut (words 78..151)
     }
 }
 

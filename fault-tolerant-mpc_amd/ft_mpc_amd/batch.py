@@ -560,6 +560,21 @@ class BatchedMPC:
         n = n.value
         return H[:n * n].reshape(n, n).copy(), g[:n].copy(), lo[:n].copy(), hi[:n].copy()
 
+    def debug_records(self, x0, ub, stuck, xref, uref=None, warmU=None):
+        """The linearisation records [B, N, 152] (csrc/ftmpc_common.h REC_*) of a host batch, from the kernel this handle's
+        lin_split_max picks for B."""
+        N, NT = self.cfg.N, self.cfg.NT
+        x0 = _f64(x0).reshape(-1, 13)
+        B = x0.shape[0]
+        ub = _f64(ub, (B, NT))
+        stuck = _f64(stuck, (B, NT))
+        xref, xs, uref, us = self._refs(B, xref, uref)
+        warm = None if warmU is None else _f64(warmU, (B, N, NT))
+        rec = np.zeros((B, N, 152))
+        self._check(self.lib.ftmpc_debug_records(self._h, B, _ptr(x0), _ptr(ub), _ptr(stuck), _ptr(xref), xs,
+                                                 _ptr(uref), us, _ptr(warm), _ptr(rec)))
+        return rec
+
 
 OUTCOME_FIELDS = (("err_int", 3, np.float64), ("err_max", 3, np.float64), ("impulse", 2, np.float64), ("settle_step", 0, np.int32),
                   ("tset_step", 0, np.int32), ("unsolved", 0, np.int32), ("first_unsolved", 0, np.int32), ("alloc_failed", 0, np.int32))

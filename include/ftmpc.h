@@ -791,6 +791,17 @@ int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B,
                          int32_t* n_out);
 
 /*
+ * Test hook: runs the linearisation alone on a host batch -- the kernel the handle's lin_split_max picks for B, with the
+ * parameters (work lists included) a solve would give it -- and copies the records back:
+ * rec_out [B * N * 152] doubles, the layout of csrc/ftmpc_common.h (REC_*), stage k of instance b at (b * N + k) * 152.
+ */
+int ftmpc_debug_records(ftmpc_handle* h, int64_t B,
+                        const double* x0, const double* ub, const double* stuck,
+                        const double* xref, int64_t xref_stride,
+                        const double* uref, int64_t uref_stride,
+                        const double* warmU, double* rec_out);
+
+/*
  * The batch axis across the GPUs of one node from ONE process.  The reference
  * never couples instances (one controller object per vehicle, spiraling_mpc.py:288-317), so device g owns
  * the contiguous range [B g / G, B (g+1) / G) (ftmpc_multi_shard_bounds); one host thread + one handle + one
