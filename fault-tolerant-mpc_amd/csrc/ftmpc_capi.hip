@@ -1992,7 +1992,8 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
-                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr);
+                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr,
+                         const ftmpc_estimator* es = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -2181,6 +2182,43 @@ static int sensor_shift(const ftmpc_sensor* se) {
     return se && se->predict == 1 && se->latency > 0 && se->latency <= FTMPC_MAX_LATENCY ? se->latency : 0;
 }
 
+// An estimator's layout and values (include/ftmpc.h, ftmpc_estimator) over the vehicles [0, B): empty when acceptable, else the
+// message, which names the field and, for an array, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string estimator_problem(const ftmpc_estimator* es, int64_t B, int64_t first = 0) {
+    if (!es) return "";
+    if (es->struct_size != (int32_t)sizeof(ftmpc_estimator))
+        return "ftmpc_estimator.struct_size is " + std::to_string(es->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_estimator));
+    if (es->every < 1) return "ftmpc_estimator.every is " + std::to_string(es->every) + ", below 1";
+    for (int k = 0; k < 4; ++k) {
+        if (!std::isfinite(es->p0[k]) || es->p0[k] < 0) return "ftmpc_estimator.p0[" + std::to_string(k) + "] is negative or not finite";
+        if (!std::isfinite(es->proc_sigma[k]) || es->proc_sigma[k] < 0)
+            return "ftmpc_estimator.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
+        if (!std::isfinite(es->meas_sigma[k]) || !(es->meas_sigma[k] > 0))
+            return "ftmpc_estimator.meas_sigma[" + std::to_string(k) + "] is not finite and > 0";
+    }
+    if (es->cov && !es->xhat) return "ftmpc_estimator.cov is given without xhat";
+    if (es->xhat)
+        for (int64_t i = 0; i < B * 13; ++i)
+            if (!std::isfinite(es->xhat[i]))
+                return "ftmpc_estimator.xhat: vehicle " + std::to_string(first + i / 13) + " has a non-finite entry (" + std::to_string(i % 13) + ")";
+    if (es->cov)
+        for (int64_t b = 0; b < B; ++b) {
+            const double* c = es->cov + b * 78;
+            for (int k = 0; k < 78; ++k)
+                if (!std::isfinite(c[k]))
+                    return "ftmpc_estimator.cov: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
+            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i)
+                if (c[k] < 0)
+                    return "ftmpc_estimator.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
+        }
+    return "";
+}
+static int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
+    const std::string msg = estimator_problem(es, B);
+    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
+}
+
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
 static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
     if (!oc) return FTMPC_OK;
@@ -2300,6 +2338,16 @@ int ftmpc_simulate_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
                                 double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                 const ftmpc_sensor* sensor) {
+    return ftmpc_simulate_estimator_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                          x_hist, not_converged, out, plant, mission, actuator, sensor, nullptr);
+}
+
+int ftmpc_simulate_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2308,17 +2356,19 @@ int ftmpc_simulate_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
     if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
+    if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
+        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
         return FTMPC_OK;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator, sensor);
+                         faults, x_hist, out, plant, mission, actuator, sensor, estimator);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2383,6 +2433,19 @@ int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
                                        const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                        const ftmpc_actuator* actuator, const ftmpc_sensor* sensor) {
+    return ftmpc_simulate_wrench_estimator_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                                 seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                                 out, plant, mission, actuator, sensor, nullptr);
+}
+
+int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
@@ -2391,17 +2454,20 @@ int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, do
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
+    if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
+        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
         return FTMPC_OK;
     }
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
     WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor);
+                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor,
+                         estimator);
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2452,13 +2518,20 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
                          const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
-                         const ftmpc_sensor* se) {
+                         const ftmpc_sensor* se, const ftmpc_estimator* es) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
+    // estimator (checked by the entry): ftmpc_filter_kernel runs between the sense kernel and the solve (phase 0) and after the plant
+    // step (phase 1).  It takes the truth-buffer path of a sensor even when the sensor is trivial or NULL (se0: latency 0, step0 0,
+    // nothing drawn); the sense kernel then does not run and y_t is the truth
+    const bool est = es != nullptr;
+    const bool sensing = !sensor_trivial(se);      // ftmpc_sense_kernel runs
+    ftmpc_sensor se0{};
+    if (est && !se) se = &se0;
     // sensor (checked by the entry): not trivial, the truth lives in d_xtrue and ftmpc_sense_kernel writes h->d_x0 before every solve;
     // lat commands wait in the ring d_ring ([lat + 1][B][NT]); a predicting sensor shifts every reference window by L = lat columns
-    const bool sense = !sensor_trivial(se);
+    const bool sense = sensing || est;
     const int lat = sense ? se->latency : 0, L = sense && se->predict ? lat : 0;
     const int64_t ncol = (int64_t)T + N + L;   // windows t .. t+N for t < T (t+L .. t+L+N under a predicting sensor)
     // (this call's own buffers: freed on every way out)
@@ -2657,6 +2730,58 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         sn.meas_hist = d_mhist;
         sn.pred_hist = d_phist;
     }
+    // the filter's state: the mean [B][13] and the packed covariance, component-major [78][B] (the caller's is vehicle-major),
+    // diag(p0^2) when none is handed over; err_sq [B][4] starts at zero
+    DevBuf<double> d_xhat, d_cov, d_ehist, d_esq;
+    std::vector<double> h_cov;
+    ftmpc::FilterParams fp{};
+    if (est) {
+        const size_t nc = (size_t)B * 78;
+        try {
+            h_cov.assign(nc, 0.0);
+        } catch (const std::bad_alloc&) {
+            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the estimator's staging array");
+        }
+        if (es->cov) {
+            for (int64_t b0 = 0; b0 < B; b0 += 64) {
+                const int64_t b1 = std::min(B, b0 + 64);
+                for (int64_t k = 0; k < 78; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_cov[(size_t)k * B + b] = es->cov[b * 78 + k];
+            }
+        } else {
+            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i) std::fill(h_cov.begin() + (size_t)k * B, h_cov.begin() + (size_t)(k + 1) * B, es->p0[i / 3] * es->p0[i / 3]);
+        }
+        HIP_TRY(h, hipMalloc(&d_cov.p, nc * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_cov, h_cov.data(), nc * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMalloc(&d_xhat.p, (size_t)B * 13 * sizeof(double)));
+        if (es->xhat) HIP_TRY(h, hipMemcpyAsync(d_xhat, es->xhat, (size_t)B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
+        if (es->est_hist) HIP_TRY(h, hipMalloc(&d_ehist.p, (size_t)T * B * 13 * sizeof(double)));
+        if (es->err_sq) {
+            HIP_TRY(h, hipMalloc(&d_esq.p, (size_t)B * 4 * sizeof(double)));
+            HIP_TRY(h, hipMemsetAsync(d_esq, 0, (size_t)B * 4 * sizeof(double), s));
+        }
+        sn.predict = 0;             // the filter propagates its own estimate over the queue, and writes pred_hist
+        sn.pred_hist = nullptr;
+        fp.B = B;
+        fp.latency = lat;
+        fp.predict = se->predict;
+        fp.nslots = lat + 1;
+        fp.y = sensing ? h->d_x0.p : d_xtrue.p;
+        fp.truth = d_xtrue;
+        fp.x0 = h->d_x0;
+        fp.xhat = d_xhat;
+        fp.cov = d_cov;
+        fp.ub = h->d_ub;
+        fp.stuck = h->d_stuck;
+        fp.ring = d_ring;
+        for (int i = 0; i < 4; ++i) {
+            fp.rsq[i] = es->meas_sigma[i] * es->meas_sigma[i];
+            fp.qsq[i] = es->proc_sigma[i] * es->proc_sigma[i];
+        }
+        fp.est_hist = d_ehist;
+        fp.pred_hist = d_phist;
+        fp.err_sq = d_esq;
+    }
     double* const d_truth = sense ? d_xtrue.p : h->d_x0.p;      // what the plant integrates and the outcomes measure
     // a continued run (step0 > 0, and the handle's last loop with a sensor ended at that step, on this batch and form, in this x):
     // its first solve is warm-started as the whole run's would be, from what the handle kept; otherwise it starts cold
@@ -2837,11 +2962,19 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         const double* const uo_t = !has_uref ? nullptr : (windows ? d_uwin.p : d_ur + (int64_t)6 * t);
         const double* const xr_t = xo_t + (int64_t)9 * L;
         const double* const ur_t = uo_t ? uo_t + (int64_t)6 * L : nullptr;
-        if (sense) {     // y_t (and its propagation over the queue) into h->d_x0; slot t mod (lat + 1) holds a_t
+        if (sensing) {     // y_t (and its propagation over the queue) into h->d_x0; slot t mod (lat + 1) holds a_t
             sn.cstep = se->step0 + t;
             sn.step = t;
             sn.slot0 = t % (lat + 1);
             hipLaunchKernelGGL(ftmpc::ftmpc_sense_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sn);
+            HIP_TRY(h, hipGetLastError());
+        }
+        if (est) {     // the update on y_t, the estimate (propagated over the queue when the sensor predicts) into h->d_x0
+            fp.init = t == 0 && !es->xhat;
+            fp.update = (se->step0 + t) % es->every == 0;
+            fp.step = t;
+            fp.slot0 = t % (lat + 1);
+            hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
             HIP_TRY(h, hipGetLastError());
         }
         const int64_t xr_s = windows ? xw : 0, ur_s = windows ? uw : 0;
@@ -2890,6 +3023,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_var_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv);
         else
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
+        if (est) {     // the time update under a_t and the controller's pattern of this step
+            fp.u = sp.u0;
+            hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
+        }
         if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
             op.step = t;
             op.ub = sp.ub;
@@ -2924,6 +3061,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                 HIP_TRY(h, hipMemcpyAsync(h_ring.data() + (size_t)j * nu, d_ring + (size_t)((T + j) % (lat + 1)) * nu, nu * sizeof(double),
                                           hipMemcpyDeviceToHost, s));
     }
+    if (est) {
+        if (es->est_hist) HIP_TRY(h, hipMemcpyAsync(es->est_hist, d_ehist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (es->err_sq) HIP_TRY(h, hipMemcpyAsync(es->err_sq, d_esq, (size_t)B * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (es->xhat) HIP_TRY(h, hipMemcpyAsync(es->xhat, d_xhat, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (es->cov) HIP_TRY(h, hipMemcpyAsync(h_cov.data(), d_cov, (size_t)B * 78 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
     if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -2952,6 +3095,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (act && ac->state)
         for (int64_t b = 0; b < B; ++b)
             for (int i = 0; i < NT; ++i) ac->state[b * NT + i] = h_aval[(size_t)i * B + b];
+    if (est && es->cov)
+        for (int64_t b0 = 0; b0 < B; b0 += 64) {
+            const int64_t b1 = std::min(B, b0 + 64);
+            for (int64_t k = 0; k < 78; ++k)
+                for (int64_t b = b0; b < b1; ++b) es->cov[b * 78 + k] = h_cov[(size_t)k * B + b];
+        }
     if (sense) {
         try {
             h->keep_x.assign(x, x + B * 13);

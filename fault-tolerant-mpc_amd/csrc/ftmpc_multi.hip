@@ -204,7 +204,7 @@ void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_
     for (int64_t t = 0; t < T; ++t) std::memcpy(dst + (t * B + lo) * w, src + t * n * w, (size_t)(n * w) * sizeof(V));
 }
 
-// The closed loops over the device slots (ftmpc_multi_simulate_sensor_batch / _wrench_sensor_batch; hull_A == nullptr: the thruster
+// The closed loops over the device slots (ftmpc_multi_simulate_estimator_batch / _wrench_estimator_batch; hull_A == nullptr: the thruster
 // form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
 // caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
 // staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
@@ -213,7 +213,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, bool wrench) {
+                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -236,6 +236,10 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         const std::string msg = sensor_problem(sensor, B, m->cfg.NT);
         if (!msg.empty()) return refuse(msg);
     }
+    {     // the estimator likewise: the parameters are uniform, xhat / cov, est_hist and err_sq are per vehicle
+        const std::string msg = estimator_problem(estimator, B);
+        if (!msg.empty()) return refuse(msg);
+    }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
         const std::string msg = mission_problem(mission, B, T, m->cfg.N, xref_traj, uref_traj, 0, sensor_shift(sensor));
         if (!msg.empty()) return refuse(msg);
@@ -248,6 +252,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
+        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
         return FTMPC_OK;
     }
     const int G = (int)m->dev.size();
@@ -307,7 +312,16 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sv.bias) sv.bias += lo * 12;
             if (sv.pending) sv.pending += lo * sv.latency * NT;
         }
+        std::vector<double> eh;
+        ftmpc_estimator ev{};
+        if (estimator) {
+            ev = *estimator;
+            if (ev.xhat) ev.xhat += lo * 13;
+            if (ev.cov) ev.cov += lo * 78;
+            if (ev.err_sq) ev.err_sq += lo * 4;
+        }
         try {
+            if (ev.est_hist && !whole) eh.resize((size_t)T * n * 13);
             if (sv.meas_hist && !whole) mh.resize((size_t)T * n * 13);
             if (sv.pred_hist && !whole) ph.resize((size_t)T * n * 13);
             bad[g].assign((size_t)T, 0);
@@ -341,18 +355,20 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (at.ticks_hist) at.ticks_hist = kh.data();
             if (sv.meas_hist) sv.meas_hist = mh.data();
             if (sv.pred_hist) sv.pred_hist = ph.data();
+            if (ev.est_hist) ev.est_hist = eh.data();
         }
-        const int rc2 = wrench ? ftmpc_simulate_wrench_sensor_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+        const int rc2 = wrench ? ftmpc_simulate_wrench_estimator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
                                                                      xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
                                                                      faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
                                                                      alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
                                                                      mission ? &mi : nullptr, actuator ? &at : nullptr,
-                                                                     sensor ? &sv : nullptr)
-                               : ftmpc_simulate_sensor_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                                     sensor ? &sv : nullptr, estimator ? &ev : nullptr)
+                               : ftmpc_simulate_estimator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
                                                                seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
                                                                bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
-                                                               actuator ? &at : nullptr, sensor ? &sv : nullptr);
+                                                               actuator ? &at : nullptr, sensor ? &sv : nullptr,
+                                                               estimator ? &ev : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -362,6 +378,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (actuator && actuator->ticks_hist) scatter_rows(actuator->ticks_hist, kh.data(), T, B, lo, n, NT);
             if (sensor && sensor->meas_hist) scatter_rows(sensor->meas_hist, mh.data(), T, B, lo, n, 13);
             if (sensor && sensor->pred_hist) scatter_rows(sensor->pred_hist, ph.data(), T, B, lo, n, 13);
+            if (estimator && estimator->est_hist) scatter_rows(estimator->est_hist, eh.data(), T, B, lo, n, 13);
         }
         return FTMPC_OK;
     });
@@ -600,7 +617,7 @@ int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, nullptr, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, nullptr, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -609,7 +626,7 @@ int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, doubl
                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                      const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, nullptr, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, nullptr, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -618,7 +635,7 @@ int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, dou
                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                        const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, nullptr, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, nullptr, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -628,7 +645,7 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, nullptr, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -639,7 +656,7 @@ int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T
                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                             const ftmpc_plant_model* plant) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, nullptr, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -650,7 +667,7 @@ int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t
                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, nullptr, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, nullptr, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -659,7 +676,7 @@ int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, nullptr, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, nullptr, nullptr, false);
 }
 
 int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -671,7 +688,7 @@ int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_
                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                                const ftmpc_actuator* actuator) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, nullptr, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, nullptr, nullptr, true);
 }
 
 int ftmpc_multi_simulate_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -681,7 +698,7 @@ int ftmpc_multi_simulate_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, doub
                                       const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                       const ftmpc_sensor* sensor) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, false);
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, nullptr, false);
 }
 
 int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -693,7 +710,31 @@ int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t 
                                              const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                              const ftmpc_actuator* actuator, const ftmpc_sensor* sensor) {
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor, true);
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor, nullptr, true);
+}
+
+int ftmpc_multi_simulate_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                         const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false);
+}
+
+int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                const ftmpc_estimator* estimator) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
+                          estimator, true);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

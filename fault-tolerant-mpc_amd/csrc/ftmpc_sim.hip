@@ -987,4 +987,346 @@ __global__ void __launch_bounds__(64) ftmpc_sense_kernel(const DeviceConsts C, c
     for (int i = 0; i < 13; ++i) P.y[b * 13 + i] = x[i];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The navigation filter (ftmpc_simulate_estimator_batch / ftmpc_simulate_wrench_estimator_batch; include/ftmpc.h, ftmpc_estimator):
+// a multiplicative (error-state) extended Kalman filter per vehicle between ftmpc_sense_kernel and the solve.  A lane per vehicle.
+// phase 0 runs before the solve: the measurement update (twelve sequential scalar updates, H = I, diagonal R), est_hist, err_sq
+// against the truth, the propagation over the d queued commands when the sensor predicts, and the handle's x0.  phase 1 runs after
+// the plant step: P <- Phi P Phi' + Q with Phi = I + dt A(x^, gen) and x^ <- one RK4 step of the controller's model.
+// The packed upper triangle of P (78 doubles) lives in registers: every index into it is a compile-time constant (the update loop is
+// unrolled, the blocks of the time update are template arguments), so nothing goes to scratch.  Phi is never formed: it is block
+// upper-bidiagonal over the 4 x 4 grid of 3 x 3 blocks (p, v, theta, w),
+//        [ I  dt I    0      0   ]
+//        [ 0    I     G      0   ]      G = -dt M [F/m]x,  H = I - dt [w]x,  W = I + dt J^-1 ([J w]x - [w]x J)
+//        [ 0    0     H    dt I  ]
+//        [ 0    0     0      W   ]
+// so block (I, J) of Phi P Phi' needs the blocks (I, J), (I+1, J), (I, J+1), (I+1, J+1) of P alone, and walking the upper triangle
+// row by row updates P in place with one 3 x 3 block of temporaries; the identity blocks are additions.  Device-side P is
+// component-major [78][B], so that the lanes of a wave read consecutive addresses.
+// ---------------------------------------------------------------------------------------------------------
+struct FilterParams {
+    int64_t B;
+    int32_t init, update;     // phase 0: x^ = y_t and no update (first step of a call without xhat); the update runs (c % every == 0)
+    int32_t latency, predict; // phase 0: the sensor's d and predict
+    int32_t nslots, slot0;    // d + 1, slot of a_t
+    const double* y;          // [B*13] y_t: what ftmpc_sense_kernel wrote, or the truth when the sensor is trivial
+    const double* truth;      // [B*13]
+    double* x0;               // [B*13] what the solve reads (the handle's x0)
+    double* xhat;             // [B*13] the mean, in/out
+    double* cov;              // [78][B] the packed covariance, in/out
+    const double* ub;         // [B*NT] the controller's pattern
+    const double* stuck;
+    const double* ring;       // nullptr (d = 0) or [(d+1)][B*NT]
+    const double* u;          // phase 1: [B*NT] a_t, the command the plant applied in this step
+    double rsq[4], qsq[4];    // meas_sigma^2, proc_sigma^2 by group
+    int64_t step;             // t (the histories' row)
+    double* est_hist;         // nullptr or [T*B*13]
+    double* pred_hist;        // nullptr or [T*B*13]
+    double* err_sq;           // nullptr or [B*4], accumulated over the call's steps
+};
+
+namespace {
+// packed index of P(i, j), upper triangle row-major
+__host__ __device__ constexpr int tri(int i, int j) {
+    return i <= j ? 12 * i - i * (i - 1) / 2 + (j - i) : 12 * j - j * (j - 1) / 2 + (i - j);
+}
+
+// gen = D ((ub > 0 ? a : 0) + stuck), accumulated inside the thruster loop (D at wave-uniform indices)
+__device__ __forceinline__ void filter_gen(const DeviceConsts& C, const double* a, const double* ub, const double* stuck, int64_t b,
+                                           double* gen) {
+    const int NT = C.NT;
+    for (int g = 0; g < 6; ++g) gen[g] = 0.0;
+    for (int i = 0; i < NT; ++i) {
+        const double t = (ub[b * NT + i] > 0.0 ? a[b * NT + i] : 0.0) + stuck[b * NT + i];
+        for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * t;
+    }
+}
+
+// one RK4 step of dt of the controller's model, the quaternion renormalised: the step ftmpc_sense_kernel predicts with
+__device__ __forceinline__ void filter_rk4(const DeviceConsts& C, double* x, const double* gen) {
+    const double dt = C.dt;
+    double k1[13], k2[13], k3[13], k4[13], s[13];
+    plant_f(C, x, gen, k1);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k1[i];
+    plant_f(C, s, gen, k2);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k2[i];
+    plant_f(C, s, gen, k3);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + dt * k3[i];
+    plant_f(C, s, gen, k4);
+    for (int i = 0; i < 13; ++i) x[i] += dt / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
+    for (int i = 6; i < 10; ++i) x[i] *= qn;
+}
+
+// q turned by the body-frame rotation vector t, renormalised (the closed form of the sensor's attitude error)
+__device__ __forceinline__ void filter_rotate(double* q, double t0, double t1, double t2) {
+    const double n = sqrt(t0 * t0 + t1 * t1 + t2 * t2);
+    const double cs = cos(0.5 * n), sn = n < 1e-8 ? 0.5 : sin(0.5 * n) / n;
+    const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
+    const double r0 = cs * qx + sn * (t2 * qy - t1 * qz + t0 * qw);
+    const double r1 = cs * qy + sn * (-t2 * qx + t0 * qz + t1 * qw);
+    const double r2 = cs * qz + sn * (t1 * qx - t0 * qy + t2 * qw);
+    const double r3 = cs * qw + sn * (-t0 * qx - t1 * qy - t2 * qz);
+    const double qn = 1.0 / sqrt(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
+    q[0] = r0 * qn; q[1] = r1 * qn; q[2] = r2 * qn; q[3] = r3 * qn;
+}
+
+// th with rotate(qh, th) = yq: c = qh . yq, s = Xi(qh)' yq (flipped when c < 0), th = 2 atan2(|s|, c) / |s| s
+__device__ __forceinline__ void filter_att_residual(const double* qh, const double* yq, double* th) {
+    const double hx = qh[0], hy = qh[1], hz = qh[2], hw = qh[3];
+    double c = hx * yq[0] + hy * yq[1] + hz * yq[2] + hw * yq[3];
+    double s0 = hw * yq[0] + hz * yq[1] - hy * yq[2] - hx * yq[3];
+    double s1 = -hz * yq[0] + hw * yq[1] + hx * yq[2] - hy * yq[3];
+    double s2 = hy * yq[0] - hx * yq[1] + hw * yq[2] - hz * yq[3];
+    if (c < 0.0) {
+        c = -c; s0 = -s0; s1 = -s1; s2 = -s2;
+    }
+    const double n = sqrt(s0 * s0 + s1 * s1 + s2 * s2);
+    const double f = n < 1e-8 ? 2.0 : 2.0 * atan2(n, c) / n;
+    th[0] = f * s0; th[1] = f * s1; th[2] = f * s2;
+}
+
+// Row k of the component-major covariance, for this block's 64 vehicles, as a wave-uniform global pointer the lane number is added
+// to as a 32-bit offset.  Without the readfirstlane the compiler folds the lane into the base and keeps 78 per-lane 64-bit addresses
+// alive between the loads and the stores: as many registers as P itself.
+typedef __attribute__((address_space(1))) double global_double;
+__device__ __forceinline__ global_double* cov_row(const double* p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (global_double*)(((unsigned long long)hi << 32) | lo);
+}
+
+// kinds of the 3 x 3 blocks of Phi
+enum : int { FK_NONE = 0, FK_ID = 1, FK_TAU = 2, FK_DENSE = 3, FK_SKEW = 4 };      // FK_SKEW: I - [h]x, M = h (3 entries)
+__host__ __device__ constexpr int fk_diag(int I) { return I < 2 ? FK_ID : (I == 2 ? FK_SKEW : FK_DENSE); }                       // Phi(I, I)
+__host__ __device__ constexpr int fk_up(int I) { return I == 1 ? FK_DENSE : (I == 3 ? FK_NONE : FK_TAU); }   // Phi(I, I+1)
+
+template <int I, int J>
+__device__ __forceinline__ void cov_load(const double* P, double* X) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) X[3 * r + c] = P[tri(3 * I + r, 3 * J + c)];
+}
+// out += M X, M of the given kind
+template <int KIND>
+__device__ __forceinline__ void blk_lmul(const double* M, double tau, const double* X, double* out) {
+    if constexpr (KIND == FK_ID) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] += X[i];
+    } else if constexpr (KIND == FK_TAU) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] += tau * X[i];
+    } else if constexpr (KIND == FK_DENSE) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[3 * r + c] += M[3 * r] * X[c] + M[3 * r + 1] * X[3 + c] + M[3 * r + 2] * X[6 + c];
+    } else if constexpr (KIND == FK_SKEW) {      // X - h x (the columns of X)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            out[c] += X[c] - (M[1] * X[6 + c] - M[2] * X[3 + c]);
+            out[3 + c] += X[3 + c] - (M[2] * X[c] - M[0] * X[6 + c]);
+            out[6 + c] += X[6 + c] - (M[0] * X[3 + c] - M[1] * X[c]);
+        }
+    }
+}
+// out += X M'
+template <int KIND>
+__device__ __forceinline__ void blk_rmul_t(const double* M, double tau, const double* X, double* out) {
+    if constexpr (KIND == FK_ID) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] += X[i];
+    } else if constexpr (KIND == FK_TAU) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[i] += tau * X[i];
+    } else if constexpr (KIND == FK_DENSE) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[3 * r + c] += X[3 * r] * M[3 * c] + X[3 * r + 1] * M[3 * c + 1] + X[3 * r + 2] * M[3 * c + 2];
+    } else if constexpr (KIND == FK_SKEW) {      // X (I - [h]x)' = X + X [h]x: the rows of X
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            out[3 * r] += X[3 * r] + (X[3 * r + 1] * M[2] - X[3 * r + 2] * M[1]);
+            out[3 * r + 1] += X[3 * r + 1] + (X[3 * r + 2] * M[0] - X[3 * r] * M[2]);
+            out[3 * r + 2] += X[3 * r + 2] + (X[3 * r] * M[1] - X[3 * r + 1] * M[0]);
+        }
+    }
+}
+// block (I, J), I <= J, of Phi P Phi' in place.  G, H, W: the dense blocks (1, 2), (2, 2), (3, 3) of Phi
+template <int I, int J>
+__device__ __forceinline__ void cov_block(double* P, const double* G, const double* H, const double* W, double tau) {
+    const double* const dI = I == 2 ? H : W;      // read for the dense kinds only
+    const double* const dJ = J == 2 ? H : W;
+    double A[9], X[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Nw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    cov_load<I, J>(P, A);
+    blk_lmul<fk_diag(I)>(dI, tau, A, X);
+    if constexpr (fk_up(I) != FK_NONE) {
+        cov_load<I + 1, J>(P, A);
+        blk_lmul<fk_up(I)>(G, tau, A, X);
+    }
+    blk_rmul_t<fk_diag(J)>(dJ, tau, X, Nw);
+    if constexpr (fk_up(J) != FK_NONE) {
+        double Y[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        cov_load<I, J + 1>(P, A);
+        blk_lmul<fk_diag(I)>(dI, tau, A, Y);
+        if constexpr (fk_up(I) != FK_NONE) {
+            cov_load<I + 1, J + 1>(P, A);
+            blk_lmul<fk_up(I)>(G, tau, A, Y);
+        }
+        blk_rmul_t<fk_up(J)>(G, tau, Y, Nw);
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (I < J || r <= c) P[tri(3 * I + r, 3 * J + c)] = Nw[3 * r + c];
+}
+}  // namespace
+
+template <int PHASE>
+__global__ void __launch_bounds__(64) ftmpc_filter_kernel(const DeviceConsts C, const FilterParams F) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= F.B) return;
+    const int64_t B = F.B;
+    double* const covb = F.cov + (int64_t)blockIdx.x * blockDim.x;
+    const unsigned lane = threadIdx.x;
+    double x[13], P[78];
+    if constexpr (PHASE == 0) {
+        double y[13];
+        for (int i = 0; i < 13; ++i) y[i] = F.y[b * 13 + i];
+        if (F.init) {
+            for (int i = 0; i < 13; ++i) x[i] = y[i];
+        } else {
+            for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        }
+        if (!F.init && F.update) {
+            // the residual's position, velocity and rate entries are formed from y and x^ where the update of their channel needs
+            // them, and x^ is read again afterwards: next to the 156 registers of P only the attitude entries and d stay live
+            double th[3], d[12];
+            filter_att_residual(x + 6, y + 6, th);
+#pragma unroll
+            for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                const int jx = j < 6 ? j : j + 1;      // channel j's entry of x (rate: past the quaternion)
+                const double rj = (j >= 6 && j < 9) ? th[j - 6] : F.y[b * 13 + jx] - F.xhat[b * 13 + jx];
+                const double sj = P[tri(j, j)] + F.rsq[j / 3];
+                const double inv = 1.0 / sj;
+                double k[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) k[i] = P[tri(i, j)] * inv;
+                const double e = rj - d[j];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) d[i] += k[i] * e;
+#pragma unroll
+                for (int a = 0; a < 12; ++a) {
+                    const double ska = sj * k[a];
+#pragma unroll
+                    for (int c = a; c < 12; ++c) P[tri(a, c)] -= ska * k[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+            {     // (a volatile read: otherwise the compiler keeps the first read's values, in scratch, instead of reading again)
+                const volatile double* const xh = F.xhat + b * 13;
+                for (int i = 0; i < 13; ++i) x[i] = xh[i];
+            }
+            for (int i = 0; i < 3; ++i) {
+                x[i] += d[i];
+                x[3 + i] += d[3 + i];
+                x[10 + i] += d[9 + i];
+            }
+            filter_rotate(x + 6, d[6], d[7], d[8]);
+        }
+        for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+        if (F.est_hist)
+            for (int i = 0; i < 13; ++i) F.est_hist[(F.step * B + b) * 13 + i] = x[i];
+        if (F.err_sq) {     // against the truth: position, velocity, attitude (the residual's theta), rate
+            double xt[13], th[3], e[4] = {0, 0, 0, 0};
+            for (int i = 0; i < 13; ++i) xt[i] = F.truth[b * 13 + i];
+            filter_att_residual(x + 6, xt + 6, th);
+            for (int i = 0; i < 3; ++i) {
+                e[0] += (x[i] - xt[i]) * (x[i] - xt[i]);
+                e[1] += (x[3 + i] - xt[3 + i]) * (x[3 + i] - xt[3 + i]);
+                e[2] += th[i] * th[i];
+                e[3] += (x[10 + i] - xt[10 + i]) * (x[10 + i] - xt[10 + i]);
+            }
+            for (int i = 0; i < 4; ++i) F.err_sq[b * 4 + i] += e[i];
+        }
+        if (F.predict) {
+            int32_t slot = F.slot0;
+#pragma unroll 1
+            for (int j = 0; j < F.latency; ++j) {
+                double gen[6];
+                filter_gen(C, F.ring + (int64_t)slot * B * C.NT, F.ub, F.stuck, b, gen);
+                slot = slot + 1 == F.nslots ? 0 : slot + 1;
+                filter_rk4(C, x, gen);
+            }
+            if (F.pred_hist)
+                for (int i = 0; i < 13; ++i) F.pred_hist[(F.step * B + b) * 13 + i] = x[i];
+        }
+        for (int i = 0; i < 13; ++i) F.x0[b * 13 + i] = x[i];
+        return;
+    }
+    // PHASE 1: the time update under the command the plant applied in this step
+    for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+#pragma unroll
+    for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+    double gen[6];
+    filter_gen(C, F.u, F.ub, F.stuck, b, gen);
+    {
+        const double dt = C.dt;
+        const double qx = x[6], qy = x[7], qz = x[8], qw = x[9];
+        const double w0 = x[10], w1 = x[11], w2 = x[12];
+        // M = Rot(q)^T, the matrix plant_f applies to F / m
+        const double M[9] = {qx * qx - qy * qy - qz * qz + qw * qw, 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw),
+                             2 * (qx * qy + qz * qw), -qx * qx + qy * qy - qz * qz + qw * qw, 2 * (qy * qz - qx * qw),
+                             2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), -qx * qx - qy * qy + qz * qz + qw * qw};
+        const double f0 = gen[0] * C.inv_mass, f1 = gen[1] * C.inv_mass, f2 = gen[2] * C.inv_mass;
+        double G[9], H[3], W[9];
+        for (int r = 0; r < 3; ++r) {      // G = -dt M [f]x
+            G[3 * r] = -dt * (M[3 * r + 1] * f2 - M[3 * r + 2] * f1);
+            G[3 * r + 1] = -dt * (M[3 * r + 2] * f0 - M[3 * r] * f2);
+            G[3 * r + 2] = -dt * (M[3 * r] * f1 - M[3 * r + 1] * f0);
+        }
+        H[0] = dt * w0; H[1] = dt * w1; H[2] = dt * w2;      // block (2, 2) is I - [H]x
+        double Jw[3], S[9];
+        for (int i = 0; i < 3; ++i) Jw[i] = C.J[3 * i] * w0 + C.J[3 * i + 1] * w1 + C.J[3 * i + 2] * w2;
+        for (int c = 0; c < 3; ++c) {      // S = [J w]x - [w]x J, column c
+            S[c] = -(-w2 * C.J[3 + c] + w1 * C.J[6 + c]);
+            S[3 + c] = -(w2 * C.J[c] - w0 * C.J[6 + c]);
+            S[6 + c] = -(-w1 * C.J[c] + w0 * C.J[3 + c]);
+        }
+        S[1] += -Jw[2]; S[2] += Jw[1];
+        S[3] += Jw[2]; S[5] += -Jw[0];
+        S[6] += -Jw[1]; S[7] += Jw[0];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                W[3 * r + c] = (r == c ? 1.0 : 0.0) + dt * (C.Jinv[3 * r] * S[c] + C.Jinv[3 * r + 1] * S[3 + c] + C.Jinv[3 * r + 2] * S[6 + c]);
+        cov_block<0, 0>(P, G, H, W, dt);
+        cov_block<0, 1>(P, G, H, W, dt);
+        cov_block<0, 2>(P, G, H, W, dt);
+        cov_block<0, 3>(P, G, H, W, dt);
+        cov_block<1, 1>(P, G, H, W, dt);
+        cov_block<1, 2>(P, G, H, W, dt);
+        cov_block<1, 3>(P, G, H, W, dt);
+        cov_block<2, 2>(P, G, H, W, dt);
+        cov_block<2, 3>(P, G, H, W, dt);
+        cov_block<3, 3>(P, G, H, W, dt);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) P[tri(i, i)] += F.qsq[i / 3];
+    }
+#pragma unroll
+    for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+    for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];     // read again: not held across the covariance
+    filter_rk4(C, x, gen);
+    for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+}
+template __global__ void ftmpc_filter_kernel<0>(const DeviceConsts, const FilterParams);
+template __global__ void ftmpc_filter_kernel<1>(const DeviceConsts, const FilterParams);
+
 }  // namespace ftmpc

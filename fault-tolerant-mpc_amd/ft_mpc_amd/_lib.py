@@ -26,7 +26,7 @@ KERNEL_AUTO, KERNEL_DENSE, KERNEL_WORKGROUP, KERNEL_RICCATI = 0, 1, 2, 3
 # every symbol include/ftmpc.h declares (tests check the list against the header)
 SYMBOLS = (
     "ftmpc_default_config", "ftmpc_create", "ftmpc_destroy", "ftmpc_last_error", "ftmpc_reserve",
-    "ftmpc_solve_batch", "ftmpc_solve_batch_device", "ftmpc_solve_sqp_batch", "ftmpc_sqp_graph_launches", "ftmpc_solve_wrench_batch", "ftmpc_eval_cost_batch", "ftmpc_simulate_batch", "ftmpc_simulate_batch_ex", "ftmpc_simulate_wrench_batch", "ftmpc_simulate_wrench_batch_ex", "ftmpc_simulate_faults_batch", "ftmpc_simulate_wrench_faults_batch", "ftmpc_simulate_outcomes_batch", "ftmpc_simulate_wrench_outcomes_batch", "ftmpc_simulate_plant_batch", "ftmpc_simulate_wrench_plant_batch", "ftmpc_simulate_mission_batch", "ftmpc_simulate_wrench_mission_batch", "ftmpc_simulate_actuator_batch", "ftmpc_simulate_wrench_actuator_batch", "ftmpc_simulate_sensor_batch", "ftmpc_simulate_wrench_sensor_batch", "ftmpc_eval_cost_wrench_batch", "ftmpc_solve_sqp_wrench_batch", "ftmpc_last_handed_over", "ftmpc_allocate_batch", "ftmpc_shift_warm", "ftmpc_set_profiling",
+    "ftmpc_solve_batch", "ftmpc_solve_batch_device", "ftmpc_solve_sqp_batch", "ftmpc_sqp_graph_launches", "ftmpc_solve_wrench_batch", "ftmpc_eval_cost_batch", "ftmpc_simulate_batch", "ftmpc_simulate_batch_ex", "ftmpc_simulate_wrench_batch", "ftmpc_simulate_wrench_batch_ex", "ftmpc_simulate_faults_batch", "ftmpc_simulate_wrench_faults_batch", "ftmpc_simulate_outcomes_batch", "ftmpc_simulate_wrench_outcomes_batch", "ftmpc_simulate_plant_batch", "ftmpc_simulate_wrench_plant_batch", "ftmpc_simulate_mission_batch", "ftmpc_simulate_wrench_mission_batch", "ftmpc_simulate_actuator_batch", "ftmpc_simulate_wrench_actuator_batch", "ftmpc_simulate_sensor_batch", "ftmpc_simulate_wrench_sensor_batch", "ftmpc_simulate_estimator_batch", "ftmpc_simulate_wrench_estimator_batch", "ftmpc_eval_cost_wrench_batch", "ftmpc_solve_sqp_wrench_batch", "ftmpc_last_handed_over", "ftmpc_allocate_batch", "ftmpc_shift_warm", "ftmpc_set_profiling",
     "ftmpc_last_kernel_ms", "ftmpc_kernel_name", "ftmpc_routed_kernel_name", "ftmpc_multi_routed_kernel_name", "ftmpc_debug_build_qp", "ftmpc_debug_records", "ftmpc_version", "ftmpc_build_id",
     "ftmpc_multi_create", "ftmpc_multi_destroy", "ftmpc_multi_last_error", "ftmpc_multi_device_count", "ftmpc_multi_worker_cpus",
     "ftmpc_multi_shard_bounds", "ftmpc_multi_solve_batch", "ftmpc_multi_upload", "ftmpc_multi_step",
@@ -36,6 +36,7 @@ SYMBOLS = (
     "ftmpc_multi_simulate_mission_batch", "ftmpc_multi_simulate_wrench_mission_batch",
     "ftmpc_multi_simulate_actuator_batch", "ftmpc_multi_simulate_wrench_actuator_batch",
     "ftmpc_multi_simulate_sensor_batch", "ftmpc_multi_simulate_wrench_sensor_batch",
+    "ftmpc_multi_simulate_estimator_batch", "ftmpc_multi_simulate_wrench_estimator_batch",
 )
 
 
@@ -118,6 +119,14 @@ class ftmpc_sensor(C.Structure):
     ]
 
 
+class ftmpc_estimator(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("every", C.c_int32), ("p0", C.c_double * 4), ("proc_sigma", C.c_double * 4),
+        ("meas_sigma", C.c_double * 4), ("xhat", C.POINTER(C.c_double)), ("cov", C.POINTER(C.c_double)),
+        ("est_hist", C.POINTER(C.c_double)), ("err_sq", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -194,6 +203,11 @@ def load_library() -> C.CDLL:
     lib.ftmpc_simulate_wrench_sensor_batch.argtypes = lib.ftmpc_simulate_wrench_actuator_batch.argtypes + [sep]
     lib.ftmpc_multi_simulate_sensor_batch.argtypes = lib.ftmpc_simulate_sensor_batch.argtypes
     lib.ftmpc_multi_simulate_wrench_sensor_batch.argtypes = lib.ftmpc_simulate_wrench_sensor_batch.argtypes
+    esp = C.POINTER(ftmpc_estimator)
+    lib.ftmpc_simulate_estimator_batch.argtypes = lib.ftmpc_simulate_sensor_batch.argtypes + [esp]
+    lib.ftmpc_simulate_wrench_estimator_batch.argtypes = lib.ftmpc_simulate_wrench_sensor_batch.argtypes + [esp]
+    lib.ftmpc_multi_simulate_estimator_batch.argtypes = lib.ftmpc_simulate_estimator_batch.argtypes
+    lib.ftmpc_multi_simulate_wrench_estimator_batch.argtypes = lib.ftmpc_simulate_wrench_estimator_batch.argtypes
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
                                                  dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, ip]

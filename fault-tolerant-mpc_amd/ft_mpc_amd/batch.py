@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None, actuator=None, sensor=None):
+                 plant=None, mission=None, actuator=None, sensor=None, estimator=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -489,11 +489,19 @@ class BatchedMPC:
         needs offset + T + N + d <= C), pending=None ([B,d,NT] commands applied in the first d steps; default zeros) and fields=(...)
         among meas [T,B,13], pred [T,B,13] and pending [B,d,NT] (the commands not yet applied at the end); they come back as
         out["sensor"].  x, x_hist and the outcomes are the truth; u is the command the plant applied in each step.
+        estimator: a navigation filter between the sensor and the solve (include/ftmpc.h, ftmpc_estimator; ft_mpc_amd.estimators
+        restates it in NumPy), an error-state extended Kalman filter per vehicle: a dict with every=1 (the measurement update runs on
+        the campaign steps c = step0 + t with c % every == 0), p0=(4,), proc_sigma=(4,), meas_sigma=(4,) (standard deviations by
+        group: position, velocity, attitude, rate), xhat=None ([B,13]) and cov=None ([B,78] packed or [B,12,12]; needs xhat), the
+        priors of the call's first step (default: the first measurement and diag(p0^2)), and fields=(...) among est [T,B,13] (the
+        estimate each solve started from, before the sensor's prediction), err_sq [B,4] (summed squared errors against the truth by
+        group), xhat [B,13] and cov [B,78] (the priors of step T, to hand to a continued run); they come back as out["estimator"].
+        With a predicting sensor the field pred of the sensor holds the estimate propagated over the queue.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor])."""
+        [, status_hist][, actuator][, sensor][, estimator])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor)
+                         plant, mission, actuator, sensor, estimator)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -775,9 +783,44 @@ def _sensor_request(sensor, B, T, NT):
     return se, keep, out, (r["latency"] if r["predict"] else 0)
 
 
+def _estimator_request(estimator, B, T):
+    """The ftmpc_estimator struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .estimators import NP, request
+    r = request(estimator, B, T)
+    es = _lib.ftmpc_estimator(struct_size=C.sizeof(_lib.ftmpc_estimator), every=r["every"])
+    for k in range(4):
+        es.p0[k], es.proc_sigma[k], es.meas_sigma[k] = float(r["p0"][k]), float(r["proc_sigma"][k]), float(r["meas_sigma"][k])
+    keep, out = [], {}
+    # xhat / cov are in/out: asked back without being handed over, they start as the library's defaults would (the first measurement
+    # cannot be staged here, so xhat then comes back through a buffer the call fills from its first step on)
+    if r["xhat"] is not None:
+        keep.append(r["xhat"])
+        es.xhat = _ptr(r["xhat"])
+        if "xhat" in r["fields"]:
+            out["xhat"] = r["xhat"]
+        cov = r["cov"]
+        if cov is None and "cov" in r["fields"]:
+            cov = np.zeros((B, NP))
+            cov[:, np.cumsum([0] + [12 - i for i in range(11)])] = np.repeat(r["p0"] ** 2, 3)[None, :]
+        if cov is not None:
+            keep.append(cov)
+            es.cov = _ptr(cov)
+            if "cov" in r["fields"]:
+                out["cov"] = cov
+    elif "xhat" in r["fields"] or "cov" in r["fields"]:
+        raise ValueError("estimator: the fields xhat and cov need estimator['xhat'] (e.g. the first measurement) to be handed in")
+    if "est" in r["fields"]:
+        out["est"] = np.zeros((T, B, 13))
+        es.est_hist = _ptr(out["est"])
+    if "err_sq" in r["fields"]:
+        out["err_sq"] = np.zeros((B, 4))
+        es.err_sq = _ptr(out["err_sq"])
+    return es, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None):
+              actuator=None, sensor=None, estimator=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -798,6 +841,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     if mission is not None or want_cost:
         ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
     se, skeep, sout, L = _sensor_request(sensor, B, T, NT) if sensor is not None else (None, None, None, 0)
+    es, ekeep, eout = _estimator_request(estimator, B, T) if estimator is not None else (None, None, None)
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -844,7 +888,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
-           or pm is not None or ms is not None or ac is not None or se is not None)
+           or pm is not None or ms is not None or ac is not None or se is not None or es is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -863,6 +907,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["actuator"] = aout
         if sout is not None:
             out["sensor"] = sout
+        if eout is not None:
+            out["estimator"] = eout
         return out
     msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
@@ -876,6 +922,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if es is not None:
+            self._check(getattr(self.lib, pre + "wrench_estimator_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None, C.byref(es)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if se is not None:
             self._check(getattr(self.lib, pre + "wrench_sensor_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -927,6 +980,12 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if es is not None:
+        self._check(getattr(self.lib, pre + "estimator_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
+            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None, C.byref(es)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if se is not None:
         self._check(getattr(self.lib, pre + "sensor_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

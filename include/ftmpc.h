@@ -753,6 +753,73 @@ int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                        const ftmpc_actuator* actuator, const ftmpc_sensor* sensor);
 
+/* A navigation filter between the sensor and the controller in the on-device closed loops: a multiplicative (error-state) extended
+ * Kalman filter per vehicle (ftmpc_filter_kernel).  With it the solve of step t no longer reads the raw sample y_t but the filter's
+ * estimate, and the measurement may come at a lower rate than the control.  The parameters are uniform over the call; xhat, cov
+ * and the outputs are per vehicle.
+ *   state: the mean x^ [13] in the layout of x, and the covariance P (12 x 12, symmetric) over the error coordinates
+ *     delta = (dp, dv, dtheta, dw) of the retraction  x [+] delta = (p + dp, v + dv, rotate(q, dtheta), w + dw),  rotate the closed
+ *     form of the sensor's attitude error (body-frame rotation vector, renormalised).  P travels packed: 78 doubles, the upper
+ *     triangle row-major.
+ *   residual y [-] x^ (12): differences for position, velocity and rate; for the attitude the theta with rotate(q^, theta) = y_q:
+ *     c = q^ . y_q, s = Xi(q^)' y_q with Omega(theta) q = Xi(q) theta; c < 0 flips y_q; theta = 2 atan2(|s|, c) / |s| s, and
+ *     theta = 2 s below |s| = 1e-8.
+ *   measurement update (H = I, R = diag(meas_sigma[g]^2) by group): twelve sequential scalar updates in channel order j = 0..11 on
+ *     d = 0:  sj = P_jj + R_j,  k = P[:, j] / sj,  d += k (r_j - d_j),  P -= sj k k';  then x^ <- x^ [+] d.  The covariance is not
+ *     reset.  Exact for a diagonal R, no inverse; only the packed triangle is updated, so P stays symmetric by construction.
+ *   time update with a_t, the command the plant applies in step t, under the controller's pattern of step t and the config's mass,
+ *     J and D (the model of the sensor's prediction):  gen = D ((ub_c > 0 ? a_t : 0) + stuck_c),  Phi = I + dt A(x^_{t|t}, gen),
+ *     P <- Phi P Phi' + diag(proc_sigma[g]^2),  then x^ <- one RK4 step of the model, renormalised.  A is the Jacobian of the error
+ *     dynamics under the retraction; its non-zero blocks are (p, v) = I, (theta, w) = I, (v, theta) = -M [F/m]x with M(q) the
+ *     body-to-inertial matrix of the model, (theta, theta) = -[w]x and (w, w) = J^-1 ([J w]x - [w]x J).
+ *   per loop step t (campaign step c = step0 + t; step0 is the sensor's, 0 without one):
+ *     1. ftmpc_sense_kernel forms y_t (without its prediction);
+ *     2. on the first step of a call that was not handed xhat: x^ = y_t, P = diag(p0[g]^2), no update.  Otherwise the update runs
+ *        when c % every == 0; when it does not, nothing is drawn from y_t.  est_hist[t] = x^_{t|t}; err_sq accumulates; when the
+ *        sensor predicts, x^_{t|t} is propagated over the d queued commands exactly as the sensor propagates y_t (that is what
+ *        pred_hist then holds); the result is the x0 of the solve;
+ *     3. solve, command queue and plant step as without the filter;
+ *     4. the time update.
+ *   A handed-over xhat / cov are the priors x^_{t|t-1}, P_{t|t-1} of the call's first step (cov NULL: diag(p0[g]^2)); on return they
+ *   hold the priors of step T, so that a continued run (with the sensor's pending and step0) is the whole run bit for bit.
+ * estimator = NULL launches exactly the kernels of the _sensor_ entries and returns their bits.  A non-NULL estimator with a trivial
+ * or NULL sensor still keeps the truth in a buffer of the call (and the handle's warm start for a continued run): then y_t = x_t and
+ * nothing is drawn.  The filter is told neither the plant's dispersion nor the actuator.
+ * FTMPC_ERR_ARG, the message naming ftmpc_estimator.<field> and, for an array, the first offending vehicle, the call's x untouched:
+ * a struct_size other than sizeof(ftmpc_estimator); every < 1; a p0 or proc_sigma negative or not finite; a meas_sigma not finite
+ * and > 0; cov without xhat; an xhat or cov entry not finite; a diagonal entry of cov below zero.
+ */
+typedef struct ftmpc_estimator {
+    int32_t struct_size;      /* sizeof(ftmpc_estimator) */
+    int32_t every;            /* >= 1: the update runs on campaign steps c with c % every == 0 */
+    double p0[4];             /* initial standard deviations: position (m), velocity (m/s), attitude (rad), rate (rad/s) */
+    double proc_sigma[4];     /* process noise standard deviations per step, by group */
+    double meas_sigma[4];     /* measurement noise standard deviations by group, > 0 */
+    double* xhat;             /* NULL or [B*13], in/out: the prior mean */
+    double* cov;              /* NULL or [B*78], in/out: the prior covariance, packed; requires xhat */
+    double* est_hist;         /* NULL or [T*B*13], output: x^_{t|t} */
+    double* err_sq;           /* NULL or [B*4], output: per vehicle the sums over the call's steps, against the truth, of
+                                 |p^ - p|^2, |v^ - v|^2, |x_t [-] x^|_theta^2, |w^ - w|^2 */
+} ftmpc_estimator;
+
+/* ftmpc_simulate_sensor_batch with the filter `estimator` (NULL: exactly ftmpc_simulate_sensor_batch). */
+int ftmpc_simulate_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator);
+
+/* ftmpc_simulate_wrench_sensor_batch with the filter `estimator` (NULL: exactly ftmpc_simulate_wrench_sensor_batch). */
+int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -920,6 +987,25 @@ int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t 
                                              int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                              const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                              const ftmpc_actuator* actuator, const ftmpc_sensor* sensor);
+/* The two entries above with the filter `estimator` (ftmpc_estimator; NULL: exactly the entries above).  The struct is checked once
+ * over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; xhat + 13 lo, cov + 78 lo and
+ * err_sq + 4 lo are read and written per shard, est_hist is copied row by row from the shard's staging as meas_hist is.
+ * ftmpc_multi_upload / _step take no estimator. */
+int ftmpc_multi_simulate_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                         const ftmpc_sensor* sensor, const ftmpc_estimator* estimator);
+int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                const ftmpc_estimator* estimator);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

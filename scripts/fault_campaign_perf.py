@@ -11,6 +11,7 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --trace kernel_trace.csv   # per-launch times of the mission kernels and of the linearise kernel
     python scripts/fault_campaign_perf.py --actuator        # also the loops with PWM thrusters (S = 16, min_on 1) and valve lag in the plant
     python scripts/fault_campaign_perf.py --sensor [--latency 0 2 8] [--predict]   # also the loops with navigation errors and latency
+    python scripts/fault_campaign_perf.py --sensor --estimator [--every M]   # and each of those once more with the navigation filter
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -38,7 +39,11 @@ kernel's share of the kernel time.
 0.01 rad, 0.005 rad/s), a bias per vehicle from ft_mpc_amd.sensors.sample_bias, no history returned, once per --latency value (default
 2) and, with --predict, once more with the delay-compensating prediction (ftmpc_sense_kernel before every solve, the plant fed from
 the command ring).  With --once it makes one call with the sensor (the first --latency, --predict as given) and one without, so that
-a kernel_stats.csv of that run holds the sense kernel next to the plant kernel, and --stats reports the time per launch of each."""
+a kernel_stats.csv of that run holds the sense kernel next to the plant kernel, and --stats reports the time per launch of each.
+--estimator (with --sensor): every sensor loop once more under BatchedMPC.simulate(estimator=...): p0 = meas_sigma = the sensor's
+sigma, proc_sigma a tenth of it, the update on every --every-th step (default 1), err_sq returned (ftmpc_filter_kernel<0> before
+every solve and <1> after every plant step).  With --once the call with the sensor also carries the filter, and --stats reports the
+time per launch of either phase and the filter's share of the kernel time."""
 import argparse
 import csv
 import json
@@ -99,11 +104,12 @@ def mission(B, N, mass):
 ACTUATOR = dict(mode="pwm", min_on=1, align="centred", tau_on=0.02, tau_off=0.01, fields=("delivered", "pulses"))
 SENSOR = dict(sigma=(1e-2, 5e-3, 1e-2, 5e-3), seed=29)
 SENSOR_BIAS = (0.05, 0.01, 0.02, 0.005)
+ESTIMATOR = dict(p0=SENSOR["sigma"], proc_sigma=tuple(0.1 * s for s in SENSOR["sigma"]), meas_sigma=SENSOR["sigma"], fields=("err_sq",))
 DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
 
 
 def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False, actuator=False, substeps=16, sensor=False,
-        latencies=(2,), predict=False):
+        latencies=(2,), predict=False, estimator=False, every=1):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -140,10 +146,11 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
                 xs = np.zeros((9, T + c["N"] + (d if pr else 0)))
                 xs[8] = 0.6
                 sensors.append((f"sensor_d{d}" + ("_predict" if pr else ""), dict(SENSOR, bias=bias, latency=d, predict=pr), xs))
+    est = dict(ESTIMATOR, every=every) if estimator and sensor else None
     if once:
         if sensor:
             label, sen, xs = sensors[-1] if predict else sensors[0]
-            mpc.simulate(x0, ub, stuck, xs, T, sensor=sen, **(witho if outcomes else withf), **kw)
+            mpc.simulate(x0, ub, stuck, xs, T, sensor=sen, estimator=est, **(witho if outcomes else withf), **kw)
         if actuator:
             mpc.simulate(x0, ub, stuck, xr, T, actuator=act, **(witho if outcomes else withf), **kw)
         if with_mission:
@@ -177,6 +184,10 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
     for label, sen, xs in sensors:
         runs += [("without_" + label, dict(plain, sensor=sen), ub, stuck), ("with_" + label, dict(withf, sensor=sen), ub, stuck)]
         refs["without_" + label] = refs["with_" + label] = xs
+        if est is not None:
+            runs += [("without_" + label + "_estimator", dict(plain, sensor=sen, estimator=est), ub, stuck),
+                     ("with_" + label + "_estimator", dict(withf, sensor=sen, estimator=est), ub, stuck)]
+            refs["without_" + label + "_estimator"] = refs["with_" + label + "_estimator"] = xs
     for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
         ref = None if "mission" in extra else refs.get(label, xr)      # a mission's tables are the reference
@@ -189,6 +200,8 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
         ms = float(np.median(ts)) * 1e3
         res[label] = dict(ms=ms, steps_per_s=B * T / (ms * 1e-3), not_converged=int(out["not_converged"].sum()),
                           alloc_failed=int(out.get("alloc_failed", np.zeros(1)).sum()))
+        if "estimator" in out:     # root mean squared position error of the estimates over the call
+            res[label]["est_rms_pos_m"] = float(np.sqrt(out["estimator"]["err_sq"][:, 0].mean() / T))
         if "actuator" in out:      # what the valves delivered and how often they opened, per vehicle and step
             res[label].update(delivered_mean_Ns=float(out["actuator"]["delivered"].mean()),
                               pulses_per_step=float(out["actuator"]["pulses"].mean()) / T)
@@ -205,6 +218,11 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
     for label, _, _ in sensors:
         res[f"ratio_{label}_over_without"] = res["without_" + label]["steps_per_s"] / res["without"]["steps_per_s"]
         res[f"ratio_{label}_over_with"] = res["with_" + label]["steps_per_s"] / res["with"]["steps_per_s"]
+        if est is not None:      # the same loop with the filter against without
+            for w in ("without_", "with_"):
+                res[f"ratio_{label}_estimator_over_{w}{label}"] = res[w + label + "_estimator"]["steps_per_s"] / res[w + label]["steps_per_s"]
+                res[f"ms_per_step_estimator_{w}{label}"] = (res[w + label + "_estimator"]["ms"] - res[w + label]["ms"]) / T
+            res["every"] = every
     if actuator:
         res["ratio_actuator_over_without"] = res["without_actuator"]["steps_per_s"] / res["without"]["steps_per_s"]
         res["ratio_actuator_over_with"] = res["with_actuator"]["steps_per_s"] / res["with"]["steps_per_s"]
@@ -238,7 +256,11 @@ def stats(path):
     vn, vus = per_launch("ftmpc_plant_step_var_kernel")
     an, aus = per_launch("ftmpc_plant_step_act_kernel")
     sn, sus = per_launch("ftmpc_sense_kernel")
-    return dict(sense_kernel_calls=sn, sense_kernel_avg_us=sus, sense_kernel_share=sn * sus * 1e3 / tot if tot else 0.0,
+    f0n, f0us = per_launch("ftmpc_filter_kernel<0>")
+    f1n, f1us = per_launch("ftmpc_filter_kernel<1>")
+    return dict(filter_update_kernel_calls=f0n, filter_update_kernel_avg_us=f0us, filter_time_kernel_calls=f1n, filter_time_kernel_avg_us=f1us,
+                filter_kernel_share=(f0n * f0us + f1n * f1us) * 1e3 / tot if tot else 0.0,
+                sense_kernel_calls=sn, sense_kernel_avg_us=sus, sense_kernel_share=sn * sus * 1e3 / tot if tot else 0.0,
                 plant_act_kernel_calls=an, plant_act_kernel_avg_us=aus, plant_act_kernel_share=an * aus * 1e3 / tot if tot else 0.0,
                 plant_kernel_calls=pn, plant_kernel_avg_us=pus, plant_var_kernel_calls=vn, plant_var_kernel_avg_us=vus,
                 total_kernel_ms=tot * 1e-6, event_kernel_ms=evt * 1e-6, event_kernel_calls=calls,
@@ -281,6 +303,8 @@ def main():
     ap.add_argument("--sensor", action="store_true")
     ap.add_argument("--latency", type=int, nargs="+", default=[2])
     ap.add_argument("--predict", action="store_true")
+    ap.add_argument("--estimator", action="store_true")
+    ap.add_argument("--every", type=int, default=1)
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -291,7 +315,8 @@ def main():
     names = list(CASES) if a.case == "all" else [a.case]
     out = []
     for n in names:
-        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps, a.sensor, tuple(a.latency), a.predict)
+        r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps, a.sensor, tuple(a.latency), a.predict,
+                a.estimator, a.every)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
