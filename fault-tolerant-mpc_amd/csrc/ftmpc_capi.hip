@@ -1993,7 +1993,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
                          const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr,
-                         const ftmpc_estimator* es = nullptr);
+                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -2219,6 +2219,73 @@ static int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es
     return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
 }
 
+// A diagnosis' layout and values (include/ftmpc.h, ftmpc_diagnosis) over the vehicles [0, B), against the estimator, the schedule and
+// the sensor of the same call: empty when acceptable, else the message, which names the field and, for an array, the first offending
+// vehicle (first: number of vehicle 0 in the caller's batch)
+static std::string diagnosis_problem(const ftmpc_diagnosis* dg, int64_t B, int NT, const ftmpc_estimator* es, const ftmpc_fault_schedule* fs,
+                                     const ftmpc_sensor* se, int64_t first = 0) {
+    if (!dg) return "";
+    if (dg->struct_size != (int32_t)sizeof(ftmpc_diagnosis))
+        return "ftmpc_diagnosis.struct_size is " + std::to_string(dg->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_diagnosis));
+    if (dg->every < 1) return "ftmpc_diagnosis.every is " + std::to_string(dg->every) + ", below 1";
+    if (es && es->every != dg->every)
+        return "ftmpc_diagnosis.every is " + std::to_string(dg->every) + ", the estimator's every is " + std::to_string(es->every);
+    if (dg->n_levels < 1 || dg->n_levels > 4) return "ftmpc_diagnosis.n_levels is " + std::to_string(dg->n_levels) + ", outside [1, 4]";
+    if (dg->max_detect < 1 || dg->max_detect > FTMPC_MAX_FAULT_EVENTS)
+        return "ftmpc_diagnosis.max_detect is " + std::to_string(dg->max_detect) + ", outside [1, FTMPC_MAX_FAULT_EVENTS]";
+    for (int l = 0; l < dg->n_levels; ++l)
+        if (!std::isfinite(dg->levels[l]) || dg->levels[l] < 0 || (l > 0 && !(dg->levels[l] > dg->levels[l - 1])))
+            return "ftmpc_diagnosis.levels[" + std::to_string(l) + "] is negative, not finite or not above the level before";
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(dg->resid_sigma[k]) || !(dg->resid_sigma[k] > 0))
+            return "ftmpc_diagnosis.resid_sigma[" + std::to_string(k) + "] is not finite and > 0";
+        if (!std::isfinite(dg->drift_sigma[k]) || dg->drift_sigma[k] < 0)
+            return "ftmpc_diagnosis.drift_sigma[" + std::to_string(k) + "] is negative or not finite";
+    }
+    if (!std::isfinite(dg->threshold) || !(dg->threshold > 0)) return "ftmpc_diagnosis.threshold is not finite and > 0";
+    if (dg->llr && !dg->state) return "ftmpc_diagnosis.llr is given without state";
+    if (!dg->state && dg->detect_step) return "ftmpc_diagnosis.detect_step is given without state";
+    if (!dg->state && dg->detect_thruster) return "ftmpc_diagnosis.detect_thruster is given without state";
+    if (!dg->state && dg->detect_level) return "ftmpc_diagnosis.detect_level is given without state";
+    if (dg->state) {
+        if (!dg->detect_step) return "ftmpc_diagnosis.detect_step is required with state";
+        if (!dg->detect_thruster) return "ftmpc_diagnosis.detect_thruster is required with state";
+        if (!dg->detect_level) return "ftmpc_diagnosis.detect_level is required with state";
+        const int64_t w = 14 + NT, H = (int64_t)NT * dg->n_levels, K = dg->max_detect;
+        for (int64_t b = 0; b < B; ++b) {
+            const double* st = dg->state + b * w;
+            for (int64_t k = 0; k < w; ++k)
+                if (!std::isfinite(st[k]))
+                    return "ftmpc_diagnosis.state: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
+            if (st[13] < 0) return "ftmpc_diagnosis.state: vehicle " + std::to_string(first + b) + " has n < 0";
+            if (dg->llr)
+                for (int64_t k = 0; k < H; ++k)
+                    if (!std::isfinite(dg->llr[b * H + k]))
+                        return "ftmpc_diagnosis.llr: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
+            bool unused = false;
+            for (int64_t k = 0; k < K; ++k) {
+                const int32_t ds = dg->detect_step[b * K + k], dt = dg->detect_thruster[b * K + k], dl = dg->detect_level[b * K + k];
+                if (ds == -1) {
+                    unused = true;
+                    continue;
+                }
+                if (ds < -1) return "ftmpc_diagnosis.detect_step: vehicle " + std::to_string(first + b) + " has an entry below -1";
+                if (unused) return "ftmpc_diagnosis.detect_step: vehicle " + std::to_string(first + b) + " has a used slot after an unused one";
+                if (dt < 0 || dt >= NT)
+                    return "ftmpc_diagnosis.detect_thruster: vehicle " + std::to_string(first + b) + " has an entry outside [0, NT)";
+                if (dl < 0 || dl >= dg->n_levels)
+                    return "ftmpc_diagnosis.detect_level: vehicle " + std::to_string(first + b) + " has an entry outside [0, n_levels)";
+            }
+        }
+    }
+    if (fs && fs->n_events > 0 && fs->detect)
+        return "ftmpc_diagnosis: ftmpc_fault_schedule.detect must be NULL (the schedule moves the plant only, the diagnosis detects)";
+    if (se && se->predict == 1 && !es)
+        return "ftmpc_diagnosis: ftmpc_sensor.predict = 1 needs an estimator (the sense kernel would predict with the pattern before the diagnosis)";
+    return "";
+}
+
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
 static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
     if (!oc) return FTMPC_OK;
@@ -2348,6 +2415,16 @@ int ftmpc_simulate_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double
                                    double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                    const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                    const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
+    return ftmpc_simulate_diagnosis_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                          x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, nullptr);
+}
+
+int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2359,16 +2436,22 @@ int ftmpc_simulate_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double
     if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
+    {
+        const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
         if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
+        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * h->cfg.NT, diagnosis->ub);
+        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * h->cfg.NT, diagnosis->stuck);
         return FTMPC_OK;
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator, sensor, estimator);
+                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2518,7 +2601,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
                          const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
-                         const ftmpc_sensor* se, const ftmpc_estimator* es) {
+                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2526,12 +2609,15 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     // step (phase 1).  It takes the truth-buffer path of a sensor even when the sensor is trivial or NULL (se0: latency 0, step0 0,
     // nothing drawn); the sense kernel then does not run and y_t is the truth
     const bool est = es != nullptr;
+    // diagnosis (checked by the entry; thruster form only): ftmpc_diagnose_kernel runs before the filter's phase 0 (phase 0) and after
+    // the plant step (phase 1); it takes the same truth-buffer path
+    const bool diag = dg != nullptr;
     const bool sensing = !sensor_trivial(se);      // ftmpc_sense_kernel runs
     ftmpc_sensor se0{};
-    if (est && !se) se = &se0;
+    if ((est || diag) && !se) se = &se0;
     // sensor (checked by the entry): not trivial, the truth lives in d_xtrue and ftmpc_sense_kernel writes h->d_x0 before every solve;
     // lat commands wait in the ring d_ring ([lat + 1][B][NT]); a predicting sensor shifts every reference window by L = lat columns
-    const bool sense = sensing || est;
+    const bool sense = sensing || est || diag;
     const int lat = sense ? se->latency : 0, L = sense && se->predict ? lat : 0;
     const int64_t ncol = (int64_t)T + N + L;   // windows t .. t+N for t < T (t+L .. t+L+N under a predicting sensor)
     // (this call's own buffers: freed on every way out)
@@ -2782,6 +2868,86 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         fp.pred_hist = d_phist;
         fp.err_sq = d_esq;
     }
+    // the diagnosis' state: xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (the caller's are vehicle-major;
+    // the statistics are filled on the device when none are handed over), the detect arrays [B][K] with the count per vehicle, the
+    // flag the repair kernel reads
+    DevBuf<double> d_dxt, d_dacc, d_dllr, d_dhist;
+    DevBuf<int32_t> d_ddet;      // [count B | switched B | step BK | thruster BK | level BK]
+    std::vector<double> h_dxt, h_dacc, h_dllr;
+    std::vector<int32_t> h_ddet;
+    ftmpc::DiagParams dp{};
+    const int dL = diag ? dg->n_levels : 0, dK = diag ? dg->max_detect : 0;
+    const int64_t dH = (int64_t)NT * dL;
+    if (diag) {
+        const size_t nd = (size_t)B * (2 + 3 * (size_t)dK);
+        try {
+            h_dxt.assign((size_t)B * 14, 0.0);
+            h_dacc.assign((size_t)B * NT, 0.0);
+            if (dg->state && dg->llr) h_dllr.assign((size_t)(B * dH), 0.0);
+            h_ddet.assign(nd, -1);
+        } catch (const std::bad_alloc&) {
+            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the diagnosis' staging arrays");
+        }
+        std::fill(h_ddet.begin(), h_ddet.begin() + 2 * B, 0);
+        HIP_TRY(h, hipMalloc(&d_dxt.p, (size_t)B * 14 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_dacc.p, (size_t)B * NT * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_dllr.p, (size_t)(B * dH) * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_ddet.p, nd * sizeof(int32_t)));
+        if (dg->state) {
+            const int64_t w = 14 + NT;
+            for (int64_t b = 0; b < B; ++b) {
+                for (int k = 0; k < 14; ++k) h_dxt[(size_t)b * 14 + k] = dg->state[b * w + k];
+                for (int i = 0; i < NT; ++i) h_dacc[(size_t)i * B + b] = dg->state[b * w + 14 + i];
+                int32_t cnt = 0;
+                for (int k = 0; k < dK; ++k) {
+                    const int32_t ds = dg->detect_step[b * dK + k];
+                    h_ddet[(size_t)(2 * B + b * dK + k)] = ds;
+                    h_ddet[(size_t)(2 * B + (B + b) * dK + k)] = ds < 0 ? -1 : dg->detect_thruster[b * dK + k];
+                    h_ddet[(size_t)(2 * B + (2 * B + b) * dK + k)] = ds < 0 ? -1 : dg->detect_level[b * dK + k];
+                    cnt += ds >= 0;
+                }
+                h_ddet[(size_t)b] = cnt;
+            }
+            HIP_TRY(h, hipMemcpyAsync(d_dxt, h_dxt.data(), h_dxt.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(d_dacc, h_dacc.data(), h_dacc.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        } else {      // (the first step's phase 0 initialises both)
+            HIP_TRY(h, hipMemsetAsync(d_dxt, 0, (size_t)B * 14 * sizeof(double), s));
+            HIP_TRY(h, hipMemsetAsync(d_dacc, 0, (size_t)B * NT * sizeof(double), s));
+        }
+        if (dg->state && dg->llr) {
+            for (int64_t b0 = 0; b0 < B; b0 += 64) {
+                const int64_t b1 = std::min(B, b0 + 64);
+                for (int64_t k = 0; k < dH; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_dllr[(size_t)(k * B + b)] = dg->llr[b * dH + k];
+            }
+            HIP_TRY(h, hipMemcpyAsync(d_dllr, h_dllr.data(), h_dllr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        } else {
+            HIP_TRY(h, hipMemsetAsync(d_dllr, 0, (size_t)(B * dH) * sizeof(double), s));
+        }
+        HIP_TRY(h, hipMemcpyAsync(d_ddet, h_ddet.data(), nd * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (dg->llr_hist) HIP_TRY(h, hipMalloc(&d_dhist.p, (size_t)(T * B * dH) * sizeof(double)));
+        dp.B = B;
+        dp.L = dL;
+        dp.K = dK;
+        dp.y = sensing ? h->d_x0.p : d_xtrue.p;
+        dp.xt = d_dxt;
+        dp.acc = d_dacc;
+        dp.llr = d_dllr;
+        for (int l = 0; l < dL; ++l) dp.levels[l] = dg->levels[l];
+        for (int k = 0; k < 2; ++k) {
+            dp.rsq[k] = dg->resid_sigma[k] * dg->resid_sigma[k];
+            dp.dsq[k] = dg->drift_sigma[k] * dg->drift_sigma[k];
+        }
+        dp.threshold = dg->threshold;
+        dp.ub = h->d_ub;
+        dp.stuck = h->d_stuck;
+        dp.count = d_ddet;
+        dp.switched = d_ddet + B;
+        dp.det_step = d_ddet + 2 * B;
+        dp.det_thruster = d_ddet + 2 * B + B * dK;
+        dp.det_level = d_ddet + 2 * B + 2 * B * dK;
+        dp.llr_hist = d_dhist;
+    }
     double* const d_truth = sense ? d_xtrue.p : h->d_x0.p;      // what the plant integrates and the outcomes measure
     // a continued run (step0 > 0, and the handle's last loop with a sensor ended at that step, on this batch and form, in this x):
     // its first solve is warm-started as the whole run's would be, from what the handle kept; otherwise it starts cold
@@ -2899,7 +3065,8 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         ev_step.assign((size_t)T, 0);
         for (int64_t i = 0; i < BE; ++i) {
             ev[i] = fs->onset[i];
-            ev[BE + i] = fs->detect ? fs->detect[i] : fs->onset[i];
+            // (under a diagnosis the schedule moves the plant only: no event is ever detected, and only onset steps launch the kernel)
+            ev[BE + i] = diag ? INT32_MAX : (fs->detect ? fs->detect[i] : fs->onset[i]);
             if (wl && fs->hull_set) ev[2 * BE + i] = fs->hull_set[i];
             if (ev[i] >= 0 && ev[i] < T) ev_step[ev[i]] = 1;
             if (ev[i] >= 0 && ev[BE + i] < T) ev_step[ev[BE + i]] = 1;
@@ -2938,6 +3105,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         }
         sp.ub = d_plant;
         sp.stuck = d_plant + B * NT;
+    } else if (diag) {     // the plant keeps the call's pattern whatever the diagnosis makes of the controller's
+        HIP_TRY(h, hipMalloc(&d_plant.p, (size_t)B * NT * 2 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
+        sp.ub = d_plant;
+        sp.stuck = d_plant + B * NT;
     }
     for (int t = 0; t < T; ++t) {
         if (E > 0 && ev_step[t]) {     // some instance switches its pattern at this step: before the solve
@@ -2968,6 +3141,22 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             sn.slot0 = t % (lat + 1);
             hipLaunchKernelGGL(ftmpc::ftmpc_sense_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sn);
             HIP_TRY(h, hipGetLastError());
+        }
+        if (diag) {     // test, decision and re-anchor on y_t; a vehicle that switched has its shifted warm start clipped to the new bounds
+            dp.init = t == 0 && !dg->state;
+            dp.anchor = (se->step0 + t) % dg->every == 0;
+            dp.cstep = (int32_t)(se->step0 + t);
+            dp.step = t;
+            hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
+            if (t > 0 || resume)
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_repair_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, B, N, NT,
+                                   (const int32_t*)dp.switched, (const double*)h->d_ub, d_warmB.p);
+            HIP_TRY(h, hipGetLastError());
+            // a pattern can change at any step without the host knowing: no small grid for a list that was empty the step before
+            h->qcnt_valid = false;
+            h->qcnt_pending = false;
+            if (!sensing && !est)     // nobody else writes the solve's x0: it is the truth
+                HIP_TRY(h, hipMemcpyAsync(h->d_x0, d_xtrue, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToDevice, s));
         }
         if (est) {     // the update on y_t, the estimate (propagated over the queue when the sensor predicts) into h->d_x0
             fp.init = t == 0 && !es->xhat;
@@ -3027,6 +3216,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             fp.u = sp.u0;
             hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
         }
+        if (diag) {     // the model's step under a_t and the controller's pattern of this step
+            dp.u = sp.u0;
+            hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
+        }
         if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
             op.step = t;
             op.ub = sp.ub;
@@ -3067,6 +3260,17 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (es->xhat) HIP_TRY(h, hipMemcpyAsync(es->xhat, d_xhat, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
         if (es->cov) HIP_TRY(h, hipMemcpyAsync(h_cov.data(), d_cov, (size_t)B * 78 * sizeof(double), hipMemcpyDeviceToHost, s));
     }
+    if (diag) {
+        if (dg->llr_hist) HIP_TRY(h, hipMemcpyAsync(dg->llr_hist, d_dhist, (size_t)(T * B * dH) * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (dg->ub) HIP_TRY(h, hipMemcpyAsync(dg->ub, h->d_ub, (size_t)B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (dg->stuck) HIP_TRY(h, hipMemcpyAsync(dg->stuck, h->d_stuck, (size_t)B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (dg->state) {
+            HIP_TRY(h, hipMemcpyAsync(h_dxt.data(), d_dxt, h_dxt.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipMemcpyAsync(h_dacc.data(), d_dacc, h_dacc.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipMemcpyAsync(h_ddet.data(), d_ddet, h_ddet.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (dg->llr) HIP_TRY(h, hipMemcpyAsync(h_dllr.data(), d_dllr, h_dllr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+    }
     if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -3095,6 +3299,20 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     if (act && ac->state)
         for (int64_t b = 0; b < B; ++b)
             for (int i = 0; i < NT; ++i) ac->state[b * NT + i] = h_aval[(size_t)i * B + b];
+    if (diag && dg->state) {
+        const int64_t w = 14 + NT;
+        for (int64_t b = 0; b < B; ++b) {
+            for (int k = 0; k < 14; ++k) dg->state[b * w + k] = h_dxt[(size_t)b * 14 + k];
+            for (int i = 0; i < NT; ++i) dg->state[b * w + 14 + i] = h_dacc[(size_t)i * B + b];
+            for (int k = 0; k < dK; ++k) {
+                dg->detect_step[b * dK + k] = h_ddet[(size_t)(2 * B + b * dK + k)];
+                dg->detect_thruster[b * dK + k] = h_ddet[(size_t)(2 * B + (B + b) * dK + k)];
+                dg->detect_level[b * dK + k] = h_ddet[(size_t)(2 * B + (2 * B + b) * dK + k)];
+            }
+            if (dg->llr)
+                for (int64_t k = 0; k < dH; ++k) dg->llr[b * dH + k] = h_dllr[(size_t)(k * B + b)];
+        }
+    }
     if (est && es->cov)
         for (int64_t b0 = 0; b0 < B; b0 += 64) {
             const int64_t b1 = std::min(B, b0 + 64);

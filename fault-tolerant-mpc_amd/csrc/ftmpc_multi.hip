@@ -213,7 +213,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench) {
+                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench,
+                   const ftmpc_diagnosis* diagnosis = nullptr) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -240,6 +241,13 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         const std::string msg = estimator_problem(estimator, B);
         if (!msg.empty()) return refuse(msg);
     }
+    if (diagnosis) {     // the diagnosis likewise (thruster form only): the parameters are uniform, the state and the outputs per vehicle
+        if (wrench) return refuse("ftmpc_diagnosis: the wrench form has no diagnosis");
+        if (faults && faults->n_events > 0 && (!faults->onset || !faults->ub || !faults->stuck))
+            return refuse("ftmpc_fault_schedule: null onset / ub / stuck");
+        const std::string msg = diagnosis_problem(diagnosis, B, m->cfg.NT, estimator, faults, sensor);
+        if (!msg.empty()) return refuse(msg);
+    }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
         const std::string msg = mission_problem(mission, B, T, m->cfg.N, xref_traj, uref_traj, 0, sensor_shift(sensor));
         if (!msg.empty()) return refuse(msg);
@@ -253,6 +261,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
         if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
+        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * m->cfg.NT, diagnosis->ub);
+        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * m->cfg.NT, diagnosis->stuck);
         return FTMPC_OK;
     }
     const int G = (int)m->dev.size();
@@ -320,7 +330,21 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (ev.cov) ev.cov += lo * 78;
             if (ev.err_sq) ev.err_sq += lo * 4;
         }
+        std::vector<double> lh;
+        ftmpc_diagnosis dv{};
+        if (diagnosis) {
+            dv = *diagnosis;
+            const int64_t K = dv.max_detect, H = (int64_t)NT * dv.n_levels;
+            if (dv.state) dv.state += lo * (14 + NT);
+            if (dv.llr) dv.llr += lo * H;
+            if (dv.detect_step) dv.detect_step += lo * K;
+            if (dv.detect_thruster) dv.detect_thruster += lo * K;
+            if (dv.detect_level) dv.detect_level += lo * K;
+            if (dv.ub) dv.ub += lo * NT;
+            if (dv.stuck) dv.stuck += lo * NT;
+        }
         try {
+            if (dv.llr_hist && !whole) lh.resize((size_t)T * n * NT * dv.n_levels);
             if (ev.est_hist && !whole) eh.resize((size_t)T * n * 13);
             if (sv.meas_hist && !whole) mh.resize((size_t)T * n * 13);
             if (sv.pred_hist && !whole) ph.resize((size_t)T * n * 13);
@@ -356,6 +380,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sv.meas_hist) sv.meas_hist = mh.data();
             if (sv.pred_hist) sv.pred_hist = ph.data();
             if (ev.est_hist) ev.est_hist = eh.data();
+            if (dv.llr_hist) dv.llr_hist = lh.data();
         }
         const int rc2 = wrench ? ftmpc_simulate_wrench_estimator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
@@ -364,11 +389,11 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                                                                      alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
                                                                      mission ? &mi : nullptr, actuator ? &at : nullptr,
                                                                      sensor ? &sv : nullptr, estimator ? &ev : nullptr)
-                               : ftmpc_simulate_estimator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                               : ftmpc_simulate_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
                                                                seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
                                                                bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
                                                                actuator ? &at : nullptr, sensor ? &sv : nullptr,
-                                                               estimator ? &ev : nullptr);
+                                                               estimator ? &ev : nullptr, diagnosis ? &dv : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -379,6 +404,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sensor && sensor->meas_hist) scatter_rows(sensor->meas_hist, mh.data(), T, B, lo, n, 13);
             if (sensor && sensor->pred_hist) scatter_rows(sensor->pred_hist, ph.data(), T, B, lo, n, 13);
             if (estimator && estimator->est_hist) scatter_rows(estimator->est_hist, eh.data(), T, B, lo, n, 13);
+            if (diagnosis && diagnosis->llr_hist) scatter_rows(diagnosis->llr_hist, lh.data(), T, B, lo, n, (int64_t)NT * dv.n_levels);
         }
         return FTMPC_OK;
     });
@@ -721,6 +747,17 @@ int ftmpc_multi_simulate_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, d
                                          const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
                           0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false);
+}
+
+int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                         const ftmpc_sensor* sensor, const ftmpc_estimator* estimator,
+                                         const ftmpc_diagnosis* diagnosis) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis);
 }
 
 int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,

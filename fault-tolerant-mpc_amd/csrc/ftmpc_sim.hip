@@ -1329,4 +1329,165 @@ __global__ void __launch_bounds__(64) ftmpc_filter_kernel(const DeviceConsts C, 
 template __global__ void ftmpc_filter_kernel<0>(const DeviceConsts, const FilterParams);
 template __global__ void ftmpc_filter_kernel<1>(const DeviceConsts, const FilterParams);
 
+// ---------------------------------------------------------------------------------------------------------
+// Thruster fault diagnosis in the closed loop (ftmpc_simulate_diagnosis_batch; include/ftmpc.h, ftmpc_diagnosis): per vehicle a bank
+// of one-sided CUSUM tests, one per hypothesis "thruster i is stuck at level l", on a parity residual: y_t against the open-loop
+// prediction xt of the controller's model from the last used measurement.  A lane per vehicle.  phase 0 runs after the sense kernel
+// and before the filter's phase 0 and the solve: test, decision (the controller's pattern switches here, as a schedule event with
+// detect = t switches it), llr_hist, re-anchor.  phase 1 runs after the plant step: xt <- one RK4 step of the model under a_t and the
+// controller's pattern, acc += the effective command, n += 1.
+// Device-side acc and llr are component-major ([NT][B], [H][B]): the lanes of a wave read consecutive addresses.  The thruster loop
+// is rolled; D, J^-1 and the levels are read at wave-uniform indices, acc_i and the statistics of thruster i are read and written
+// inside the loop, the levels (at most 4) are unrolled and the arg-max is carried: no local array is indexed by the loop variable.
+// A vehicle that switched writes switched[b] = 1; ftmpc_diagnose_repair_kernel then clips its shifted warm start to the new bounds,
+// a lane per (vehicle, stage), the repair of ftmpc_fault_event_kernel.
+// ---------------------------------------------------------------------------------------------------------
+struct DiagParams {
+    int64_t B;
+    int32_t init, anchor;     // phase 0: first step of a call without state; c % every == 0 (the test may run, xt is re-anchored)
+    int32_t L, K;             // levels per thruster, max_detect
+    int32_t cstep, pad0;      // c = step0 + t: what detect_step records
+    int64_t step;             // t (the history's row)
+    const double* y;          // [B*13] y_t
+    double* xt;               // [B*14] the prediction and n, in/out
+    double* acc;              // [NT][B]
+    double* llr;              // [H][B]
+    double levels[4];
+    double rsq[2], dsq[2];    // resid_sigma^2, drift_sigma^2: velocity, rate
+    double threshold;
+    double* ub;               // [B*NT] the controller's pattern, switched on a detection
+    double* stuck;
+    int32_t* count;           // [B] detections made
+    int32_t* det_step;        // [B*K]
+    int32_t* det_thruster;
+    int32_t* det_level;
+    int32_t* switched;        // [B] phase 0 writes 1 where the pattern switched at this step, else 0
+    double* llr_hist;         // nullptr or [T*B*H]
+    const double* u;          // phase 1: [B*NT] a_t, the command the plant applied in this step
+};
+
+template <int PHASE>
+__global__ void __launch_bounds__(64) ftmpc_diagnose_kernel(const DeviceConsts C, const DiagParams P) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int64_t B = P.B;
+    const int NT = C.NT, L = P.L, H = NT * L;
+    double x[13];
+    if constexpr (PHASE == 0) {
+        double y[13];
+        for (int i = 0; i < 13; ++i) y[i] = P.y[b * 13 + i];
+        double* const hist = P.llr_hist ? P.llr_hist + (P.step * B + b) * H : nullptr;
+        int32_t sw = 0;
+        bool tested = false;
+        if (P.init) {
+#pragma unroll 1
+            for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+        } else {
+            const double n = P.xt[b * 14 + 13];
+            const int32_t cnt = P.count[b];
+            if (P.anchor && n >= 1.0 && cnt < P.K) {
+                tested = true;
+                for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+                // rho_v = M(q~)' (y_v - v~), M the matrix plant_f applies to F / m;  r_w = y_w - w~
+                const double qx = x[6], qy = x[7], qz = x[8], qw = x[9];
+                const double R00 = qx * qx - qy * qy - qz * qz + qw * qw, R01 = 2 * (qx * qy + qz * qw), R02 = 2 * (qx * qz - qy * qw);
+                const double R10 = 2 * (qx * qy - qz * qw), R11 = -qx * qx + qy * qy - qz * qz + qw * qw, R12 = 2 * (qy * qz + qx * qw);
+                const double R20 = 2 * (qx * qz + qy * qw), R21 = 2 * (qy * qz - qx * qw), R22 = -qx * qx - qy * qy + qz * qz + qw * qw;
+                const double e0 = y[3] - x[3], e1 = y[4] - x[4], e2 = y[5] - x[5];
+                const double rv0 = R00 * e0 + R01 * e1 + R02 * e2;
+                const double rv1 = R10 * e0 + R11 * e1 + R12 * e2;
+                const double rv2 = R20 * e0 + R21 * e1 + R22 * e2;
+                const double rw0 = y[10] - x[10], rw1 = y[11] - x[11], rw2 = y[12] - x[12];
+                const double isv = 1.0 / (P.rsq[0] + n * P.dsq[0]), isw = 1.0 / (P.rsq[1] + n * P.dsq[1]);
+                const double kv = C.dt * C.inv_mass, dt = C.dt;
+                double best = P.threshold;
+                int besth = -1;
+#pragma unroll 1
+                for (int i = 0; i < NT; ++i) {
+                    const bool live = P.ub[b * NT + i] > 0.0;
+                    const double acci = P.acc[(int64_t)i * B + b];
+                    const double d0 = C.D[i], d1 = C.D[MAX_NT + i], d2 = C.D[2 * MAX_NT + i];
+                    const double t0 = C.D[3 * MAX_NT + i], t1 = C.D[4 * MAX_NT + i], t2 = C.D[5 * MAX_NT + i];
+                    const double g0 = kv * d0, g1 = kv * d1, g2 = kv * d2;      // the signature per unit of delta
+                    const double h0 = dt * (C.Jinv[0] * t0 + C.Jinv[1] * t1 + C.Jinv[2] * t2);
+                    const double h1 = dt * (C.Jinv[3] * t0 + C.Jinv[4] * t1 + C.Jinv[5] * t2);
+                    const double h2 = dt * (C.Jinv[6] * t0 + C.Jinv[7] * t1 + C.Jinv[8] * t2);
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) {
+                        if (l < L) {
+                            const int64_t k = (int64_t)(i * L + l);
+                            double v = 0.0;
+                            if (live) {
+                                const double delta = n * P.levels[l] - acci;
+                                const double a0 = g0 * delta, a1 = g1 * delta, a2 = g2 * delta;
+                                const double w0 = h0 * delta, w1 = h1 * delta, w2 = h2 * delta;
+                                const double z = ((a0 * rv0 + a1 * rv1 + a2 * rv2) - 0.5 * (a0 * a0 + a1 * a1 + a2 * a2)) * isv +
+                                                 ((w0 * rw0 + w1 * rw1 + w2 * rw2) - 0.5 * (w0 * w0 + w1 * w1 + w2 * w2)) * isw;
+                                v = fmax(0.0, P.llr[k * B + b] + z);
+                            }
+                            P.llr[k * B + b] = v;
+                            if (hist) hist[k] = v;
+                            if (v > best) {      // (strictly: a tie stays with the lowest index)
+                                best = v;
+                                besth = (int)k;
+                            }
+                        }
+                    }
+                }
+                if (besth >= 0) {
+                    const int i = besth / L, l = besth - i * L;
+                    const double lv = l == 0 ? P.levels[0] : (l == 1 ? P.levels[1] : (l == 2 ? P.levels[2] : P.levels[3]));
+                    P.det_step[b * P.K + cnt] = P.cstep;
+                    P.det_thruster[b * P.K + cnt] = i;
+                    P.det_level[b * P.K + cnt] = l;
+                    P.count[b] = cnt + 1;
+                    P.ub[b * NT + i] = 0.0;
+                    P.stuck[b * NT + i] = lv;
+#pragma unroll 1
+                    for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+                    sw = 1;
+                }
+            }
+        }
+        if (hist && !tested) {
+#pragma unroll 1
+            for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+        }
+        P.switched[b] = sw;
+        if (P.init || P.anchor) {
+            for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = y[i];
+            P.xt[b * 14 + 13] = 0.0;
+#pragma unroll 1
+            for (int i = 0; i < NT; ++i) P.acc[(int64_t)i * B + b] = 0.0;
+        }
+        return;
+    }
+    // PHASE 1: the model's step under the command the plant applied, c_i = ub_c,i > 0 ? a_t,i : 0
+    for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+    double gen[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll 1
+    for (int i = 0; i < NT; ++i) {
+        const double c = P.ub[b * NT + i] > 0.0 ? P.u[b * NT + i] : 0.0;
+        const double t = c + P.stuck[b * NT + i];
+        for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * t;
+        P.acc[(int64_t)i * B + b] += c;
+    }
+    filter_rk4(C, x, gen);
+    for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = x[i];
+    P.xt[b * 14 + 13] += 1.0;
+}
+template __global__ void ftmpc_diagnose_kernel<0>(const DeviceConsts, const DiagParams);
+template __global__ void ftmpc_diagnose_kernel<1>(const DeviceConsts, const DiagParams);
+
+// The warm-start repair after a detection: U clipped elementwise to [0, ub_new], what ftmpc_fault_event_kernel does at a detected event
+__global__ void __launch_bounds__(64) ftmpc_diagnose_repair_kernel(int64_t B, int N, int NT, const int32_t* switched, const double* ub,
+                                                                  double* warmU) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * N) return;
+    const int64_t b = i / N;
+    if (!switched[b]) return;
+    double* w = warmU + i * NT;
+    for (int j = 0; j < NT; ++j) w[j] = fmin(fmax(w[j], 0.0), ub[b * NT + j]);
+}
+
 }  // namespace ftmpc

@@ -37,6 +37,7 @@ SYMBOLS = (
     "ftmpc_multi_simulate_actuator_batch", "ftmpc_multi_simulate_wrench_actuator_batch",
     "ftmpc_multi_simulate_sensor_batch", "ftmpc_multi_simulate_wrench_sensor_batch",
     "ftmpc_multi_simulate_estimator_batch", "ftmpc_multi_simulate_wrench_estimator_batch",
+    "ftmpc_simulate_diagnosis_batch", "ftmpc_multi_simulate_diagnosis_batch",
 )
 
 
@@ -127,6 +128,16 @@ class ftmpc_estimator(C.Structure):
     ]
 
 
+class ftmpc_diagnosis(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("every", C.c_int32), ("n_levels", C.c_int32), ("max_detect", C.c_int32),
+        ("levels", C.c_double * 4), ("resid_sigma", C.c_double * 2), ("drift_sigma", C.c_double * 2), ("threshold", C.c_double),
+        ("state", C.POINTER(C.c_double)), ("llr", C.POINTER(C.c_double)),
+        ("detect_step", C.POINTER(C.c_int32)), ("detect_thruster", C.POINTER(C.c_int32)), ("detect_level", C.POINTER(C.c_int32)),
+        ("ub", C.POINTER(C.c_double)), ("stuck", C.POINTER(C.c_double)), ("llr_hist", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -208,6 +219,8 @@ def load_library() -> C.CDLL:
     lib.ftmpc_simulate_wrench_estimator_batch.argtypes = lib.ftmpc_simulate_wrench_sensor_batch.argtypes + [esp]
     lib.ftmpc_multi_simulate_estimator_batch.argtypes = lib.ftmpc_simulate_estimator_batch.argtypes
     lib.ftmpc_multi_simulate_wrench_estimator_batch.argtypes = lib.ftmpc_simulate_wrench_estimator_batch.argtypes
+    lib.ftmpc_simulate_diagnosis_batch.argtypes = lib.ftmpc_simulate_estimator_batch.argtypes + [C.POINTER(ftmpc_diagnosis)]
+    lib.ftmpc_multi_simulate_diagnosis_batch.argtypes = lib.ftmpc_simulate_diagnosis_batch.argtypes
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
                                                  dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, ip]

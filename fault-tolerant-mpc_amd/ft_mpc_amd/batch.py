@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None, actuator=None, sensor=None, estimator=None):
+                 plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -497,11 +497,21 @@ class BatchedMPC:
         estimate each solve started from, before the sensor's prediction), err_sq [B,4] (summed squared errors against the truth by
         group), xhat [B,13] and cov [B,78] (the priors of step T, to hand to a continued run); they come back as out["estimator"].
         With a predicting sensor the field pred of the sensor holds the estimate propagated over the queue.
+        diagnosis: the controller finds thruster faults itself (include/ftmpc.h, ftmpc_diagnosis; ft_mpc_amd.diagnosis restates it in
+        NumPy; thruster formulation only): a bank of CUSUM tests per vehicle, one per hypothesis "thruster i stuck at level l", on
+        the measurement against the model's open-loop prediction.  A dict with every=1, levels=(0.0, F_MAX), resid_sigma=(2,)
+        (velocity, rate; diagnosis.default_sigma), drift_sigma=(0, 0), threshold, max_detect=2, state=None ([B,14+NT]), llr=None
+        ([B,NT*L]), detect=None ((step, thruster, level), each [B,max_detect]) -- what a previous call returned, for a continued run --
+        and fields=(...) among detect, pattern, llr_hist, state (default: all).  They come back as out["diagnosis"]: step, thruster,
+        level [B,max_detect] (-1: unused), ub, stuck [B,NT] (the controller's pattern after the last step), llr_hist [T,B,NT*L],
+        state, llr.  With `faults` the schedule then moves the plant only and detect_delay is not used.  A call without state that
+        asks for detect or state starts from xt = x0, n = 0, which the first step's re-anchor replaces by the first measurement
+        when step0 % every == 0.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
         [, status_hist][, actuator][, sensor][, estimator])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator)
+                         plant, mission, actuator, sensor, estimator, diagnosis)
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -818,9 +828,46 @@ def _estimator_request(estimator, B, T):
     return es, keep, out
 
 
+def _diagnosis_request(diagnosis, x0, B, T, NT, estimator, sensor):
+    """The ftmpc_diagnosis struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .diagnosis import request
+    r = request(diagnosis, B, T, NT, estimator, sensor, F_MAX)
+    L, K = r["levels"].size, r["max_detect"]
+    dg = _lib.ftmpc_diagnosis(struct_size=C.sizeof(_lib.ftmpc_diagnosis), every=r["every"], n_levels=L, max_detect=K,
+                              threshold=r["threshold"])
+    for k in range(L):
+        dg.levels[k] = float(r["levels"][k])
+    for k in range(2):
+        dg.resid_sigma[k], dg.drift_sigma[k] = float(r["resid_sigma"][k]), float(r["drift_sigma"][k])
+    keep, out = [], {}
+    state, llr, det = r["state"], r["llr"], r["detect"]
+    if state is None and ("detect" in r["fields"] or "state" in r["fields"]):
+        # state, llr and the detect arrays are in/out: asked back without being handed over, the run starts from xt = x0, n = 0
+        state = np.zeros((B, 14 + NT))
+        state[:, 0:13] = x0
+        det = tuple(np.full((B, K), -1, np.int32) for _ in range(3))
+    if state is not None:
+        if llr is None and "state" in r["fields"]:      # (not handed over and not asked back: filled on the device, nothing staged)
+            llr = np.zeros((B, NT * L))
+        keep += [state, llr, *det]
+        dg.state, dg.llr = _ptr(state), _ptr(llr)
+        dg.detect_step, dg.detect_thruster, dg.detect_level = (_ptr(a, C.c_int32) for a in det)
+        if "detect" in r["fields"]:
+            out["step"], out["thruster"], out["level"] = det
+        if "state" in r["fields"]:
+            out["state"], out["llr"] = state, llr
+    if "pattern" in r["fields"]:
+        out["ub"], out["stuck"] = np.zeros((B, NT)), np.zeros((B, NT))
+        dg.ub, dg.stuck = _ptr(out["ub"]), _ptr(out["stuck"])
+    if "llr_hist" in r["fields"]:
+        out["llr_hist"] = np.zeros((T, B, NT * L))
+        dg.llr_hist = _ptr(out["llr_hist"])
+    return dg, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -842,6 +889,9 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
     se, skeep, sout, L = _sensor_request(sensor, B, T, NT) if sensor is not None else (None, None, None, 0)
     es, ekeep, eout = _estimator_request(estimator, B, T) if estimator is not None else (None, None, None)
+    if diagnosis is not None and formulation == "wrench":
+        raise ValueError("diagnosis: thruster formulation only (the wrench form would need a hull table per hypothesis)")
+    dg, dkeep, dout = _diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor) if diagnosis is not None else (None, None, None)
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -872,6 +922,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         keep = [onset, detect, eub, est]
         sched = _lib.ftmpc_fault_schedule(struct_size=C.sizeof(_lib.ftmpc_fault_schedule), n_events=onset.shape[1],
                                           onset=_ptr(onset, C.c_int32), detect=_ptr(detect, C.c_int32), ub=_ptr(eub), stuck=_ptr(est))
+        if dg is not None:      # the schedule moves the plant only: the diagnosis detects
+            sched.detect = None
         if formulation == "wrench":
             if hull is not None and ("ev_set" not in hull or np.shape(hull["ev_set"]) != onset.shape):
                 raise ValueError("with faults `hull` must be None or ft_mpc_amd.faults.fault_hull_tables of the same schedule")
@@ -888,7 +940,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
-           or pm is not None or ms is not None or ac is not None or se is not None or es is not None)
+           or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -909,6 +961,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["sensor"] = sout
         if eout is not None:
             out["estimator"] = eout
+        if dout is not None:
+            out["diagnosis"] = dout
         return out
     msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
@@ -980,6 +1034,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if dg is not None:
+        self._check(getattr(self.lib, pre + "diagnosis_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
+            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+            C.byref(es) if es is not None else None, C.byref(dg)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if es is not None:
         self._check(getattr(self.lib, pre + "estimator_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

@@ -1,0 +1,240 @@
+"""Thruster fault diagnosis on the host: NumPy restatements of what BatchedMPC.simulate(diagnosis=...) runs on the device before every
+solve (include/ftmpc.h, ftmpc_diagnosis; csrc/ftmpc_sim.hip, ftmpc_diagnose_kernel).
+
+Per vehicle a bank of one-sided CUSUM tests, one per hypothesis "thruster i is stuck at level l" (index i L + l; a dead thruster is
+level 0), on a parity residual: the measurement y_t against xt, the open-loop prediction of the controller's model from the last used
+measurement.  With n the model steps since that measurement and acc_i the sum over them of the effective command of thruster i:
+  signature   delta = n levels[l] - acc_i,  a_v = (dt / m) D[0:3, i] delta,  a_w = dt J^-1 D[3:6, i] delta
+  test_step   r = y [-] xt,  rho_v = M(q~)' r[3:6],  r_w = r[9:12],  s = resid_sigma^2 + n drift_sigma^2 (velocity, rate),
+              z = (a_v . rho_v - |a_v|^2 / 2) / s_v + (a_w . r_w - |a_w|^2 / 2) / s_w,  llr = max(0, llr + z); 0 where ub_c,i == 0
+  decision    the largest statistic above the threshold is detected (a tie: the lowest index): ub_c,i = 0, stuck_c,i = levels[l],
+              every statistic of the vehicle back to 0
+  propagate   xt <- one RK4 step of the model under c_i = ub_c,i > 0 ? a_t,i : 0 and stuck_c, acc += c, n += 1
+replay runs the loop's diagnosis for one vehicle from the recorded measurements and applied commands.
+
+The signature is first order in dt; a dead thruster that is not commanded has none, and neither has a thruster stuck at the level it
+is commanded at; a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's test; a
+detection is never withdrawn; position and attitude are not used; the diagnosis is told neither the plant's dispersion nor the
+actuator."""
+from __future__ import annotations
+
+import numpy as np
+
+from .estimators import _body_to_inertial, _cfg_model, residual
+from .sensors import predict
+
+MAX_LEVELS = 4
+MAX_DETECT = 8          # FTMPC_MAX_FAULT_EVENTS
+FIELDS = ("detect", "pattern", "llr_hist", "state")
+
+
+def default_sigma(sensor_sigma, noise=(0.0, 0.0, 0.0, 0.0)):
+    """resid_sigma (2,) for a sensor with standard deviations sensor_sigma (4,) and process noise amplitudes noise (4,):
+    sqrt(2 sigma^2 + noise^2) for the velocity and rate groups (the residual is a difference of two measurements)."""
+    s = np.asarray(sensor_sigma, dtype=np.float64).reshape(4)
+    a = np.asarray(noise, dtype=np.float64).reshape(4)
+    return np.sqrt(2.0 * s[[1, 3]] ** 2 + a[[1, 3]] ** 2)
+
+
+def signature(n, acc, levels, cfg):
+    """(a_v [NT,L,3], a_w [NT,L,3]): what "thruster i stuck at level l over the last n steps" adds to the body-frame velocity and
+    to the rate, against a model that applied acc [NT] in sum."""
+    D, m, J = _cfg_model(cfg)
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    delta = float(n) * lv[None, :] - np.asarray(acc, dtype=np.float64).reshape(-1, 1)            # [NT, L]
+    gv = (float(cfg.dt) / m) * D[0:3].T                                                          # [NT, 3]
+    gw = float(cfg.dt) * np.linalg.solve(J, D[3:6]).T
+    return gv[:, None, :] * delta[:, :, None], gw[:, None, :] * delta[:, :, None]
+
+
+def test_step(llr, y, xt, n, acc, ub, spec, cfg):
+    """The statistics [NT,L] after the test of one step (after the max(0, .), before a detection's reset)."""
+    lv = np.asarray(spec["levels"], dtype=np.float64).reshape(-1)
+    rs = np.asarray(spec["resid_sigma"], dtype=np.float64).reshape(2)
+    ds = np.asarray(spec.get("drift_sigma", (0.0, 0.0)), dtype=np.float64).reshape(2)
+    xt = np.asarray(xt, dtype=np.float64).reshape(13)
+    r = residual(y, xt)
+    rho_v = _body_to_inertial(xt[6:10]).T @ r[3:6]
+    r_w = r[9:12]
+    s_v, s_w = rs[0] ** 2 + n * ds[0] ** 2, rs[1] ** 2 + n * ds[1] ** 2
+    a_v, a_w = signature(n, acc, lv, cfg)
+    z = (a_v @ rho_v - 0.5 * (a_v * a_v).sum(-1)) / s_v + (a_w @ r_w - 0.5 * (a_w * a_w).sum(-1)) / s_w
+    out = np.maximum(0.0, np.asarray(llr, dtype=np.float64).reshape(z.shape) + z)
+    out[np.asarray(ub).reshape(-1) <= 0] = 0.0
+    return out
+
+
+test_step.__test__ = False      # (not a test of the suite, whatever its name)
+
+
+def propagate(xt, n, acc, u, ub, stuck, cfg):
+    """(xt, n, acc) after the model's step under the applied command u [NT] and the controller's pattern."""
+    c = np.where(np.asarray(ub).reshape(-1) > 0, np.asarray(u, dtype=np.float64).reshape(-1), 0.0)
+    return predict(xt, np.asarray(u, dtype=np.float64).reshape(1, -1), ub, stuck, cfg), n + 1, np.asarray(acc, dtype=np.float64) + c
+
+
+def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None):
+    """The loop's diagnosis for ONE vehicle.  meas [T,13]: the y_t; applied_u [T,NT]: the a_t (u_hist); ub, stuck [NT]: the
+    controller's pattern at the call's start; spec: dict(every, levels, resid_sigma, drift_sigma, threshold, max_detect); state
+    [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned.
+    Returns dict(llr_hist [T,NT*L], detections [(step, thruster, level)], ub [T,NT], stuck [T,NT] (the pattern each solve saw),
+    ub_end, stuck_end, state [14+NT], llr [NT*L], peak [T] (the largest statistic of every step that tested, else nan))."""
+    meas = np.asarray(meas, dtype=np.float64).reshape(-1, 13)
+    T = meas.shape[0]
+    u = np.asarray(applied_u, dtype=np.float64).reshape(T, -1)
+    NT = u.shape[1]
+    ub = np.array(ub, dtype=np.float64).reshape(NT)
+    stuck = np.array(stuck, dtype=np.float64).reshape(NT)
+    lv = np.asarray(spec["levels"], dtype=np.float64).reshape(-1)
+    L = lv.size
+    every, K, thr = int(spec.get("every", 1)), int(spec.get("max_detect", 2)), float(spec["threshold"])
+    det = [] if detections is None else [tuple(int(v) for v in d) for d in detections]
+    if state is None:
+        xt, n, acc = None, 0, np.zeros(NT)
+    else:
+        state = np.asarray(state, dtype=np.float64).reshape(14 + NT)
+        xt, n, acc = state[0:13].copy(), float(state[13]), state[14:].copy()
+    s = np.zeros((NT, L)) if llr is None else np.array(llr, dtype=np.float64).reshape(NT, L)
+    hist, peak = np.empty((T, NT * L)), np.full(T, np.nan)
+    ubh, sth = np.empty((T, NT)), np.empty((T, NT))
+    for t in range(T):
+        c = int(step0) + t
+        if xt is None:
+            xt, n, acc, s = meas[t].copy(), 0, np.zeros(NT), np.zeros((NT, L))
+            hist[t] = 0.0
+        else:
+            if c % every == 0 and n >= 1 and len(det) < K:
+                s = test_step(s, meas[t], xt, n, acc, ub, spec, cfg)
+                hist[t] = s.reshape(-1)
+                peak[t] = hist[t].max()
+                if peak[t] > thr:
+                    k = int(np.argmax(hist[t]))      # (the first of equal maxima)
+                    det.append((c, k // L, k % L))
+                    ub[k // L], stuck[k // L] = 0.0, lv[k % L]
+                    s = np.zeros((NT, L))
+            else:
+                hist[t] = s.reshape(-1)
+            if c % every == 0:
+                xt, n, acc = meas[t].copy(), 0, np.zeros(NT)
+        ubh[t], sth[t] = ub, stuck
+        xt, n, acc = propagate(xt, n, acc, u[t], ub, stuck, cfg)
+    return dict(llr_hist=hist, detections=det, ub=ubh, stuck=sth, ub_end=ub, stuck_end=stuck,
+                state=np.concatenate([xt, [float(n)], acc]), llr=s.reshape(-1), peak=peak)
+
+
+def pattern(ub, stuck, detections, levels):
+    """The controller's pattern (ub [NT], stuck [NT]) after the detections [(step, thruster, level)] of one vehicle."""
+    ub = np.array(ub, dtype=np.float64)
+    stuck = np.array(stuck, dtype=np.float64)
+    for _, i, l in detections:
+        if i >= 0:
+            ub[i], stuck[i] = 0.0, float(np.asarray(levels).reshape(-1)[l])
+    return ub, stuck
+
+
+def detections_of(step, thruster, level):
+    """[B] lists of (step, thruster, level) from the arrays [B,K] the call returns (-1: unused slot)."""
+    step = np.asarray(step)
+    return [[(int(step[b, k]), int(thruster[b, k]), int(level[b, k])) for k in range(step.shape[1]) if step[b, k] >= 0]
+            for b in range(step.shape[0])]
+
+
+def score(faults, detections):
+    """faults: per vehicle a list of (onset, thruster, level) events that happened; detections: per vehicle a list of
+    (step, thruster, level).  An event is matched to the first unmatched detection of its thruster at or after its onset; an event
+    left over is matched to the first unmatched detection at or after its onset, which then blames the wrong thruster; what is left
+    of the events was missed, what is left of the detections are false alarms.
+    Returns dict(delay [per event: detect_step - onset, or None when missed], missed, wrong_thruster, wrong_level, false_alarms)."""
+    delay, missed, wrong_t, wrong_l, false_alarms = [], 0, 0, 0, 0
+    for ev, det in zip(faults, detections):
+        ev, det = sorted(ev), sorted(det)
+        used, hit = [False] * len(det), [None] * len(ev)
+        for same in (True, False):
+            for j, (onset, thr, _) in enumerate(ev):
+                if hit[j] is None:
+                    hit[j] = next((k for k, d in enumerate(det) if not used[k] and d[0] >= onset and (d[1] == thr) == same), None)
+                    if hit[j] is not None:
+                        used[hit[j]] = True
+        for j, (onset, thr, lvl) in enumerate(ev):
+            if hit[j] is None:
+                delay.append(None)
+                missed += 1
+                continue
+            delay.append(det[hit[j]][0] - onset)
+            if det[hit[j]][1] != thr:
+                wrong_t += 1
+            elif det[hit[j]][2] != lvl:
+                wrong_l += 1
+        false_alarms += used.count(False)
+    return dict(delay=delay, missed=missed, wrong_thruster=wrong_t, wrong_level=wrong_l, false_alarms=false_alarms)
+
+
+def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None):
+    """The checks BatchedMPC.simulate makes on a diagnosis dict before the call reaches the library (the library's own refusals, raised
+    from Python too); returns the dict with defaults filled in: every, levels (L,), resid_sigma (2,), drift_sigma (2,), threshold,
+    max_detect, state [B,14+NT] | None, llr [B,NT*L] | None, detect (step, thruster, level) [B,K] | None, fields."""
+    spec = dict(diagnosis)
+    out = dict(every=spec.pop("every", 1), levels=spec.pop("levels", None), resid_sigma=spec.pop("resid_sigma", None),
+               drift_sigma=spec.pop("drift_sigma", (0.0, 0.0)), threshold=spec.pop("threshold", None),
+               max_detect=spec.pop("max_detect", 2), state=spec.pop("state", None), llr=spec.pop("llr", None),
+               detect=spec.pop("detect", None), fields=tuple(spec.pop("fields", FIELDS)))
+    if spec:
+        raise ValueError(f"diagnosis: unknown keys {sorted(spec)}")
+    if int(out["every"]) != out["every"] or int(out["every"]) < 1:
+        raise ValueError(f"diagnosis['every'] must be an integer >= 1, not {out['every']}")
+    out["every"] = int(out["every"])
+    if estimator is not None and int(estimator.get("every", 1)) != out["every"]:
+        raise ValueError(f"diagnosis['every'] = {out['every']} differs from estimator['every'] = {estimator.get('every', 1)}")
+    if out["levels"] is None:
+        if f_max is None:
+            raise ValueError("diagnosis['levels'] is required")
+        out["levels"] = (0.0, f_max)
+    lv = out["levels"] = np.asarray(out["levels"], dtype=np.float64).reshape(-1)
+    if not 1 <= lv.size <= MAX_LEVELS:
+        raise ValueError(f"diagnosis['levels'] must hold 1..{MAX_LEVELS} values (n_levels)")
+    if not (np.isfinite(lv).all() and (lv >= 0).all() and (np.diff(lv) > 0).all()):
+        raise ValueError("diagnosis['levels'] must be finite, >= 0 and strictly increasing")
+    if int(out["max_detect"]) != out["max_detect"] or not 1 <= int(out["max_detect"]) <= MAX_DETECT:
+        raise ValueError(f"diagnosis['max_detect'] must be an integer in [1, {MAX_DETECT}]")
+    K = out["max_detect"] = int(out["max_detect"])
+    if out["resid_sigma"] is None:
+        raise ValueError("diagnosis['resid_sigma'] is required: 2 values (velocity, rate), e.g. diagnosis.default_sigma")
+    out["resid_sigma"] = np.asarray(out["resid_sigma"], dtype=np.float64)
+    if out["resid_sigma"].shape != (2,) or not (np.isfinite(out["resid_sigma"]).all() and (out["resid_sigma"] > 0).all()):
+        raise ValueError("diagnosis['resid_sigma'] must be 2 finite values > 0")
+    out["drift_sigma"] = np.asarray(out["drift_sigma"], dtype=np.float64)
+    if out["drift_sigma"].shape != (2,) or not (np.isfinite(out["drift_sigma"]).all() and (out["drift_sigma"] >= 0).all()):
+        raise ValueError("diagnosis['drift_sigma'] must be 2 finite values >= 0")
+    if out["threshold"] is None or not (np.isfinite(out["threshold"]) and out["threshold"] > 0):
+        raise ValueError("diagnosis['threshold'] must be finite and > 0")
+    out["threshold"] = float(out["threshold"])
+    if any(f not in FIELDS for f in out["fields"]):
+        raise ValueError(f"diagnosis['fields'] must be among {list(FIELDS)}")
+    if out["state"] is None and (out["llr"] is not None or out["detect"] is not None):
+        raise ValueError("diagnosis['llr'] and diagnosis['detect'] require diagnosis['state']")
+    H = NT * lv.size
+    if out["state"] is not None:
+        if out["detect"] is None:
+            raise ValueError("diagnosis['state'] requires diagnosis['detect'] = (step, thruster, level)")
+        out["state"] = np.array(out["state"], dtype=np.float64)           # copies: the call writes into them
+        if out["state"].shape != (B, 14 + NT) or not np.isfinite(out["state"]).all():
+            raise ValueError(f"diagnosis['state'] must be finite with shape {(B, 14 + NT)}")
+        if (out["state"][:, 13] < 0).any():
+            raise ValueError("diagnosis['state'] has n < 0")
+        if out["llr"] is not None:
+            out["llr"] = np.array(out["llr"], dtype=np.float64)
+            if out["llr"].shape != (B, H) or not np.isfinite(out["llr"]).all():
+                raise ValueError(f"diagnosis['llr'] must be finite with shape {(B, H)}")
+        det = tuple(np.array(a, dtype=np.int32) for a in out["detect"])
+        if len(det) != 3 or any(a.shape != (B, K) for a in det):
+            raise ValueError(f"diagnosis['detect'] must be (step, thruster, level), each of shape {(B, K)}")
+        used = det[0] >= 0
+        if (det[0] < -1).any() or (used[:, 1:] & ~used[:, :-1]).any():
+            raise ValueError("diagnosis['detect']: a step below -1, or a used slot after an unused one")
+        if ((det[1][used] < 0) | (det[1][used] >= NT)).any() or ((det[2][used] < 0) | (det[2][used] >= lv.size)).any():
+            raise ValueError("diagnosis['detect']: a thruster outside [0, NT) or a level outside [0, n_levels)")
+        out["detect"] = det
+    if sensor is not None and sensor.get("predict") and estimator is None:
+        raise ValueError("diagnosis: a predicting sensor needs an estimator (the sensor alone would predict with the pattern "
+                         "before the diagnosis)")
+    return out

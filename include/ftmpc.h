@@ -820,6 +820,81 @@ int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                           const ftmpc_estimator* estimator);
 
+/* Thruster fault diagnosis in the on-device closed loop (thruster form: one QP, or the thruster SQP, per step).  Without this struct
+ * the controller learns of a fault at the step the schedule's `detect` names.  With it the controller finds the fault itself: per
+ * vehicle a bank of one-sided CUSUM tests, one per hypothesis "thruster i is stuck at level l" (a dead thruster is level 0), driven by
+ * a parity residual: the measurement against an open-loop prediction of the controller's model from the last used measurement.  When
+ * a statistic crosses the threshold the controller's pattern switches on the device, before that step's solve, exactly as a
+ * schedule event with detect = t switches it, the repair of the warm start included.  The parameters are uniform over the call; the
+ * state and the outputs are per vehicle.
+ *   NT thrusters, L = n_levels, H = NT L hypotheses, thruster i at level l has index i L + l; (ub_c, stuck_c) is the controller's
+ *   pattern; c = step0 + t the campaign step (step0 the sensor's, 0 without one); K = max_detect.
+ *   state per vehicle: xt [13] the prediction from the last used measurement, n the model steps since, acc [NT] the sum over those
+ *   steps of the effective command, llr [H] the statistics.
+ *   per loop step t:
+ *     1. ftmpc_sense_kernel forms y_t (a trivial or NULL sensor: the truth, kept in a buffer of the call as under an estimator);
+ *     2. phase 0, before the filter's phase 0 and the solve.  On the first step of a call that was not handed `state`: xt = y_t,
+ *        n = 0, acc = 0, llr = 0 and no test.  Otherwise, when c % every == 0, n >= 1 and fewer than K detections have been made:
+ *          r = y_t [-] xt (the filter's residual);  rho_v = M(q~)' r[3:6] with q~ the quaternion of xt and M the model's
+ *          body-to-inertial matrix;  r_w = r[9:12];  s_v = resid_sigma[0]^2 + n drift_sigma[0]^2, s_w with index 1;
+ *          for every thruster i with ub_c,i > 0 and every level l:  delta = n levels[l] - acc_i,  a_v = (dt / m) D[0:3, i] delta,
+ *          a_w = dt J^-1 D[3:6, i] delta,  z = (a_v . rho_v - a_v . a_v / 2) / s_v + (a_w . r_w - a_w . a_w / 2) / s_w,
+ *          llr = max(0, llr + z);  the statistics of a thruster with ub_c,i == 0 are 0.
+ *        If the largest statistic exceeds `threshold`, its hypothesis (a tie: the lowest index) is detected: detect_step[k] = c,
+ *        detect_thruster[k] = i, detect_level[k] = l with k the vehicle's detection count; the controller's pattern becomes
+ *        ub_c,i = 0, stuck_c,i = levels[l]; when t > 0, or the handle resumes a warm start, the shifted warm start U is clipped
+ *        elementwise to [0, ub_new]; all H statistics of the vehicle are set to 0.  llr_hist[t] holds the statistics after the
+ *        max(0, .) and before a detection's reset (on a step without a test: the carried values).  Whenever c % every == 0, test or
+ *        not: xt = y_t, n = 0, acc = 0.
+ *     3. filter phase 0 (when an estimator is given), solve, command queue and plant step as without the struct: they see the new
+ *        pattern in the step of the detection;
+ *     4. phase 1, after the plant step, with a_t the command the plant applied in step t:  c_i = ub_c,i > 0 ? a_t,i : 0,
+ *        gen = D (c + stuck_c),  xt <- one RK4 step of the model, renormalised (the filter's step),  acc_i += c_i,  n += 1.
+ * With a fault schedule the schedule moves the PLANT only: its `detect` must be NULL and is not consulted.  Without one the plant
+ * keeps the call's ub / stuck whatever the diagnosis decides.
+ * Limits: the signature is first order in dt (one rotation per test, the gyroscopic coupling of the difference neglected); a dead
+ * thruster that is not commanded has no signature, and neither has a thruster stuck at the level it is commanded at (stuck on while the
+ * controller saturates it); a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's
+ * test; a detection is never withdrawn; position and attitude are not used; the diagnosis is told neither the plant dispersion nor the
+ * actuator (resid_sigma / drift_sigma have to cover them).
+ * A continued run (state, llr and the detect arrays handed over, the returned ub / stuck as the call's pattern, the sensor's
+ * pending / step0, the filter's xhat / cov, the schedule shifted) is the whole run bit for bit.
+ * FTMPC_ERR_ARG, the message naming ftmpc_diagnosis.<field> and, for an array, the first offending vehicle, the call's x untouched:
+ * a struct_size other than sizeof(ftmpc_diagnosis); every < 1, or different from a given estimator's every; n_levels outside [1, 4];
+ * max_detect outside [1, FTMPC_MAX_FAULT_EVENTS]; a level negative, not finite or not above the one before; a resid_sigma not
+ * finite and > 0; a drift_sigma negative or not finite; a threshold not finite and > 0; llr or a detect array without state; state
+ * without the three detect arrays; a non-finite state or llr entry; n < 0; a handed detect entry out of range, or a used slot after
+ * an unused one; a fault schedule with detect != NULL; a sensor with predict = 1 and no estimator (the sense kernel would predict
+ * with the old pattern before the diagnosis runs).
+ */
+typedef struct ftmpc_diagnosis {
+    int32_t struct_size;       /* sizeof(ftmpc_diagnosis) */
+    int32_t every;             /* >= 1: the test runs on campaign steps c with c % every == 0 */
+    int32_t n_levels;          /* L, 1..4 */
+    int32_t max_detect;        /* K, 1..FTMPC_MAX_FAULT_EVENTS */
+    double levels[4];          /* N, finite, >= 0, strictly increasing */
+    double resid_sigma[2];     /* > 0: velocity (m/s), rate (rad/s) */
+    double drift_sigma[2];     /* >= 0, per model step */
+    double threshold;          /* > 0 */
+    double* state;             /* NULL or [B*(14+NT)] in/out: xt[13], n, acc[NT] */
+    double* llr;               /* NULL or [B*H] in/out; requires state */
+    int32_t* detect_step;      /* NULL or [B*max_detect] in/out, -1 = unused; a handed state requires all three */
+    int32_t* detect_thruster;
+    int32_t* detect_level;
+    double* ub;                /* NULL or [B*NT] out: the controller's pattern after the last step */
+    double* stuck;
+    double* llr_hist;          /* NULL or [T*B*H] out */
+} ftmpc_diagnosis;
+
+/* ftmpc_simulate_estimator_batch with the diagnosis `diagnosis` (NULL: exactly ftmpc_simulate_estimator_batch).  The wrench form has
+ * no diagnosis: it would need a hull table per hypothesis. */
+int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -1006,6 +1081,17 @@ int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32
                                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                                 const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                 const ftmpc_estimator* estimator);
+/* ftmpc_multi_simulate_estimator_batch with the diagnosis `diagnosis` (ftmpc_diagnosis; NULL: exactly that entry).  The struct is
+ * checked once over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; state + (14 + NT) lo,
+ * llr + H lo, the detect arrays + max_detect lo and ub / stuck + NT lo are read and written per shard, llr_hist is copied row by row
+ * from the shard's staging as est_hist is.  ftmpc_multi_upload / _step take no diagnosis. */
+int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                         const ftmpc_sensor* sensor, const ftmpc_estimator* estimator,
+                                         const ftmpc_diagnosis* diagnosis);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

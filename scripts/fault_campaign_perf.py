@@ -12,6 +12,7 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --actuator        # also the loops with PWM thrusters (S = 16, min_on 1) and valve lag in the plant
     python scripts/fault_campaign_perf.py --sensor [--latency 0 2 8] [--predict]   # also the loops with navigation errors and latency
     python scripts/fault_campaign_perf.py --sensor --estimator [--every M]   # and each of those once more with the navigation filter
+    python scripts/fault_campaign_perf.py --case thruster --diagnosis       # and the sensor loops once more with the fault diagnosis
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -43,7 +44,14 @@ a kernel_stats.csv of that run holds the sense kernel next to the plant kernel, 
 --estimator (with --sensor): every sensor loop once more under BatchedMPC.simulate(estimator=...): p0 = meas_sigma = the sensor's
 sigma, proc_sigma a tenth of it, the update on every --every-th step (default 1), err_sq returned (ftmpc_filter_kernel<0> before
 every solve and <1> after every plant step).  With --once the call with the sensor also carries the filter, and --stats reports the
-time per launch of either phase and the filter's share of the kernel time."""
+time per launch of either phase and the filter's share of the kernel time.
+--diagnosis (thruster form; without --sensor a sensor of latency 0 is added): every sensor loop that a diagnosis accepts (no
+prediction without the filter) once more under BatchedMPC.simulate(diagnosis=...): levels (0, f_max), resid_sigma =
+diagnosis.default_sigma of the sensor and the process noise, threshold 18, the test on every --every-th step, the detections
+returned (ftmpc_diagnose_kernel<0> and the repair kernel before every solve, <1> after every plant step).  The loop without a
+schedule is the cost of the diagnosis on unchanged solves; with the schedule the controller learns of the fault from the diagnosis
+instead of at the onset, and the result holds diagnosis.score.  With --once the call with the sensor also carries the diagnosis, and
+--stats reports the time per launch of either phase."""
 import argparse
 import csv
 import json
@@ -105,11 +113,12 @@ ACTUATOR = dict(mode="pwm", min_on=1, align="centred", tau_on=0.02, tau_off=0.01
 SENSOR = dict(sigma=(1e-2, 5e-3, 1e-2, 5e-3), seed=29)
 SENSOR_BIAS = (0.05, 0.01, 0.02, 0.005)
 ESTIMATOR = dict(p0=SENSOR["sigma"], proc_sigma=tuple(0.1 * s for s in SENSOR["sigma"]), meas_sigma=SENSOR["sigma"], fields=("err_sq",))
+DIAGNOSIS = dict(levels=(0.0, 3.4), threshold=18.0, max_detect=2, fields=("detect",))
 DISPERSION = dict(mass_rel=0.10, inertia_rel=0.10, gain_rel=0.05, com_offset=0.01, force=0.05, torque=0.005)
 
 
 def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_mission=False, actuator=False, substeps=16, sensor=False,
-        latencies=(2,), predict=False, estimator=False, every=1):
+        latencies=(2,), predict=False, estimator=False, every=1, diagnosis=False):
     import ft_mpc_amd
     c = CASES[name]
     cfg = ft_mpc_amd.MPCConfig(N=c["N"], NT=c["NT"], dtype=c["dtype"], max_iters=60 if c["formulation"] == "wrench" else 0)
@@ -147,10 +156,18 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
                 xs[8] = 0.6
                 sensors.append((f"sensor_d{d}" + ("_predict" if pr else ""), dict(SENSOR, bias=bias, latency=d, predict=pr), xs))
     est = dict(ESTIMATOR, every=every) if estimator and sensor else None
+    diag = None
+    if diagnosis and c["formulation"] == "thruster":
+        from ft_mpc_amd.diagnosis import default_sigma, detections_of, score
+        diag = dict(DIAGNOSIS, every=every, resid_sigma=default_sigma(SENSOR["sigma"], (1e-3,) * 4))
+        if not sensors:
+            sensors.append(("sensor_d0", dict(SENSOR, latency=0), xr))
+    with_diag = lambda sen: diag is not None and not (sen.get("predict") and est is None)
     if once:
-        if sensor:
+        if sensors:
             label, sen, xs = sensors[-1] if predict else sensors[0]
-            mpc.simulate(x0, ub, stuck, xs, T, sensor=sen, estimator=est, **(witho if outcomes else withf), **kw)
+            mpc.simulate(x0, ub, stuck, xs, T, sensor=sen, estimator=est, diagnosis=diag if with_diag(sen) else None,
+                         **(witho if outcomes else withf), **kw)
         if actuator:
             mpc.simulate(x0, ub, stuck, xr, T, actuator=act, **(witho if outcomes else withf), **kw)
         if with_mission:
@@ -188,6 +205,11 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
             runs += [("without_" + label + "_estimator", dict(plain, sensor=sen, estimator=est), ub, stuck),
                      ("with_" + label + "_estimator", dict(withf, sensor=sen, estimator=est), ub, stuck)]
             refs["without_" + label + "_estimator"] = refs["with_" + label + "_estimator"] = xs
+        if with_diag(sen):
+            e = "_estimator" if est is not None else ""
+            runs += [("without_" + label + e + "_diagnosis", dict(plain, sensor=sen, estimator=est, diagnosis=diag), ub, stuck),
+                     ("with_" + label + e + "_diagnosis", dict(withf, sensor=sen, estimator=est, diagnosis=diag), ub, stuck)]
+            refs["without_" + label + e + "_diagnosis"] = refs["with_" + label + e + "_diagnosis"] = xs
     for label, extra, u, s in runs:
         u, s = np.ascontiguousarray(u), np.ascontiguousarray(s)
         ref = None if "mission" in extra else refs.get(label, xr)      # a mission's tables are the reference
@@ -202,6 +224,17 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
                           alloc_failed=int(out.get("alloc_failed", np.zeros(1)).sum()))
         if "estimator" in out:     # root mean squared position error of the estimates over the call
             res[label]["est_rms_pos_m"] = float(np.sqrt(out["estimator"]["err_sq"][:, 0].mean() / T))
+        if "diagnosis" in out:     # what was found: against the schedule's events where the loop has one, else every detection is false
+            det = detections_of(*(out["diagnosis"][k] for k in ("step", "thruster", "level")))
+            ev = [[] for _ in range(B)]
+            if "faults" in extra:
+                new = (f["ub"][:, 0] == 0) & (u > 0)
+                ev = [[(int(f["onset"][b, 0]), int(i), -1) for i in np.flatnonzero(new[b])] for b in range(B)]
+            sc = score(ev, det)
+            delays = [d for d in sc.pop("delay") if d is not None]
+            sc.pop("wrong_level")      # (the events stick at a random intensity: no level is the right one)
+            res[label].update(detections=int(sum(len(d) for d in det)), score=sc,
+                              delay_mean=float(np.mean(delays)) if delays else None, delay_max=int(max(delays)) if delays else None)
         if "actuator" in out:      # what the valves delivered and how often they opened, per vehicle and step
             res[label].update(delivered_mean_Ns=float(out["actuator"]["delivered"].mean()),
                               pulses_per_step=float(out["actuator"]["pulses"].mean()) / T)
@@ -222,6 +255,13 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
             for w in ("without_", "with_"):
                 res[f"ratio_{label}_estimator_over_{w}{label}"] = res[w + label + "_estimator"]["steps_per_s"] / res[w + label]["steps_per_s"]
                 res[f"ms_per_step_estimator_{w}{label}"] = (res[w + label + "_estimator"]["ms"] - res[w + label]["ms"]) / T
+            res["every"] = every
+        if with_diag(dict(predict="_predict" in label)):      # the same loop with the diagnosis against without
+            e = "_estimator" if est is not None else ""
+            for w in ("without_", "with_"):
+                res[f"ratio_{label}{e}_diagnosis_over_{w}{label}{e}"] = res[w + label + e + "_diagnosis"]["steps_per_s"] / res[w + label + e]["steps_per_s"]
+                res[f"ms_per_call_diagnosis_{w}{label}{e}"] = res[w + label + e + "_diagnosis"]["ms"] - res[w + label + e]["ms"]
+                res[f"ms_per_step_diagnosis_{w}{label}{e}"] = (res[w + label + e + "_diagnosis"]["ms"] - res[w + label + e]["ms"]) / T
             res["every"] = every
     if actuator:
         res["ratio_actuator_over_without"] = res["without_actuator"]["steps_per_s"] / res["without"]["steps_per_s"]
@@ -258,7 +298,13 @@ def stats(path):
     sn, sus = per_launch("ftmpc_sense_kernel")
     f0n, f0us = per_launch("ftmpc_filter_kernel<0>")
     f1n, f1us = per_launch("ftmpc_filter_kernel<1>")
-    return dict(filter_update_kernel_calls=f0n, filter_update_kernel_avg_us=f0us, filter_time_kernel_calls=f1n, filter_time_kernel_avg_us=f1us,
+    d0n, d0us = per_launch("ftmpc_diagnose_kernel<0>")
+    d1n, d1us = per_launch("ftmpc_diagnose_kernel<1>")
+    rn, rus = per_launch("ftmpc_diagnose_repair_kernel")
+    return dict(diagnose_test_kernel_calls=d0n, diagnose_test_kernel_avg_us=d0us, diagnose_model_kernel_calls=d1n, diagnose_model_kernel_avg_us=d1us,
+                diagnose_repair_kernel_calls=rn, diagnose_repair_kernel_avg_us=rus,
+                diagnose_kernel_share=(d0n * d0us + d1n * d1us + rn * rus) * 1e3 / tot if tot else 0.0,
+                filter_update_kernel_calls=f0n, filter_update_kernel_avg_us=f0us, filter_time_kernel_calls=f1n, filter_time_kernel_avg_us=f1us,
                 filter_kernel_share=(f0n * f0us + f1n * f1us) * 1e3 / tot if tot else 0.0,
                 sense_kernel_calls=sn, sense_kernel_avg_us=sus, sense_kernel_share=sn * sus * 1e3 / tot if tot else 0.0,
                 plant_act_kernel_calls=an, plant_act_kernel_avg_us=aus, plant_act_kernel_share=an * aus * 1e3 / tot if tot else 0.0,
@@ -305,6 +351,7 @@ def main():
     ap.add_argument("--predict", action="store_true")
     ap.add_argument("--estimator", action="store_true")
     ap.add_argument("--every", type=int, default=1)
+    ap.add_argument("--diagnosis", action="store_true")
     a = ap.parse_args()
     if a.stats:
         print(json.dumps(stats(a.stats)))
@@ -316,7 +363,7 @@ def main():
     out = []
     for n in names:
         r = run(n, a.reps, a.once, a.outcomes, a.slots, a.dispersion, a.mission, a.actuator, a.substeps, a.sensor, tuple(a.latency), a.predict,
-                a.estimator, a.every)
+                a.estimator, a.every, a.diagnosis)
         if r is not None:
             print(json.dumps(r))
             out.append(r)
