@@ -1975,6 +1975,42 @@ int ftmpc_debug_records(ftmpc_handle* h, int64_t B, const double* x0, const doub
     return FTMPC_OK;
 }
 
+int ftmpc_debug_struct_grad(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                            const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                            const double* warmU, const float* d, int32_t form, double* g_out) {
+    if (!h || !d || !g_out || B <= 0 || form < 0 || form > 1) return FTMPC_ERR_ARG;
+    const int N = h->cfg.N, NT = h->cfg.NT;
+    if (h->use_f64 || N > ftmpc::SGD_NMAX || NT > 8)
+        return fail(h, FTMPC_ERR_ARG, "the gradient hook serves the fp32 path with N <= 21 and NT <= 8 (the shapes whose sweeps exchange through LDS)");
+    // the records, as ftmpc_debug_records leaves them on the device
+    std::vector<double> rec((size_t)B * N * ftmpc::REC_STRIDE);
+    int rc = ftmpc_debug_records(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, warmU, rec.data());
+    if (rc != FTMPC_OK) return rc;
+    hipStream_t s = h->stream;
+    const int64_t words = B * N * NT;
+    DevBuf<float> d_d;
+    DevBuf<double> d_g;
+    if ((rc = d_d.ensure(h, words)) != FTMPC_OK || (rc = d_g.ensure(h, words)) != FTMPC_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(d_d, d, (size_t)words * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(d_g, 0, (size_t)words * sizeof(double), s));
+    ftmpc::StructGradDebugParams q;
+    q.B = B;
+    q.rec = h->rec;
+    q.ub = h->d_ub;
+    q.d = d_d;
+    q.g = d_g;
+    // fewer workgroups than instances (from B = 2 on): a wave meets the LDS its previous instance left behind
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((B + 2) / 3, 4 * (int64_t)h->num_cu));
+    if (form == 1)
+        hipLaunchKernelGGL(ftmpc::ftmpc_struct_grad_debug_kernel<true>, dim3(grid), dim3(64), 0, s, h->dc, q);
+    else
+        hipLaunchKernelGGL(ftmpc::ftmpc_struct_grad_debug_kernel<false>, dim3(grid), dim3(64), 0, s, h->dc, q);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(g_out, d_g, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return FTMPC_OK;
+}
+
 int ftmpc_simulate_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                          const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                          double* u_hist, int32_t* not_converged) {

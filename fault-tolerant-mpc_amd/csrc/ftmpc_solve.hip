@@ -685,12 +685,203 @@ static_assert(offsetof(DeviceConsts, Q) == offsetof(DeviceConsts, D) + 8 * CT_Q 
               offsetof(DeviceConsts, P) == offsetof(DeviceConsts, D) + 8 * CT_P && offsetof(DeviceConsts, LPt) == offsetof(DeviceConsts, D) + 8 * CT_LPT &&
               offsetof(DeviceConsts, sq2Q) == offsetof(DeviceConsts, D) + 8 * CT_SQ2Q && offsetof(DeviceConsts, rho) == offsetof(DeviceConsts, D) + 8 * CT_WORDS,
               "the constant table is the run D .. sq2Q of DeviceConsts");
+// ---- the same two sweeps as row-per-lane float64 FMAs (struct_grad_at<.., VEC = true>) ----------------------------------
+// A float64 MFMA holds the pipe that the fp32 MFMAs and the VALU share for 64 cycles and does 1024 multiply-adds for at most
+// 52 useful ones; a matrix-vector product does not belong there.  Here lane m < 13 owns row m of [A_k | B_k] (forward) or of
+// A_k' (adjoint; lanes 16..21 the rows of B_k'), fetches its matrix entries from the stage record through the same word table,
+// and takes the vector it multiplies from LDS at wave-uniform addresses (broadcast reads, which do not use that pipe): 19
+// v_fma_f64 per forward stage and 13 + 6 per adjoint stage.  Everything is exchanged through LDS (one wave, in-order LDS: a
+// compiler barrier orders it), so this form exists only where the stage storage and the gradient are in LDS.
+// The sums are taken in the MFMA form's own order (two accumulators: columns 0-3, 8-11, wrench 0-3 | 4-7, 12, wrench 4-5).
+// Scratch: SGV_WORDS doubles behind the wrench perturbations (gout + GOFF + 8 N): dc | lambda | z.
+constexpr int SGV_DC = 0, SGV_LAM = 16, SGV_Z = 32, SGV_WORDS = 40;
+template <int GOFF, class CPtr>
+__device__ __forceinline__ void struct_grad_vec(int N, double dt, CPtr ctab, glb_cf64* recg, lds_f64* recd, lds_cf32* s_Da,
+                                                lds_cf32* dnat, lds_f64* sS, lds_f64* gout, int na, int lane) {
+#pragma clang fp contract(off)      // (every fused multiply-add below is spelled out)
+    const int m = lane & 15;
+    const int m9 = (m < 9) ? m : 8;                      // clamped row of the nine costed components
+    lds_f64* const genS = gout + GOFF;
+    lds_f64* const dcL = genS + 8 * N + SGV_DC;
+    lds_f64* const lamL = genS + 8 * N + SGV_LAM;
+    lds_f64* const zL = genS + 8 * N + SGV_Z;
+    if (lane == 0) {
+        recd[REC_STRIDE] = 0.0;
+        recd[REC_STRIDE + 1] = 1.0;
+        recd[REC_STRIDE + 2] = dt;
+    }
+    if (lane < 16) dcL[lane] = 0.0;                      // dc_0 = 0
+    // record prefetch as in the MFMA form: four stages ahead, four statically named register sets, branch-free
+    double pf[4][3];
+    const int w2 = (lane + 128 < REC_STRIDE) ? lane + 128 : REC_STRIDE - 1;
+    const int d2 = (lane + 128 < REC_STRIDE) ? lane + 128 : REC_STRIDE + 3;
+    auto issue_rec = [&](auto SL, int kk) {
+        constexpr int sl = decltype(SL)::value;
+        glb_cf64* r = recg + (int64_t)kk * REC_STRIDE;
+        pf[sl][0] = r[lane];
+        pf[sl][1] = r[lane + 64];
+        pf[sl][2] = r[w2];
+    };
+    auto stage_to_lds = [&](auto SL) {
+        constexpr int sl = decltype(SL)::value;
+        recd[lane] = pf[sl][0];
+        recd[lane + 64] = pf[sl][1];
+        recd[d2] = pf[sl][2];
+    };
+    using S0 = std::integral_constant<int, 0>;
+    using S1 = std::integral_constant<int, 1>;
+    using S2 = std::integral_constant<int, 2>;
+    using S3 = std::integral_constant<int, 3>;
+    const int N4 = N & ~3;
+    issue_rec(S0{}, 0);
+    issue_rec(S1{}, (1 < N) ? 1 : 0);
+    issue_rec(S2{}, (2 < N) ? 2 : 0);
+    issue_rec(S3{}, (3 < N) ? 3 : 0);
+    // wrench perturbations gen_k = Da d_k of all stages (the same sums as the MFMA form)
+    for (int t = lane; t < N * 8; t += 64) {
+        const int k = t >> 3, g = t & 7;
+        double acc = 0.0;
+        if (g < 6)
+            for (int a = 0; a < na; ++a) acc = __builtin_fma((double)s_Da[g * MAX_NT + a], (double)dnat[k * na + a], acc);
+        genS[t] = acc;
+    }
+    // this lane's row of [A | B]: where its 19 entries lie in the stage record (rows 13..15: the zero word)
+    lds_f64* pX[19];
+#pragma unroll
+    for (int c = 0; c < 19; ++c) pX[c] = recd + k_aoff.v[m][c];
+    const double qm = ctab[CT_Q + m9];
+    wave_lds_fence();
+    // ---- forward sweep: dc_{k+1} = A_k dc_k + B_k gen_k,  s_{k+1} = W (e_bar + dc_{k+1})[0:9] ----
+    const bool hand_on = N4 == N;
+    auto fwd = [&](auto SL, int k) {
+        wave_lds_fence();
+        stage_to_lds(SL);
+        issue_rec(SL, (k + 4 < N) ? k + 4 : (hand_on ? 2 * N - 5 - k : N - 1));
+        wave_lds_fence();
+        lds_f64* const gk = genS + k * 8;
+        double x[19];
+#pragma unroll
+        for (int c = 0; c < 13; ++c) x[c] = dcL[c];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) x[13 + c] = gk[c];
+        double nx = 0.0, ny = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) nx = __builtin_fma(*pX[c], x[c], nx);
+#pragma unroll
+        for (int c = 4; c < 8; ++c) ny = __builtin_fma(*pX[c], x[c], ny);
+#pragma unroll
+        for (int c = 8; c < 12; ++c) nx = __builtin_fma(*pX[c], x[c], nx);
+        ny = __builtin_fma(*pX[12], x[12], ny);
+#pragma unroll
+        for (int c = 13; c < 17; ++c) nx = __builtin_fma(*pX[c], x[c], nx);
+#pragma unroll
+        for (int c = 17; c < 19; ++c) ny = __builtin_fma(*pX[c], x[c], ny);
+        const double v = nx + ny;
+        wave_lds_fence();
+        if (lane < 13) dcL[lane] = v;
+        double t;
+        if (k + 1 == N) {   // terminal weight P (9 x 9): row m9 against the new dc
+            wave_lds_fence();
+            t = 0.0;
+#pragma unroll
+            for (int j = 0; j < 9; ++j) t = __builtin_fma((double)ctab[CT_P + 9 * m9 + j], dcL[j], t);
+        } else {
+            t = qm * v;
+        }
+        const double s = recd[REC_WE + m9] + t;
+        if (lane < 9) sS[(k + 1) * 9 + lane] = s;
+    };
+    for (int k = 0; k < N4; k += 4) {
+        fwd(S0{}, k);
+        fwd(S1{}, k + 1);
+        fwd(S2{}, k + 2);
+        fwd(S3{}, k + 3);
+    }
+    for (int k = N4; k < N; ++k) {   // N not a multiple of 4: the tail reloads its stage (latency exposed)
+        issue_rec(S0{}, k);
+        fwd(S0{}, k);
+    }
+    wave_lds_fence();
+    // ---- adjoint sweep (stage N-1-i uses register set i & 3) ----
+    // lanes 0..12: row m of A_k' (column m of the table); lanes 16..21: row g of B_k' (column 13 + g); the rest: the zero word
+    const bool isB = lane >= 16 && lane < 22;
+    const int gi = isB ? lane - 16 : 0;
+    const int col = (lane < 13) ? lane : (isB ? 13 + gi : 19);
+    lds_f64* pT[13];
+#pragma unroll
+    for (int r = 0; r < 13; ++r) pT[r] = recd + k_aoff.v[r][col];
+    const double rg = isB ? (double)ctab[CT_R + gi] : 0.0;
+    double da[6];                                         // column a = lane of Da
+#pragma unroll
+    for (int g = 0; g < 6; ++g) da[g] = (double)s_Da[g * MAX_NT + m];
+    {   // lambda_N = [s_N; 0]
+        const double sN = sS[N * 9 + m9];
+        if (lane < 16) lamL[lane] = (lane < 9) ? sN : 0.0;
+    }
+    auto adj = [&](auto SL, int k) {
+        wave_lds_fence();
+        stage_to_lds(SL);
+        issue_rec(SL, (k - 4 >= 0) ? k - 4 : 0);
+        wave_lds_fence();
+        double l[13];
+#pragma unroll
+        for (int r = 0; r < 13; ++r) l[r] = lamL[r];
+        double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a0 = __builtin_fma(*pT[r], l[r], a0);
+#pragma unroll
+        for (int r = 4; r < 8; ++r) a1 = __builtin_fma(*pT[r], l[r], a1);
+#pragma unroll
+        for (int r = 8; r < 12; ++r) a0 = __builtin_fma(*pT[r], l[r], a0);
+        a1 = __builtin_fma(*pT[12], l[12], a1);
+        const double v = a0 + a1;
+        // z_g = B_k' lambda_{k+1} + R ut_bar + R gen_k (lanes 16..21);  lambda_k = A_k' lambda_{k+1} + [s_k; 0] (lanes 0..12)
+        lds_f64* const ap = isB ? recd + REC_RUT + gi : sS + k * 9 + m9;
+        const double av = *ap;
+        const double add = (isB || lane < 9) ? av : 0.0;
+        const double res = __builtin_fma(rg, genS[k * 8 + gi], v + add);      // (rg = 0 on the lambda rows)
+        wave_lds_fence();
+        if (isB) zL[gi] = res;
+        if (lane < 13 && k > 0) lamL[lane] = res;
+        wave_lds_fence();
+        // g_{k,a} = 2 Da[:,a]' z
+        double ga = 0.0;
+#pragma unroll
+        for (int g = 0; g < 6; ++g) ga = __builtin_fma(da[g], zL[g], ga);
+        if (lane < na) gout[k * na + lane] = 2.0 * ga;
+    };
+    if (!hand_on) {
+        issue_rec(S0{}, N - 1);
+        issue_rec(S1{}, (N - 2 >= 0) ? N - 2 : 0);
+        issue_rec(S2{}, (N - 3 >= 0) ? N - 3 : 0);
+        issue_rec(S3{}, (N - 4 >= 0) ? N - 4 : 0);
+    }
+    int ka = N - 1;
+    for (; ka >= 3; ka -= 4) {
+        adj(S0{}, ka);
+        adj(S1{}, ka - 1);
+        adj(S2{}, ka - 2);
+        adj(S3{}, ka - 3);
+    }
+    for (; ka >= 0; --ka) {
+        issue_rec(S0{}, ka);
+        adj(S0{}, ka);
+    }
+    wave_lds_fence();
+}
+
 // GOFF: offset (doubles) of the wrench scratch behind the gradient (>= n)
+// VEC: the vector form above instead of the MFMA chains (LDS exchange only)
 // SPtr: stage storage, lds_f64* when it fits behind the vectors, else glb_f64* (long horizons).  GPtr: the gradient and the wrench
 // perturbations, lds_f64* (the tile area of the build, dead during the iteration) or glb_f64* (the global slot).  CPtr: see above.
-template <class SPtr, class GPtr, class CPtr, int GOFF = 160>
+template <class SPtr, class GPtr, class CPtr, int GOFF = 160, bool VEC = false>
 __device__ __noinline__ void struct_grad_at(int N, double dt, CPtr ctab, glb_cf64* recg, lds_f64* recd, lds_cf32* s_Da,
                                             lds_cf32* dnat, SPtr sS, GPtr gout, int na, int lane) {
+    if constexpr (VEC) {
+        static_assert(std::is_same<SPtr, lds_f64*>::value && std::is_same<GPtr, lds_f64*>::value, "the vector form exchanges through LDS");
+        struct_grad_vec<GOFF>(N, dt, ctab, recg, recd, s_Da, dnat, sS, gout, na, lane);
+        return;
+    }
     constexpr int ZERO = REC_STRIDE;
     // lanes exchange the wrench perturbations, the stage storage and the gradient: through LDS a compiler barrier orders them
     // (one wave, in-order LDS), through the global slot the stores must have landed
@@ -1006,6 +1197,9 @@ static_assert(tile_row_ok(), "state-component permutation of the sensitivity til
 #endif
 #ifndef FTMPC_F32_OCC
 #define FTMPC_F32_OCC 2
+#endif
+#ifndef FTMPC_F32_GRAD_VEC
+#define FTMPC_F32_GRAD_VEC 1           // float64 gradient sweeps as vector FMAs where they exchange through LDS (NB = 8, N <= 21); 0: MFMA chains
 #endif
 template <int NB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 8) ? FTMPC_F32_OCC : 1, (NB == 8) ? FTMPC_F32_OCC : 1))) ftmpc_solve_f32_kernel(const DeviceConsts C, const SolveParams P) {
@@ -1482,13 +1676,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
                 // build where that is free during the iteration (NB = 8 at two waves: the Hessian lives in the global slot) and the
                 // stage storage is in LDS as well (NB = 8: N <= 21); every other case exchanges through the global slot as before.
                 constexpr bool GLDS = OCC2;
-                static_assert(!GLDS || (160 + 8 * (SAVAIL / 72 - 1)) * 2 <= BUILD_WORDS, "gradient and wrench perturbations beyond the tile area");
+                // With everything in LDS the sweeps run as vector FMAs (struct_grad_vec: FTMPC_F32_GRAD_VEC, 0 = the MFMA chains), whose
+                // three exchange vectors lie behind the wrench perturbations.
+                static_assert(!GLDS || (160 + 8 * (SAVAIL / 72 - 1) + SGV_WORDS) * 2 <= BUILD_WORDS,
+                              "gradient, wrench perturbations and the vector form's exchange beyond the tile area");
                 lds_f64* const gout_l = (lds_f64*)reinterpret_cast<double*>(tiles);
                 const bool s_in_lds = (N + 1) * 72 <= SAVAIL;
                 if (s_in_lds) {
                     if constexpr (GLDS)
-                        struct_grad_at(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
-                                    (lds_f64*)reinterpret_cast<double*>(dvp), gout_l, na, lane);
+                        struct_grad_at<lds_f64*, lds_f64*, CPtr, 160, (FTMPC_F32_GRAD_VEC != 0)>(
+                            N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
+                            (lds_f64*)reinterpret_cast<double*>(dvp), gout_l, na, lane);
                     else
                         struct_grad_at(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)reinterpret_cast<double*>(recbuf), (lds_cf32*)s_Da, (lds_cf32*)xvp,
                                     (lds_f64*)reinterpret_cast<double*>(dvp), (glb_f64*)gout, na, lane);
@@ -1893,5 +2091,62 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((NB == 
 template __global__ void ftmpc_solve_f32_kernel<8>(const DeviceConsts, const SolveParams);
 template __global__ void ftmpc_solve_f32_kernel<9>(const DeviceConsts, const SolveParams);
 template __global__ void ftmpc_solve_f32_kernel<10>(const DeviceConsts, const SolveParams);
+
+// ---- test hook (ftmpc_debug_struct_grad): the float64 reference gradient alone, either form, at a caller-supplied d ----
+// One wave per workgroup loops over the instances b = blockIdx.x, + gridDim.x, ..; s_Da, the constant table and d in natural
+// order are prepared as the prologue of ftmpc_solve_f32_kernel prepares them, and everything is exchanged through LDS (the
+// case both forms serve).  LDS is not cleared between instances on purpose: what one leaves behind meets the next.
+constexpr int SGD_NMAX = 21;                  // longest horizon with the stage storage in LDS (NB = 8)
+constexpr int SGD_GOFF = 176;                 // n <= 21 * 8 = 168 here (the solve kernels: n <= 160)
+struct StructGradDebugParams {
+    int64_t B;
+    const void* rec;        // [B*N*REC_STRIDE] doubles
+    const double* ub;       // [B*NT]
+    const float* d;         // [B*N*NT], instance b's n = N na values first, natural order (stage-major)
+    double* g;              // [B*N*NT], likewise
+};
+template <bool VEC>
+__global__ void __launch_bounds__(64) ftmpc_struct_grad_debug_kernel(const DeviceConsts C, const StructGradDebugParams P) {
+    __shared__ __attribute__((aligned(16))) double s_g[SGD_GOFF + 8 * SGD_NMAX + SGV_WORDS];
+    __shared__ __attribute__((aligned(16))) double s_rec[REC_STRIDE + 4];
+    __shared__ __attribute__((aligned(16))) double s_stage[(SGD_NMAX + 1) * 9];
+    __shared__ __attribute__((aligned(16))) float s_d[SGD_NMAX * MAX_NT];
+    __shared__ __attribute__((aligned(16))) float s_Da[6 * MAX_NT];
+    __shared__ int s_act[MAX_NT];
+    __shared__ double s_ctab[CT_WORDS];
+    karg_cf64* const kctab = (karg_cf64*)((__attribute__((address_space(4))) const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(DeviceConsts, D));
+    for (int i = threadIdx.x; i < CT_WORDS; i += 64) s_ctab[i] = kctab[i];
+    wave_lds_fence();
+    lds_cf64* const ctab = (lds_cf64*)s_ctab;
+    const int lane = threadIdx.x;
+    const int N = C.N, NT = C.NT;
+    if (N > SGD_NMAX || NT > 8) return;      // (the host entry refuses these shapes)
+    for (int64_t inst = blockIdx.x; inst < P.B; inst += gridDim.x) {
+        wave_lds_fence();
+        double ub_l = 0.0;
+        if (lane < NT) ub_l = P.ub[inst * NT + lane];
+        const unsigned long long amask = __ballot(lane < NT && ub_l > 0.0);
+        const int na = __popcll(amask);
+        const int n = N * na;
+        double* const gb = P.g + inst * (int64_t)N * NT;
+        if (na == 0) continue;
+        const int myrank = __popcll(amask & ((1ull << lane) - 1ull));
+        if (lane < NT && ub_l > 0.0) s_act[myrank] = lane;
+        wave_lds_fence();
+        if (lane < na) {
+#pragma unroll
+            for (int g = 0; g < 6; ++g) s_Da[g * MAX_NT + lane] = (float)ctab[CT_D + g * MAX_NT + s_act[lane]];
+        }
+        for (int e = lane; e < n; e += 64) s_d[e] = P.d[inst * (int64_t)N * NT + e];
+        wave_lds_fence();
+        const double* recg = reinterpret_cast<const double*>(P.rec) + inst * (int64_t)N * REC_STRIDE;
+        struct_grad_at<lds_f64*, lds_f64*, lds_cf64*, SGD_GOFF, VEC>(N, C.dt, ctab, (glb_cf64*)recg, (lds_f64*)s_rec, (lds_cf32*)s_Da, (lds_cf32*)s_d,
+                                                                    (lds_f64*)s_stage, (lds_f64*)s_g, na, lane);
+        wave_lds_fence();
+        for (int e = lane; e < n; e += 64) gb[e] = s_g[e];
+    }
+}
+template __global__ void ftmpc_struct_grad_debug_kernel<false>(const DeviceConsts, const StructGradDebugParams);
+template __global__ void ftmpc_struct_grad_debug_kernel<true>(const DeviceConsts, const StructGradDebugParams);
 
 }  // namespace ftmpc

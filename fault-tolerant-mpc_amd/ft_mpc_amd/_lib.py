@@ -27,7 +27,7 @@ KERNEL_AUTO, KERNEL_DENSE, KERNEL_WORKGROUP, KERNEL_RICCATI = 0, 1, 2, 3
 SYMBOLS = (
     "ftmpc_default_config", "ftmpc_create", "ftmpc_destroy", "ftmpc_last_error", "ftmpc_reserve",
     "ftmpc_solve_batch", "ftmpc_solve_batch_device", "ftmpc_solve_sqp_batch", "ftmpc_sqp_graph_launches", "ftmpc_solve_wrench_batch", "ftmpc_eval_cost_batch", "ftmpc_simulate_batch", "ftmpc_simulate_batch_ex", "ftmpc_simulate_wrench_batch", "ftmpc_simulate_wrench_batch_ex", "ftmpc_simulate_faults_batch", "ftmpc_simulate_wrench_faults_batch", "ftmpc_simulate_outcomes_batch", "ftmpc_simulate_wrench_outcomes_batch", "ftmpc_simulate_plant_batch", "ftmpc_simulate_wrench_plant_batch", "ftmpc_simulate_mission_batch", "ftmpc_simulate_wrench_mission_batch", "ftmpc_simulate_actuator_batch", "ftmpc_simulate_wrench_actuator_batch", "ftmpc_simulate_sensor_batch", "ftmpc_simulate_wrench_sensor_batch", "ftmpc_simulate_estimator_batch", "ftmpc_simulate_wrench_estimator_batch", "ftmpc_eval_cost_wrench_batch", "ftmpc_solve_sqp_wrench_batch", "ftmpc_last_handed_over", "ftmpc_allocate_batch", "ftmpc_shift_warm", "ftmpc_set_profiling",
-    "ftmpc_last_kernel_ms", "ftmpc_kernel_name", "ftmpc_routed_kernel_name", "ftmpc_multi_routed_kernel_name", "ftmpc_debug_build_qp", "ftmpc_debug_records", "ftmpc_version", "ftmpc_build_id",
+    "ftmpc_last_kernel_ms", "ftmpc_kernel_name", "ftmpc_routed_kernel_name", "ftmpc_multi_routed_kernel_name", "ftmpc_debug_build_qp", "ftmpc_debug_records", "ftmpc_debug_struct_grad", "ftmpc_version", "ftmpc_build_id",
     "ftmpc_multi_create", "ftmpc_multi_destroy", "ftmpc_multi_last_error", "ftmpc_multi_device_count", "ftmpc_multi_worker_cpus",
     "ftmpc_multi_shard_bounds", "ftmpc_multi_solve_batch", "ftmpc_multi_upload", "ftmpc_multi_step",
     "ftmpc_multi_download", "ftmpc_multi_set_profiling", "ftmpc_multi_last_kernel_ms",
@@ -240,6 +240,7 @@ def load_library() -> C.CDLL:
     lib.ftmpc_debug_build_qp.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, C.c_int64,
                                          dp, C.c_int64, dp, dp, dp, ip]
     lib.ftmpc_debug_records.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp]
+    lib.ftmpc_debug_struct_grad.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, C.POINTER(C.c_float), C.c_int32, dp]
     lib.ftmpc_version.restype = C.c_int32
     lib.ftmpc_build_id.restype = C.c_char_p
     lib.ftmpc_multi_create.argtypes = [C.POINTER(ftmpc_config), ip, C.c_int32, C.POINTER(vp)]

@@ -593,6 +593,23 @@ class BatchedMPC:
                                                  _ptr(uref), us, _ptr(warm), _ptr(rec)))
         return rec
 
+    def debug_struct_grad(self, x0, ub, stuck, xref, d, form, uref=None, warmU=None):
+        """The float64 reference gradient of the fp32 solve kernels at `d` [B, N*NT] (float32; an instance's n = N*na values
+        first, stage-major over its active thrusters), without the 2 rho (ubar + d) term: [B, N*NT] float64 in the same layout.
+        form 0: the MFMA chains, 1: the vector FMAs.  fp32 handles with N <= 21, NT <= 8."""
+        N, NT = self.cfg.N, self.cfg.NT
+        x0 = _f64(x0).reshape(-1, 13)
+        B = x0.shape[0]
+        ub = _f64(ub, (B, NT))
+        stuck = _f64(stuck, (B, NT))
+        xref, xs, uref, us = self._refs(B, xref, uref)
+        warm = None if warmU is None else _f64(warmU, (B, N, NT))
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(B, N * NT)
+        g = np.zeros((B, N * NT))
+        self._check(self.lib.ftmpc_debug_struct_grad(self._h, B, _ptr(x0), _ptr(ub), _ptr(stuck), _ptr(xref), xs,
+                                                     _ptr(uref), us, _ptr(warm), _ptr(d, C.c_float), int(form), _ptr(g)))
+        return g
+
 
 OUTCOME_FIELDS = (("err_int", 3, np.float64), ("err_max", 3, np.float64), ("impulse", 2, np.float64), ("settle_step", 0, np.int32),
                   ("tset_step", 0, np.int32), ("unsolved", 0, np.int32), ("first_unsolved", 0, np.int32), ("alloc_failed", 0, np.int32))

@@ -944,6 +944,21 @@ int ftmpc_debug_records(ftmpc_handle* h, int64_t B,
                         const double* warmU, double* rec_out);
 
 /*
+ * Test hook: the float64 reference gradient of the fp32 solve kernels (csrc/ftmpc_solve.hip, struct_grad_at) alone.  Linearises
+ * the host batch as ftmpc_debug_records does, then evaluates, per instance b with na active thrusters and n = N * na variables,
+ *     g = 2 Bbar' Wbar (e_bar + Bbar d) + 2 Da' R (ut_bar + Da d)          (without the 2 rho (u_bar + d) term)
+ * at the caller's d: d [B * N * NT] floats, instance b's n values first at b * N * NT, stage-major over the active thrusters in
+ * ascending order; g_out [B * N * NT] doubles in the same layout (the rest zero).
+ * form 0: the sweeps as float64 MFMA chains; form 1: as row-per-lane vector FMAs.  Both exchange through LDS, which limits the
+ * hook to fp32 handles with N <= 21 and NT <= 8.  The launch has fewer workgroups than instances.
+ */
+int ftmpc_debug_struct_grad(ftmpc_handle* h, int64_t B,
+                            const double* x0, const double* ub, const double* stuck,
+                            const double* xref, int64_t xref_stride,
+                            const double* uref, int64_t uref_stride,
+                            const double* warmU, const float* d, int32_t form, double* g_out);
+
+/*
  * The batch axis across the GPUs of one node from ONE process.  The reference
  * never couples instances (one controller object per vehicle, spiraling_mpc.py:288-317), so device g owns
  * the contiguous range [B g / G, B (g+1) / G) (ftmpc_multi_shard_bounds); one host thread + one handle + one
