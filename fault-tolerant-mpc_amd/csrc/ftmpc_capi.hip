@@ -2022,6 +2022,8 @@ struct WrenchLoop {      // the two-stage structure inside the closed loop: hull
     bool has_set;
     int32_t* alloc_failed;   // host [T] or null
     double penalty;          // the wrench SQP's merit weight (sqp_iters > 0)
+    double* out_hull_b;      // host [B*hull_rows] or null: the controller's offsets after the last step
+    int32_t* no_hull_step;   // host [B] or null, in/out (under a diagnosis): the step of the first detection that left no hull
 };
 
 static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
@@ -2322,6 +2324,19 @@ static std::string diagnosis_problem(const ftmpc_diagnosis* dg, int64_t B, int N
     return "";
 }
 
+// What the wrench form adds to a diagnosis' refusals: the schedule of such a call moves the plant only, so it carries no hull tables,
+// and a handed no_hull_step entry is -1 or a step (first: number of vehicle 0 in the caller's batch)
+static std::string wrench_diagnosis_problem(const ftmpc_fault_schedule* fs, const int32_t* no_hull_step, int64_t B, int64_t first = 0) {
+    if (fs && fs->struct_size == (int32_t)sizeof(ftmpc_fault_schedule)) {
+        if (fs->hull_set) return "ftmpc_diagnosis: ftmpc_fault_schedule.hull_set must be NULL (the schedule moves the plant only, the diagnosis rebuilds the offsets)";
+        if (fs->hull_b) return "ftmpc_diagnosis: ftmpc_fault_schedule.hull_b must be NULL (the schedule moves the plant only, the diagnosis rebuilds the offsets)";
+    }
+    if (no_hull_step)
+        for (int64_t b = 0; b < B; ++b)
+            if (no_hull_step[b] < -1) return "no_hull_step: vehicle " + std::to_string(first + b) + " has an entry below -1";
+    return "";
+}
+
 // An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
 static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
     if (!oc) return FTMPC_OK;
@@ -2565,28 +2580,96 @@ int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
                                           const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                           const ftmpc_estimator* estimator) {
+    return ftmpc_simulate_wrench_diagnosis_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                                 seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                                 out, plant, mission, actuator, sensor, estimator, nullptr, nullptr, nullptr);
+}
+
+int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                          int32_t* no_hull_step) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    if ((rc = check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK) return rc;
+    if (diagnosis) {     // the schedule moves the plant only: checked as the thruster form's, which has no hull fields
+        const std::string msg = wrench_diagnosis_problem(faults, no_hull_step, B);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
+    if ((rc = diagnosis ? check_schedule(h, B, faults, false, 0, false) : check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK)
+        return rc;
     if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
     if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
     if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
     if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
+    {
+        const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
         if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
+        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * h->cfg.NT, diagnosis->ub);
+        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * h->cfg.NT, diagnosis->stuck);
+        if (out_hull_b && B > 0 && hull_rows > 0) std::copy(hull_b, hull_b + B * hull_rows, out_hull_b);
         return FTMPC_OK;
     }
     if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
-    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0};
+    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0,
+                  out_hull_b, diagnosis ? no_hull_step : nullptr};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
                          sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor,
-                         estimator);
+                         estimator, diagnosis);
+}
+
+int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const double* stuck, const double* hull_A, int32_t n_sets,
+                             const int32_t* hull_set, int32_t hull_rows, double* out_b, int32_t* out_flat) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0 || !ub || !stuck || !hull_A || !out_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
+    if (hull_rows < 1 || hull_rows > FTMPC_MAX_HULL_ROWS || n_sets < 1) return fail(h, FTMPC_ERR_ARG, "hull_rows out of range (1..128) or no hull table");
+    if (hull_set)   // the kernel indexes hull_A by these
+        for (int64_t b = 0; b < B; ++b)
+            if (hull_set[b] < 0 || hull_set[b] >= n_sets)
+                return fail(h, FTMPC_ERR_ARG, "hull_set[" + std::to_string(b) + "] = " + std::to_string(hull_set[b]) + " is not a table number in [0, n_sets)");
+    if (B == 0) return FTMPC_OK;
+    const int NT = h->cfg.NT;
+    const size_t nA = (size_t)n_sets * hull_rows * 6, nP = (size_t)B * NT, nB = (size_t)B * hull_rows;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DevBuf<double> d_A, d_pat, d_b;
+    DevBuf<int32_t> d_int;      // [flat B | hull_set B]
+    HIP_TRY(h, hipMalloc(&d_A.p, nA * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&d_pat.p, 2 * nP * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&d_b.p, nB * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&d_int.p, 2 * (size_t)B * sizeof(int32_t)));
+    HIP_TRY(h, hipMemcpyAsync(d_A, hull_A, nA * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_pat, ub, nP * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_pat + nP, stuck, nP * sizeof(double), hipMemcpyHostToDevice, s));
+    if (hull_set) HIP_TRY(h, hipMemcpyAsync(d_int + B, hull_set, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    ftmpc::HullOffsets ho{};
+    ho.B = B;
+    ho.hull_rows = hull_rows;
+    ho.ub = d_pat;
+    ho.stuck = d_pat + nP;
+    ho.hullA = d_A;
+    ho.hullset = hull_set ? d_int + B : nullptr;
+    ho.out_b = d_b;
+    ho.flat = d_int;
+    hipLaunchKernelGGL(ftmpc::ftmpc_hull_offsets_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, ho);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_b, d_b, nB * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_flat) HIP_TRY(h, hipMemcpyAsync(out_flat, d_int, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return FTMPC_OK;
 }
 
 int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2645,8 +2728,9 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
     // step (phase 1).  It takes the truth-buffer path of a sensor even when the sensor is trivial or NULL (se0: latency 0, step0 0,
     // nothing drawn); the sense kernel then does not run and y_t is the truth
     const bool est = es != nullptr;
-    // diagnosis (checked by the entry; thruster form only): ftmpc_diagnose_kernel runs before the filter's phase 0 (phase 0) and after
-    // the plant step (phase 1); it takes the same truth-buffer path
+    // diagnosis (checked by the entry): ftmpc_diagnose_kernel runs before the filter's phase 0 (phase 0) and after the plant step
+    // (phase 1); it takes the same truth-buffer path.  On the wrench form ftmpc_hull_offsets_kernel and ftmpc_hull_switch_kernel follow
+    // phase 0: the offsets of the vehicles that switched, from the pattern the controller now holds
     const bool diag = dg != nullptr;
     const bool sensing = !sensor_trivial(se);      // ftmpc_sense_kernel runs
     ftmpc_sensor se0{};
@@ -2984,6 +3068,41 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         dp.det_level = d_ddet + 2 * B + 2 * B * dK;
         dp.llr_hist = d_dhist;
     }
+    // ... on the wrench form: the new offsets [B][hull_rows] and [flat B | no_hull B]
+    DevBuf<double> d_hbnew;
+    DevBuf<int32_t> d_hflat;
+    ftmpc::HullOffsets ho{};
+    ftmpc::HullSwitch hw{};
+    if (diag && wl) {
+        const int R = wl->hull_rows;
+        HIP_TRY(h, hipMalloc(&d_hbnew.p, (size_t)B * R * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_hflat.p, 2 * (size_t)B * sizeof(int32_t)));
+        if (wl->no_hull_step)
+            HIP_TRY(h, hipMemcpyAsync(d_hflat + B, wl->no_hull_step, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        else
+            HIP_TRY(h, hipMemsetAsync(d_hflat + B, 0xFF, (size_t)B * sizeof(int32_t), s));
+        ho.B = B;
+        ho.hull_rows = R;
+        ho.switched = dp.switched;
+        ho.ub = h->d_ub;
+        ho.stuck = h->d_stuck;
+        ho.hullA = h->d_hullA;
+        ho.hullset = wl->has_set ? h->d_hullset.p : nullptr;
+        ho.out_b = d_hbnew;
+        ho.flat = d_hflat;
+        hw.B = B;
+        hw.hull_rows = R;
+        hw.switched = dp.switched;
+        hw.flat = d_hflat;
+        hw.ub = h->d_ub;
+        hw.stuck = h->d_stuck;
+        hw.hullA = h->d_hullA;
+        hw.hullset = ho.hullset;
+        hw.new_b = d_hbnew;
+        hw.hullb = h->d_hullb;
+        hw.warmG = h->d_warmG;
+        hw.no_hull = d_hflat + B;
+    }
     double* const d_truth = sense ? d_xtrue.p : h->d_x0.p;      // what the plant integrates and the outcomes measure
     // a continued run (step0 > 0, and the handle's last loop with a sensor ended at that step, on this batch and form, in this x):
     // its first solve is warm-started as the whole run's would be, from what the handle kept; otherwise it starts cold
@@ -3115,7 +3234,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         HIP_TRY(h, hipMemcpyAsync(d_fpat + BE * NT, fs->stuck, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        if (wl) {
+        if (wl && !diag) {     // (under a diagnosis no event is detected: the schedule carries no hull tables)
             HIP_TRY(h, hipMalloc(&d_fhb.p, (size_t)BE * wl->hull_rows * sizeof(double)));
             HIP_TRY(h, hipMemcpyAsync(d_fhb, fs->hull_b, (size_t)BE * wl->hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
         }
@@ -3184,7 +3303,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             dp.cstep = (int32_t)(se->step0 + t);
             dp.step = t;
             hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
-            if (t > 0 || resume)
+            if (wl) {     // two launches: the switch kernel's lanes read the offsets the first one wrote
+                hw.repair = t > 0 || resume;
+                hw.cstep = dp.cstep;
+                hipLaunchKernelGGL(ftmpc::ftmpc_hull_offsets_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, ho);
+                hipLaunchKernelGGL(ftmpc::ftmpc_hull_switch_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, hw);
+            } else if (t > 0 || resume)
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_repair_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, B, N, NT,
                                    (const int32_t*)dp.switched, (const double*)h->d_ub, d_warmB.p);
             HIP_TRY(h, hipGetLastError());
@@ -3307,6 +3431,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             if (dg->llr) HIP_TRY(h, hipMemcpyAsync(h_dllr.data(), d_dllr, h_dllr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
         }
     }
+    if (wl && wl->out_hull_b)
+        HIP_TRY(h, hipMemcpyAsync(wl->out_hull_b, h->d_hullb, (size_t)B * wl->hull_rows * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (diag && wl && wl->no_hull_step)
+        HIP_TRY(h, hipMemcpyAsync(wl->no_hull_step, d_hflat + B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
     if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));

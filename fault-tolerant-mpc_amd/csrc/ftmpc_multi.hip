@@ -214,7 +214,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                    const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench,
-                   const ftmpc_diagnosis* diagnosis = nullptr) {
+                   const ftmpc_diagnosis* diagnosis = nullptr, double* out_hull_b = nullptr, int32_t* no_hull_step = nullptr) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -241,8 +241,11 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         const std::string msg = estimator_problem(estimator, B);
         if (!msg.empty()) return refuse(msg);
     }
-    if (diagnosis) {     // the diagnosis likewise (thruster form only): the parameters are uniform, the state and the outputs per vehicle
-        if (wrench) return refuse("ftmpc_diagnosis: the wrench form has no diagnosis");
+    if (diagnosis) {     // the diagnosis likewise: the parameters are uniform, the state and the outputs per vehicle
+        if (wrench) {
+            const std::string msg = wrench_diagnosis_problem(faults, no_hull_step, B);
+            if (!msg.empty()) return refuse(msg);
+        }
         if (faults && faults->n_events > 0 && (!faults->onset || !faults->ub || !faults->stuck))
             return refuse("ftmpc_fault_schedule: null onset / ub / stuck");
         const std::string msg = diagnosis_problem(diagnosis, B, m->cfg.NT, estimator, faults, sensor);
@@ -263,6 +266,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
         if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * m->cfg.NT, diagnosis->ub);
         if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * m->cfg.NT, diagnosis->stuck);
+        if (wrench && out_hull_b && B > 0) std::copy(hull_b, hull_b + B * hull_rows, out_hull_b);
         return FTMPC_OK;
     }
     const int G = (int)m->dev.size();
@@ -382,13 +386,15 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (ev.est_hist) ev.est_hist = eh.data();
             if (dv.llr_hist) dv.llr_hist = lh.data();
         }
-        const int rc2 = wrench ? ftmpc_simulate_wrench_estimator_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+        const int rc2 = wrench ? ftmpc_simulate_wrench_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
                                                                      xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
                                                                      faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
                                                                      alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
                                                                      mission ? &mi : nullptr, actuator ? &at : nullptr,
-                                                                     sensor ? &sv : nullptr, estimator ? &ev : nullptr)
+                                                                     sensor ? &sv : nullptr, estimator ? &ev : nullptr,
+                                                                     diagnosis ? &dv : nullptr, out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
+                                                                     no_hull_step ? no_hull_step + lo : nullptr)
                                : ftmpc_simulate_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
                                                                seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
                                                                bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
@@ -772,6 +778,21 @@ int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
                           backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
                           estimator, true);
+}
+
+int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                                int32_t* no_hull_step) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
+                          estimator, true, diagnosis, out_hull_b, no_hull_step);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

@@ -1490,4 +1490,112 @@ __global__ void __launch_bounds__(64) ftmpc_diagnose_repair_kernel(int64_t B, in
     for (int j = 0; j < NT; ++j) w[j] = fmin(fmax(w[j], 0.0), ub[b * NT + j]);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The diagnosis on the two-stage form (ftmpc_simulate_wrench_diagnosis_batch, ftmpc_hull_offsets_batch).  The input hull is a zonotope:
+// its facet normals are the directions orthogonal to five independent generators, so the normals of a pattern with fewer live
+// thrusters are among those of the pattern it started from, and only the offsets change:
+//   c_i = a_r . D_i,   b_r = sum_i (c_i (ub_i / 2 + stuck_i) + |c_i| ub_i / 2)
+// A row that is no longer a facet stays a supporting half-space.  A row of exactly six zeros is padding (b_r = 1).  The pattern is
+// flat (its live thrusters do not span R^6: no two-stage form) when a non-padding row has no width,
+//   w_r = sum_i |c_i| ub_i <= 1e-9 |a_r|_1 max|D| max_i ub_i.
+// ftmpc_hull_offsets_kernel: a lane per vehicle, the row loop and the thruster loop rolled, six normal entries in registers, D at
+// wave-uniform indices; `switched` (nullptr: every vehicle) limits it to the vehicles the diagnosis flagged.  The one kernel serves the
+// stand-alone entry and the loop, so both produce the same bits.
+// ftmpc_hull_switch_kernel: a lane per (vehicle, stage), after the offsets kernel.  Flat: no_hull takes the campaign step if it was -1,
+// nothing else changes.  Otherwise stage 0's lane copies the new offsets into the controller's, and (repair) every lane pulls its own
+// stage of the shifted warm start towards the new centre, as ftmpc_fault_event_kernel does at a detected event; the lanes read the
+// offsets kernel's buffer, never what stage 0 writes.
+// ---------------------------------------------------------------------------------------------------------
+struct HullOffsets {
+    int64_t B;
+    int32_t hull_rows, pad0;
+    const int32_t* switched;   // nullptr or [B]
+    const double* ub;          // [B*NT]
+    const double* stuck;
+    const double* hullA;       // [n_sets*hull_rows*6]
+    const int32_t* hullset;    // nullptr (one table) or [B]
+    double* out_b;             // [B*hull_rows]
+    int32_t* flat;             // nullptr or [B]
+};
+
+__global__ void __launch_bounds__(64) ftmpc_hull_offsets_kernel(const DeviceConsts C, const HullOffsets P) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    if (P.switched && !P.switched[b]) return;
+    const int NT = C.NT, R = P.hull_rows;
+    const double* const ub = P.ub + b * NT;
+    const double* const stuck = P.stuck + b * NT;
+    const double* const A = P.hullA + (P.hullset ? (int64_t)P.hullset[b] : 0) * R * 6;
+    double dmax = 0.0, umax = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < NT; ++i) {
+        umax = fmax(umax, ub[i]);
+        for (int g = 0; g < 6; ++g) dmax = fmax(dmax, fabs(C.D[g * MAX_NT + i]));
+    }
+    const double wtol = 1e-9 * dmax * umax;
+    int32_t flat = 0;
+#pragma unroll 1
+    for (int r = 0; r < R; ++r) {
+        const double a0 = A[r * 6], a1 = A[r * 6 + 1], a2 = A[r * 6 + 2], a3 = A[r * 6 + 3], a4 = A[r * 6 + 4], a5 = A[r * 6 + 5];
+        const double a1n = fabs(a0) + fabs(a1) + fabs(a2) + fabs(a3) + fabs(a4) + fabs(a5);
+        double acc = 0.0, w = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) {
+            double c = a0 * C.D[i];
+            c += a1 * C.D[MAX_NT + i];
+            c += a2 * C.D[2 * MAX_NT + i];
+            c += a3 * C.D[3 * MAX_NT + i];
+            c += a4 * C.D[4 * MAX_NT + i];
+            c += a5 * C.D[5 * MAX_NT + i];
+            const double u = ub[i], ac = fabs(c);
+            acc += c * (0.5 * u + stuck[i]) + ac * (0.5 * u);
+            w += ac * u;
+        }
+        const bool pad = a1n == 0.0;
+        P.out_b[b * R + r] = pad ? 1.0 : acc;
+        if (!pad && w <= a1n * wtol) flat = 1;
+    }
+    if (P.flat) P.flat[b] = flat;
+}
+
+struct HullSwitch {
+    int64_t B;
+    int32_t hull_rows, repair;
+    int32_t cstep, pad0;
+    const int32_t* switched;   // [B]
+    const int32_t* flat;       // [B]
+    const double* ub;          // [B*NT] the controller's pattern after the switch
+    const double* stuck;
+    const double* hullA;
+    const int32_t* hullset;    // nullptr or [B]
+    const double* new_b;       // [B*hull_rows] what ftmpc_hull_offsets_kernel wrote
+    double* hullb;             // [B*hull_rows] the controller's offsets
+    double* warmG;             // [B*N*6]
+    int32_t* no_hull;          // [B]
+};
+
+__global__ void __launch_bounds__(64) ftmpc_hull_switch_kernel(const DeviceConsts C, const HullSwitch P) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = C.N;
+    if (i >= P.B * N) return;
+    const int64_t b = i / N;
+    const int k = (int)(i % N);
+    if (!P.switched[b]) return;
+    if (P.flat[b]) {
+        if (k == 0 && P.no_hull[b] < 0) P.no_hull[b] = P.cstep;
+        return;
+    }
+    const int R = P.hull_rows;
+    const double* const nb = P.new_b + b * R;
+    if (k == 0)
+        for (int r = 0; r < R; ++r) P.hullb[b * R + r] = nb[r];
+    if (!P.repair) return;
+    double ctr[6], t[6], p[6];
+    hull_centre(C, P.ub + b * C.NT, P.stuck + b * C.NT, ctr);
+    double* g = P.warmG + (b * N + k) * 6;
+    for (int j = 0; j < 6; ++j) t[j] = g[j];
+    if (hull_pull(t, ctr, P.hullA + (P.hullset ? (int64_t)P.hullset[b] : 0) * R * 6, nb, R, p) > 0.0)
+        for (int j = 0; j < 6; ++j) g[j] = p[j];
+}
+
 }  // namespace ftmpc

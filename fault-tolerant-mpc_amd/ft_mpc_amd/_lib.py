@@ -38,6 +38,7 @@ SYMBOLS = (
     "ftmpc_multi_simulate_sensor_batch", "ftmpc_multi_simulate_wrench_sensor_batch",
     "ftmpc_multi_simulate_estimator_batch", "ftmpc_multi_simulate_wrench_estimator_batch",
     "ftmpc_simulate_diagnosis_batch", "ftmpc_multi_simulate_diagnosis_batch",
+    "ftmpc_hull_offsets_batch", "ftmpc_simulate_wrench_diagnosis_batch", "ftmpc_multi_simulate_wrench_diagnosis_batch",
 )
 
 
@@ -221,6 +222,9 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_wrench_estimator_batch.argtypes = lib.ftmpc_simulate_wrench_estimator_batch.argtypes
     lib.ftmpc_simulate_diagnosis_batch.argtypes = lib.ftmpc_simulate_estimator_batch.argtypes + [C.POINTER(ftmpc_diagnosis)]
     lib.ftmpc_multi_simulate_diagnosis_batch.argtypes = lib.ftmpc_simulate_diagnosis_batch.argtypes
+    lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes = lib.ftmpc_simulate_wrench_estimator_batch.argtypes + [C.POINTER(ftmpc_diagnosis), dp, ip]
+    lib.ftmpc_multi_simulate_wrench_diagnosis_batch.argtypes = lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes
+    lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
                                                  dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, ip]

@@ -498,7 +498,7 @@ class BatchedMPC:
         group), xhat [B,13] and cov [B,78] (the priors of step T, to hand to a continued run); they come back as out["estimator"].
         With a predicting sensor the field pred of the sensor holds the estimate propagated over the queue.
         diagnosis: the controller finds thruster faults itself (include/ftmpc.h, ftmpc_diagnosis; ft_mpc_amd.diagnosis restates it in
-        NumPy; thruster formulation only): a bank of CUSUM tests per vehicle, one per hypothesis "thruster i stuck at level l", on
+        NumPy): a bank of CUSUM tests per vehicle, one per hypothesis "thruster i stuck at level l", on
         the measurement against the model's open-loop prediction.  A dict with every=1, levels=(0.0, F_MAX), resid_sigma=(2,)
         (velocity, rate; diagnosis.default_sigma), drift_sigma=(0, 0), threshold, max_detect=2, state=None ([B,14+NT]), llr=None
         ([B,NT*L]), detect=None ((step, thruster, level), each [B,max_detect]) -- what a previous call returned, for a continued run --
@@ -507,11 +507,34 @@ class BatchedMPC:
         state, llr.  With `faults` the schedule then moves the plant only and detect_delay is not used.  A call without state that
         asks for detect or state starts from xt = x0, n = 0, which the first step's re-anchor replaces by the first measurement
         when step0 % every == 0.
+        On formulation="wrench" the diagnosis is opt-in, rebuild_hull=True in the dict (ftmpc_simulate_wrench_diagnosis_batch): after a
+        detection the device recomputes the offsets of the vehicle's hull rows for the new pattern (the normals of the pattern it
+        started from stay; input_bounds.hull_offsets restates it), so `hull` must be the tables of the call's pattern (the default).
+        out["diagnosis"] gains hull_b [B,rows], the controller's offsets after the last step, and no_hull [B], the step of the first
+        detection that left a pattern without a hull (-1: none; the offsets then stay as they were); hand both back as
+        diagnosis["hull_b"] / diagnosis["no_hull"] for a continued run.  With `faults` no event hull tables are built.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
         [, status_hist][, actuator][, sensor][, estimator])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
                          plant, mission, actuator, sensor, estimator, diagnosis)
+
+    def hull_offsets(self, ub, stuck, hull):
+        """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
+        on the device (ftmpc_hull_offsets_batch; input_bounds.hull_offsets restates it).  Returns dict(b [B,rows], flat [B] bool)."""
+        NT = self.cfg.NT
+        ub = _f64(ub).reshape(-1, NT)
+        B = ub.shape[0]
+        stuck = _f64(stuck, (B, NT))
+        A = np.ascontiguousarray(hull["A"], dtype=np.float64).reshape(-1, int(hull["rows"]), 6)
+        hs = np.ascontiguousarray(hull["set"], dtype=np.int32).reshape(-1)
+        if hs.shape != (B,):
+            raise ValueError(f"hull['set'] must have shape {(B,)}")
+        b = np.empty((B, A.shape[1]))
+        flat = np.empty(B, np.int32)
+        self._check(self.lib.ftmpc_hull_offsets_batch(self._h, B, _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32),
+                                                      A.shape[1], _ptr(b), _ptr(flat, C.c_int32)))
+        return dict(b=b, flat=flat.astype(bool))
 
     def sqp_graph_launches(self) -> int:
         """Calls of solve_sqp_device on this handle that were replayed from the recorded hipGraph (ftmpc_sqp_graph_launches)."""
@@ -906,8 +929,21 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
     se, skeep, sout, L = _sensor_request(sensor, B, T, NT) if sensor is not None else (None, None, None, 0)
     es, ekeep, eout = _estimator_request(estimator, B, T) if estimator is not None else (None, None, None)
-    if diagnosis is not None and formulation == "wrench":
-        raise ValueError("diagnosis: thruster formulation only (the wrench form would need a hull table per hypothesis)")
+    rebuild, d_hb, d_nh = False, None, None
+    if diagnosis is not None:     # the wrench form's keys are taken out here: ft_mpc_amd.diagnosis.request knows the common ones
+        diagnosis = dict(diagnosis)
+        rebuild = bool(diagnosis.pop("rebuild_hull", False))
+        d_hb, d_nh = diagnosis.pop("hull_b", None), diagnosis.pop("no_hull", None)
+        if formulation == "wrench" and not rebuild:
+            raise ValueError("diagnosis: thruster formulation only, unless diagnosis['rebuild_hull'] is True (the wrench form then "
+                             "recomputes the hull offsets of the new pattern on the device after a detection)")
+        if formulation != "wrench" and (rebuild or d_hb is not None or d_nh is not None):
+            raise ValueError("diagnosis['rebuild_hull'], ['hull_b'] and ['no_hull'] belong to formulation='wrench' (the thruster "
+                             "formulation has no hull)")
+        if formulation == "wrench":
+            d_nh = np.full(B, -1, np.int32) if d_nh is None else np.array(d_nh, dtype=np.int32)      # (a copy: the call writes into it)
+            if d_nh.shape != (B,) or (d_nh < -1).any():
+                raise ValueError(f"diagnosis['no_hull'] must have shape {(B,)} and no entry below -1")
     dg, dkeep, dout = _diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor) if diagnosis is not None else (None, None, None)
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
@@ -941,7 +977,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                           onset=_ptr(onset, C.c_int32), detect=_ptr(detect, C.c_int32), ub=_ptr(eub), stuck=_ptr(est))
         if dg is not None:      # the schedule moves the plant only: the diagnosis detects
             sched.detect = None
-        if formulation == "wrench":
+        if formulation == "wrench" and dg is None:
             if hull is not None and ("ev_set" not in hull or np.shape(hull["ev_set"]) != onset.shape):
                 raise ValueError("with faults `hull` must be None or ft_mpc_amd.faults.fault_hull_tables of the same schedule")
             fh = fault_hull_tables(self.D, ub, stuck, eub, est, onset) if hull is None else hull
@@ -993,6 +1029,19 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         hs = np.ascontiguousarray(hull["set"], dtype=np.int32)
         hb = np.ascontiguousarray(hull["b"], dtype=np.float64)
         abad = np.zeros(T, np.int32)
+        if dg is not None:
+            if d_hb is not None:      # a continued run: the offsets the previous call returned
+                hb = np.array(d_hb, dtype=np.float64)
+                if hb.shape != (B, int(hull["rows"])) or not np.isfinite(hb).all():
+                    raise ValueError(f"diagnosis['hull_b'] must be finite with shape {(B, int(hull['rows']))}")
+            dout["hull_b"], dout["no_hull"] = np.empty((B, int(hull["rows"]))), d_nh
+            self._check(getattr(self.lib, pre + "wrench_diagnosis_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+                C.byref(es) if es is not None else None, C.byref(dg), _ptr(dout["hull_b"]), _ptr(d_nh, C.c_int32)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if es is not None:
             self._check(getattr(self.lib, pre + "wrench_estimator_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),

@@ -136,7 +136,8 @@ class MultiGPUMPC:
         uniform, its bias, pending commands and histories per vehicle (ftmpc_multi_simulate_sensor_batch / _wrench_sensor_batch); the parameters of
         `estimator` are uniform, its priors, history and error sums per vehicle (ftmpc_multi_simulate_estimator_batch /
         _wrench_estimator_batch); the parameters of `diagnosis` are uniform, its state, detections, pattern and history per vehicle
-        (ftmpc_multi_simulate_diagnosis_batch; thruster formulation only)."""
+        (ftmpc_multi_simulate_diagnosis_batch; on the wrench formulation, with rebuild_hull=True, also hull_b and no_hull:
+        ftmpc_multi_simulate_wrench_diagnosis_batch)."""
         from .batch import _simulate
         return _simulate(self, True, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, 0, None, plant,

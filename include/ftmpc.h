@@ -887,13 +887,55 @@ typedef struct ftmpc_diagnosis {
 } ftmpc_diagnosis;
 
 /* ftmpc_simulate_estimator_batch with the diagnosis `diagnosis` (NULL: exactly ftmpc_simulate_estimator_batch).  The wrench form has
- * no diagnosis: it would need a hull table per hypothesis. */
+ * its own entry, ftmpc_simulate_wrench_diagnosis_batch below: it needs no hull table per hypothesis, only new offsets. */
 int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
                                    const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                    int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                    double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                    const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                    const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis);
+
+/* The offsets of the input hull for other patterns on the SAME normals.  The hull {D u : 0 <= u_i <= ub_i, dead or stuck thrusters at
+ * stuck_i} is a zonotope whose facet normals are the directions orthogonal to five independent generators, so the normals of a
+ * pattern with fewer live thrusters are among those of the pattern it started from; only the offsets change.  For row r of vehicle
+ * b's table hull_A[hull_set[b]] (hull_set NULL: table 0), with D the handle's config's:
+ *   c_i = sum_g a_g D[g, i],   b_r = sum_i (c_i (ub_i / 2 + stuck_i) + |c_i| ub_i / 2)     (g and i ascending)
+ * A row that is no longer a facet of the new pattern stays a supporting half-space, so the set is described exactly.  A row whose six
+ * entries are exactly 0 is padding: b_r = 1.  out_flat[b] (NULL: not asked for) is 1 when a non-padding row has no width,
+ *   w_r = sum_i |c_i| ub_i <= 1e-9 |a_r|_1 max|D| max_i ub_i,
+ * i.e. the live thrusters no longer span R^6 and the two-stage form does not exist for the pattern, else 0.
+ * The caller's contract: a vehicle's table holds the facet normals of an index set that contains the pattern's live thrusters (the
+ * table of the pattern the vehicle started from).  Host buffers: ub, stuck [B*NT], hull_A [n_sets*hull_rows*6], hull_set NULL or [B],
+ * out_b [B*hull_rows], out_flat NULL or [B].  ftmpc_hull_offsets_kernel, a lane per vehicle; the closed loop below runs the same
+ * kernel, so both give the same bits. */
+int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const double* stuck, const double* hull_A, int32_t n_sets,
+                             const int32_t* hull_set, int32_t hull_rows, double* out_b, int32_t* out_flat);
+
+/* ftmpc_simulate_wrench_estimator_batch with the diagnosis `diagnosis` (NULL: exactly that entry, kernel for kernel).  The loop of
+ * ftmpc_diagnosis above on the two-stage form.  Per step: sense; diagnosis phase 0 (as on the thruster form: it switches ub_c /
+ * stuck_c and records the detection); the hull step; filter phase 0; solve, allocation, command queue and plant step; diagnosis
+ * phase 1; filter phase 1.  The hull step, for the vehicles that switched in this step:
+ *   - ftmpc_hull_offsets_kernel evaluates the offsets of the new pattern on the vehicle's table and the flat criterion;
+ *   - not flat: the controller's hull_b becomes the new offsets, hull_set[b] does not change, and when t > 0, or the handle resumes a
+ *     warm start, every stage of the shifted warm start G is pulled towards the new hull centre as at a detected schedule event;
+ *   - flat: the detection stands (detect arrays and the controller's pattern as phase 0 left them), hull_b and the warm start are
+ *     left untouched, and no_hull_step[b] takes the campaign step c if it was -1.
+ * The caller's contract for the table: a vehicle's table must hold the facet normals of its STARTING index set (the live thrusters
+ * of the call's ub), which is what hull tables built from the call's pattern give; every later pattern has its normals among them.
+ * out_hull_b: NULL or [B*hull_rows], the controller's offsets after the last step.  no_hull_step: NULL or [B], in/out, -1 = none; for a
+ * continued run hand back both (out_hull_b as the next call's hull_b) with the diagnosis' own carry-over.
+ * With a fault schedule the schedule moves the PLANT only: its detect, hull_set and hull_b must be NULL.
+ * FTMPC_ERR_ARG, the call's x untouched: the refusals of ftmpc_simulate_diagnosis_batch, and with a diagnosis a schedule whose
+ * hull_set or hull_b is set (the message names the field) and a no_hull_step entry below -1 (it names the vehicle). */
+int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                          int32_t* no_hull_step);
 
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
@@ -1107,6 +1149,20 @@ int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, d
                                          const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                          const ftmpc_sensor* sensor, const ftmpc_estimator* estimator,
                                          const ftmpc_diagnosis* diagnosis);
+/* ftmpc_multi_simulate_wrench_estimator_batch with the diagnosis `diagnosis` (NULL: exactly that entry) as
+ * ftmpc_simulate_wrench_diagnosis_batch runs it.  The struct and no_hull_step are checked once over the whole batch; per shard the
+ * diagnosis' arrays as in ftmpc_multi_simulate_diagnosis_batch, out_hull_b + hull_rows lo and no_hull_step + lo.
+ * ftmpc_multi_upload / _step take no diagnosis. */
+int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                                int32_t* no_hull_step);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);

@@ -13,6 +13,7 @@ event at a random step in [1, T) that breaks one more healthy thruster (stuck at
     python scripts/fault_campaign_perf.py --sensor [--latency 0 2 8] [--predict]   # also the loops with navigation errors and latency
     python scripts/fault_campaign_perf.py --sensor --estimator [--every M]   # and each of those once more with the navigation filter
     python scripts/fault_campaign_perf.py --case thruster --diagnosis       # and the sensor loops once more with the fault diagnosis
+    python scripts/fault_campaign_perf.py --case wrench64 --diagnosis       # the same on the two-stage form (rebuild_hull=True)
 
 Timed: the whole simulate call with the hull tables built beforehand; also the loop without a schedule but with the after-event
 pattern from step 0 on, which brackets what the fault itself does to the QPs.
@@ -45,7 +46,8 @@ a kernel_stats.csv of that run holds the sense kernel next to the plant kernel, 
 sigma, proc_sigma a tenth of it, the update on every --every-th step (default 1), err_sq returned (ftmpc_filter_kernel<0> before
 every solve and <1> after every plant step).  With --once the call with the sensor also carries the filter, and --stats reports the
 time per launch of either phase and the filter's share of the kernel time.
---diagnosis (thruster form; without --sensor a sensor of latency 0 is added): every sensor loop that a diagnosis accepts (no
+--diagnosis (without --sensor a sensor of latency 0 is added; on the wrench cases with rebuild_hull=True: ftmpc_hull_offsets_kernel and
+ftmpc_hull_switch_kernel follow phase 0 in place of the repair kernel, and the result also counts the vehicles left without a hull): every sensor loop that a diagnosis accepts (no
 prediction without the filter) once more under BatchedMPC.simulate(diagnosis=...): levels (0, f_max), resid_sigma =
 diagnosis.default_sigma of the sensor and the process noise, threshold 18, the test on every --every-th step, the detections
 returned (ftmpc_diagnose_kernel<0> and the repair kernel before every solve, <1> after every plant step).  The loop without a
@@ -157,9 +159,11 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
                 sensors.append((f"sensor_d{d}" + ("_predict" if pr else ""), dict(SENSOR, bias=bias, latency=d, predict=pr), xs))
     est = dict(ESTIMATOR, every=every) if estimator and sensor else None
     diag = None
-    if diagnosis and c["formulation"] == "thruster":
+    if diagnosis:
         from ft_mpc_amd.diagnosis import default_sigma, detections_of, score
         diag = dict(DIAGNOSIS, every=every, resid_sigma=default_sigma(SENSOR["sigma"], (1e-3,) * 4))
+        if c["formulation"] == "wrench":
+            diag["rebuild_hull"] = True
         if not sensors:
             sensors.append(("sensor_d0", dict(SENSOR, latency=0), xr))
     with_diag = lambda sen: diag is not None and not (sen.get("predict") and est is None)
@@ -235,6 +239,8 @@ def run(name, reps, once=False, outcomes=False, slots=0, dispersion=False, with_
             sc.pop("wrong_level")      # (the events stick at a random intensity: no level is the right one)
             res[label].update(detections=int(sum(len(d) for d in det)), score=sc,
                               delay_mean=float(np.mean(delays)) if delays else None, delay_max=int(max(delays)) if delays else None)
+            if "no_hull" in out["diagnosis"]:
+                res[label]["no_hull"] = int((out["diagnosis"]["no_hull"] >= 0).sum())
         if "actuator" in out:      # what the valves delivered and how often they opened, per vehicle and step
             res[label].update(delivered_mean_Ns=float(out["actuator"]["delivered"].mean()),
                               pulses_per_step=float(out["actuator"]["pulses"].mean()) / T)
@@ -301,7 +307,11 @@ def stats(path):
     d0n, d0us = per_launch("ftmpc_diagnose_kernel<0>")
     d1n, d1us = per_launch("ftmpc_diagnose_kernel<1>")
     rn, rus = per_launch("ftmpc_diagnose_repair_kernel")
-    return dict(diagnose_test_kernel_calls=d0n, diagnose_test_kernel_avg_us=d0us, diagnose_model_kernel_calls=d1n, diagnose_model_kernel_avg_us=d1us,
+    hon, hous = per_launch("ftmpc_hull_offsets_kernel")
+    hsn, hsus = per_launch("ftmpc_hull_switch_kernel")
+    return dict(hull_offsets_kernel_calls=hon, hull_offsets_kernel_avg_us=hous, hull_switch_kernel_calls=hsn, hull_switch_kernel_avg_us=hsus,
+                hull_kernel_share=(hon * hous + hsn * hsus) * 1e3 / tot if tot else 0.0,
+                diagnose_test_kernel_calls=d0n, diagnose_test_kernel_avg_us=d0us, diagnose_model_kernel_calls=d1n, diagnose_model_kernel_avg_us=d1us,
                 diagnose_repair_kernel_calls=rn, diagnose_repair_kernel_avg_us=rus,
                 diagnose_kernel_share=(d0n * d0us + d1n * d1us + rn * rus) * 1e3 / tot if tot else 0.0,
                 filter_update_kernel_calls=f0n, filter_update_kernel_avg_us=f0us, filter_time_kernel_calls=f1n, filter_time_kernel_avg_us=f1us,
