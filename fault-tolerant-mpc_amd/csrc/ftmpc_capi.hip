@@ -80,6 +80,9 @@ struct ftmpc_handle {
     std::vector<double> keep_x;
     int64_t keep_B = 0, keep_step = -1;
     bool keep_wrench = false;
+    // the estimated disturbance [B*6] the next linearisation takes (ftmpc_disturbance.compensate = 1: set around the solve of a loop
+    // step; ftmpc_debug_records_disturbance), nullptr: the plain instantiations
+    const double* lin_dist = nullptr;
     // allocation operator (ftmpc_allocate_batch)
     DevBuf<double> d_atau, d_aub, d_au;
     DevBuf<int32_t> d_ast, d_ait;
@@ -466,6 +469,15 @@ int dense_ensure(ftmpc_handle* h) {
 void launch_linearize(ftmpc_handle* h, int64_t B, int blocks, hipStream_t s, const ftmpc::LinParams& lp) {
     // shares of the 13 directions per 64 instances: as many as keep about one wave per SIMD (1024 on the device)
     const int shares = B <= h->lin_split_max ? 13 : (B <= 2 * h->lin_split_max ? 4 : (B <= 5 * h->lin_split_max ? 2 : 1));
+    if (lp.dist) {     // the same grids with the estimated disturbance in the rollout
+        if (shares == 13)
+            hipLaunchKernelGGL((ftmpc::ftmpc_linearize_kernel<double, 1, 1>), dim3(blocks, 13), dim3(64), 0, s, h->dc, lp);
+        else if (shares > 1)
+            hipLaunchKernelGGL((ftmpc::ftmpc_linearize_kernel<double, 2, 1>), dim3(blocks, shares), dim3(64), 0, s, h->dc, lp);
+        else
+            hipLaunchKernelGGL((ftmpc::ftmpc_linearize_kernel<double, 0, 1>), dim3(blocks), dim3(64), 0, s, h->dc, lp);
+        return;
+    }
     if (shares == 13)
         hipLaunchKernelGGL((ftmpc::ftmpc_linearize_kernel<double, 1>), dim3(blocks, 13), dim3(64), 0, s, h->dc, lp);
     else if (shares > 1)
@@ -495,6 +507,7 @@ int enqueue(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, cons
     lp.out_eN = h->tset ? h->d_eN : nullptr;
     lp.tcost = h->d_tcost;
     lp.out_cbar = h->sbounds ? h->d_cbar : nullptr;
+    lp.dist = h->lin_dist;
     const int nvar = h->use_f64 ? 0 : (h->nb_max <= 8 ? 1 : (h->nb_max == 9 ? 2 : 3));   // one-wave fp32 instantiations in use
     lp.qlist = h->use_f64 ? nullptr : h->d_qlist;
     lp.qcount = h->d_qctl;
@@ -1939,9 +1952,27 @@ int ftmpc_debug_build_qp(ftmpc_handle* h, int64_t B, const double* x0, const dou
     return FTMPC_OK;
 }
 
+static int debug_records(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                         const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                         const double* warmU, const double* dist, double* rec_out);
+
 int ftmpc_debug_records(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
                         const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
                         const double* warmU, double* rec_out) {
+    return debug_records(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, warmU, nullptr, rec_out);
+}
+
+int ftmpc_debug_records_disturbance(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                    const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                                    const double* warmU, const double* dist, double* rec_out) {
+    if (!h || !dist) return FTMPC_ERR_ARG;
+    return debug_records(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, warmU, dist, rec_out);
+}
+
+// dist != nullptr: the DIST instantiation of the linearise kernel with that estimate
+static int debug_records(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                         const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                         const double* warmU, const double* dist, double* rec_out) {
     if (!h || !rec_out || B <= 0) return FTMPC_ERR_ARG;
     int rc = check_strides(h, xref_stride, uref_stride, uref);
     if (rc != FTMPC_OK) return rc;
@@ -1963,6 +1994,12 @@ int ftmpc_debug_records(ftmpc_handle* h, int64_t B, const double* x0, const doub
     lp.out_eN = h->tset ? h->d_eN : nullptr;
     lp.tcost = h->d_tcost;
     lp.out_cbar = h->sbounds ? h->d_cbar : nullptr;
+    DevBuf<double> d_dist;
+    if (dist) {
+        HIP_TRY(h, hipMalloc(&d_dist.p, (size_t)B * 6 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_dist, dist, (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+        lp.dist = d_dist;
+    }
     const int nvar = h->use_f64 ? 0 : (h->nb_max <= 8 ? 1 : (h->nb_max == 9 ? 2 : 3));
     lp.qlist = h->use_f64 ? nullptr : h->d_qlist;
     lp.qcount = h->d_qctl;
@@ -2031,7 +2068,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
                          const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr,
-                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr);
+                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr, const ftmpc_disturbance* db = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -2252,6 +2289,42 @@ static std::string estimator_problem(const ftmpc_estimator* es, int64_t B, int64
         }
     return "";
 }
+// A disturbance estimate's layout and values (include/ftmpc.h, ftmpc_disturbance) over the vehicles [0, B), against the estimator and
+// the SQP count: empty when acceptable, else the message
+static std::string disturbance_problem(const ftmpc_disturbance* db, int64_t B, const ftmpc_estimator* es, int32_t sqp_iters, int64_t first = 0) {
+    if (!db) return "";
+    if (db->struct_size != (int32_t)sizeof(ftmpc_disturbance))
+        return "ftmpc_disturbance.struct_size is " + std::to_string(db->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_disturbance));
+    if (!es) return "ftmpc_disturbance needs an estimator (ftmpc_estimator): the disturbance states augment its filter";
+    if (sqp_iters > 0) return "ftmpc_disturbance: sqp_iters must be 0 (the cost kernels of the SQP do not know the estimate)";
+    if (db->compensate != 0 && db->compensate != 1) return "ftmpc_disturbance.compensate is " + std::to_string(db->compensate) + ", outside {0, 1}";
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(db->p0[k]) || db->p0[k] < 0) return "ftmpc_disturbance.p0[" + std::to_string(k) + "] is negative or not finite";
+        if (!std::isfinite(db->proc_sigma[k]) || db->proc_sigma[k] < 0)
+            return "ftmpc_disturbance.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
+    }
+    if (db->cross && !db->force) return "ftmpc_disturbance.cross is given without force";
+    if (db->cross && !db->torque) return "ftmpc_disturbance.cross is given without torque";
+    if (db->cross && !es->xhat) return "ftmpc_disturbance.cross is given without ftmpc_estimator.xhat";
+    if (db->cov && !db->cross) return "ftmpc_disturbance.cov is given without cross";
+    const double* const arr[4] = {db->force, db->torque, db->cross, db->cov};
+    const char* const name[4] = {"force", "torque", "cross", "cov"};
+    const int64_t width[4] = {3, 3, 72, 21};
+    for (int a = 0; a < 4; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < B * width[a]; ++i)
+                if (!std::isfinite(arr[a][i]))
+                    return std::string("ftmpc_disturbance.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
+                           " has a non-finite entry (" + std::to_string(i % width[a]) + ")";
+    if (db->cov)
+        for (int64_t b = 0; b < B; ++b)
+            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
+                if (db->cov[b * 21 + k] < 0)
+                    return "ftmpc_disturbance.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
+    return "";
+}
+
 static int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
     const std::string msg = estimator_problem(es, B);
     return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
@@ -2476,6 +2549,17 @@ int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double
                                    double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                    const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                    const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis) {
+    return ftmpc_simulate_disturbance_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                            x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, nullptr);
+}
+
+int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                     const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                     const ftmpc_disturbance* disturbance) {
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2491,6 +2575,10 @@ int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double
         const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
         if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
     }
+    {
+        const std::string msg = disturbance_problem(disturbance, B, estimator, sqp_iters);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
@@ -2502,7 +2590,7 @@ int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis);
+                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2720,7 +2808,7 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
                          const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
-                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg) {
+                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg, const ftmpc_disturbance* db) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -2987,6 +3075,55 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         fp.est_hist = d_ehist;
         fp.pred_hist = d_phist;
         fp.err_sq = d_esq;
+    }
+    // disturbance estimate (checked by the entry; it needs the estimator): P_xd [72][B] and P_dd [21][B] component-major (the caller's
+    // are vehicle-major), 0 and diag(p0^2) when none is handed over; the estimate itself [B][6] = (f^, t^), what the linearise
+    // kernel's DIST instantiations and ftmpc_diagnose_dist_kernel read; the gain slot [168][B] between the two passes of the update
+    const bool dist = db != nullptr;
+    DevBuf<double> d_dcross, d_dcovd, d_dest, d_dgain, d_dfh, d_dth;
+    std::vector<double> h_dcross, h_dcovd, h_dest;
+    ftmpc::DistParams dq{};
+    if (dist) {
+        try {
+            h_dcross.assign((size_t)B * 72, 0.0);
+            h_dcovd.assign((size_t)B * 21, 0.0);
+            h_dest.assign((size_t)B * 6, 0.0);
+        } catch (const std::bad_alloc&) {
+            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the disturbance estimate's staging arrays");
+        }
+        for (int64_t b0 = 0; b0 < B; b0 += 64) {
+            const int64_t b1 = std::min(B, b0 + 64);
+            if (db->cross)
+                for (int64_t k = 0; k < 72; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_dcross[(size_t)k * B + b] = db->cross[b * 72 + k];
+            if (db->cov)
+                for (int64_t k = 0; k < 21; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_dcovd[(size_t)k * B + b] = db->cov[b * 21 + k];
+        }
+        if (!db->cov)
+            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
+                std::fill(h_dcovd.begin() + (size_t)k * B, h_dcovd.begin() + (size_t)(k + 1) * B, db->p0[i / 3] * db->p0[i / 3]);
+        for (int64_t b = 0; b < B; ++b)
+            for (int k = 0; k < 3; ++k) {
+                if (db->force) h_dest[(size_t)b * 6 + k] = db->force[b * 3 + k];
+                if (db->torque) h_dest[(size_t)b * 6 + 3 + k] = db->torque[b * 3 + k];
+            }
+        HIP_TRY(h, hipMalloc(&d_dcross.p, (size_t)B * 72 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_dcovd.p, (size_t)B * 21 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_dest.p, (size_t)B * 6 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_dgain.p, (size_t)B * 168 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_dcross, h_dcross.data(), (size_t)B * 72 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_dcovd, h_dcovd.data(), (size_t)B * 21 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_dest, h_dest.data(), (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+        if (db->force_hist) HIP_TRY(h, hipMalloc(&d_dfh.p, (size_t)T * B * 3 * sizeof(double)));
+        if (db->torque_hist) HIP_TRY(h, hipMalloc(&d_dth.p, (size_t)T * B * 3 * sizeof(double)));
+        dq.cross = d_dcross;
+        dq.covd = d_dcovd;
+        dq.dist = d_dest;
+        dq.gain = d_dgain;
+        for (int k = 0; k < 2; ++k) dq.qdsq[k] = db->proc_sigma[k] * db->proc_sigma[k];
+        dq.force_hist = d_dfh;
+        dq.torque_hist = d_dth;
     }
     // the diagnosis' state: xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (the caller's are vehicle-major;
     // the statistics are filled on the device when none are handed over), the detect arrays [B][K] with the count per vehicle, the
@@ -3323,7 +3460,11 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             fp.update = (se->step0 + t) % es->every == 0;
             fp.step = t;
             fp.slot0 = t % (lat + 1);
-            hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
+            if (dist) {     // the x pass and the d pass of the augmented update; the d pass writes the solve's x0
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+            } else
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
             HIP_TRY(h, hipGetLastError());
         }
         const int64_t xr_s = windows ? xw : 0, ur_s = windows ? uw : 0;
@@ -3357,8 +3498,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                 hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
                                    d_abad + t);
         } else {
+            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into the linearisation
             rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, xr_t, xr_s, ur_t, ur_s,
                          (t > 0 || resume) ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
+            h->lin_dist = nullptr;
         }
         if (rc != FTMPC_OK) return rc;
         if (lat > 0) {     // u_t waits lat steps: into the slot behind the newest; the plant and the outcomes get the slot of a_t
@@ -3374,11 +3517,19 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
         if (est) {     // the time update under a_t and the controller's pattern of this step
             fp.u = sp.u0;
-            hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
+            if (dist) {     // P_xx, then P_xd, P_dd, the cross terms of P_xx and the mean
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<2>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<3>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+            } else
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
         }
-        if (diag) {     // the model's step under a_t and the controller's pattern of this step
+        if (diag) {     // the model's step under a_t and the controller's pattern of this step (with the estimate: d^_{t|t})
             dp.u = sp.u0;
-            hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
+            if (dist)
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_dist_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp,
+                                   (const double*)d_dest.p);
+            else
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
         }
         if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
             op.step = t;
@@ -3419,6 +3570,13 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (es->err_sq) HIP_TRY(h, hipMemcpyAsync(es->err_sq, d_esq, (size_t)B * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
         if (es->xhat) HIP_TRY(h, hipMemcpyAsync(es->xhat, d_xhat, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
         if (es->cov) HIP_TRY(h, hipMemcpyAsync(h_cov.data(), d_cov, (size_t)B * 78 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (dist) {
+        if (db->force_hist) HIP_TRY(h, hipMemcpyAsync(db->force_hist, d_dfh, (size_t)T * B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (db->torque_hist) HIP_TRY(h, hipMemcpyAsync(db->torque_hist, d_dth, (size_t)T * B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (db->force || db->torque) HIP_TRY(h, hipMemcpyAsync(h_dest.data(), d_dest, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (db->cross) HIP_TRY(h, hipMemcpyAsync(h_dcross.data(), d_dcross, (size_t)B * 72 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (db->cov) HIP_TRY(h, hipMemcpyAsync(h_dcovd.data(), d_dcovd, (size_t)B * 21 * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     if (diag) {
         if (dg->llr_hist) HIP_TRY(h, hipMemcpyAsync(dg->llr_hist, d_dhist, (size_t)(T * B * dH) * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3475,6 +3633,22 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             }
             if (dg->llr)
                 for (int64_t k = 0; k < dH; ++k) dg->llr[b * dH + k] = h_dllr[(size_t)(k * B + b)];
+        }
+    }
+    if (dist) {
+        for (int64_t b = 0; b < B; ++b)
+            for (int k = 0; k < 3; ++k) {
+                if (db->force) db->force[b * 3 + k] = h_dest[(size_t)b * 6 + k];
+                if (db->torque) db->torque[b * 3 + k] = h_dest[(size_t)b * 6 + 3 + k];
+            }
+        for (int64_t b0 = 0; b0 < B; b0 += 64) {
+            const int64_t b1 = std::min(B, b0 + 64);
+            if (db->cross)
+                for (int64_t k = 0; k < 72; ++k)
+                    for (int64_t b = b0; b < b1; ++b) db->cross[b * 72 + k] = h_dcross[(size_t)k * B + b];
+            if (db->cov)
+                for (int64_t k = 0; k < 21; ++k)
+                    for (int64_t b = b0; b < b1; ++b) db->cov[b * 21 + k] = h_dcovd[(size_t)k * B + b];
         }
     }
     if (est && es->cov)

@@ -185,7 +185,10 @@ __device__ inline void flush_half(const double* stg, double* g, int rowg, int nr
 // the work lists and e_N); every block repeats the cheap nonlinear rollout and stage blocks, so a small batch spreads
 // over more waves and each wave does a fraction of the work -- same arithmetic per direction, same record bits
 // (tests/test_gpu_parity.py).  The host takes it where the full-record kernel would leave most of the device idle.
-template <typename OutT, int SHARE>   // 0: full records; 1: one direction per block; 2: gridDim.y shares of the 13 directions
+// DIST = 1 (ftmpc_simulate_disturbance_batch with compensate = 1, ftmpc_debug_records_disturbance): the rollout and the stage blocks take
+// the estimated disturbance P.dist [B*6] = (f^ inertial, t^ body): every RK4 stage is evaluated at tau + t^, and f^ / m is added to
+// dv after the rotation (it is inertial, so it enters neither ab nor Vq).  rut keeps the COMMANDED gen; the tangent loop is the same code.
+template <typename OutT, int SHARE, int DIST = 0>   // SHARE 0: full records; 1: one direction per block; 2: gridDim.y shares of the 13 directions
 __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts C, const LinParams P) {
     static_assert(sizeof(OutT) == 8, "records are float64");
     constexpr bool DIRS = SHARE != 0;
@@ -271,6 +274,13 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
     const double dt = C.dt;
     const double acoef[4] = {0.0, 0.5 * dt, 0.5 * dt, dt};
     const double wcoef[4] = {1.0, 2.0, 2.0, 1.0};
+    double dfm[3] = {0, 0, 0}, dtq[3] = {0, 0, 0};      // DIST: f^ / m and t^
+    if constexpr (DIST != 0) {
+        for (int i = 0; i < 3; ++i) {
+            dfm[i] = P.dist[b * 6 + i] * C.inv_mass;
+            dtq[i] = P.dist[b * 6 + 3 + i];
+        }
+    }
 
     for (int k = 0; k < N; ++k) {
         // total wrench gen = D (ubar + stuck), ubar = clip(warm, 0, ub) (0 for broken thrusters)
@@ -304,6 +314,11 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
         }
         const double* F = gen;
         const double* tau = gen + 3;
+        double taud[3];
+        if constexpr (DIST != 0) {
+            for (int i = 0; i < 3; ++i) taud[i] = gen[3 + i] + dtq[i];
+            tau = taud;
+        }
 
         // ---- RK4 stage points + blocks ----
         StageBlk S[4];
@@ -313,6 +328,8 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
             for (int j = 0; j < 3; ++j) wi[j] = w[j] + (i ? acoef[i] * kw[i - 1][j] : 0.0);
             for (int j = 0; j < 4; ++j) qi[j] = q[j] + (i ? acoef[i] * kq[i - 1][j] : 0.0);
             stage_eval(C, wi, qi, F, tau, kw[i], kq[i], kv[i], S[i]);
+            if constexpr (DIST != 0)
+                for (int j = 0; j < 3; ++j) kv[i][j] += dfm[j];
         }
 
         // ---- tangents for the 13 input directions [w0(3), q0(4), F(3), tau(3)] ----
@@ -434,6 +451,9 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
 template __global__ void ftmpc_linearize_kernel<double, 0>(const DeviceConsts, const LinParams);
 template __global__ void ftmpc_linearize_kernel<double, 1>(const DeviceConsts, const LinParams);
 template __global__ void ftmpc_linearize_kernel<double, 2>(const DeviceConsts, const LinParams);
+template __global__ void ftmpc_linearize_kernel<double, 0, 1>(const DeviceConsts, const LinParams);
+template __global__ void ftmpc_linearize_kernel<double, 1, 1>(const DeviceConsts, const LinParams);
+template __global__ void ftmpc_linearize_kernel<double, 2, 1>(const DeviceConsts, const LinParams);
 
 // ---------------------------------------------------------------------------------------------------------
 // Cost of the nonlinear program for given thruster sequences (merit function of the line-search SQP; include/ftmpc.h

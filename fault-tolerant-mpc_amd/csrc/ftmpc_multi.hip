@@ -214,7 +214,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                    const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench,
-                   const ftmpc_diagnosis* diagnosis = nullptr, double* out_hull_b = nullptr, int32_t* no_hull_step = nullptr) {
+                   const ftmpc_diagnosis* diagnosis = nullptr, double* out_hull_b = nullptr, int32_t* no_hull_step = nullptr,
+                   const ftmpc_disturbance* disturbance = nullptr) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -249,6 +250,10 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         if (faults && faults->n_events > 0 && (!faults->onset || !faults->ub || !faults->stuck))
             return refuse("ftmpc_fault_schedule: null onset / ub / stuck");
         const std::string msg = diagnosis_problem(diagnosis, B, m->cfg.NT, estimator, faults, sensor);
+        if (!msg.empty()) return refuse(msg);
+    }
+    {     // the disturbance estimate likewise: the parameters are uniform, force / torque / cross / cov and the histories per vehicle
+        const std::string msg = disturbance_problem(disturbance, B, estimator, sqp_iters);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
@@ -347,7 +352,18 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (dv.ub) dv.ub += lo * NT;
             if (dv.stuck) dv.stuck += lo * NT;
         }
+        std::vector<double> fh, th;
+        ftmpc_disturbance bv{};
+        if (disturbance) {
+            bv = *disturbance;
+            if (bv.force) bv.force += lo * 3;
+            if (bv.torque) bv.torque += lo * 3;
+            if (bv.cross) bv.cross += lo * 72;
+            if (bv.cov) bv.cov += lo * 21;
+        }
         try {
+            if (bv.force_hist && !whole) fh.resize((size_t)T * n * 3);
+            if (bv.torque_hist && !whole) th.resize((size_t)T * n * 3);
             if (dv.llr_hist && !whole) lh.resize((size_t)T * n * NT * dv.n_levels);
             if (ev.est_hist && !whole) eh.resize((size_t)T * n * 13);
             if (sv.meas_hist && !whole) mh.resize((size_t)T * n * 13);
@@ -385,6 +401,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sv.pred_hist) sv.pred_hist = ph.data();
             if (ev.est_hist) ev.est_hist = eh.data();
             if (dv.llr_hist) dv.llr_hist = lh.data();
+            if (bv.force_hist) bv.force_hist = fh.data();
+            if (bv.torque_hist) bv.torque_hist = th.data();
         }
         const int rc2 = wrench ? ftmpc_simulate_wrench_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                      hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
@@ -395,11 +413,12 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                                                                      sensor ? &sv : nullptr, estimator ? &ev : nullptr,
                                                                      diagnosis ? &dv : nullptr, out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
                                                                      no_hull_step ? no_hull_step + lo : nullptr)
-                               : ftmpc_simulate_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
-                                                               seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                               bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
-                                                               actuator ? &at : nullptr, sensor ? &sv : nullptr,
-                                                               estimator ? &ev : nullptr, diagnosis ? &dv : nullptr);
+                               : ftmpc_simulate_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj,
+                                                                 noise, seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                                 bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
+                                                                 actuator ? &at : nullptr, sensor ? &sv : nullptr,
+                                                                 estimator ? &ev : nullptr, diagnosis ? &dv : nullptr,
+                                                                 disturbance ? &bv : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -411,6 +430,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sensor && sensor->pred_hist) scatter_rows(sensor->pred_hist, ph.data(), T, B, lo, n, 13);
             if (estimator && estimator->est_hist) scatter_rows(estimator->est_hist, eh.data(), T, B, lo, n, 13);
             if (diagnosis && diagnosis->llr_hist) scatter_rows(diagnosis->llr_hist, lh.data(), T, B, lo, n, (int64_t)NT * dv.n_levels);
+            if (disturbance && disturbance->force_hist) scatter_rows(disturbance->force_hist, fh.data(), T, B, lo, n, 3);
+            if (disturbance && disturbance->torque_hist) scatter_rows(disturbance->torque_hist, th.data(), T, B, lo, n, 3);
         }
         return FTMPC_OK;
     });
@@ -764,6 +785,19 @@ int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, d
                                          const ftmpc_diagnosis* diagnosis) {
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
                           0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis);
+}
+
+int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                           const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                           int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                           double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                           const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                           const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                           const ftmpc_disturbance* disturbance) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis,
+                          nullptr, nullptr, disturbance);
 }
 
 int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,

@@ -1598,4 +1598,359 @@ __global__ void __launch_bounds__(64) ftmpc_hull_switch_kernel(const DeviceConst
         for (int j = 0; j < 6; ++j) g[j] = p[j];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Disturbance estimation (ftmpc_simulate_disturbance_batch; include/ftmpc.h, ftmpc_disturbance): the navigation filter augmented by
+// six states per vehicle, a constant force f^ [3] in the inertial frame and a constant torque t^ [3] in the body frame (frames and
+// units of ftmpc_plant_model.force / .torque).  The error coordinates are (dp, dv, dtheta, dw, df, dt), 18 in all; the covariance
+// travels in three pieces, P_xx (the estimator's 78 packed doubles), P_xd (12 x 6, row-major) and P_dd (packed upper triangle, 21), so
+// that no lane ever holds all 171 doubles.  With H = [I 0] the x part of the update (P_xx, k_x, s_j, e_j) never reads P_xd or P_dd, and
+// Phi = [[Phi_xx, E], [0, I]] with E non-zero in two blocks, (v, f) = (dt / m) I and (w, t) = dt J^-1.  Four launches per loop step,
+// a lane per vehicle, every index into a register array a compile-time constant:
+//   PHASE 0  before the solve: ftmpc_filter_kernel<0>'s update of x^ and P_xx (78 doubles in registers), est_hist and err_sq; it
+//            leaves the twelve gain columns k_x, s_j and e_j = r_j - delta_j in the per-vehicle slot `gain` ([168][B])
+//   PHASE 1  holds P_xd and P_dd (93 doubles) and consumes the slot: k_d = P_xd[j, :]' / s_j, delta_d += k_d e_j,
+//            P_xd -= s_j k_x k_d', P_dd -= s_j k_d k_d'; then f^ += delta_d[0:3], t^ += delta_d[3:6], force_hist / torque_hist, the
+//            propagation of x^ over the queued commands with the model with the estimate (pred_hist), and the solve's x0
+//   PHASE 2  after the plant step: P_xx <- Phi_xx P_xx Phi_xx' + Q, ftmpc_filter_kernel<1>'s covariance walk
+//   PHASE 3  Y = Phi_xx P_xd, Z = E P_dd;  P_xx += Y E' + E Y' + Z E' (read-modify-write of the rows PHASE 2 wrote),
+//            P_xd <- Y + Z, P_dd += Q_d, then x^ <- one RK4 step of the model with the estimate, renormalised (f^, t^ unchanged)
+// The model with the estimate is plant_f_var with the config's m and J:  v' = (Rot(q)^T F + f^) / m,  w' = J^-1 (tau + t^ - w x J w).
+// Device-side P_xd, P_dd and the slot are component-major ([k][B]) as P_xx is; the estimate itself is vehicle-major [B][6] (f^, t^),
+// the array the linearise kernel's DIST instantiations and ftmpc_diagnose_dist_kernel read.  (The kernels stand at the end of the file
+// so that the build logs keep the source lines of every kernel above.)
+// ---------------------------------------------------------------------------------------------------------
+struct DistParams {
+    double* cross;            // [72][B] P_xd, k = 6 i + c, in/out
+    double* covd;             // [21][B] P_dd packed, in/out
+    double* dist;             // [B*6] f^, t^, in/out
+    double* gain;             // [168][B]: k_x of channel j at 12 j + i, s_j at 144 + j, e_j at 156 + j
+    double qdsq[2];           // proc_sigma^2 of the disturbance: force, torque
+    double* force_hist;       // nullptr or [T*B*3]: f^_{t|t}
+    double* torque_hist;      // nullptr or [T*B*3]
+};
+
+namespace {
+// packed index of P_dd(i, j), upper triangle row-major
+__host__ __device__ constexpr int tri6(int i, int j) {
+    return i <= j ? 6 * i - i * (i - 1) / 2 + (j - i) : 6 * j - j * (j - 1) / 2 + (i - j);
+}
+
+// one RK4 step of dt of the model with the estimate d = (f^, t^), the quaternion renormalised
+__device__ __forceinline__ void filter_rk4_dist(const DeviceConsts& C, double* x, const double* gen, const double* d) {
+    const double dt = C.dt;
+    const double g[6] = {gen[0], gen[1], gen[2], gen[3] + d[3], gen[4] + d[4], gen[5] + d[5]};
+    const double fm[3] = {d[0] * C.inv_mass, d[1] * C.inv_mass, d[2] * C.inv_mass};
+    double k1[13], k2[13], k3[13], k4[13], s[13];
+    plant_f_var(C.inv_mass, C.J, C.Jinv, fm, x, g, k1);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k1[i];
+    plant_f_var(C.inv_mass, C.J, C.Jinv, fm, s, g, k2);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + 0.5 * dt * k2[i];
+    plant_f_var(C.inv_mass, C.J, C.Jinv, fm, s, g, k3);
+    for (int i = 0; i < 13; ++i) s[i] = x[i] + dt * k3[i];
+    plant_f_var(C.inv_mass, C.J, C.Jinv, fm, s, g, k4);
+    for (int i = 0; i < 13; ++i) x[i] += dt / 6.0 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    const double qn = 1.0 / sqrt(x[6] * x[6] + x[7] * x[7] + x[8] * x[8] + x[9] * x[9]);
+    for (int i = 6; i < 10; ++i) x[i] *= qn;
+}
+
+// the dense blocks of Phi_xx about x under gen, as ftmpc_filter_kernel<1> forms them: G = -dt M [F/m]x, H = dt w, W
+__device__ __forceinline__ void filter_phi(const DeviceConsts& C, const double* x, const double* gen, double* G, double* H, double* W) {
+    const double dt = C.dt;
+    const double qx = x[6], qy = x[7], qz = x[8], qw = x[9];
+    const double w0 = x[10], w1 = x[11], w2 = x[12];
+    const double M[9] = {qx * qx - qy * qy - qz * qz + qw * qw, 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw),
+                         2 * (qx * qy + qz * qw), -qx * qx + qy * qy - qz * qz + qw * qw, 2 * (qy * qz - qx * qw),
+                         2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), -qx * qx - qy * qy + qz * qz + qw * qw};
+    const double f0 = gen[0] * C.inv_mass, f1 = gen[1] * C.inv_mass, f2 = gen[2] * C.inv_mass;
+    for (int r = 0; r < 3; ++r) {
+        G[3 * r] = -dt * (M[3 * r + 1] * f2 - M[3 * r + 2] * f1);
+        G[3 * r + 1] = -dt * (M[3 * r + 2] * f0 - M[3 * r] * f2);
+        G[3 * r + 2] = -dt * (M[3 * r] * f1 - M[3 * r + 1] * f0);
+    }
+    H[0] = dt * w0; H[1] = dt * w1; H[2] = dt * w2;
+    double Jw[3], S[9];
+    for (int i = 0; i < 3; ++i) Jw[i] = C.J[3 * i] * w0 + C.J[3 * i + 1] * w1 + C.J[3 * i + 2] * w2;
+    for (int c = 0; c < 3; ++c) {
+        S[c] = -(-w2 * C.J[3 + c] + w1 * C.J[6 + c]);
+        S[3 + c] = -(w2 * C.J[c] - w0 * C.J[6 + c]);
+        S[6 + c] = -(-w1 * C.J[c] + w0 * C.J[3 + c]);
+    }
+    S[1] += -Jw[2]; S[2] += Jw[1];
+    S[3] += Jw[2]; S[5] += -Jw[0];
+    S[6] += -Jw[1]; S[7] += Jw[0];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            W[3 * r + c] = (r == c ? 1.0 : 0.0) + dt * (C.Jinv[3 * r] * S[c] + C.Jinv[3 * r + 1] * S[3 + c] + C.Jinv[3 * r + 2] * S[6 + c]);
+}
+
+// sum_c M[i][c] E[j][c] for a 6-column row M of P_xd's shape: E[3 + r][r] = kf (j in the v block), E[9 + r][3 + s] = dt J^-1[r][s]
+// (j in the w block); i and j are constants once the callers' loops are unrolled
+__device__ __forceinline__ double dist_row_et(const DeviceConsts& C, const double* Mi, int j, double kf) {
+    if (j >= 3 && j < 6) return kf * Mi[j - 3];
+    const int r = j - 9;
+    return C.dt * (C.Jinv[3 * r] * Mi[3] + C.Jinv[3 * r + 1] * Mi[4] + C.Jinv[3 * r + 2] * Mi[5]);
+}
+__host__ __device__ constexpr bool dist_vw(int i) { return (i >= 3 && i < 6) || i >= 9; }
+}  // namespace
+
+template <int PHASE>
+__global__ void __launch_bounds__(64) ftmpc_filter_dist_kernel(const DeviceConsts C, const FilterParams F, const DistParams D) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= F.B) return;
+    const int64_t B = F.B;
+    const int64_t blk = (int64_t)blockIdx.x * blockDim.x;
+    double* const covb = F.cov + blk;
+    double* const gainb = D.gain + blk;
+    double* const crossb = D.cross + blk;
+    double* const covdb = D.covd + blk;
+    const unsigned lane = threadIdx.x;
+    if constexpr (PHASE == 0) {
+        double x[13], P[78], y[13];
+        for (int i = 0; i < 13; ++i) y[i] = F.y[b * 13 + i];
+        if (F.init) {
+            for (int i = 0; i < 13; ++i) x[i] = y[i];
+        } else {
+            for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        }
+        if (!F.init && F.update) {
+            double th[3], d[12];
+            filter_att_residual(x + 6, y + 6, th);
+#pragma unroll
+            for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                const int jx = j < 6 ? j : j + 1;
+                const double rj = (j >= 6 && j < 9) ? th[j - 6] : F.y[b * 13 + jx] - F.xhat[b * 13 + jx];
+                const double sj = P[tri(j, j)] + F.rsq[j / 3];
+                const double inv = 1.0 / sj;
+                double k[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) k[i] = P[tri(i, j)] * inv;
+                const double e = rj - d[j];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) cov_row(gainb + (int64_t)(12 * j + i) * B)[lane] = k[i];
+                cov_row(gainb + (int64_t)(144 + j) * B)[lane] = sj;
+                cov_row(gainb + (int64_t)(156 + j) * B)[lane] = e;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) d[i] += k[i] * e;
+#pragma unroll
+                for (int a = 0; a < 12; ++a) {
+                    const double ska = sj * k[a];
+#pragma unroll
+                    for (int c = a; c < 12; ++c) P[tri(a, c)] -= ska * k[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+            {     // (a volatile read, as in ftmpc_filter_kernel<0>: x^ is not held across the covariance)
+                const volatile double* const xh = F.xhat + b * 13;
+                for (int i = 0; i < 13; ++i) x[i] = xh[i];
+            }
+            for (int i = 0; i < 3; ++i) {
+                x[i] += d[i];
+                x[3 + i] += d[3 + i];
+                x[10 + i] += d[9 + i];
+            }
+            filter_rotate(x + 6, d[6], d[7], d[8]);
+        }
+        for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+        if (F.est_hist)
+            for (int i = 0; i < 13; ++i) F.est_hist[(F.step * B + b) * 13 + i] = x[i];
+        if (F.err_sq) {
+            double xt[13], th[3], e[4] = {0, 0, 0, 0};
+            for (int i = 0; i < 13; ++i) xt[i] = F.truth[b * 13 + i];
+            filter_att_residual(x + 6, xt + 6, th);
+            for (int i = 0; i < 3; ++i) {
+                e[0] += (x[i] - xt[i]) * (x[i] - xt[i]);
+                e[1] += (x[3 + i] - xt[3 + i]) * (x[3 + i] - xt[3 + i]);
+                e[2] += th[i] * th[i];
+                e[3] += (x[10 + i] - xt[10 + i]) * (x[10 + i] - xt[10 + i]);
+            }
+            for (int i = 0; i < 4; ++i) F.err_sq[b * 4 + i] += e[i];
+        }
+        return;
+    } else if constexpr (PHASE == 1) {
+        double dd[6];
+        for (int c = 0; c < 6; ++c) dd[c] = D.dist[b * 6 + c];
+        if (!F.init && F.update) {
+            double X[72], Pd[21], del[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 72; ++k) X[k] = cov_row(crossb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) Pd[k] = cov_row(covdb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                const double sj = cov_row(gainb + (int64_t)(144 + j) * B)[lane];
+                const double e = cov_row(gainb + (int64_t)(156 + j) * B)[lane];
+                const double inv = 1.0 / sj;
+                double kd[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) kd[c] = X[6 * j + c] * inv;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) del[c] += kd[c] * e;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) {
+                    const double ski = sj * cov_row(gainb + (int64_t)(12 * j + i) * B)[lane];
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) X[6 * i + c] -= ski * kd[c];
+                }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const double ska = sj * kd[a];
+#pragma unroll
+                    for (int c = a; c < 6; ++c) Pd[tri6(a, c)] -= ska * kd[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 72; ++k) cov_row(crossb + (int64_t)k * B)[lane] = X[k];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) cov_row(covdb + (int64_t)k * B)[lane] = Pd[k];
+            for (int c = 0; c < 6; ++c) dd[c] += del[c];
+            for (int c = 0; c < 6; ++c) D.dist[b * 6 + c] = dd[c];
+        }
+        if (D.force_hist)
+            for (int c = 0; c < 3; ++c) D.force_hist[(F.step * B + b) * 3 + c] = dd[c];
+        if (D.torque_hist)
+            for (int c = 0; c < 3; ++c) D.torque_hist[(F.step * B + b) * 3 + c] = dd[3 + c];
+        double x[13];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        if (F.predict) {
+            int32_t slot = F.slot0;
+#pragma unroll 1
+            for (int j = 0; j < F.latency; ++j) {
+                double gen[6];
+                filter_gen(C, F.ring + (int64_t)slot * B * C.NT, F.ub, F.stuck, b, gen);
+                slot = slot + 1 == F.nslots ? 0 : slot + 1;
+                filter_rk4_dist(C, x, gen, dd);
+            }
+            if (F.pred_hist)
+                for (int i = 0; i < 13; ++i) F.pred_hist[(F.step * B + b) * 13 + i] = x[i];
+        }
+        for (int i = 0; i < 13; ++i) F.x0[b * 13 + i] = x[i];
+        return;
+    } else if constexpr (PHASE == 2) {
+        double x[13], P[78], gen[6], G[9], H[3], W[9];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+#pragma unroll
+        for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+        filter_gen(C, F.u, F.ub, F.stuck, b, gen);
+        filter_phi(C, x, gen, G, H, W);
+        const double dt = C.dt;
+        cov_block<0, 0>(P, G, H, W, dt);
+        cov_block<0, 1>(P, G, H, W, dt);
+        cov_block<0, 2>(P, G, H, W, dt);
+        cov_block<0, 3>(P, G, H, W, dt);
+        cov_block<1, 1>(P, G, H, W, dt);
+        cov_block<1, 2>(P, G, H, W, dt);
+        cov_block<1, 3>(P, G, H, W, dt);
+        cov_block<2, 2>(P, G, H, W, dt);
+        cov_block<2, 3>(P, G, H, W, dt);
+        cov_block<3, 3>(P, G, H, W, dt);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) P[tri(i, i)] += F.qsq[i / 3];
+#pragma unroll
+        for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+        return;
+    } else {
+        double x[13], gen[6], G[9], H[3], W[9];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        filter_gen(C, F.u, F.ub, F.stuck, b, gen);
+        filter_phi(C, x, gen, G, H, W);
+        const double dt = C.dt, kf = C.dt * C.inv_mass;
+        double Zv[18], Zw[18];      // Z = E P_dd: the rows of the v block and of the w block
+        {
+            double Pd[21];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) Pd[k] = cov_row(covdb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    Zv[6 * r + c] = kf * Pd[tri6(r, c)];
+                    Zw[6 * r + c] = dt * (C.Jinv[3 * r] * Pd[tri6(3, c)] + C.Jinv[3 * r + 1] * Pd[tri6(4, c)] + C.Jinv[3 * r + 2] * Pd[tri6(5, c)]);
+                }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) Pd[tri6(i, i)] += D.qdsq[i / 3];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) cov_row(covdb + (int64_t)k * B)[lane] = Pd[k];
+        }
+        double X[72];
+#pragma unroll
+        for (int k = 0; k < 72; ++k) X[k] = cov_row(crossb + (int64_t)k * B)[lane];
+        // Y = Phi_xx P_xd in place: row block I needs the old blocks I and I + 1 alone
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const double p0 = X[c], p1 = X[6 + c], p2 = X[12 + c];
+            const double v0 = X[18 + c], v1 = X[24 + c], v2 = X[30 + c];
+            const double a0 = X[36 + c], a1 = X[42 + c], a2 = X[48 + c];
+            const double r0 = X[54 + c], r1 = X[60 + c], r2 = X[66 + c];
+            X[c] = p0 + dt * v0;
+            X[6 + c] = p1 + dt * v1;
+            X[12 + c] = p2 + dt * v2;
+            X[18 + c] = v0 + (G[0] * a0 + G[1] * a1 + G[2] * a2);
+            X[24 + c] = v1 + (G[3] * a0 + G[4] * a1 + G[5] * a2);
+            X[30 + c] = v2 + (G[6] * a0 + G[7] * a1 + G[8] * a2);
+            X[36 + c] = a0 - (H[1] * a2 - H[2] * a1) + dt * r0;
+            X[42 + c] = a1 - (H[2] * a0 - H[0] * a2) + dt * r1;
+            X[48 + c] = a2 - (H[0] * a1 - H[1] * a0) + dt * r2;
+            X[54 + c] = W[0] * r0 + W[1] * r1 + W[2] * r2;
+            X[60 + c] = W[3] * r0 + W[4] * r1 + W[5] * r2;
+            X[66 + c] = W[6] * r0 + W[7] * r1 + W[8] * r2;
+        }
+        // P_xx(i, j) += (Y E')(i, j) + (Y E')(j, i) + (Z E')(i, j), i <= j: zero unless i or j lies in the v or the w block
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+#pragma unroll
+            for (int j = i; j < 12; ++j) {
+                if (!dist_vw(i) && !dist_vw(j)) continue;
+                double t = 0.0;
+                if (dist_vw(j)) t += dist_row_et(C, X + 6 * i, j, kf);
+                if (dist_vw(i)) t += dist_row_et(C, X + 6 * j, i, kf);
+                if (dist_vw(i) && dist_vw(j)) t += dist_row_et(C, i < 6 ? Zv + 6 * (i - 3) : Zw + 6 * (i - 9), j, kf);
+                cov_row(covb + (int64_t)tri(i, j) * B)[lane] += t;
+            }
+        // P_xd = Y + Z
+#pragma unroll
+        for (int k = 0; k < 18; ++k) {
+            X[18 + k] += Zv[k];
+            X[54 + k] += Zw[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 72; ++k) cov_row(crossb + (int64_t)k * B)[lane] = X[k];
+        double dd[6];
+        for (int c = 0; c < 6; ++c) dd[c] = D.dist[b * 6 + c];
+        filter_rk4_dist(C, x, gen, dd);
+        for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+    }
+}
+template __global__ void ftmpc_filter_dist_kernel<0>(const DeviceConsts, const FilterParams, const DistParams);
+template __global__ void ftmpc_filter_dist_kernel<1>(const DeviceConsts, const FilterParams, const DistParams);
+template __global__ void ftmpc_filter_dist_kernel<2>(const DeviceConsts, const FilterParams, const DistParams);
+template __global__ void ftmpc_filter_dist_kernel<3>(const DeviceConsts, const FilterParams, const DistParams);
+
+// phase 1 of ftmpc_diagnose_kernel with the model with the estimate: xt <- one RK4 step under a_t, the controller's pattern and
+// (f^, t^) of this step's filter update; acc and n as there.  The test (phase 0) is ftmpc_diagnose_kernel<0>'s.
+__global__ void __launch_bounds__(64) ftmpc_diagnose_dist_kernel(const DeviceConsts C, const DiagParams P, const double* dist) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int64_t B = P.B;
+    const int NT = C.NT;
+    double x[13], dd[6];
+    for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+    for (int c = 0; c < 6; ++c) dd[c] = dist[b * 6 + c];
+    double gen[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll 1
+    for (int i = 0; i < NT; ++i) {
+        const double c = P.ub[b * NT + i] > 0.0 ? P.u[b * NT + i] : 0.0;
+        const double t = c + P.stuck[b * NT + i];
+        for (int g = 0; g < 6; ++g) gen[g] += C.D[g * MAX_NT + i] * t;
+        P.acc[(int64_t)i * B + b] += c;
+    }
+    filter_rk4_dist(C, x, gen, dd);
+    for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = x[i];
+    P.xt[b * 14 + 13] += 1.0;
+}
+
 }  // namespace ftmpc

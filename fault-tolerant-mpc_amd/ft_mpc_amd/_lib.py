@@ -39,6 +39,7 @@ SYMBOLS = (
     "ftmpc_multi_simulate_estimator_batch", "ftmpc_multi_simulate_wrench_estimator_batch",
     "ftmpc_simulate_diagnosis_batch", "ftmpc_multi_simulate_diagnosis_batch",
     "ftmpc_hull_offsets_batch", "ftmpc_simulate_wrench_diagnosis_batch", "ftmpc_multi_simulate_wrench_diagnosis_batch",
+    "ftmpc_simulate_disturbance_batch", "ftmpc_multi_simulate_disturbance_batch", "ftmpc_debug_records_disturbance",
 )
 
 
@@ -139,6 +140,14 @@ class ftmpc_diagnosis(C.Structure):
     ]
 
 
+class ftmpc_disturbance(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("compensate", C.c_int32), ("p0", C.c_double * 2), ("proc_sigma", C.c_double * 2),
+        ("force", C.POINTER(C.c_double)), ("torque", C.POINTER(C.c_double)), ("cross", C.POINTER(C.c_double)),
+        ("cov", C.POINTER(C.c_double)), ("force_hist", C.POINTER(C.c_double)), ("torque_hist", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -224,6 +233,8 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_diagnosis_batch.argtypes = lib.ftmpc_simulate_diagnosis_batch.argtypes
     lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes = lib.ftmpc_simulate_wrench_estimator_batch.argtypes + [C.POINTER(ftmpc_diagnosis), dp, ip]
     lib.ftmpc_multi_simulate_wrench_diagnosis_batch.argtypes = lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes
+    lib.ftmpc_simulate_disturbance_batch.argtypes = lib.ftmpc_simulate_diagnosis_batch.argtypes + [C.POINTER(ftmpc_disturbance)]
+    lib.ftmpc_multi_simulate_disturbance_batch.argtypes = lib.ftmpc_simulate_disturbance_batch.argtypes
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
@@ -244,6 +255,7 @@ def load_library() -> C.CDLL:
     lib.ftmpc_debug_build_qp.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, C.c_int64,
                                          dp, C.c_int64, dp, dp, dp, ip]
     lib.ftmpc_debug_records.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp]
+    lib.ftmpc_debug_records_disturbance.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_debug_struct_grad.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, C.POINTER(C.c_float), C.c_int32, dp]
     lib.ftmpc_version.restype = C.c_int32
     lib.ftmpc_build_id.restype = C.c_char_p

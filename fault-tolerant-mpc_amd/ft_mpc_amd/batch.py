@@ -447,7 +447,7 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None):
+                 plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -513,11 +513,21 @@ class BatchedMPC:
         out["diagnosis"] gains hull_b [B,rows], the controller's offsets after the last step, and no_hull [B], the step of the first
         detection that left a pattern without a hull (-1: none; the offsets then stay as they were); hand both back as
         diagnosis["hull_b"] / diagnosis["no_hull"] for a continued run.  With `faults` no event hull tables are built.
+        disturbance: the estimator's filter augmented by a constant force f^ (inertial frame, N) and torque t^ (body frame, N m) per
+        vehicle, the frames and units of plant["force"] / plant["torque"], and the estimate given to every consumer of the
+        controller's model (include/ftmpc.h, ftmpc_disturbance; ft_mpc_amd.disturbances restates it in NumPy; thruster formulation,
+        sqp_iters = 0, needs `estimator`): a dict with p0=(2,), proc_sigma=(2,) (standard deviations of force and torque: initial, and
+        per step), compensate=True (the linearisation the QP is built from uses the estimate too, which removes the steady offset of
+        a constant disturbance; False: only the filter and the diagnosis do, the controller stays nominal), force=None, torque=None
+        ([B,3], the estimates to start from; default 0), cross=None ([B,72] or [B,12,6]; needs force, torque and estimator["xhat"])
+        and cov=None ([B,21] packed or [B,6,6]; needs cross) -- what a previous call returned, for a continued run -- and
+        fields=(...) among force_hist, torque_hist [T,B,3] (the estimates each solve saw) and state (force, torque [B,3], cross
+        [B,72], cov [B,21]: the priors of step T); they come back as out["disturbance"].
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator, diagnosis)
+                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -614,6 +624,22 @@ class BatchedMPC:
         rec = np.zeros((B, N, 152))
         self._check(self.lib.ftmpc_debug_records(self._h, B, _ptr(x0), _ptr(ub), _ptr(stuck), _ptr(xref), xs,
                                                  _ptr(uref), us, _ptr(warm), _ptr(rec)))
+        return rec
+
+    def debug_records_disturbance(self, x0, ub, stuck, xref, dist, uref=None, warmU=None):
+        """debug_records through the linearise kernel's instantiation with the estimated disturbance dist [B,6] = (f^ inertial,
+        t^ body): what a loop with disturbance["compensate"] launches (ftmpc_debug_records_disturbance)."""
+        N, NT = self.cfg.N, self.cfg.NT
+        x0 = _f64(x0).reshape(-1, 13)
+        B = x0.shape[0]
+        ub = _f64(ub, (B, NT))
+        stuck = _f64(stuck, (B, NT))
+        dist = _f64(dist, (B, 6))
+        xref, xs, uref, us = self._refs(B, xref, uref)
+        warm = None if warmU is None else _f64(warmU, (B, N, NT))
+        rec = np.zeros((B, N, 152))
+        self._check(self.lib.ftmpc_debug_records_disturbance(self._h, B, _ptr(x0), _ptr(ub), _ptr(stuck), _ptr(xref), xs,
+                                                             _ptr(uref), us, _ptr(warm), _ptr(dist), _ptr(rec)))
         return rec
 
     def debug_struct_grad(self, x0, ub, stuck, xref, d, form, uref=None, warmU=None):
@@ -905,9 +931,44 @@ def _diagnosis_request(diagnosis, x0, B, T, NT, estimator, sensor):
     return dg, keep, out
 
 
+def _disturbance_request(disturbance, B, T, estimator, sqp_iters, formulation):
+    """The ftmpc_disturbance struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .disturbances import NC, NDD, request
+    r = request(disturbance, B, T, estimator, sqp_iters, formulation)
+    db = _lib.ftmpc_disturbance(struct_size=C.sizeof(_lib.ftmpc_disturbance), compensate=int(r["compensate"]))
+    for k in range(2):
+        db.p0[k], db.proc_sigma[k] = float(r["p0"][k]), float(r["proc_sigma"][k])
+    keep, out = [], {}
+    force, torque, cross, cov = r["force"], r["torque"], r["cross"], r["cov"]
+    if "state" in r["fields"]:
+        # in/out: asked back without being handed over, they start as the library's defaults would; cross and cov need the
+        # estimator's xhat (without it the first step initialises the filter on the device and nothing is staged)
+        force = np.zeros((B, 3)) if force is None else force
+        torque = np.zeros((B, 3)) if torque is None else torque
+        if estimator.get("xhat") is not None:
+            cross = np.zeros((B, NC)) if cross is None else cross
+            if cov is None:
+                cov = np.zeros((B, NDD))
+                cov[:, np.cumsum([0, 6, 5, 4, 3, 2])] = np.repeat(r["p0"] ** 2, 3)[None, :]
+        elif cross is not None or cov is not None:
+            raise ValueError("disturbance['cross'] requires estimator['xhat']")
+        out["force"], out["torque"] = force, torque
+        if cross is not None:
+            out["cross"], out["cov"] = cross, cov
+    keep += [force, torque, cross, cov]
+    db.force, db.torque, db.cross, db.cov = _ptr(force), _ptr(torque), _ptr(cross), _ptr(cov)
+    if "force_hist" in r["fields"]:
+        out["force_hist"] = np.zeros((T, B, 3))
+        db.force_hist = _ptr(out["force_hist"])
+    if "torque_hist" in r["fields"]:
+        out["torque_hist"] = np.zeros((T, B, 3))
+        db.torque_hist = _ptr(out["torque_hist"])
+    return db, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None, diagnosis=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -945,6 +1006,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             if d_nh.shape != (B,) or (d_nh < -1).any():
                 raise ValueError(f"diagnosis['no_hull'] must have shape {(B,)} and no entry below -1")
     dg, dkeep, dout = _diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor) if diagnosis is not None else (None, None, None)
+    db, bkeep, bout = (_disturbance_request(disturbance, B, T, estimator, sqp_iters, formulation) if disturbance is not None
+                       else (None, None, None))
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -993,7 +1056,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     pm, pkeep = _plant_request(plant, B, NT) if plant is not None else (None, None)
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
-           or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None)
+           or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
+           or db is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1016,6 +1080,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["estimator"] = eout
         if dout is not None:
             out["diagnosis"] = dout
+        if bout is not None:
+            out["disturbance"] = bout
         return out
     msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
@@ -1100,6 +1166,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if db is not None:
+        self._check(getattr(self.lib, pre + "disturbance_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
+            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+            C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None, C.byref(db)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if dg is not None:
         self._check(getattr(self.lib, pre + "diagnosis_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

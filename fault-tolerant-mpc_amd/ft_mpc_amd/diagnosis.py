@@ -67,16 +67,24 @@ def test_step(llr, y, xt, n, acc, ub, spec, cfg):
 test_step.__test__ = False      # (not a test of the suite, whatever its name)
 
 
-def propagate(xt, n, acc, u, ub, stuck, cfg):
-    """(xt, n, acc) after the model's step under the applied command u [NT] and the controller's pattern."""
+def propagate(xt, n, acc, u, ub, stuck, cfg, force=None, torque=None):
+    """(xt, n, acc) after the model's step under the applied command u [NT] and the controller's pattern; force / torque [3]: the
+    estimated disturbance of the step (ft_mpc_amd.disturbances), None: the model without one."""
     c = np.where(np.asarray(ub).reshape(-1) > 0, np.asarray(u, dtype=np.float64).reshape(-1), 0.0)
-    return predict(xt, np.asarray(u, dtype=np.float64).reshape(1, -1), ub, stuck, cfg), n + 1, np.asarray(acc, dtype=np.float64) + c
+    if force is None and torque is None:
+        xn = predict(xt, np.asarray(u, dtype=np.float64).reshape(1, -1), ub, stuck, cfg)
+    else:
+        from .disturbances import predict as predict_dist
+        xn = predict_dist(xt, np.zeros(3) if force is None else force, np.zeros(3) if torque is None else torque,
+                          np.asarray(u, dtype=np.float64).reshape(1, -1), ub, stuck, cfg)
+    return xn, n + 1, np.asarray(acc, dtype=np.float64) + c
 
 
-def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None):
+def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None):
     """The loop's diagnosis for ONE vehicle.  meas [T,13]: the y_t; applied_u [T,NT]: the a_t (u_hist); ub, stuck [NT]: the
     controller's pattern at the call's start; spec: dict(every, levels, resid_sigma, drift_sigma, threshold, max_detect); state
-    [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned.
+    [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned; force / torque [T,3]: the
+    estimated disturbance of each step (simulate(disturbance=...): force_hist / torque_hist) for the propagation, None: without.
     Returns dict(llr_hist [T,NT*L], detections [(step, thruster, level)], ub [T,NT], stuck [T,NT] (the pattern each solve saw),
     ub_end, stuck_end, state [14+NT], llr [NT*L], peak [T] (the largest statistic of every step that tested, else nan))."""
     meas = np.asarray(meas, dtype=np.float64).reshape(-1, 13)
@@ -117,7 +125,8 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
             if c % every == 0:
                 xt, n, acc = meas[t].copy(), 0, np.zeros(NT)
         ubh[t], sth[t] = ub, stuck
-        xt, n, acc = propagate(xt, n, acc, u[t], ub, stuck, cfg)
+        xt, n, acc = propagate(xt, n, acc, u[t], ub, stuck, cfg, None if force is None else np.asarray(force)[t],
+                               None if torque is None else np.asarray(torque)[t])
     return dict(llr_hist=hist, detections=det, ub=ubh, stuck=sth, ub_end=ub, stuck_end=stuck,
                 state=np.concatenate([xt, [float(n)], acc]), llr=s.reshape(-1), peak=peak)
 

@@ -937,6 +937,69 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                           int32_t* no_hull_step);
 
+/* On-device disturbance estimation and offset-free control (thruster form, one QP per step).  The filter of ftmpc_estimator is
+ * augmented by six states per vehicle: f^ [3], a constant force in the inertial frame (N), and t^ [3], a constant torque in the body
+ * frame (N m): the frames and units of ftmpc_plant_model.force / .torque.  The estimate is given to every consumer of the
+ * controller's model: the filter's own prediction, the diagnosis' prediction and, compensate = 1, the linearisation the QP is built
+ * from, which removes the steady tracking offset a constant disturbance leaves under the nominal MPC (it has no integral action).
+ * The parameters are uniform over the call; the state and the outputs are per vehicle.
+ *   error coordinates (dp, dv, dtheta, dw, df, dt), 18 in all; the covariance travels in three pieces: P_xx = ftmpc_estimator.cov
+ *   (78 packed), P_xd = cross (12 x 6, row-major, 72) and P_dd = cov (packed upper triangle, row-major, 21).
+ *   the model with the estimate, the plant's own equation (ftmpc_plant_model) with the config's m, J and D:
+ *     v' = (Rot(q)^T F + f^) / m,   w' = J^-1 (tau + t^ - w x J w),   f^ and t^ held over the step.
+ *   measurement update, when the estimator's update runs, H = [I 0] and the estimator's R: its twelve sequential scalar updates
+ *     carried over all 18 coordinates:  s_j = P_jj + R_j,  k = P[:, j] / s_j (18 entries),  delta += k (r_j - delta_j),
+ *     P -= s_j k k';  then x^ <- x^ [+] delta[0:12], f^ += delta[12:15], t^ += delta[15:18].
+ *   time update, with a_t and gen as in the estimator:  Phi = [[Phi_xx, Phi_xd], [0, I]], Phi_xx the estimator's (its G block from
+ *     F / m), Phi_xd with two non-zero blocks (v, f) = (dt / m) I and (w, t) = dt J^-1,
+ *     P <- Phi P Phi' + diag(estimator.proc_sigma[g]^2, proc_sigma[0]^2 x 3, proc_sigma[1]^2 x 3);  x^ <- one RK4 step of the
+ *     model with the estimate, renormalised;  f^ and t^ unchanged.
+ *   per loop step t (campaign step c = step0 + t):
+ *     1. ftmpc_sense_kernel forms y_t; the diagnosis' phase 0 (test, decision, re-anchor) as without the struct;
+ *     2. filter phase 0 (ftmpc_filter_dist_kernel<0>, <1>).  On the first step of a call that was not handed xhat: x^ = y_t,
+ *        P_xx = diag(estimator.p0[g]^2), P_xd = 0, P_dd = diag(p0[0]^2 x 3, p0[1]^2 x 3), f^ / t^ the handed values or 0, no update.
+ *        Otherwise the update runs when c % every == 0.  est_hist[t] = x^_{t|t}, force_hist[t] = f^_{t|t}, torque_hist[t] = t^_{t|t};
+ *        when the sensor predicts, x^_{t|t} is propagated over the d queued commands with the model with the estimate (pred_hist);
+ *        the result is the x0 of the solve;
+ *     3. the solve.  compensate = 1: the linearise kernel's DIST instantiation rolls the orbit-centre model out under tau + t^ and
+ *        f^ / m (d^_{t|t}); the cost's R .* (gen - ur - f_virt) keeps the commanded gen.  compensate = 0: the plain instantiation,
+ *        so the controller stays nominal (the A/B switch of a campaign).  Command queue and plant step as without the struct;
+ *     4. the diagnosis' phase 1 with the model with the estimate d^_{t|t} (ftmpc_diagnose_dist_kernel); the filter's time update
+ *        (ftmpc_filter_dist_kernel<2>, <3>).
+ * A handed force / torque / cross / cov are the priors of the call's first step; on return they hold the priors of step T, so that a
+ * continued run (with the estimator's xhat / cov, the sensor's pending / step0 and the diagnosis' carry-over) is the whole run bit for
+ * bit.  disturbance = NULL launches exactly the kernels of ftmpc_simulate_diagnosis_batch and returns its bits.
+ * Not served: the two-stage wrench form (ftmpc_simulate_wrench_* has no disturbance entry), the SQP loops (the cost kernels do not
+ * know the estimate), m / J / D (a gain or centre-of-mass error shows up as a command-dependent part of (f^, t^)), per-vehicle filter
+ * parameters, ftmpc_multi_upload / _step.  Known limit: an undetected stuck thruster is a constant body wrench, so a slow t^ absorbs
+ * its torque signature over time; proc_sigma has to be small against the CUSUM's detection time.
+ * FTMPC_ERR_ARG, the message naming ftmpc_disturbance.<field> and, for an array, the first offending vehicle, the call's x untouched:
+ * a struct_size other than sizeof(ftmpc_disturbance); no estimator; sqp_iters > 0; compensate outside {0, 1}; a p0 or proc_sigma
+ * negative or not finite; cross without force, torque or the estimator's xhat; cov without cross; a force, torque, cross or cov entry
+ * not finite; a diagonal entry of cov below zero.
+ */
+typedef struct ftmpc_disturbance {
+    int32_t struct_size;   /* sizeof(ftmpc_disturbance) */
+    int32_t compensate;    /* 0 / 1 */
+    double p0[2];          /* initial standard deviations: force (N), torque (N m), >= 0 */
+    double proc_sigma[2];  /* per step, >= 0 */
+    double* force;         /* NULL (start at 0) or [B*3] in/out */
+    double* torque;        /* NULL or [B*3] in/out */
+    double* cross;         /* NULL or [B*72] in/out; requires force, torque and estimator->xhat */
+    double* cov;           /* NULL or [B*21] in/out; requires cross */
+    double* force_hist;    /* NULL or [T*B*3] out: f^_{t|t} */
+    double* torque_hist;   /* NULL or [T*B*3] out */
+} ftmpc_disturbance;
+
+/* ftmpc_simulate_diagnosis_batch with the disturbance estimate `disturbance` (NULL: exactly ftmpc_simulate_diagnosis_batch). */
+int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                     const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                     const ftmpc_disturbance* disturbance);
+
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
  * not launched), for slot < min(n_slots, FTMPC_KERNEL_SLOTS); ftmpc_kernel_name(slot) is the kernel's name as it appears
@@ -984,6 +1047,15 @@ int ftmpc_debug_records(ftmpc_handle* h, int64_t B,
                         const double* xref, int64_t xref_stride,
                         const double* uref, int64_t uref_stride,
                         const double* warmU, double* rec_out);
+
+/* Test hook: ftmpc_debug_records through the linearise kernel's DIST instantiation (the one a loop with
+ * ftmpc_disturbance.compensate = 1 launches) with the estimated disturbance dist [B*6]: per vehicle f^ [3] (inertial, N), then
+ * t^ [3] (body, N m).  With dist all zero the records are the bits of ftmpc_debug_records. */
+int ftmpc_debug_records_disturbance(ftmpc_handle* h, int64_t B,
+                                    const double* x0, const double* ub, const double* stuck,
+                                    const double* xref, int64_t xref_stride,
+                                    const double* uref, int64_t uref_stride,
+                                    const double* warmU, const double* dist, double* rec_out);
 
 /*
  * Test hook: the float64 reference gradient of the fp32 solve kernels (csrc/ftmpc_solve.hip, struct_grad_at) alone.  Linearises
@@ -1163,6 +1235,18 @@ int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32
                                                 const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                 const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                                 int32_t* no_hull_step);
+/* ftmpc_multi_simulate_diagnosis_batch with the disturbance estimate `disturbance` (ftmpc_disturbance; NULL: exactly that entry).
+ * The struct is checked once over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; force /
+ * torque + 3 lo, cross + 72 lo and cov + 21 lo are read and written per shard, force_hist / torque_hist are copied row by row from
+ * the shard's staging as llr_hist is.  ftmpc_multi_upload / _step take no disturbance. */
+int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                           const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                           int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                           double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                           const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                           const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                           const ftmpc_disturbance* disturbance);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
