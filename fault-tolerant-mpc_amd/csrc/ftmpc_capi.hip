@@ -193,6 +193,7 @@ struct ftmpc_handle {
     // cost and terminal-set violation of the start point and of the result | flags and counters (as d_sqF) | merits of all trial points
     // (cap_swsqp instances: d_swG, d_swT, d_swJ, d_swF)
     DevBuf<double> d_swG, d_swT, d_swJ, d_swJall, d_swX;
+    DevBuf<double> d_ldist;            // the caller's estimate [B*6] of the ftmpc_*_wrench_disturbance_batch entries (lin_dist points at it)
     DevBuf<int32_t> d_swF;
     int64_t cap_swsqp = 0;
     // kernel 13: the two-stage form in float64 by the Riccati recursion (no terminal set, N <= 40, up to 128 hull rows)
@@ -1482,6 +1483,7 @@ static int wrench_qp_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool
     lp.out_eN = h->d_eN;
     lp.tcost = h->d_tcost;
     lp.out_cbar = h->sbounds ? h->d_cbar.p : nullptr;      // the linearisation trajectory (about warmG, or D stuck) for the state rows
+    lp.dist = h->lin_dist;      // (launch_linearize picks the DIST grid)
     launch_linearize(h, B, (int)((B + 63) / 64), s, lp);
     HIP_TRY(h, hipGetLastError());
     // the wrench problem stops at mu 1e-10 unless the caller asked otherwise (general rows: see ftmpc_config.mu_stop)
@@ -1573,10 +1575,63 @@ static int wrench_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool ha
     return wrench_alloc_enqueue(h, B, forked);
 }
 
+// The estimate of a ftmpc_*_wrench_disturbance_batch entry: dist [B*6] staged into h->d_ldist and h->lin_dist pointed at it for as
+// long as the scope lives (wrench_qp_enqueue, cost_wrench_params read it), cleared on every way out.  dist = nullptr: nothing is set.
+struct LinDistScope {
+    ftmpc_handle* h;
+    explicit LinDistScope(ftmpc_handle* hh) : h(hh) {}
+    LinDistScope(const LinDistScope&) = delete;
+    LinDistScope& operator=(const LinDistScope&) = delete;
+    ~LinDistScope() { h->lin_dist = nullptr; }
+    int stage(int64_t B, const double* dist) {
+        if (!dist) return FTMPC_OK;
+        int rc = h->d_ldist.ensure(h, B * 6);
+        if (rc != FTMPC_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->d_ldist, dist, (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->lin_dist = h->d_ldist;
+        return FTMPC_OK;
+    }
+};
+static int check_dist(ftmpc_handle* h, int64_t B, const double* dist) {
+    if (!dist) return fail(h, FTMPC_ERR_ARG, "dist is NULL (the plain entry takes no estimate)");
+    for (int64_t i = 0; i < B * 6; ++i)
+        if (!std::isfinite(dist[i]))
+            return fail(h, FTMPC_ERR_ARG, "dist: vehicle " + std::to_string(i / 6) + " has a non-finite entry (" + std::to_string(i % 6) + ")");
+    return FTMPC_OK;
+}
+
+static int solve_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                        const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, double* warmG,
+                        double* out_u0, double* out_tau0, double* out_G, int32_t* status, int32_t* iters, int32_t* alloc_status,
+                        const double* dist);
+
 int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
                              const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
                              const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, double* warmG,
                              double* out_u0, double* out_tau0, double* out_G, int32_t* status, int32_t* iters, int32_t* alloc_status) {
+    return solve_wrench(h, B, x0, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref, xref_stride, uref, uref_stride, warmG, out_u0,
+                        out_tau0, out_G, status, iters, alloc_status, nullptr);
+}
+
+int ftmpc_solve_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                         int32_t hull_rows, const double* xref, int64_t xref_stride, const double* uref,
+                                         int64_t uref_stride, double* warmG, const double* dist, double* out_u0, double* out_tau0,
+                                         double* out_G, int32_t* status, int32_t* iters, int32_t* alloc_status) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0) return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
+    const int rc = check_dist(h, B, dist);
+    if (rc != FTMPC_OK) return rc;
+    return solve_wrench(h, B, x0, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref, xref_stride, uref, uref_stride, warmG, out_u0,
+                        out_tau0, out_G, status, iters, alloc_status, dist);
+}
+
+static int solve_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                        const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, double* warmG,
+                        double* out_u0, double* out_tau0, double* out_G, int32_t* status, int32_t* iters, int32_t* alloc_status,
+                        const double* dist) {
     if (!h) return FTMPC_ERR_ARG;
     if (B < 0 || !x0 || !ub || !stuck || !xref || !out_u0 || !hull_A || !hull_b)
         return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
@@ -1589,6 +1644,8 @@ int ftmpc_solve_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const
     if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmG) HIP_TRY(h, hipMemcpyAsync(h->d_warmG, warmG, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    LinDistScope ds(h);
+    if ((rc = ds.stage(B, dist)) != FTMPC_OK) return rc;
     if ((rc = wrench_enqueue(h, B, hull_rows, hull_set != nullptr, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride,
                              warmG ? h->d_warmG : nullptr)) != FTMPC_OK)
         return rc;
@@ -1649,7 +1706,16 @@ static ftmpc::CostWrenchParams cost_wrench_params(const ftmpc_handle* h, int64_t
     fill_term(h, cw);
     cw.sigma = sigma;
     cw.out_merit = cw.out_cost = cw.out_tviol = cw.out_X = nullptr;
+    cw.dist = h->lin_dist;
     return cw;
+}
+
+// the wrench cost / merit kernel over `lanes` lanes: the DIST instantiation under an estimate (cw.dist), else the plain one
+static void launch_cost_wrench(const ftmpc_handle* h, int64_t lanes, hipStream_t s, const ftmpc::CostWrenchParams& cw) {
+    if (cw.dist)
+        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel<1>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, h->dc, cw);
+    else
+        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel<0>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, h->dc, cw);
 }
 
 // One wrench SQP solve over DEVICE buffers (h->d_x0 / d_ub / d_stuck, the hull tables staged by wrench_prepare, the given reference
@@ -1683,7 +1749,7 @@ static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_
         c0.G = S.U;
         c0.out_merit = S.J;
         c0.out_cost = h->d_swJ + 2 * B;
-        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, c0);
+        launch_cost_wrench(h, B, s, c0);
     }
     HIP_TRY(h, hipGetLastError());
     for (int it = 0; it < sqp_iters; ++it) {
@@ -1698,7 +1764,7 @@ static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_
         ct.todo = S.todo;
         ct.ntrial = backtracks;
         ct.out_merit = h->d_swJall;
-        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B * backtracks + 63) / 64)), dim3(64), 0, s, h->dc, ct);
+        launch_cost_wrench(h, B * backtracks, s, ct);
         hipLaunchKernelGGL(ftmpc::ftmpc_sqp_pick_kernel, dim3(gB), dim3(256), 0, s, S);
         hipLaunchKernelGGL(ftmpc::ftmpc_sqpw_close_kernel, dim3(gE), dim3(256), 0, s, S);     // new iterate -> Ut
         hipLaunchKernelGGL(ftmpc::ftmpc_sqp_count_kernel, dim3(gB), dim3(256), 0, s, S);
@@ -1712,7 +1778,7 @@ static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_
         cf.out_cost = h->d_swJ + 3 * B;
         cf.out_tviol = h->d_swJ + 4 * B;
         cf.out_X = want_X ? h->d_swX : nullptr;
-        hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, cf);
+        launch_cost_wrench(h, B, s, cf);
     }
     // second stage, once: allocation of the final tau_0 (on an fp32 handle pulled inside the float64 hull first, as kernel 11 does)
     if (hull_fp32(h, hull_rows))
@@ -1725,9 +1791,29 @@ static int sqpw_enqueue(ftmpc_handle* h, int64_t B, int32_t hull_rows, bool has_
     return wrench_alloc_enqueue(h, B, false);
 }
 
+static int eval_cost_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck, const double* xref,
+                            int64_t xref_stride, const double* uref, int64_t uref_stride, const double* G, const double* dist,
+                            double* out_cost, double* out_tviol);
+
 int ftmpc_eval_cost_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck, const double* xref,
                                  int64_t xref_stride, const double* uref, int64_t uref_stride, const double* G, double* out_cost,
                                  double* out_tviol) {
+    return eval_cost_wrench(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, G, nullptr, out_cost, out_tviol);
+}
+
+int ftmpc_eval_cost_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                             const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                                             const double* G, const double* dist, double* out_cost, double* out_tviol) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0) return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
+    const int rc = check_dist(h, B, dist);
+    if (rc != FTMPC_OK) return rc;
+    return eval_cost_wrench(h, B, x0, ub, stuck, xref, xref_stride, uref, uref_stride, G, dist, out_cost, out_tviol);
+}
+
+static int eval_cost_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck, const double* xref,
+                            int64_t xref_stride, const double* uref, int64_t uref_stride, const double* G, const double* dist,
+                            double* out_cost, double* out_tviol) {
     (void)ub;
     (void)stuck;
     if (!h) return FTMPC_ERR_ARG;
@@ -1744,11 +1830,13 @@ int ftmpc_eval_cost_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, c
     HIP_TRY(h, hipMemcpyAsync(h->d_x0, x0, B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->d_swG, G, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    LinDistScope ds(h);
+    if ((rc = ds.stage(B, dist)) != FTMPC_OK) return rc;
     ftmpc::CostWrenchParams cw = cost_wrench_params(h, B, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride, 0.0);
     cw.G = h->d_swG;
     cw.out_merit = h->d_swJ;
     cw.out_tviol = h->d_swJ + B;
-    hipLaunchKernelGGL(ftmpc::ftmpc_cost_wrench_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, cw);
+    launch_cost_wrench(h, B, s, cw);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(out_cost, h->d_swJ, B * sizeof(double), hipMemcpyDeviceToHost, s));
     if (out_tviol) HIP_TRY(h, hipMemcpyAsync(out_tviol, h->d_swJ + B, B * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1766,12 +1854,46 @@ static int sqpw_check(ftmpc_handle* h, int32_t sqp_iters, int32_t backtracks, do
     return FTMPC_OK;
 }
 
+static int solve_sqp_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                            const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, const double* warmG,
+                            const double* dist, int32_t sqp_iters, int32_t backtracks, double tol, double penalty, double* out_u0,
+                            double* out_tau0, double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol,
+                            int32_t* out_sqp_iters, int32_t* out_iters, int32_t* status, int32_t* alloc_status);
+
 int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
                                  const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
                                  const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, const double* warmG,
                                  int32_t sqp_iters, int32_t backtracks, double tol, double penalty, double* out_u0, double* out_tau0,
                                  double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol, int32_t* out_sqp_iters,
                                  int32_t* out_iters, int32_t* status, int32_t* alloc_status) {
+    return solve_sqp_wrench(h, B, x0, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref, xref_stride, uref, uref_stride, warmG,
+                            nullptr, sqp_iters, backtracks, tol, penalty, out_u0, out_tau0, out_G, out_X, out_cost, out_cost0, out_tviol,
+                            out_sqp_iters, out_iters, status, alloc_status);
+}
+
+int ftmpc_solve_sqp_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                             const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                             int32_t hull_rows, const double* xref, int64_t xref_stride, const double* uref,
+                                             int64_t uref_stride, const double* warmG, const double* dist, int32_t sqp_iters,
+                                             int32_t backtracks, double tol, double penalty, double* out_u0, double* out_tau0,
+                                             double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol,
+                                             int32_t* out_sqp_iters, int32_t* out_iters, int32_t* status, int32_t* alloc_status) {
+    if (!h) return FTMPC_ERR_ARG;
+    if (B < 0) return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
+    const int rc = check_dist(h, B, dist);
+    if (rc != FTMPC_OK) return rc;
+    return solve_sqp_wrench(h, B, x0, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref, xref_stride, uref, uref_stride, warmG,
+                            dist, sqp_iters, backtracks, tol, penalty, out_u0, out_tau0, out_G, out_X, out_cost, out_cost0, out_tviol,
+                            out_sqp_iters, out_iters, status, alloc_status);
+}
+
+static int solve_sqp_wrench(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
+                            const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride, const double* warmG,
+                            const double* dist, int32_t sqp_iters, int32_t backtracks, double tol, double penalty, double* out_u0,
+                            double* out_tau0, double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol,
+                            int32_t* out_sqp_iters, int32_t* out_iters, int32_t* status, int32_t* alloc_status) {
     if (!h) return FTMPC_ERR_ARG;
     if (B < 0 || !x0 || !ub || !stuck || !xref || !out_u0 || !hull_A || !hull_b)
         return fail(h, FTMPC_ERR_ARG, "null buffer or negative batch");
@@ -1786,6 +1908,8 @@ int ftmpc_solve_sqp_wrench_batch(ftmpc_handle* h, int64_t B, const double* x0, c
     if ((rc = stage_inputs(h, B, x0, ub, stuck)) != FTMPC_OK) return rc;
     if ((rc = stage_refs(h, B, xref, xref_stride, uref, uref_stride)) != FTMPC_OK) return rc;
     if (warmG) HIP_TRY(h, hipMemcpyAsync(h->d_warmG, warmG, B * N * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+    LinDistScope ds(h);
+    if ((rc = ds.stage(B, dist)) != FTMPC_OK) return rc;
     ftmpc::SqpState S;
     if ((rc = sqpw_enqueue(h, B, hull_rows, hull_set != nullptr, h->d_xref, xref_stride, uref ? h->d_uref : nullptr, uref_stride,
                            warmG ? h->d_warmG : nullptr, sqp_iters, backtracks, tol, penalty > 0 ? penalty : FTMPC_SQPW_PENALTY,
@@ -2682,6 +2806,21 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                           int32_t* no_hull_step) {
+    return ftmpc_simulate_wrench_disturbance_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
+                                                   noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
+                                                   alloc_failed, out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b,
+                                                   no_hull_step, nullptr);
+}
+
+int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                            uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                            const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                            int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                            const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                            int32_t* no_hull_step, const ftmpc_disturbance* disturbance) {
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
@@ -2702,6 +2841,10 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
         const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
         if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
     }
+    {     // (the wrench SQP's cost kernel knows the estimate: sqp_iters > 0 is served here)
+        const std::string msg = disturbance_problem(disturbance, B, estimator, 0);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
@@ -2716,7 +2859,7 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
                   out_hull_b, diagnosis ? no_hull_step : nullptr};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
                          sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor,
-                         estimator, diagnosis);
+                         estimator, diagnosis, disturbance);
 }
 
 int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const double* stuck, const double* hull_A, int32_t n_sets,
@@ -3472,8 +3615,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         const double* Gfin = h->d_G;
         if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
             ftmpc::SqpState S;
+            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into every linearisation and cost launch
             rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
                               (t > 0 || resume) ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
+            h->lin_dist = nullptr;
             if (rc == FTMPC_OK) {
                 Gfin = S.U;
                 sp.status = S.status;
@@ -3492,8 +3637,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                                          hipMemcpyDeviceToDevice, s));
             }
         } else if (wl) {         // the reference's two-stage structure: wrench MPC with the hull rows, then allocation
+            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into the linearisation
             rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
                                 (t > 0 || resume) ? h->d_warmG.p : nullptr);
+            h->lin_dist = nullptr;
             if (rc == FTMPC_OK && d_abad)
                 hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
                                    d_abad + t);

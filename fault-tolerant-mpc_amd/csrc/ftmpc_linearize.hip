@@ -608,8 +608,16 @@ struct CostWrenchParams {
     const double* Gq = nullptr;
     const int32_t* todo = nullptr;
     int32_t ntrial = 0;
+    // the estimated disturbance [B*6] = (f^ inertial in N, t^ body in N m) of the DIST = 1 instantiation; nullptr: the plain one
+    const double* dist = nullptr;
 };
 
+// DIST = 1 (ftmpc_eval_cost_wrench_disturbance_batch, the wrench SQP under an estimate): the rollout takes the estimate exactly where
+// ftmpc_linearize_kernel<.., 1> puts it -- every RK4 stage is evaluated at tau + t^, and f^ / m is added to dv after the rotation (it
+// is inertial, so it enters neither ab nor the dw x r term).  The R .* (gen - ur - f_virt) term keeps the COMMANDED wrench; the tracking
+// terms, the terminal cost, the terminal-set violation and out_X are those of the disturbed rollout.  Lane b * ntrial + j reads the
+// estimate of instance b.
+template <int DIST = 0>
 __global__ void __launch_bounds__(64) ftmpc_cost_wrench_kernel(const DeviceConsts C, const CostWrenchParams P) {
     const int64_t lane_id = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t b = P.ntrial > 0 ? lane_id / P.ntrial : lane_id;
@@ -640,6 +648,13 @@ __global__ void __launch_bounds__(64) ftmpc_cost_wrench_kernel(const DeviceConst
     const double* xref = P.xref + b * P.xref_stride;
     const double* uref = P.uref ? P.uref + b * P.uref_stride : nullptr;
     const double dt = C.dt;
+    double dfm[3] = {0, 0, 0}, dtq[3] = {0, 0, 0};      // DIST: f^ / m and t^
+    if constexpr (DIST != 0) {
+        for (int i = 0; i < 3; ++i) {
+            dfm[i] = P.dist[b * 6 + i] * C.inv_mass;
+            dtq[i] = P.dist[b * 6 + 3 + i];
+        }
+    }
     double cost = 0.0, viol = 0.0;
     for (int k = 0; k < N; ++k) {
         double gen[6];
@@ -662,22 +677,33 @@ __global__ void __launch_bounds__(64) ftmpc_cost_wrench_kernel(const DeviceConst
         // RK4 (sys_model.py:152-158), no quaternion renormalisation; the stage sum k1 + 2 k2 + 2 k3 + k4 accumulated in
         // the order ftmpc_cost_kernel evaluates it (four 13-vectors live instead of six)
         double acc[13], kk[13], t[13];
+        // (the commanded wrench is spent: under DIST the torque the model sees is tau + t^, as in the linearise kernel)
+        if constexpr (DIST != 0)
+            for (int i = 0; i < 3; ++i) gen[3 + i] += dtq[i];
         centre_rhs(C, s, gen, kk);
+        if constexpr (DIST != 0)
+            for (int i = 0; i < 3; ++i) kk[3 + i] += dfm[i];
         for (int i = 0; i < 13; ++i) {
             acc[i] = kk[i];
             t[i] = s[i] + 0.5 * dt * kk[i];
         }
         centre_rhs(C, t, gen, kk);
+        if constexpr (DIST != 0)
+            for (int i = 0; i < 3; ++i) kk[3 + i] += dfm[i];
         for (int i = 0; i < 13; ++i) {
             acc[i] += 2.0 * kk[i];
             t[i] = s[i] + 0.5 * dt * kk[i];
         }
         centre_rhs(C, t, gen, kk);
+        if constexpr (DIST != 0)
+            for (int i = 0; i < 3; ++i) kk[3 + i] += dfm[i];
         for (int i = 0; i < 13; ++i) {
             acc[i] += 2.0 * kk[i];
             t[i] = s[i] + dt * kk[i];
         }
         centre_rhs(C, t, gen, kk);
+        if constexpr (DIST != 0)
+            for (int i = 0; i < 3; ++i) kk[3 + i] += dfm[i];
         for (int i = 0; i < 13; ++i) s[i] += dt / 6.0 * (acc[i] + kk[i]);
         if (X)
             for (int i = 0; i < 13; ++i) X[(k + 1) * 13 + i] = s[i];
@@ -700,5 +726,8 @@ __global__ void __launch_bounds__(64) ftmpc_cost_wrench_kernel(const DeviceConst
     if (P.out_cost) P.out_cost[lane_id] = cost;
     if (P.out_tviol) P.out_tviol[lane_id] = viol;
 }
+
+template __global__ void ftmpc_cost_wrench_kernel<0>(const DeviceConsts, const CostWrenchParams);
+template __global__ void ftmpc_cost_wrench_kernel<1>(const DeviceConsts, const CostWrenchParams);
 
 }  // namespace ftmpc

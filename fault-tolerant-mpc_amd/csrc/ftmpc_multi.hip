@@ -253,7 +253,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         if (!msg.empty()) return refuse(msg);
     }
     {     // the disturbance estimate likewise: the parameters are uniform, force / torque / cross / cov and the histories per vehicle
-        const std::string msg = disturbance_problem(disturbance, B, estimator, sqp_iters);
+        const std::string msg = disturbance_problem(disturbance, B, estimator, wrench ? 0 : sqp_iters);      // (the wrench SQP is served)
         if (!msg.empty()) return refuse(msg);
     }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
@@ -404,15 +404,17 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (bv.force_hist) bv.force_hist = fh.data();
             if (bv.torque_hist) bv.torque_hist = th.data();
         }
-        const int rc2 = wrench ? ftmpc_simulate_wrench_diagnosis_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
-                                                                     hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
-                                                                     xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
-                                                                     faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
-                                                                     alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
-                                                                     mission ? &mi : nullptr, actuator ? &at : nullptr,
-                                                                     sensor ? &sv : nullptr, estimator ? &ev : nullptr,
-                                                                     diagnosis ? &dv : nullptr, out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
-                                                                     no_hull_step ? no_hull_step + lo : nullptr)
+        const int rc2 = wrench ? ftmpc_simulate_wrench_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
+                                                                       hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
+                                                                       xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
+                                                                       faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
+                                                                       alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
+                                                                       mission ? &mi : nullptr, actuator ? &at : nullptr,
+                                                                       sensor ? &sv : nullptr, estimator ? &ev : nullptr,
+                                                                       diagnosis ? &dv : nullptr,
+                                                                       out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
+                                                                       no_hull_step ? no_hull_step + lo : nullptr,
+                                                                       disturbance ? &bv : nullptr)
                                : ftmpc_simulate_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj,
                                                                  noise, seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
                                                                  bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
@@ -827,6 +829,21 @@ int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32
     return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
                           backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
                           estimator, true, diagnosis, out_hull_b, no_hull_step);
+}
+
+int ftmpc_multi_simulate_wrench_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                  const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                  int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                                  const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                                  double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                  int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                  const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                  const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                                  int32_t* no_hull_step, const ftmpc_disturbance* disturbance) {
+    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
+                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
+                          estimator, true, diagnosis, out_hull_b, no_hull_step, disturbance);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

@@ -40,6 +40,8 @@ SYMBOLS = (
     "ftmpc_simulate_diagnosis_batch", "ftmpc_multi_simulate_diagnosis_batch",
     "ftmpc_hull_offsets_batch", "ftmpc_simulate_wrench_diagnosis_batch", "ftmpc_multi_simulate_wrench_diagnosis_batch",
     "ftmpc_simulate_disturbance_batch", "ftmpc_multi_simulate_disturbance_batch", "ftmpc_debug_records_disturbance",
+    "ftmpc_simulate_wrench_disturbance_batch", "ftmpc_multi_simulate_wrench_disturbance_batch",
+    "ftmpc_eval_cost_wrench_disturbance_batch", "ftmpc_solve_wrench_disturbance_batch", "ftmpc_solve_sqp_wrench_disturbance_batch",
 )
 
 
@@ -235,10 +237,19 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_wrench_diagnosis_batch.argtypes = lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes
     lib.ftmpc_simulate_disturbance_batch.argtypes = lib.ftmpc_simulate_diagnosis_batch.argtypes + [C.POINTER(ftmpc_disturbance)]
     lib.ftmpc_multi_simulate_disturbance_batch.argtypes = lib.ftmpc_simulate_disturbance_batch.argtypes
+    lib.ftmpc_simulate_wrench_disturbance_batch.argtypes = lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes + [C.POINTER(ftmpc_disturbance)]
+    lib.ftmpc_multi_simulate_wrench_disturbance_batch.argtypes = lib.ftmpc_simulate_wrench_disturbance_batch.argtypes
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,
                                                  dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, ip]
+    # (the plain entries with dist [B*6] inserted after G / warmG)
+    lib.ftmpc_eval_cost_wrench_disturbance_batch.argtypes = (lib.ftmpc_eval_cost_wrench_batch.argtypes[:10] + [dp]
+                                                             + lib.ftmpc_eval_cost_wrench_batch.argtypes[10:])
+    lib.ftmpc_solve_wrench_disturbance_batch.argtypes = (lib.ftmpc_solve_wrench_batch.argtypes[:15] + [dp]
+                                                         + lib.ftmpc_solve_wrench_batch.argtypes[15:])
+    lib.ftmpc_solve_sqp_wrench_disturbance_batch.argtypes = (lib.ftmpc_solve_sqp_wrench_batch.argtypes[:15] + [dp]
+                                                             + lib.ftmpc_solve_sqp_wrench_batch.argtypes[15:])
     lib.ftmpc_last_handed_over.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.ftmpc_sqp_graph_launches.argtypes = [vp]
     lib.ftmpc_sqp_graph_launches.restype = C.c_int64

@@ -321,11 +321,13 @@ class BatchedMPC:
         return dict(u0=u0, U=U, cost=J, cost0=J0, sqp_iters=nmaj, iters=ipm, status=st)
 
     # -- the reference's two-stage structure: 6-D generalized-force QP with the input hull, then allocation ----
-    def solve_wrench(self, x0, ub, stuck, xref, uref=None, warmG=None, return_G=False, hull=None):
+    def solve_wrench(self, x0, ub, stuck, xref, uref=None, warmG=None, return_G=False, hull=None, dist=None):
         """One MPC step in generalized-force space (reference: spiraling_mpc.py:87-238 with the per-stage hull rows
         :133-137,175-177) followed by the min-norm allocation (control_allocator.py:65-94).
         x0 [B,13], ub/stuck [B,NT]; warmG [B,N,6] or None (in/out: total wrenches, already shifted);
         hull: dict from controllers.tools.input_bounds.hull_tables (built here when None).
+        dist [B,6] or None: the estimated disturbance per vehicle (f^ inertial in N, t^ body in N m) the linearisation rolls the
+        model out under (ftmpc_solve_wrench_disturbance_batch; the hull, the allocation and the cost's R term keep the commanded wrench).
         Returns dict(u0 [B,NT], tau0 [B,6], G [B,N,6]|None, status [B], iters [B], alloc_status [B]); instances whose
         healthy thrusters do not span R^6 have no hull: status 3, u0 = tau0 = NaN (use `solve` for them)."""
         from .controllers.tools.input_bounds import hull_tables
@@ -365,10 +367,16 @@ class BatchedMPC:
         o_u0, o_t0 = np.empty((b, NT)), np.empty((b, 6))
         o_G = np.empty((b, N, 6)) if return_G else None
         o_st, o_it, o_as = np.empty(b, np.int32), np.empty(b, np.int32), np.empty(b, np.int32)
-        self._check(self.lib.ftmpc_solve_wrench_batch(
-            self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-            int(hull["rows"]), _ptr(xref), xs, _ptr(uref), us, _ptr(W), _ptr(o_u0), _ptr(o_t0), _ptr(o_G),
-            _ptr(o_st, C.c_int32), _ptr(o_it, C.c_int32), _ptr(o_as, C.c_int32)))
+        if dist is not None:
+            self._check(self.lib.ftmpc_solve_wrench_disturbance_batch(
+                self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xref), xs, _ptr(uref), us, _ptr(W), _ptr(take(_f64(dist, (B, 6)))), _ptr(o_u0), _ptr(o_t0),
+                _ptr(o_G), _ptr(o_st, C.c_int32), _ptr(o_it, C.c_int32), _ptr(o_as, C.c_int32)))
+        else:
+            self._check(self.lib.ftmpc_solve_wrench_batch(
+                self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xref), xs, _ptr(uref), us, _ptr(W), _ptr(o_u0), _ptr(o_t0), _ptr(o_G),
+                _ptr(o_st, C.c_int32), _ptr(o_it, C.c_int32), _ptr(o_as, C.c_int32)))
         u0[sel], tau0[sel], status[sel], iters[sel], ast[sel] = o_u0, o_t0, o_st, o_it, o_as
         if return_G:
             G[sel] = o_G
@@ -377,28 +385,36 @@ class BatchedMPC:
         return dict(u0=u0, tau0=tau0, G=G, status=status, iters=iters, alloc_status=ast)
 
     # -- the reference's nonlinear program in its own formulation: line-search SQP over the wrench sequences --------------
-    def eval_cost_wrench(self, x0, xref, G, uref=None, return_tviol=False):
+    def eval_cost_wrench(self, x0, xref, G, uref=None, return_tviol=False, dist=None):
         """Cost of the NONLINEAR program in the generalized-force formulation for total-wrench sequences G [B,N,6] -> [B]
         (include/ftmpc.h ftmpc_eval_cost_wrench_batch: nonlinear rollout, no rho term, full terminal cost when
-        MPCConfig.terminal_cost is set).  return_tviol: (cost, terminal-set violation sum_r max(0, A e_N - b)) instead."""
+        MPCConfig.terminal_cost is set).  return_tviol: (cost, terminal-set violation sum_r max(0, A e_N - b)) instead.
+        dist [B,6] or None: the rollout runs under the estimated disturbance (f^ inertial, t^ body) per vehicle
+        (ftmpc_eval_cost_wrench_disturbance_batch); the R term keeps the commanded G."""
         N = self.cfg.N
         x0 = _f64(x0).reshape(-1, 13)
         B = x0.shape[0]
         G = _f64(G, (B, N, 6))
         xref, xs, uref, us = self._refs(B, xref, uref)
         J, V = np.empty(B), np.empty(B)
-        self._check(self.lib.ftmpc_eval_cost_wrench_batch(self._h, B, _ptr(x0), None, None, _ptr(xref), xs, _ptr(uref), us, _ptr(G),
-                                                          _ptr(J), _ptr(V)))
+        if dist is not None:
+            self._check(self.lib.ftmpc_eval_cost_wrench_disturbance_batch(self._h, B, _ptr(x0), None, None, _ptr(xref), xs, _ptr(uref), us,
+                                                                          _ptr(G), _ptr(_f64(dist, (B, 6))), _ptr(J), _ptr(V)))
+        else:
+            self._check(self.lib.ftmpc_eval_cost_wrench_batch(self._h, B, _ptr(x0), None, None, _ptr(xref), xs, _ptr(uref), us, _ptr(G),
+                                                              _ptr(J), _ptr(V)))
         return (J, V) if return_tviol else J
 
     def solve_sqp_wrench(self, x0, ub, stuck, xref, uref=None, warmG=None, hull=None, sqp_iters=10, backtracks=8, tol=1e-9,
-                         penalty=0.0, return_X=False):
+                         penalty=0.0, return_X=False, dist=None):
         """Line-search SQP towards the reference's NLP in its own formulation (spiraling_mpc.py:87-238: generalized-force decision,
         input hull at every stage, terminal set and full terminal cost when configured, RK4 dynamics), entirely on the device
         (include/ftmpc.h ftmpc_solve_sqp_wrench_batch): each major iteration solves the wrench QP of solve_wrench linearised about
         the current G, then backtracks along G_qp - G on the merit J + penalty * terminal-set violation (penalty <= 0: the library
         default); u0 is the min-norm allocation of the final tau_0.  warmG [B,N,6] or None (tau_k = D stuck; read only); hull as
-        solve_wrench.  Returns dict(u0 [B,NT], tau0 [B,6], G [B,N,6], X [B,N+1,13] | None (centre states under G), cost [B],
+        solve_wrench.  dist [B,6] or None: every linearisation and every cost / merit evaluation runs under the estimated disturbance
+        (f^ inertial, t^ body) per vehicle (ftmpc_solve_sqp_wrench_disturbance_batch), so X, cost, cost0 and tviol are the disturbed
+        program's.  Returns dict(u0 [B,NT], tau0 [B,6], G [B,N,6], X [B,N+1,13] | None (centre states under G), cost [B],
         cost0 [B] (at the start point), tviol [B], sqp_iters [B], iters [B] (IPM iterations summed), status [B] of the last QP,
         alloc_status [B]); instances whose healthy thrusters do not span R^6 have no hull: status 3, NaN outputs."""
         from .controllers.tools.input_bounds import hull_tables
@@ -433,11 +449,15 @@ class BatchedMPC:
                  cost=np.empty(b), cost0=np.empty(b), tviol=np.empty(b), sqp_iters=np.empty(b, np.int32), iters=np.empty(b, np.int32),
                  status=np.empty(b, np.int32), alloc_status=np.empty(b, np.int32))
         ip = lambda a: _ptr(a, C.c_int32)
-        self._check(self.lib.ftmpc_solve_sqp_wrench_batch(
-            self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], ip(hs), _ptr(hb), int(hull["rows"]),
-            _ptr(xref), xs, _ptr(uref), us, _ptr(W), int(sqp_iters), int(backtracks), float(tol), float(penalty),
-            _ptr(o["u0"]), _ptr(o["tau0"]), _ptr(o["G"]), _ptr(o["X"]), _ptr(o["cost"]), _ptr(o["cost0"]), _ptr(o["tviol"]),
-            ip(o["sqp_iters"]), ip(o["iters"]), ip(o["status"]), ip(o["alloc_status"])))
+        head = (self._h, b, _ptr(take(x0)), _ptr(take(ub)), _ptr(take(stuck)), _ptr(A), A.shape[0], ip(hs), _ptr(hb), int(hull["rows"]),
+                _ptr(xref), xs, _ptr(uref), us, _ptr(W))
+        tail = (int(sqp_iters), int(backtracks), float(tol), float(penalty),
+                _ptr(o["u0"]), _ptr(o["tau0"]), _ptr(o["G"]), _ptr(o["X"]), _ptr(o["cost"]), _ptr(o["cost0"]), _ptr(o["tviol"]),
+                ip(o["sqp_iters"]), ip(o["iters"]), ip(o["status"]), ip(o["alloc_status"]))
+        if dist is not None:
+            self._check(self.lib.ftmpc_solve_sqp_wrench_disturbance_batch(*head, _ptr(take(_f64(dist, (B, 6)))), *tail))
+        else:
+            self._check(self.lib.ftmpc_solve_sqp_wrench_batch(*head, *tail))
         for k, v in o.items():
             if v is not None:
                 out[k][sel] = v
@@ -516,7 +536,8 @@ class BatchedMPC:
         disturbance: the estimator's filter augmented by a constant force f^ (inertial frame, N) and torque t^ (body frame, N m) per
         vehicle, the frames and units of plant["force"] / plant["torque"], and the estimate given to every consumer of the
         controller's model (include/ftmpc.h, ftmpc_disturbance; ft_mpc_amd.disturbances restates it in NumPy; thruster formulation,
-        sqp_iters = 0, needs `estimator`): a dict with p0=(2,), proc_sigma=(2,) (standard deviations of force and torque: initial, and
+        sqp_iters = 0, needs `estimator`; with the opt-in key wrench=True: formulation="wrench" with sqp_iters >= 0,
+        ftmpc_simulate_wrench_disturbance_batch, the hulls, the allocation and the terminal set staying nominal): a dict with p0=(2,), proc_sigma=(2,) (standard deviations of force and torque: initial, and
         per step), compensate=True (the linearisation the QP is built from uses the estimate too, which removes the steady offset of
         a constant disturbance; False: only the filter and the diagnosis do, the controller stays nominal), force=None, torque=None
         ([B,3], the estimates to start from; default 0), cross=None ([B,72] or [B,12,6]; needs force, torque and estimator["xhat"])
@@ -1101,6 +1122,16 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                 if hb.shape != (B, int(hull["rows"])) or not np.isfinite(hb).all():
                     raise ValueError(f"diagnosis['hull_b'] must be finite with shape {(B, int(hull['rows']))}")
             dout["hull_b"], dout["no_hull"] = np.empty((B, int(hull["rows"]))), d_nh
+        if db is not None:      # (disturbance['wrench'] = True; with or without a diagnosis)
+            self._check(getattr(self.lib, pre + "wrench_disturbance_batch")(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+                C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None,
+                _ptr(dout["hull_b"]) if dg is not None else None, _ptr(d_nh, C.c_int32) if dg is not None else None, C.byref(db)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
+        if dg is not None:
             self._check(getattr(self.lib, pre + "wrench_diagnosis_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
                 int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),

@@ -11,6 +11,8 @@ coordinates are (dp, dv, dtheta, dw, df, dt), 18 in all; the covariance travels 
   update       H = [I 0], R = diag(meas_sigma[g]^2): the estimator's twelve sequential scalar updates over all 18 coordinates
   propagate    Phi = [[Phi_xx, Phi_xd], [0, I]], Phi_xd = dt [0; I / m; 0; J^-1] in the blocks (v, f) and (w, t);
                P <- Phi P Phi' + diag(proc_sigma_x^2, proc_sigma_d^2); the mean takes model_step, f^ and t^ stay
+  rollout_centre  centre_step stage by stage under per-stage commanded wrenches: what the wrench cost kernel rolls out under the
+               estimate (the two-stage wrench form, disturbance["wrench"] = True, with one QP or the wrench SQP per step)
 replay runs the loop's augmented filter for one vehicle from the recorded measurements and applied commands.
 
 Not estimated: m, J, D (a gain or centre-of-mass error shows up as a command-dependent part of (f^, t^)).  An undetected stuck thruster
@@ -95,6 +97,19 @@ def centre_step(c, gen, f, t, cfg, r=None):
         ab = gen[0:3] / m + np.cross(dw, r) + np.cross(w, np.cross(w, r))
         return np.concatenate([v, _rot(q).T @ ab + f / m, dw, 0.5 * _omega(w) @ q])
     return _rk4(rhs, np.array(c, dtype=np.float64).reshape(13), float(cfg.dt))
+
+
+def rollout_centre(c0, G, f, t, cfg, r=None):
+    """[N+1, 13] centre states c_0 .. c_N under the per-stage COMMANDED wrenches G [N,6] with the estimate (f [3] inertial, t [3]
+    body) held over the horizon: centre_step applied stage by stage from c0 [13] -- the rollout of the linearise kernel's DIST
+    instantiations about warmG = G and of the wrench cost kernel under the estimate (its out_X)."""
+    G = np.asarray(G, dtype=np.float64).reshape(-1, 6)
+    r = centre_r(cfg) if r is None else r
+    X = np.empty((G.shape[0] + 1, 13))
+    X[0] = np.asarray(c0, dtype=np.float64).reshape(13)
+    for k in range(G.shape[0]):
+        X[k + 1] = centre_step(X[k], G[k], f, t, cfg, r)
+    return X
 
 
 def retract18(x, f, t, d):
@@ -225,19 +240,31 @@ def replay(meas, u_applied, ub, stuck, est_spec, dist_spec, cfg, xhat=None, cov=
 def request(disturbance, B, T, estimator=None, sqp_iters=0, formulation="thruster"):
     """The checks BatchedMPC.simulate makes on a disturbance dict before the call reaches the library (the library's own refusals,
     raised from Python too); returns the dict with defaults filled in: p0 (2,), proc_sigma (2,), compensate (bool), force / torque
-    [B,3] | None, cross [B,72] | None, cov [B,21] | None, fields."""
+    [B,3] | None, cross [B,72] | None, cov [B,21] | None, fields, wrench (bool).
+    The opt-in key wrench=True asks for the two-stage wrench form (ftmpc_simulate_wrench_disturbance_batch): formulation must then be
+    "wrench" and sqp_iters >= 0 is accepted (the wrench SQP's cost kernel knows the estimate).  Without the key the call is the
+    thruster form's with one QP per step, and the wrench formulation and sqp_iters > 0 are refused as before."""
     spec = dict(disturbance)
     out = dict(p0=spec.pop("p0", None), proc_sigma=spec.pop("proc_sigma", None), compensate=spec.pop("compensate", True),
                force=spec.pop("force", None), torque=spec.pop("torque", None), cross=spec.pop("cross", None), cov=spec.pop("cov", None),
                fields=tuple(spec.pop("fields", FIELDS)))
+    wrench = spec.pop("wrench", False)
     if spec:
         raise ValueError(f"disturbance: unknown keys {sorted(spec)}")
-    if formulation != "thruster":
+    if wrench not in (0, 1, True, False):
+        raise ValueError(f"disturbance['wrench'] must be 0 / 1 (False / True), not {wrench}")
+    out["wrench"] = bool(wrench)
+    if out["wrench"]:
+        if formulation != "wrench":
+            raise ValueError("disturbance['wrench'] = True asks for the two-stage wrench form: formulation must be 'wrench'")
+    elif formulation != "thruster":
         raise ValueError("disturbance: thruster formulation only (the two-stage wrench form has no disturbance entry)")
     if estimator is None:
         raise ValueError("disturbance needs an estimator: the disturbance states augment its filter")
-    if int(sqp_iters) > 0:
+    if int(sqp_iters) > 0 and not out["wrench"]:
         raise ValueError("disturbance: sqp_iters must be 0 (the cost kernels of the SQP do not know the estimate)")
+    if int(sqp_iters) < 0:
+        raise ValueError("disturbance: sqp_iters must be >= 0")
     if out["compensate"] not in (0, 1, True, False):
         raise ValueError(f"disturbance['compensate'] must be 0 / 1 (False / True), not {out['compensate']}")
     out["compensate"] = bool(out["compensate"])

@@ -138,7 +138,8 @@ class MultiGPUMPC:
         _wrench_estimator_batch); the parameters of `diagnosis` are uniform, its state, detections, pattern and history per vehicle
         (ftmpc_multi_simulate_diagnosis_batch; on the wrench formulation, with rebuild_hull=True, also hull_b and no_hull:
         ftmpc_multi_simulate_wrench_diagnosis_batch); the parameters of `disturbance` are uniform, its estimates, covariance pieces and
-        histories per vehicle (ftmpc_multi_simulate_disturbance_batch)."""
+        histories per vehicle (ftmpc_multi_simulate_disturbance_batch; with wrench=True in the dict on the wrench formulation,
+        sqp_iters >= 0: ftmpc_multi_simulate_wrench_disturbance_batch)."""
         from .batch import _simulate
         return _simulate(self, True, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, 0, None, plant,

@@ -937,7 +937,8 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                           int32_t* no_hull_step);
 
-/* On-device disturbance estimation and offset-free control (thruster form, one QP per step).  The filter of ftmpc_estimator is
+/* On-device disturbance estimation and offset-free control (thruster form with one QP per step: this entry; the two-stage wrench form
+ * with one QP or the wrench SQP per step: ftmpc_simulate_wrench_disturbance_batch below).  The filter of ftmpc_estimator is
  * augmented by six states per vehicle: f^ [3], a constant force in the inertial frame (N), and t^ [3], a constant torque in the body
  * frame (N m): the frames and units of ftmpc_plant_model.force / .torque.  The estimate is given to every consumer of the
  * controller's model: the filter's own prediction, the diagnosis' prediction and, compensate = 1, the linearisation the QP is built
@@ -969,8 +970,8 @@ int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T,
  * A handed force / torque / cross / cov are the priors of the call's first step; on return they hold the priors of step T, so that a
  * continued run (with the estimator's xhat / cov, the sensor's pending / step0 and the diagnosis' carry-over) is the whole run bit for
  * bit.  disturbance = NULL launches exactly the kernels of ftmpc_simulate_diagnosis_batch and returns its bits.
- * Not served: the two-stage wrench form (ftmpc_simulate_wrench_* has no disturbance entry), the SQP loops (the cost kernels do not
- * know the estimate), m / J / D (a gain or centre-of-mass error shows up as a command-dependent part of (f^, t^)), per-vehicle filter
+ * Not served: the thruster-form SQP loop (ftmpc_cost_kernel does not know the estimate; the wrench form's SQP does, see
+ * ftmpc_simulate_wrench_disturbance_batch), m / J / D (a gain or centre-of-mass error shows up as a command-dependent part of (f^, t^)), per-vehicle filter
  * parameters, ftmpc_multi_upload / _step.  Known limit: an undetected stuck thruster is a constant body wrench, so a slow t^ absorbs
  * its torque signature over time; proc_sigma has to be small against the CUSUM's detection time.
  * FTMPC_ERR_ARG, the message naming ftmpc_disturbance.<field> and, for an array, the first offending vehicle, the call's x untouched:
@@ -999,6 +1000,51 @@ int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                      const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                      const ftmpc_disturbance* disturbance);
+
+/* The disturbance estimate on the two-stage wrench form: ftmpc_simulate_wrench_diagnosis_batch with `disturbance` (NULL: exactly that
+ * entry's kernels and bits; ftmpc_simulate_wrench_diagnosis_batch IS this entry with NULL).  The filter and the diagnosis work on the
+ * applied thruster commands, so they are the thruster form's (ftmpc_filter_dist_kernel, ftmpc_diagnose_dist_kernel); the hull rows,
+ * the terminal set and the allocation constrain and allocate the COMMANDED wrench and stay nominal.  sqp_iters >= 0 is served: under
+ * compensate = 1 the wrench SQP takes d^_{t|t} in every linearisation (the linearise kernel's DIST instantiations about the iterate)
+ * AND in every launch of its cost / merit kernel (ftmpc_cost_wrench_kernel<1>: the start point, the line-search trials, the final
+ * rollout), which agree term for term.  Per loop step:
+ *   1. sense;  2. the diagnosis' phase 0;  3. hull offsets and hull switch (under a diagnosis);  4. ftmpc_filter_dist_kernel<0>, <1>;
+ *   5. the solve (one wrench QP, or the wrench SQP) with d^_{t|t} when compensate = 1;  6. the allocation of the commanded
+ *   tau_0 - D stuck;  7. the command queue;  8. the plant step;  9. ftmpc_diagnose_dist_kernel;  10. ftmpc_filter_dist_kernel<2>, <3>.
+ * FTMPC_ERR_ARG with the call's x untouched: what ftmpc_simulate_disturbance_batch refuses except sqp_iters > 0, what
+ * ftmpc_simulate_wrench_diagnosis_batch refuses (state bounds with sqp_iters > 0 among it).  The thruster-form SQP loop stays refused
+ * by ftmpc_simulate_disturbance_batch (ftmpc_cost_kernel does not know the estimate). */
+int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                            uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                            const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                            int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                            const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                            int32_t* no_hull_step, const ftmpc_disturbance* disturbance);
+
+/* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
+ * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
+ * after G / warmG; the rollout of the cost and of the linearisation sees tau + t^ at every RK4 stage and f^ / m added to the inertial
+ * acceleration, the R .* (tau - ur - f_virt) term keeps the commanded wrench, the terminal-set violation, the terminal cost and out_X
+ * are those of the disturbed rollout.  With dist all zero each returns the bits of its plain entry.  dist NULL or with a non-finite
+ * entry: FTMPC_ERR_ARG. */
+int ftmpc_eval_cost_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                             const double* xref, int64_t xref_stride, const double* uref, int64_t uref_stride,
+                                             const double* G, const double* dist, double* out_cost, double* out_tviol);
+int ftmpc_solve_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                         int32_t hull_rows, const double* xref, int64_t xref_stride, const double* uref,
+                                         int64_t uref_stride, double* warmG, const double* dist, double* out_u0, double* out_tau0,
+                                         double* out_G, int32_t* status, int32_t* iters, int32_t* alloc_status);
+int ftmpc_solve_sqp_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, const double* x0, const double* ub, const double* stuck,
+                                             const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                             int32_t hull_rows, const double* xref, int64_t xref_stride, const double* uref,
+                                             int64_t uref_stride, const double* warmG, const double* dist, int32_t sqp_iters,
+                                             int32_t backtracks, double tol, double penalty, double* out_u0, double* out_tau0,
+                                             double* out_G, double* out_X, double* out_cost, double* out_cost0, double* out_tviol,
+                                             int32_t* out_sqp_iters, int32_t* out_iters, int32_t* status, int32_t* alloc_status);
 
 /* Per-kernel device timing of the LAST solve call, measured with hipEvents on the launch
  * stream when enabled.  ms[slot] is the duration of kernel slot `slot` (0 when that kernel was
@@ -1247,6 +1293,19 @@ int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T,
                                            const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                            const ftmpc_disturbance* disturbance);
+/* ftmpc_multi_simulate_wrench_diagnosis_batch with the disturbance estimate `disturbance` (NULL: exactly that entry) as
+ * ftmpc_simulate_wrench_disturbance_batch runs it (sqp_iters >= 0).  The struct is checked once over the whole batch; the shards read
+ * and write its arrays by pointer offset and the two histories are scattered as in ftmpc_multi_simulate_disturbance_batch. */
+int ftmpc_multi_simulate_wrench_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                                  const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                                  int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                                  const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                                  double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                                  int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                                  const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                                  const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                                  int32_t* no_hull_step, const ftmpc_disturbance* disturbance);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
