@@ -14,29 +14,26 @@
 // (omega0, q0, F, tau) -- the Jacobians the reference obtains from CasADi AD
 // (ft_mpc/controllers/spiraling_mpc.py:217-230).  SURVEY.md Appendix A lists the formulas.
 //
-// Work per instance ~ N * (4 dynamics evaluations + 13 * 4 tangent steps) ~ 0.1 MFLOP (86 k float64
-// multiply-adds), but the kernel is 7 % of the headline step and not bound by that arithmetic.  It runs
-// one wave per SIMD (256 VGPRs + 256 AGPRs, 40 448 B of LDS), so nothing hides a wait, and the four
-// stage blocks (4 x 67 doubles = 536 registers) do not fit the register file: the tangent loop spends
-// more instructions on copies between the register halves and on spill traffic than on arithmetic.
-// What bounds it is the issue rate of that instruction stream; the write-out is no longer part of it
-// (CHANGELOG, "Linearise kernel: lean record write-out").
+// Work per instance ~ N * (4 dynamics evaluations + 13 * 4 tangent steps), but the kernel is not bound by
+// that arithmetic.  It runs one wave per SIMD (256 VGPRs + 256 AGPRs, 40 448 B of LDS), so nothing hides
+// a wait, and the four stage blocks (4 x 67 doubles = 536 registers) do not fit the register file: what
+// bounds it is the issue rate of an instruction stream that is mostly the tangent section, arithmetic plus
+// copies between the register halves.  Much of the generic tangent step multiplies by exact zeros (the q0
+// directions never move w, the F directions move neither w nor q, ...), so the full-record kernel runs the
+// tangents by direction group (w0, q0, F, tau), each group with only the terms that can be non-zero
+// (ftmpc_tangent.h: contraction off, every fma spelled out in the shape the compiler gives the generic
+// expression, so the record values are those of the generic loop).  The split kernels keep the generic
+// loop, contracted by the compiler: they are the reference the full-record kernel is tested against
+// (tests/test_gpu_linearize_records.py, tests/test_gpu_linearize_groups.py).  The write-out is not part of
+// the bound (CHANGELOG, "Linearise kernel: lean record write-out").
 #include <hip/hip_runtime.h>
 
 #include "ftmpc_common.h"
+#include "ftmpc_tangent.h"
 
 namespace ftmpc {
 
 namespace {
-
-struct StageBlk {
-    double Fww[9];   // d wdot / d w
-    double Fqw[12];  // d qdot / d w   (4x3)
-    double Fqq[16];  // d qdot / d q   (4x4)
-    double Vw[9];    // d vdot / d w
-    double Vq[12];   // d vdot / d q   (3x4)
-    double RT[9];    // Rot(q)^T  (body -> world), ft_mpc/util/utils.py:15-19 transposed
-};
 
 __device__ inline void cross3(const double a[3], const double b[3], double o[3]) {
     o[0] = a[1] * b[2] - a[2] * b[1];
@@ -334,70 +331,126 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
 
         // ---- tangents for the 13 input directions [w0(3), q0(4), F(3), tau(3)] ----
         pk = k;
-        for (int j = jlo; j < jhi; ++j) {
-            pbase = (j < 7) ? 0 : REC_BPF;
-            double tw0[3] = {0, 0, 0}, tq0[4] = {0, 0, 0, 0}, tF[3] = {0, 0, 0}, tT[3] = {0, 0, 0};
-            if (j < 3) tw0[j] = 1.0;
-            else if (j < 7) tq0[j - 3] = 1.0;
-            else if (j < 10) tF[j - 7] = 1.0;
-            else tT[j - 10] = 1.0;
-            // wrench contributions common to all stage points
-            double jt[3], at[3];
-            mat3vec(C.Jinv, tT, jt);   // d wdot / d tau * tT
-            mat3vec(C.ArT, tT, at);    // d a_b / d tau * tT
-            for (int i = 0; i < 3; ++i) at[i] += tF[i] * C.inv_mass;
-            double tkw[3] = {0, 0, 0}, tkq[4] = {0, 0, 0, 0};
-            double sw[3] = {0, 0, 0}, sq[4] = {0, 0, 0, 0}, sv[3] = {0, 0, 0}, sp[3] = {0, 0, 0};
-            for (int i = 0; i < 4; ++i) {
-                double tw[3], tq[4];
-                for (int a = 0; a < 3; ++a) tw[a] = tw0[a] + acoef[i] * tkw[a];
-                for (int a = 0; a < 4; ++a) tq[a] = tq0[a] + acoef[i] * tkq[a];
-                const StageBlk& B = S[i];
-                double nkw[3], nkq[4], nkv[3], rv[3];
-                for (int a = 0; a < 3; ++a)
-                    nkw[a] = B.Fww[3 * a] * tw[0] + B.Fww[3 * a + 1] * tw[1] + B.Fww[3 * a + 2] * tw[2] + jt[a];
-                for (int a = 0; a < 4; ++a)
-                    nkq[a] = B.Fqw[3 * a] * tw[0] + B.Fqw[3 * a + 1] * tw[1] + B.Fqw[3 * a + 2] * tw[2] +
-                             B.Fqq[4 * a] * tq[0] + B.Fqq[4 * a + 1] * tq[1] + B.Fqq[4 * a + 2] * tq[2] + B.Fqq[4 * a + 3] * tq[3];
-                mat3vec(B.RT, at, rv);
-                for (int a = 0; a < 3; ++a)
-                    nkv[a] = B.Vw[3 * a] * tw[0] + B.Vw[3 * a + 1] * tw[1] + B.Vw[3 * a + 2] * tw[2] +
-                             B.Vq[4 * a] * tq[0] + B.Vq[4 * a + 1] * tq[1] + B.Vq[4 * a + 2] * tq[2] + B.Vq[4 * a + 3] * tq[3] + rv[a];
-                for (int a = 0; a < 3; ++a) { tkw[a] = nkw[a]; sw[a] += wcoef[i] * nkw[a]; }
-                for (int a = 0; a < 4; ++a) { tkq[a] = nkq[a]; sq[a] += wcoef[i] * nkq[a]; }
-                for (int a = 0; a < 3; ++a) { sv[a] += wcoef[i] * nkv[a]; if (i < 3) sp[a] += nkv[a]; }
+        if constexpr (SHARE == 0) {
+            // S[0].Vq and S[0].Fqq are used here, in the basic block that evaluates them.  The w0 loop does not read them (tq = 0 at
+            // stage point 0), and what only a later group reads the compiler moves down to that group -- away from the products it
+            // is contracted with in stage_eval (F / m into a_b, which Vq is formed from), which then round on their own: other record
+            // bits than the split kernels'.  The statements are empty; the zero diagonal of Fqq stays a constant.
+            for (int e = 0; e < 12; ++e) asm volatile("" ::"v"(S[0].Vq[e]));
+            for (int e = 0; e < 16; ++e)
+                if (e % 5 != 0) asm volatile("" ::"v"(S[0].Fqq[e]));
+            const tangent::Coef K = {acoef[1], acoef[3], dt / 6.0, dt * dt / 6.0};
+            tangent::Words o;
+            pbase = 0;
+#pragma unroll 1
+            for (int j = 0; j < 3; ++j) {       // w0
+                const double tw0[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+                tangent::dir_w0(S, K, tw0, o);
+                for (int a = 0; a < 3; ++a) {
+                    put(REC_APW + 3 * a + j, o.p[a]);
+                    put(REC_AVW + 3 * a + j, o.v[a]);
+                    put(REC_AWW + 3 * a + j, o.w[a]);
+                }
+                for (int a = 0; a < 4; ++a) put(REC_AQW + 3 * a + j, o.q[a]);
             }
-            const double c6 = dt / 6.0, c26 = dt * dt / 6.0;
-            if (j < 3) {
+#pragma unroll 1
+            for (int jj = 0; jj < 4; ++jj) {    // q0
+                const double tq0[4] = {jj == 0 ? 1.0 : 0.0, jj == 1 ? 1.0 : 0.0, jj == 2 ? 1.0 : 0.0, jj == 3 ? 1.0 : 0.0};
+                tangent::dir_q0(S, K, tq0, o);
                 for (int a = 0; a < 3; ++a) {
-                    put(REC_APW + 3 * a + j, c26 * sp[a]);
-                    put(REC_AVW + 3 * a + j, c6 * sv[a]);
-                    put(REC_AWW + 3 * a + j, tw0[a] + c6 * sw[a]);
+                    put(REC_APQ + 4 * a + jj, o.p[a]);
+                    put(REC_AVQ + 4 * a + jj, o.v[a]);
                 }
-                for (int a = 0; a < 4; ++a) put(REC_AQW + 3 * a + j, c6 * sq[a]);
-            } else if (j < 7) {
-                const int jj = j - 3;
-                for (int a = 0; a < 3; ++a) {
-                    put(REC_APQ + 4 * a + jj, c26 * sp[a]);
-                    put(REC_AVQ + 4 * a + jj, c6 * sv[a]);
-                }
-                for (int a = 0; a < 4; ++a) put(REC_AQQ + 4 * a + jj, tq0[a] + c6 * sq[a]);
-            } else if (j < 10) {
-                const int jj = j - 7;
-                for (int a = 0; a < 3; ++a) {
-                    put(REC_BPF - REC_BPF + 3 * a + jj, c26 * sp[a]);
-                    put(REC_BVF - REC_BPF + 3 * a + jj, c6 * sv[a]);
-                }
-            } else {
-                const int jj = j - 10;
-                for (int a = 0; a < 3; ++a) {
-                    put(REC_BPT - REC_BPF + 3 * a + jj, c26 * sp[a]);
-                    put(REC_BVT - REC_BPF + 3 * a + jj, c6 * sv[a]);
-                    put(REC_BWT - REC_BPF + 3 * a + jj, c6 * sw[a]);
-                }
-                for (int a = 0; a < 4; ++a) put(REC_BQT - REC_BPF + 3 * a + jj, c6 * sq[a]);
+                for (int a = 0; a < 4; ++a) put(REC_AQQ + 4 * a + jj, o.q[a]);
             }
-            if (!DIRS && j == 6) flush(k, false);   // the A blocks (words 0..78) are complete
+            flush(k, false);   // the A blocks (words 0..78) are complete
+            pbase = REC_BPF;
+            auto put_F = [&](int jj) {
+                for (int a = 0; a < 3; ++a) {
+                    put(REC_BPF - REC_BPF + 3 * a + jj, o.p[a]);
+                    put(REC_BVF - REC_BPF + 3 * a + jj, o.v[a]);
+                }
+            };
+            tangent::dir_F<0>(S, K, C.inv_mass, o); put_F(0);
+            tangent::dir_F<1>(S, K, C.inv_mass, o); put_F(1);
+            tangent::dir_F<2>(S, K, C.inv_mass, o); put_F(2);
+#pragma unroll 1
+            for (int jj = 0; jj < 3; ++jj) {    // tau
+                const double tT[3] = {jj == 0 ? 1.0 : 0.0, jj == 1 ? 1.0 : 0.0, jj == 2 ? 1.0 : 0.0};
+                tangent::dir_tau(S, K, C.Jinv, C.ArT, tT, o);
+                for (int a = 0; a < 3; ++a) {
+                    put(REC_BPT - REC_BPF + 3 * a + jj, o.p[a]);
+                    put(REC_BVT - REC_BPF + 3 * a + jj, o.v[a]);
+                    put(REC_BWT - REC_BPF + 3 * a + jj, o.w[a]);
+                }
+                for (int a = 0; a < 4; ++a) put(REC_BQT - REC_BPF + 3 * a + jj, o.q[a]);
+            }
+        } else {
+            // the split kernels: one generic loop over their share of the directions, contracted by the compiler
+            for (int j = jlo; j < jhi; ++j) {
+                pbase = (j < 7) ? 0 : REC_BPF;
+                double tw0[3] = {0, 0, 0}, tq0[4] = {0, 0, 0, 0}, tF[3] = {0, 0, 0}, tT[3] = {0, 0, 0};
+                if (j < 3) tw0[j] = 1.0;
+                else if (j < 7) tq0[j - 3] = 1.0;
+                else if (j < 10) tF[j - 7] = 1.0;
+                else tT[j - 10] = 1.0;
+                // wrench contributions common to all stage points
+                double jt[3], at[3];
+                mat3vec(C.Jinv, tT, jt);   // d wdot / d tau * tT
+                mat3vec(C.ArT, tT, at);    // d a_b / d tau * tT
+                for (int i = 0; i < 3; ++i) at[i] += tF[i] * C.inv_mass;
+                double tkw[3] = {0, 0, 0}, tkq[4] = {0, 0, 0, 0};
+                double sw[3] = {0, 0, 0}, sq[4] = {0, 0, 0, 0}, sv[3] = {0, 0, 0}, sp[3] = {0, 0, 0};
+                for (int i = 0; i < 4; ++i) {
+                    double tw[3], tq[4];
+                    for (int a = 0; a < 3; ++a) tw[a] = tw0[a] + acoef[i] * tkw[a];
+                    for (int a = 0; a < 4; ++a) tq[a] = tq0[a] + acoef[i] * tkq[a];
+                    const StageBlk& B = S[i];
+                    double nkw[3], nkq[4], nkv[3], rv[3];
+                    for (int a = 0; a < 3; ++a)
+                        nkw[a] = B.Fww[3 * a] * tw[0] + B.Fww[3 * a + 1] * tw[1] + B.Fww[3 * a + 2] * tw[2] + jt[a];
+                    for (int a = 0; a < 4; ++a)
+                        nkq[a] = B.Fqw[3 * a] * tw[0] + B.Fqw[3 * a + 1] * tw[1] + B.Fqw[3 * a + 2] * tw[2] +
+                                 B.Fqq[4 * a] * tq[0] + B.Fqq[4 * a + 1] * tq[1] + B.Fqq[4 * a + 2] * tq[2] + B.Fqq[4 * a + 3] * tq[3];
+                    mat3vec(B.RT, at, rv);
+                    for (int a = 0; a < 3; ++a)
+                        nkv[a] = B.Vw[3 * a] * tw[0] + B.Vw[3 * a + 1] * tw[1] + B.Vw[3 * a + 2] * tw[2] +
+                                 B.Vq[4 * a] * tq[0] + B.Vq[4 * a + 1] * tq[1] + B.Vq[4 * a + 2] * tq[2] + B.Vq[4 * a + 3] * tq[3] + rv[a];
+                    for (int a = 0; a < 3; ++a) { tkw[a] = nkw[a]; sw[a] += wcoef[i] * nkw[a]; }
+                    for (int a = 0; a < 4; ++a) { tkq[a] = nkq[a]; sq[a] += wcoef[i] * nkq[a]; }
+                    for (int a = 0; a < 3; ++a) { sv[a] += wcoef[i] * nkv[a]; if (i < 3) sp[a] += nkv[a]; }
+                }
+                const double c6 = dt / 6.0, c26 = dt * dt / 6.0;
+                if (j < 3) {
+                    for (int a = 0; a < 3; ++a) {
+                        put(REC_APW + 3 * a + j, c26 * sp[a]);
+                        put(REC_AVW + 3 * a + j, c6 * sv[a]);
+                        put(REC_AWW + 3 * a + j, tw0[a] + c6 * sw[a]);
+                    }
+                    for (int a = 0; a < 4; ++a) put(REC_AQW + 3 * a + j, c6 * sq[a]);
+                } else if (j < 7) {
+                    const int jj = j - 3;
+                    for (int a = 0; a < 3; ++a) {
+                        put(REC_APQ + 4 * a + jj, c26 * sp[a]);
+                        put(REC_AVQ + 4 * a + jj, c6 * sv[a]);
+                    }
+                    for (int a = 0; a < 4; ++a) put(REC_AQQ + 4 * a + jj, tq0[a] + c6 * sq[a]);
+                } else if (j < 10) {
+                    const int jj = j - 7;
+                    for (int a = 0; a < 3; ++a) {
+                        put(REC_BPF - REC_BPF + 3 * a + jj, c26 * sp[a]);
+                        put(REC_BVF - REC_BPF + 3 * a + jj, c6 * sv[a]);
+                    }
+                } else {
+                    const int jj = j - 10;
+                    for (int a = 0; a < 3; ++a) {
+                        put(REC_BPT - REC_BPF + 3 * a + jj, c26 * sp[a]);
+                        put(REC_BVT - REC_BPF + 3 * a + jj, c6 * sv[a]);
+                        put(REC_BWT - REC_BPF + 3 * a + jj, c6 * sw[a]);
+                    }
+                    for (int a = 0; a < 4; ++a) put(REC_BQT - REC_BPF + 3 * a + jj, c6 * sq[a]);
+                }
+            }
         }
 
         // ---- advance the nonlinear rollout (no quaternion renormalisation, sys_model.py:152-158) ----
