@@ -269,6 +269,9 @@ int build_consts(const ftmpc_config& c, DeviceConsts& d, std::string& why) {
     std::memcpy(d.J, c.J, sizeof(d.J));
     if (!inv3(c.J, d.Jinv)) { why = "J is singular"; return FTMPC_ERR_ARG; }
     std::memcpy(d.r, c.r, sizeof(d.r));
+    d.r_y[1] = c.r[1];      // (the other components stay 0 from the memset)
+    d.r_xz[0] = c.r[0];
+    d.r_xz[2] = c.r[2];
     std::memcpy(d.fvirt, c.f_virt, sizeof(d.fvirt));
     // ArT = -[r]x Jinv
     const double* r = c.r;

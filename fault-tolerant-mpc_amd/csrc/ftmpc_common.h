@@ -70,6 +70,9 @@ struct DeviceConsts {
     double rho;
     double mu_stop;
     double mu_refine;       // take the float64 reference gradient once mu falls below this (<= 0: never)
+    // r = r_y + r_xz = (0, r[1], 0) + (r[0], 0, r[2]) for the linearise kernel: the sums over r_y are left to the compiler's
+    // contraction (one product each), the r_xz part is added in a fixed shape (ftmpc_linearize.hip, stage_eval)
+    double r_y[3], r_xz[3];
 };
 
 // non-quadratic terminal-cost terms (include/ftmpc.h ftmpc_config.tc_*), device copy

@@ -54,6 +54,32 @@ __device__ inline void skew_mul(const double a[3], const double M[9], double o[9
     }
 }
 
+// The same three helpers with contraction off: every product and every sum rounds on its own, whatever code surrounds them.
+// They carry the r_xz = (r[0], 0, r[2]) part of the lever arm (DeviceConsts::r_y, r_xz).  The sums over the whole r have two
+// non-zero products once r[0] or r[2] is non-zero, and the compiler then contracted them one way in the full-record and the
+// one-direction kernels and another way in the shares kernel (records 1e-14 apart); with r_xz = 0 every term here is an exact
+// zero, so the reference vehicle's records keep their bits.
+__device__ inline void cross3_plain(const double a[3], const double b[3], double o[3]) {
+    FTMPC_TAN_NOCONTRACT
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__device__ inline void mat3vec_plain(const double M[9], const double v[3], double o[3]) {
+    FTMPC_TAN_NOCONTRACT
+    for (int i = 0; i < 3; ++i) o[i] = (M[3 * i] * v[0] + M[3 * i + 1] * v[1]) + M[3 * i + 2] * v[2];
+}
+
+__device__ inline void skew_mul_plain(const double a[3], const double M[9], double o[9]) {
+    FTMPC_TAN_NOCONTRACT
+    for (int j = 0; j < 3; ++j) {
+        o[0 + j] = a[1] * M[6 + j] - a[2] * M[3 + j];
+        o[3 + j] = a[2] * M[0 + j] - a[0] * M[6 + j];
+        o[6 + j] = a[0] * M[3 + j] - a[1] * M[0 + j];
+    }
+}
+
 // Rot(q)^T for q = [x,y,z,w]; no unit-norm assumption (utils.py:15-19)
 __device__ inline void rotT(const double q[4], double RT[9]) {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
@@ -82,10 +108,19 @@ __device__ inline void stage_eval(const DeviceConsts& C, const double w[3], cons
     dq[3] = 0.5 * (-w[0] * q[0] - w[1] * q[1] - w[2] * q[2]);
     // a_b = F/m + wdot x r + w x (w x r)   (spiral_model.py:67-71)
     double wxr[3], wxwxr[3], dwxr[3], ab[3];
-    cross3(w, C.r, wxr);
+    cross3(w, C.r_y, wxr);
     cross3(w, wxr, wxwxr);
-    cross3(dw, C.r, dwxr);
+    cross3(dw, C.r_y, dwxr);
     for (int i = 0; i < 3; ++i) ab[i] = F[i] * C.inv_mass + dwxr[i] + wxwxr[i];
+    double wxrx[3];      // w x r_xz: its part of a_b here, of d a_b / d w below
+    {
+        FTMPC_TAN_NOCONTRACT
+        double wxwxrx[3], dwxrx[3];
+        cross3_plain(w, C.r_xz, wxrx);
+        cross3_plain(w, wxrx, wxwxrx);
+        cross3_plain(dw, C.r_xz, dwxrx);
+        for (int i = 0; i < 3; ++i) ab[i] = ab[i] + (dwxrx[i] + wxwxrx[i]);
+    }
     rotT(q, S.RT);
     mat3vec(S.RT, ab, dv);
     // ---- blocks ----
@@ -101,11 +136,20 @@ __device__ inline void stage_eval(const DeviceConsts& C, const double w[3], cons
             S.Fww[3 * i + j] = -(C.Jinv[3 * i] * M1[j] + C.Jinv[3 * i + 1] * M1[3 + j] + C.Jinv[3 * i + 2] * M1[6 + j]);
     // d a_b / d w = -[r]x Fww - [w x r]x - [w]x [r]x
     double rF[9], wr[9], dab[9];
-    skew_mul(C.r, S.Fww, rF);
-    const double SR[9] = {0, -C.r[2], C.r[1], C.r[2], 0, -C.r[0], -C.r[1], C.r[0], 0};
+    skew_mul(C.r_y, S.Fww, rF);
+    const double SR[9] = {0, -C.r_y[2], C.r_y[1], C.r_y[2], 0, -C.r_y[0], -C.r_y[1], C.r_y[0], 0};
     skew_mul(w, SR, wr);
     const double SW[9] = {0, -wxr[2], wxr[1], wxr[2], 0, -wxr[0], -wxr[1], wxr[0], 0};
     for (int i = 0; i < 9; ++i) dab[i] = -rF[i] - SW[i] - wr[i];
+    {
+        FTMPC_TAN_NOCONTRACT
+        double rFx[9], wrx[9];
+        skew_mul_plain(C.r_xz, S.Fww, rFx);
+        const double SRx[9] = {0, -C.r_xz[2], C.r_xz[1], C.r_xz[2], 0, -C.r_xz[0], -C.r_xz[1], C.r_xz[0], 0};
+        skew_mul_plain(w, SRx, wrx);
+        const double SWx[9] = {0, -wxrx[2], wxrx[1], wxrx[2], 0, -wxrx[0], -wxrx[1], wxrx[0], 0};
+        for (int i = 0; i < 9; ++i) dab[i] = dab[i] - ((rFx[i] + SWx[i]) + wrx[i]);
+    }
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
             S.Vw[3 * i + j] = S.RT[3 * i] * dab[j] + S.RT[3 * i + 1] * dab[3 + j] + S.RT[3 * i + 2] * dab[6 + j];
@@ -235,12 +279,23 @@ __global__ void __launch_bounds__(64) ftmpc_linearize_kernel(const DeviceConsts 
     {
         double RT[9], wxr[3], a[3], c[3];
         rotT(q, RT);
-        cross3(w, C.r, wxr);
-        mat3vec(RT, C.r, a);
+        cross3(w, C.r_y, wxr);
+        mat3vec(RT, C.r_y, a);
         mat3vec(RT, wxr, c);
         for (int i = 0; i < 3; ++i) {
             pos[i] = x[i] + a[i];
             vel[i] = x[3 + i] + c[i];
+        }
+        {   // the r_xz part of the lever arm, in a fixed shape (see cross3_plain)
+            FTMPC_TAN_NOCONTRACT
+            double wxrx[3], ax[3], cx[3];
+            cross3_plain(w, C.r_xz, wxrx);
+            mat3vec_plain(RT, C.r_xz, ax);
+            mat3vec_plain(RT, wxrx, cx);
+            for (int i = 0; i < 3; ++i) {
+                pos[i] = pos[i] + ax[i];
+                vel[i] = vel[i] + cx[i];
+            }
         }
     }
     double ubv[MAX_NT], stk[MAX_NT];

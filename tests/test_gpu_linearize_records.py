@@ -71,8 +71,9 @@ def _inputs(d, warm):
     return dict(x0=d["x0"], ub=d["ub"], stuck=d["stuck"], xref=d["xref"])
 
 
-def _check_against_oracle(rec, mpc, d, warm, N, NT, insts, terminal_we=True):
-    cfg = qo.QPConfig(N=N, NT=NT)
+def _check_against_oracle(rec, mpc, d, warm, N, NT, insts, terminal_we=True, cfg=None, tol=TOL):
+    """cfg: the QPConfig equal to the handle's constants (None: the default vehicle); tol: of each block's scale"""
+    cfg = qo.QPConfig(N=N, NT=NT) if cfg is None else cfg
     fv = np.concatenate([cfg.f_virt, np.zeros(3)])
     for b in insts:
         ub, stuck = d["ub"][b], d["stuck"][b]
@@ -84,14 +85,14 @@ def _check_against_oracle(rec, mpc, d, warm, N, NT, insts, terminal_we=True):
             for name, (m, (r0, r1), (c0, c1)) in BLOCKS.items():
                 ref = (A if m == "A" else Bg)[k][r0:r1, c0:c1]
                 got = r[REC[name]:REC[name] + ref.size].reshape(ref.shape)
-                assert np.abs(got - ref).max() <= TOL * max(1.0, np.abs(ref).max()), (b, k, name)
+                assert np.abs(got - ref).max() <= tol * max(1.0, np.abs(ref).max()), (b, k, name)
             e = cbar[k + 1][0:9] - xr[:, k + 1]
             if k + 1 < N or terminal_we:
                 we = cfg.Q * e if k + 1 < N else mpc.P @ e
-                assert np.abs(r[REC["WE"]:REC["WE"] + 9] - we).max() <= TOL * max(1.0, np.abs(we).max()), (b, k, "WE")
+                assert np.abs(r[REC["WE"]:REC["WE"] + 9] - we).max() <= tol * max(1.0, np.abs(we).max()), (b, k, "WE")
             u_r = np.zeros(6) if ur is None else np.concatenate([rm.rot(cbar[k][9:13]).T @ ur[0:3, k], ur[3:6, k]])
             rut = cfg.R * (cfg.D @ (Ubar[k] + stuck) - u_r - fv)
-            assert np.abs(r[REC["RUT"]:REC["RUT"] + 6] - rut).max() <= TOL * max(1.0, np.abs(rut).max()), (b, k, "RUT")
+            assert np.abs(r[REC["RUT"]:REC["RUT"] + 6] - rut).max() <= tol * max(1.0, np.abs(rut).max()), (b, k, "RUT")
             assert r[REC["USED"]] == 0.0
 
 
