@@ -2195,7 +2195,8 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
                          double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
                          const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr,
-                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr, const ftmpc_disturbance* db = nullptr);
+                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr, const ftmpc_disturbance* db = nullptr,
+                         const ftmpc_bias_estimate* be = nullptr);
 
 // A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
 // message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
@@ -2451,6 +2452,40 @@ static std::string disturbance_problem(const ftmpc_disturbance* db, int64_t B, c
                     return "ftmpc_disturbance.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
     return "";
 }
+// A bias estimate's layout and values (include/ftmpc.h, ftmpc_bias_estimate) over the vehicles [0, B), against the estimator and the
+// disturbance estimate of the same call: empty when acceptable, else the message
+static std::string bias_problem(const ftmpc_bias_estimate* be, int64_t B, const ftmpc_estimator* es, const ftmpc_disturbance* db,
+                                int64_t first = 0) {
+    if (!be) return "";
+    if (be->struct_size != (int32_t)sizeof(ftmpc_bias_estimate))
+        return "ftmpc_bias_estimate.struct_size is " + std::to_string(be->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_bias_estimate));
+    if (!es) return "ftmpc_bias_estimate needs an estimator (ftmpc_estimator): the bias states augment its filter";
+    if (db) return "ftmpc_bias_estimate with a disturbance (ftmpc_disturbance) in the same call: 24 filter states are not served";
+    for (int k = 0; k < 2; ++k) {
+        if (!std::isfinite(be->p0[k]) || be->p0[k] < 0) return "ftmpc_bias_estimate.p0[" + std::to_string(k) + "] is negative or not finite";
+        if (!std::isfinite(be->proc_sigma[k]) || be->proc_sigma[k] < 0)
+            return "ftmpc_bias_estimate.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
+    }
+    if (be->cross && !be->bias) return "ftmpc_bias_estimate.cross is given without bias";
+    if (be->cross && !es->xhat) return "ftmpc_bias_estimate.cross is given without ftmpc_estimator.xhat";
+    if (be->cov && !be->cross) return "ftmpc_bias_estimate.cov is given without cross";
+    const double* const arr[3] = {be->bias, be->cross, be->cov};
+    const char* const name[3] = {"bias", "cross", "cov"};
+    const int64_t width[3] = {6, 72, 21};
+    for (int a = 0; a < 3; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < B * width[a]; ++i)
+                if (!std::isfinite(arr[a][i]))
+                    return std::string("ftmpc_bias_estimate.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
+                           " has a non-finite entry (" + std::to_string(i % width[a]) + ")";
+    if (be->cov)
+        for (int64_t b = 0; b < B; ++b)
+            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
+                if (be->cov[b * 21 + k] < 0)
+                    return "ftmpc_bias_estimate.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
+    return "";
+}
 
 static int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
     const std::string msg = estimator_problem(es, B);
@@ -2687,6 +2722,25 @@ int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                      const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                      const ftmpc_disturbance* disturbance) {
+    return ftmpc_simulate_bias_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                     x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, nullptr);
+}
+
+// the ABI guard of a bias estimate, before the handle is looked at (so that it needs no device): the message goes to the handle's
+// error, or to the one ftmpc_last_error(NULL) returns
+static int check_bias_size(ftmpc_handle* h, const ftmpc_bias_estimate* be) {
+    if (be && be->struct_size != (int32_t)sizeof(ftmpc_bias_estimate)) return fail(h, FTMPC_ERR_ARG, bias_problem(be, 0, nullptr, nullptr));
+    return FTMPC_OK;
+}
+
+int ftmpc_simulate_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                              const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                              int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                              double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                              const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                              const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                              const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
+    if (check_bias_size(h, bias_estimate) != FTMPC_OK) return FTMPC_ERR_ARG;
     if (!h) return FTMPC_ERR_ARG;
     if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
     if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
@@ -2706,6 +2760,10 @@ int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
         const std::string msg = disturbance_problem(disturbance, B, estimator, sqp_iters);
         if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
     }
+    {     // (the estimate reaches the solve through x0 alone: sqp_iters >= 0 is served)
+        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
@@ -2717,7 +2775,7 @@ int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance);
+                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
 }
 
 int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -2824,6 +2882,23 @@ int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t 
                                             const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                             const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                             int32_t* no_hull_step, const ftmpc_disturbance* disturbance) {
+    return ftmpc_simulate_wrench_bias_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                            seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                            out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b, no_hull_step,
+                                            disturbance, nullptr);
+}
+
+int ftmpc_simulate_wrench_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                     int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                     uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                     const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                     int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                     const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                     int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                     const ftmpc_bias_estimate* bias_estimate) {
+    if (check_bias_size(h, bias_estimate) != FTMPC_OK) return FTMPC_ERR_ARG;
     if (!h) return FTMPC_ERR_ARG;
     int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
     if (rc != FTMPC_OK) return rc;
@@ -2848,6 +2923,10 @@ int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t 
         const std::string msg = disturbance_problem(disturbance, B, estimator, 0);
         if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
     }
+    {
+        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
+        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    }
     if (B == 0 || T == 0) {
         zero_mission_cost(mission, B);
         zero_actuator_sums(actuator, B);
@@ -2862,7 +2941,7 @@ int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t 
                   out_hull_b, diagnosis ? no_hull_step : nullptr};
     return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
                          sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor,
-                         estimator, diagnosis, disturbance);
+                         estimator, diagnosis, disturbance, bias_estimate);
 }
 
 int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const double* stuck, const double* hull_A, int32_t n_sets,
@@ -2954,7 +3033,8 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                          const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
                          const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
                          const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
-                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg, const ftmpc_disturbance* db) {
+                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg, const ftmpc_disturbance* db,
+                         const ftmpc_bias_estimate* be) {
     int rc;
     const int N = h->cfg.N, NT = h->cfg.NT;
     hipStream_t s = h->stream;
@@ -3191,6 +3271,10 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         } else {
             for (int i = 0, k = 0; i < 12; k += 12 - i, ++i) std::fill(h_cov.begin() + (size_t)k * B, h_cov.begin() + (size_t)(k + 1) * B, es->p0[i / 3] * es->p0[i / 3]);
         }
+        if (be && !be->cross)     // a bias estimate without handed pieces: P_mm = P_xx + HB diag(p0_b^2) HB' (see the bias block below)
+            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i)
+                if ((i >= 3 && i < 6) || i >= 9)
+                    for (int64_t b = 0; b < B; ++b) h_cov[(size_t)k * B + b] += be->p0[i >= 9] * be->p0[i >= 9];
         HIP_TRY(h, hipMalloc(&d_cov.p, nc * sizeof(double)));
         HIP_TRY(h, hipMemcpyAsync(d_cov, h_cov.data(), nc * sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMalloc(&d_xhat.p, (size_t)B * 13 * sizeof(double)));
@@ -3270,6 +3354,57 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         for (int k = 0; k < 2; ++k) dq.qdsq[k] = db->proc_sigma[k] * db->proc_sigma[k];
         dq.force_hist = d_dfh;
         dq.torque_hist = d_dth;
+    }
+    // bias estimate (checked by the entry; it needs the estimator and excludes the disturbance estimate): the pieces in measured
+    // coordinates, P_mb [72][B] and P_bb [21][B] component-major with P_mm in d_cov; b^ [B][6]; the gain slot [168][B].  Without a
+    // handed cross the bias prior is independent of the state error, and the pieces are T diag(P_xx, P_bb) T'
+    const bool bias = be != nullptr;
+    DevBuf<double> d_bcross, d_bcovb, d_best, d_bgain, d_bhist;
+    std::vector<double> h_bcross, h_bcovb;
+    ftmpc::BiasParams bq{};
+    if (bias) {
+        try {
+            h_bcross.assign((size_t)B * 72, 0.0);
+            h_bcovb.assign((size_t)B * 21, 0.0);
+        } catch (const std::bad_alloc&) {
+            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the bias estimate's staging arrays");
+        }
+        const double pb[2] = {be->p0[0] * be->p0[0], be->p0[1] * be->p0[1]};
+        for (int64_t b0 = 0; b0 < B; b0 += 64) {
+            const int64_t b1 = std::min(B, b0 + 64);
+            if (be->cross)
+                for (int64_t k = 0; k < 72; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_bcross[(size_t)k * B + b] = be->cross[b * 72 + k];
+            if (be->cov)
+                for (int64_t k = 0; k < 21; ++k)
+                    for (int64_t b = b0; b < b1; ++b) h_bcovb[(size_t)k * B + b] = be->cov[b * 21 + k];
+        }
+        if (!be->cov)
+            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i) std::fill(h_bcovb.begin() + (size_t)k * B, h_bcovb.begin() + (size_t)(k + 1) * B, pb[i / 3]);
+        if (!be->cross) {
+            for (int r = 0; r < 3; ++r) {
+                const int kv = 6 * (3 + r) + r, kw = 6 * (9 + r) + 3 + r;      // HB's ones
+                std::fill(h_bcross.begin() + (size_t)kv * B, h_bcross.begin() + (size_t)(kv + 1) * B, pb[0]);
+                std::fill(h_bcross.begin() + (size_t)kw * B, h_bcross.begin() + (size_t)(kw + 1) * B, pb[1]);
+            }
+        }
+        HIP_TRY(h, hipMalloc(&d_bcross.p, (size_t)B * 72 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_bcovb.p, (size_t)B * 21 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_best.p, (size_t)B * 6 * sizeof(double)));
+        HIP_TRY(h, hipMalloc(&d_bgain.p, (size_t)B * 168 * sizeof(double)));
+        HIP_TRY(h, hipMemcpyAsync(d_bcross, h_bcross.data(), (size_t)B * 72 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_bcovb, h_bcovb.data(), (size_t)B * 21 * sizeof(double), hipMemcpyHostToDevice, s));
+        if (be->bias)
+            HIP_TRY(h, hipMemcpyAsync(d_best, be->bias, (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
+        else
+            HIP_TRY(h, hipMemsetAsync(d_best, 0, (size_t)B * 6 * sizeof(double), s));
+        if (be->bias_hist) HIP_TRY(h, hipMalloc(&d_bhist.p, (size_t)T * B * 6 * sizeof(double)));
+        bq.cross = d_bcross;
+        bq.covb = d_bcovb;
+        bq.bias = d_best;
+        bq.gain = d_bgain;
+        for (int k = 0; k < 2; ++k) bq.qbsq[k] = be->proc_sigma[k] * be->proc_sigma[k];
+        bq.bias_hist = d_bhist;
     }
     // the diagnosis' state: xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (the caller's are vehicle-major;
     // the statistics are filled on the device when none are handed over), the detect arrays [B][K] with the count per vehicle, the
@@ -3609,6 +3744,9 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             if (dist) {     // the x pass and the d pass of the augmented update; the d pass writes the solve's x0
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+            } else if (bias) {     // the x pass in measured coordinates and the bias pass, which completes x^ and writes the solve's x0
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
             } else
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
             HIP_TRY(h, hipGetLastError());
@@ -3670,6 +3808,9 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
             if (dist) {     // P_xx, then P_xd, P_dd, the cross terms of P_xx and the mean
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<2>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<3>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
+            } else if (bias) {     // P_mm, then P_mb, P_bb, the cross terms of P_mm and the mean
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<2>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<3>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
             } else
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
         }
@@ -3727,6 +3868,12 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
         if (db->force || db->torque) HIP_TRY(h, hipMemcpyAsync(h_dest.data(), d_dest, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
         if (db->cross) HIP_TRY(h, hipMemcpyAsync(h_dcross.data(), d_dcross, (size_t)B * 72 * sizeof(double), hipMemcpyDeviceToHost, s));
         if (db->cov) HIP_TRY(h, hipMemcpyAsync(h_dcovd.data(), d_dcovd, (size_t)B * 21 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (bias) {
+        if (be->bias_hist) HIP_TRY(h, hipMemcpyAsync(be->bias_hist, d_bhist, (size_t)T * B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (be->bias) HIP_TRY(h, hipMemcpyAsync(be->bias, d_best, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (be->cross) HIP_TRY(h, hipMemcpyAsync(h_bcross.data(), d_bcross, (size_t)B * 72 * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (be->cov) HIP_TRY(h, hipMemcpyAsync(h_bcovb.data(), d_bcovb, (size_t)B * 21 * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     if (diag) {
         if (dg->llr_hist) HIP_TRY(h, hipMemcpyAsync(dg->llr_hist, d_dhist, (size_t)(T * B * dH) * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3801,6 +3948,16 @@ static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const
                     for (int64_t b = b0; b < b1; ++b) db->cov[b * 21 + k] = h_dcovd[(size_t)k * B + b];
         }
     }
+    if (bias)
+        for (int64_t b0 = 0; b0 < B; b0 += 64) {
+            const int64_t b1 = std::min(B, b0 + 64);
+            if (be->cross)
+                for (int64_t k = 0; k < 72; ++k)
+                    for (int64_t b = b0; b < b1; ++b) be->cross[b * 72 + k] = h_bcross[(size_t)k * B + b];
+            if (be->cov)
+                for (int64_t k = 0; k < 21; ++k)
+                    for (int64_t b = b0; b < b1; ++b) be->cov[b * 21 + k] = h_bcovb[(size_t)k * B + b];
+        }
     if (est && es->cov)
         for (int64_t b0 = 0; b0 < B; b0 += 64) {
             const int64_t b1 = std::min(B, b0 + 64);

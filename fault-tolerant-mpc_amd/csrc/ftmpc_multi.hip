@@ -215,7 +215,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                    int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                    const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench,
                    const ftmpc_diagnosis* diagnosis = nullptr, double* out_hull_b = nullptr, int32_t* no_hull_step = nullptr,
-                   const ftmpc_disturbance* disturbance = nullptr) {
+                   const ftmpc_disturbance* disturbance = nullptr, const ftmpc_bias_estimate* bias_estimate = nullptr) {
     if (!m) return FTMPC_ERR_ARG;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
@@ -254,6 +254,10 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
     }
     {     // the disturbance estimate likewise: the parameters are uniform, force / torque / cross / cov and the histories per vehicle
         const std::string msg = disturbance_problem(disturbance, B, estimator, wrench ? 0 : sqp_iters);      // (the wrench SQP is served)
+        if (!msg.empty()) return refuse(msg);
+    }
+    {     // the bias estimate likewise (thruster form only): the parameters are uniform, bias / cross / cov and the history per vehicle
+        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
@@ -361,7 +365,16 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (bv.cross) bv.cross += lo * 72;
             if (bv.cov) bv.cov += lo * 21;
         }
+        std::vector<double> bh;
+        ftmpc_bias_estimate sb{};
+        if (bias_estimate) {
+            sb = *bias_estimate;
+            if (sb.bias) sb.bias += lo * 6;
+            if (sb.cross) sb.cross += lo * 72;
+            if (sb.cov) sb.cov += lo * 21;
+        }
         try {
+            if (sb.bias_hist && !whole) bh.resize((size_t)T * n * 6);
             if (bv.force_hist && !whole) fh.resize((size_t)T * n * 3);
             if (bv.torque_hist && !whole) th.resize((size_t)T * n * 3);
             if (dv.llr_hist && !whole) lh.resize((size_t)T * n * NT * dv.n_levels);
@@ -403,6 +416,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (dv.llr_hist) dv.llr_hist = lh.data();
             if (bv.force_hist) bv.force_hist = fh.data();
             if (bv.torque_hist) bv.torque_hist = th.data();
+            if (sb.bias_hist) sb.bias_hist = bh.data();
         }
         const int rc2 = wrench ? ftmpc_simulate_wrench_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
                                                                        hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
@@ -415,12 +429,12 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
                                                                        out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
                                                                        no_hull_step ? no_hull_step + lo : nullptr,
                                                                        disturbance ? &bv : nullptr)
-                               : ftmpc_simulate_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj,
-                                                                 noise, seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                                 bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
-                                                                 actuator ? &at : nullptr, sensor ? &sv : nullptr,
-                                                                 estimator ? &ev : nullptr, diagnosis ? &dv : nullptr,
-                                                                 disturbance ? &bv : nullptr);
+                               : ftmpc_simulate_bias_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
+                                                          seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
+                                                          bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
+                                                          actuator ? &at : nullptr, sensor ? &sv : nullptr, estimator ? &ev : nullptr,
+                                                          diagnosis ? &dv : nullptr, disturbance ? &bv : nullptr,
+                                                          bias_estimate ? &sb : nullptr);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
             if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
@@ -434,6 +448,7 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (diagnosis && diagnosis->llr_hist) scatter_rows(diagnosis->llr_hist, lh.data(), T, B, lo, n, (int64_t)NT * dv.n_levels);
             if (disturbance && disturbance->force_hist) scatter_rows(disturbance->force_hist, fh.data(), T, B, lo, n, 3);
             if (disturbance && disturbance->torque_hist) scatter_rows(disturbance->torque_hist, th.data(), T, B, lo, n, 3);
+            if (bias_estimate && bias_estimate->bias_hist) scatter_rows(bias_estimate->bias_hist, bh.data(), T, B, lo, n, 6);
         }
         return FTMPC_OK;
     });
@@ -800,6 +815,19 @@ int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T,
     return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
                           0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis,
                           nullptr, nullptr, disturbance);
+}
+
+int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                    const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                    int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                    double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                    const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                    const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                    const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                    const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
+    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis,
+                          nullptr, nullptr, disturbance, bias_estimate);
 }
 
 int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,

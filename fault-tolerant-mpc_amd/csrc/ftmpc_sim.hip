@@ -1953,4 +1953,244 @@ __global__ void __launch_bounds__(64) ftmpc_diagnose_dist_kernel(const DeviceCon
     P.xt[b * 14 + 13] += 1.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Sensor bias estimation (ftmpc_simulate_bias_batch; include/ftmpc.h, ftmpc_bias_estimate): the navigation filter augmented by six
+// states per vehicle, a constant velocity bias b_v^ [3] (m/s) and a constant rate bias b_w^ [3] (rad/s):  y_v = v + b_v + n,
+// y_w = w + b_w + n.  The pieces travel in the MEASURED error coordinates m = (dp, dv + db_v, dtheta, dw + db_w) with b = (db_v, db_w)
+// unchanged, P^m = T P T', T = [[I, HB], [0, I]]: there H = [I 0], so the x pass of the update is the estimator's own on P_mm and the
+// structure is ftmpc_filter_dist_kernel's: P_mm (78 packed), P_mb (12 x 6) and P_bb (21 packed), component-major [k][B], the 168-double
+// gain slot between the two passes, every index into a register array a compile-time constant.  Four launches per loop step:
+//   PHASE 0  before the solve: the estimator's update of P_mm with the residual y [-] x~, x~ = x^ with v^ + b_v^ and w^ + b_w^;
+//            x^ <- x^ [+] delta_m; the gain slot as ftmpc_filter_dist_kernel<0> leaves it
+//   PHASE 1  holds P_mb and P_bb and consumes the slot (delta_b); v^ -= delta_b[0:3], w^ -= delta_b[3:6] (delta_x = delta_m -
+//            HB delta_b), b^ += delta_b; est_hist, bias_hist, err_sq, the propagation of x^ over the queued commands with the plain
+//            model (the bias does not enter the dynamics; pred_hist) and the solve's x0
+//   PHASE 2  after the plant step: P_mm <- Phi_xx P_mm Phi_xx' + Q_xx, ftmpc_filter_kernel<1>'s covariance walk
+//   PHASE 3  csrc/ftmpc_bias_block.h: Y = Phi_xx P_mb, Z = E P_bb, E = (I - Phi_xx) HB;  P_mm += Y E' + E Y' + Z E' + the Q^m
+//            diagonal terms,  P_mb <- Y + Z + Q_xb,  P_bb += Q_bb;  then x^ <- one plain RK4 step, renormalised (b^ unchanged)
+// On the first step of a call without xhat, x^ = y_t with b^ taken off the velocity and the rate.
+// ---------------------------------------------------------------------------------------------------------
+}  // namespace ftmpc
+#include "ftmpc_bias_block.h"      // (included here, not at the top: the build logs keep the source lines of every kernel above)
+namespace ftmpc {
+struct BiasParams {
+    double* cross;            // [72][B] P_mb, k = 6 i + c, in/out
+    double* covb;             // [21][B] P_bb packed, in/out
+    double* bias;             // [B*6] b_v^, b_w^, in/out
+    double* gain;             // [168][B]: k_x of channel j at 12 j + i, s_j at 144 + j, e_j at 156 + j
+    double qbsq[2];           // proc_sigma^2 of the bias: velocity, rate
+    double* bias_hist;        // nullptr or [T*B*6]: b^_{t|t}
+};
+
+template <int PHASE>
+__global__ void __launch_bounds__(64) ftmpc_filter_bias_kernel(const DeviceConsts C, const FilterParams F, const BiasParams D) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= F.B) return;
+    const int64_t B = F.B;
+    const int64_t blk = (int64_t)blockIdx.x * blockDim.x;
+    double* const covb = F.cov + blk;
+    double* const gainb = D.gain + blk;
+    double* const crossb = D.cross + blk;
+    double* const covbb = D.covb + blk;
+    const unsigned lane = threadIdx.x;
+    if constexpr (PHASE == 0) {
+        double x[13], P[78], y[13];
+        for (int i = 0; i < 13; ++i) y[i] = F.y[b * 13 + i];
+        if (F.init) {
+            for (int i = 0; i < 13; ++i) x[i] = y[i];
+        } else {
+            for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        }
+        if (!F.init && F.update) {
+            double th[3], d[12];
+            filter_att_residual(x + 6, y + 6, th);
+#pragma unroll
+            for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d[i] = 0.0;
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                const int jx = j < 6 ? j : j + 1;
+                double rj;
+                if (j >= 6 && j < 9)
+                    rj = th[j - 6];
+                else if (j < 3)
+                    rj = F.y[b * 13 + jx] - F.xhat[b * 13 + jx];
+                else      // velocity and rate: against x~ = x^ + b^
+                    rj = F.y[b * 13 + jx] - (F.xhat[b * 13 + jx] + D.bias[b * 6 + (j < 6 ? j - 3 : j - 6)]);
+                const double sj = P[tri(j, j)] + F.rsq[j / 3];
+                const double inv = 1.0 / sj;
+                double k[12];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) k[i] = P[tri(i, j)] * inv;
+                const double e = rj - d[j];
+#pragma unroll
+                for (int i = 0; i < 12; ++i) cov_row(gainb + (int64_t)(12 * j + i) * B)[lane] = k[i];
+                cov_row(gainb + (int64_t)(144 + j) * B)[lane] = sj;
+                cov_row(gainb + (int64_t)(156 + j) * B)[lane] = e;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) d[i] += k[i] * e;
+#pragma unroll
+                for (int a = 0; a < 12; ++a) {
+                    const double ska = sj * k[a];
+#pragma unroll
+                    for (int c = a; c < 12; ++c) P[tri(a, c)] -= ska * k[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+            {     // (a volatile read, as in ftmpc_filter_kernel<0>: x^ is not held across the covariance)
+                const volatile double* const xh = F.xhat + b * 13;
+                for (int i = 0; i < 13; ++i) x[i] = xh[i];
+            }
+            for (int i = 0; i < 3; ++i) {
+                x[i] += d[i];
+                x[3 + i] += d[3 + i];
+                x[10 + i] += d[9 + i];
+            }
+            filter_rotate(x + 6, d[6], d[7], d[8]);
+        }
+        for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];      // x^ [+] delta_m: the bias pass takes HB delta_b off
+        return;
+    } else if constexpr (PHASE == 1) {
+        double bb[6], x[13];
+        for (int c = 0; c < 6; ++c) bb[c] = D.bias[b * 6 + c];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        if (F.init) {
+            for (int c = 0; c < 3; ++c) {
+                x[3 + c] -= bb[c];
+                x[10 + c] -= bb[3 + c];
+            }
+        }
+        if (!F.init && F.update) {
+            double X[72], Pb[21], del[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 72; ++k) X[k] = cov_row(crossb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) Pb[k] = cov_row(covbb + (int64_t)k * B)[lane];
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                const double sj = cov_row(gainb + (int64_t)(144 + j) * B)[lane];
+                const double e = cov_row(gainb + (int64_t)(156 + j) * B)[lane];
+                const double inv = 1.0 / sj;
+                double kd[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) kd[c] = X[6 * j + c] * inv;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) del[c] += kd[c] * e;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) {
+                    const double ski = sj * cov_row(gainb + (int64_t)(12 * j + i) * B)[lane];
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) X[6 * i + c] -= ski * kd[c];
+                }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const double ska = sj * kd[a];
+#pragma unroll
+                    for (int c = a; c < 6; ++c) Pb[tri6(a, c)] -= ska * kd[c];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 72; ++k) cov_row(crossb + (int64_t)k * B)[lane] = X[k];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) cov_row(covbb + (int64_t)k * B)[lane] = Pb[k];
+            for (int c = 0; c < 3; ++c) {      // delta_x = delta_m - HB delta_b
+                x[3 + c] -= del[c];
+                x[10 + c] -= del[3 + c];
+            }
+            for (int c = 0; c < 6; ++c) bb[c] += del[c];
+            for (int c = 0; c < 6; ++c) D.bias[b * 6 + c] = bb[c];
+        }
+        if (F.init || F.update)
+            for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+        if (F.est_hist)
+            for (int i = 0; i < 13; ++i) F.est_hist[(F.step * B + b) * 13 + i] = x[i];
+        if (D.bias_hist)
+            for (int c = 0; c < 6; ++c) D.bias_hist[(F.step * B + b) * 6 + c] = bb[c];
+        if (F.err_sq) {     // against the truth: position, velocity, attitude (the residual's theta), rate
+            double xt[13], th[3], e[4] = {0, 0, 0, 0};
+            for (int i = 0; i < 13; ++i) xt[i] = F.truth[b * 13 + i];
+            filter_att_residual(x + 6, xt + 6, th);
+            for (int i = 0; i < 3; ++i) {
+                e[0] += (x[i] - xt[i]) * (x[i] - xt[i]);
+                e[1] += (x[3 + i] - xt[3 + i]) * (x[3 + i] - xt[3 + i]);
+                e[2] += th[i] * th[i];
+                e[3] += (x[10 + i] - xt[10 + i]) * (x[10 + i] - xt[10 + i]);
+            }
+            for (int i = 0; i < 4; ++i) F.err_sq[b * 4 + i] += e[i];
+        }
+        if (F.predict) {
+            int32_t slot = F.slot0;
+#pragma unroll 1
+            for (int j = 0; j < F.latency; ++j) {
+                double gen[6];
+                filter_gen(C, F.ring + (int64_t)slot * B * C.NT, F.ub, F.stuck, b, gen);
+                slot = slot + 1 == F.nslots ? 0 : slot + 1;
+                filter_rk4(C, x, gen);
+            }
+            if (F.pred_hist)
+                for (int i = 0; i < 13; ++i) F.pred_hist[(F.step * B + b) * 13 + i] = x[i];
+        }
+        for (int i = 0; i < 13; ++i) F.x0[b * 13 + i] = x[i];
+        return;
+    } else if constexpr (PHASE == 2) {
+        double x[13], P[78], gen[6], G[9], H[3], W[9];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+#pragma unroll
+        for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+        filter_gen(C, F.u, F.ub, F.stuck, b, gen);
+        filter_phi(C, x, gen, G, H, W);
+        const double dt = C.dt;
+        cov_block<0, 0>(P, G, H, W, dt);
+        cov_block<0, 1>(P, G, H, W, dt);
+        cov_block<0, 2>(P, G, H, W, dt);
+        cov_block<0, 3>(P, G, H, W, dt);
+        cov_block<1, 1>(P, G, H, W, dt);
+        cov_block<1, 2>(P, G, H, W, dt);
+        cov_block<1, 3>(P, G, H, W, dt);
+        cov_block<2, 2>(P, G, H, W, dt);
+        cov_block<2, 3>(P, G, H, W, dt);
+        cov_block<3, 3>(P, G, H, W, dt);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) P[tri(i, i)] += F.qsq[i / 3];
+#pragma unroll
+        for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+        return;
+    } else {
+        double x[13], gen[6], G[9], H[3], W[9], EW[9];
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+        filter_gen(C, F.u, F.ub, F.stuck, b, gen);
+        filter_phi(C, x, gen, G, H, W);
+        const double dt = C.dt;
+        const double qb[2] = {D.qbsq[0], D.qbsq[1]};
+        ftmpc_bias::e_block(W, EW);
+        double Pb[21], Zw[18], X[72];     // Pb stays P_bb of before Q_bb: Z = E P_bb is formed from it where it is used
+#pragma unroll
+        for (int k = 0; k < 21; ++k) Pb[k] = cov_row(covbb + (int64_t)k * B)[lane];
+        ftmpc_bias::z_rows_w(EW, Pb, Zw);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) cov_row(covbb + (int64_t)tri6(i, i) * B)[lane] = Pb[tri6(i, i)] + qb[i / 3];
+#pragma unroll
+        for (int k = 0; k < 72; ++k) X[k] = cov_row(crossb + (int64_t)k * B)[lane];
+        ftmpc_bias::phi_x(dt, G, H, W, X);
+        // (read-modify-write of the rows PHASE 2 wrote)
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+#pragma unroll
+            for (int j = i; j < 12; ++j)
+                if (ftmpc_bias::xx_touched(i, j))
+                    cov_row(covb + (int64_t)tri(i, j) * B)[lane] += ftmpc_bias::xx_gain(dt, EW, X, Pb, Zw, qb, i, j);
+        ftmpc_bias::xb_finish(dt, Pb, Zw, qb, X);
+#pragma unroll
+        for (int k = 0; k < 72; ++k) cov_row(crossb + (int64_t)k * B)[lane] = X[k];
+        filter_rk4(C, x, gen);
+        for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+    }
+}
+template __global__ void ftmpc_filter_bias_kernel<0>(const DeviceConsts, const FilterParams, const BiasParams);
+template __global__ void ftmpc_filter_bias_kernel<1>(const DeviceConsts, const FilterParams, const BiasParams);
+template __global__ void ftmpc_filter_bias_kernel<2>(const DeviceConsts, const FilterParams, const BiasParams);
+template __global__ void ftmpc_filter_bias_kernel<3>(const DeviceConsts, const FilterParams, const BiasParams);
+
 }  // namespace ftmpc

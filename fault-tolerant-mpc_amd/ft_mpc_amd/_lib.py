@@ -42,6 +42,7 @@ SYMBOLS = (
     "ftmpc_simulate_disturbance_batch", "ftmpc_multi_simulate_disturbance_batch", "ftmpc_debug_records_disturbance",
     "ftmpc_simulate_wrench_disturbance_batch", "ftmpc_multi_simulate_wrench_disturbance_batch",
     "ftmpc_eval_cost_wrench_disturbance_batch", "ftmpc_solve_wrench_disturbance_batch", "ftmpc_solve_sqp_wrench_disturbance_batch",
+    "ftmpc_simulate_bias_batch", "ftmpc_simulate_wrench_bias_batch", "ftmpc_multi_simulate_bias_batch",
 )
 
 
@@ -150,6 +151,14 @@ class ftmpc_disturbance(C.Structure):
     ]
 
 
+class ftmpc_bias_estimate(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double * 2), ("proc_sigma", C.c_double * 2),
+        ("bias", C.POINTER(C.c_double)), ("cross", C.POINTER(C.c_double)), ("cov", C.POINTER(C.c_double)),
+        ("bias_hist", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -239,6 +248,9 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_disturbance_batch.argtypes = lib.ftmpc_simulate_disturbance_batch.argtypes
     lib.ftmpc_simulate_wrench_disturbance_batch.argtypes = lib.ftmpc_simulate_wrench_diagnosis_batch.argtypes + [C.POINTER(ftmpc_disturbance)]
     lib.ftmpc_multi_simulate_wrench_disturbance_batch.argtypes = lib.ftmpc_simulate_wrench_disturbance_batch.argtypes
+    lib.ftmpc_simulate_bias_batch.argtypes = lib.ftmpc_simulate_disturbance_batch.argtypes + [C.POINTER(ftmpc_bias_estimate)]
+    lib.ftmpc_multi_simulate_bias_batch.argtypes = lib.ftmpc_simulate_bias_batch.argtypes
+    lib.ftmpc_simulate_wrench_bias_batch.argtypes = lib.ftmpc_simulate_wrench_disturbance_batch.argtypes + [C.POINTER(ftmpc_bias_estimate)]
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,

@@ -467,7 +467,8 @@ class BatchedMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0,
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
-                 plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None):
+                 plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None,
+                 bias_estimate=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -544,11 +545,20 @@ class BatchedMPC:
         and cov=None ([B,21] packed or [B,6,6]; needs cross) -- what a previous call returned, for a continued run -- and
         fields=(...) among force_hist, torque_hist [T,B,3] (the estimates each solve saw) and state (force, torque [B,3], cross
         [B,72], cov [B,21]: the priors of step T); they come back as out["disturbance"].
+        bias_estimate: the estimator's filter augmented by a constant bias of the velocity measurement b_v^ (m/s) and of the rate
+        measurement b_w^ (rad/s) per vehicle, the channels 3..5 and 9..11 of sensor["bias"] (include/ftmpc.h, ftmpc_bias_estimate;
+        ft_mpc_amd.biases restates it in NumPy; both formulations, sqp_iters >= 0, needs `estimator`, not together with
+        `disturbance`): a dict with p0=(2,), proc_sigma=(2,) (standard deviations of the velocity and the rate bias: initial, and per
+        step), bias=None ([B,6], the estimates to start from; default 0), cross=None ([B,72] or [B,12,6]; needs bias and
+        estimator["xhat"]) and cov=None ([B,21] packed or [B,6,6]; needs cross) -- what a previous call returned, for a continued
+        run: the pieces travel in the measured coordinates of ft_mpc_amd.biases, and estimator["cov"] is then P_mm -- and
+        fields=(...) among bias_hist [T,B,6] (the estimates of each step) and state (bias [B,6], cross [B,72], cov [B,21]: the
+        priors of step T); they come back as out["bias_estimate"].
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance)
+                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -987,9 +997,57 @@ def _disturbance_request(disturbance, B, T, estimator, sqp_iters, formulation):
     return db, keep, out
 
 
+def _bias_request(bias_estimate, B, T, estimator, disturbance, es, ekeep):
+    """The ftmpc_bias_estimate struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .biases import NC, NDD, request
+    from .estimators import NP
+    r = request(bias_estimate, B, T, estimator, disturbance)
+    be = _lib.ftmpc_bias_estimate(struct_size=C.sizeof(_lib.ftmpc_bias_estimate))
+    for k in range(2):
+        be.p0[k], be.proc_sigma[k] = float(r["p0"][k]), float(r["proc_sigma"][k])
+    keep, out = [], {}
+    bias, cross, cov = r["bias"], r["cross"], r["cov"]
+    if "state" in r["fields"]:
+        # in/out: asked back without being handed over, they start as the library's defaults would; cross and cov need the
+        # estimator's xhat (without it the first step initialises the filter on the device and nothing is staged)
+        bias = np.zeros((B, 6)) if bias is None else bias
+        if estimator.get("xhat") is not None:
+            pb = np.repeat(r["p0"] ** 2, 3)
+            if cross is None:
+                # the pieces in measured coordinates the library forms when no cross is handed (ft_mpc_amd.biases.prior): the
+                # estimator's covariance gains p0^2 on its velocity and rate diagonals and is handed over as P_mm
+                covx = next((a for a in ekeep if a.shape == (B, NP)), None)
+                if covx is None:
+                    covx = np.zeros((B, NP))
+                    covx[:, np.cumsum([0] + [12 - i for i in range(11)])] = np.repeat(np.array(list(es.p0)) ** 2, 3)[None, :]
+                    keep.append(covx)
+                    es.cov = _ptr(covx)
+                tri = np.cumsum([0] + [12 - i for i in range(11)])
+                covx[:, tri[3:6]] += pb[None, 0:3]
+                covx[:, tri[9:12]] += pb[None, 3:6]
+                cross = np.zeros((B, 12, 6))
+                cross[:, np.arange(3, 6), np.arange(0, 3)] = pb[None, 0:3]
+                cross[:, np.arange(9, 12), np.arange(3, 6)] = pb[None, 3:6]
+                cross = cross.reshape(B, NC)
+            if cov is None:
+                cov = np.zeros((B, NDD))
+                cov[:, np.cumsum([0, 6, 5, 4, 3, 2])] = pb[None, :]
+        elif cross is not None or cov is not None:
+            raise ValueError("bias_estimate['cross'] requires estimator['xhat']")
+        out["bias"] = bias
+        if cross is not None:
+            out["cross"], out["cov"] = cross, cov
+    keep += [bias, cross, cov]
+    be.bias, be.cross, be.cov = _ptr(bias), _ptr(cross), _ptr(cov)
+    if "bias_hist" in r["fields"]:
+        out["bias_hist"] = np.zeros((T, B, 6))
+        be.bias_hist = _ptr(out["bias_hist"])
+    return be, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -1029,6 +1087,10 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     dg, dkeep, dout = _diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor) if diagnosis is not None else (None, None, None)
     db, bkeep, bout = (_disturbance_request(disturbance, B, T, estimator, sqp_iters, formulation) if disturbance is not None
                        else (None, None, None))
+    if bias_estimate is not None and multi and formulation == "wrench":
+        raise ValueError("bias_estimate: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
+    be, bekeep, beout = (_bias_request(bias_estimate, B, T, estimator, disturbance, es, ekeep) if bias_estimate is not None
+                         else (None, None, None))
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -1078,7 +1140,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
            or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
-           or db is not None)
+           or db is not None or be is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1103,6 +1165,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["diagnosis"] = dout
         if bout is not None:
             out["disturbance"] = bout
+        if beout is not None:
+            out["bias_estimate"] = beout
         return out
     msp = C.byref(ms) if ms is not None else None
     pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
@@ -1122,6 +1186,15 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                 if hb.shape != (B, int(hull["rows"])) or not np.isfinite(hb).all():
                     raise ValueError(f"diagnosis['hull_b'] must be finite with shape {(B, int(hull['rows']))}")
             dout["hull_b"], dout["no_hull"] = np.empty((B, int(hull["rows"]))), d_nh
+        if be is not None:      # (with or without a diagnosis; a disturbance in the same call has been refused)
+            self._check(self.lib.ftmpc_simulate_wrench_bias_batch(
+                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
+                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
+                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
+                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+                C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None,
+                _ptr(dout["hull_b"]) if dg is not None else None, _ptr(d_nh, C.c_int32) if dg is not None else None, None, C.byref(be)))
+            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
         if db is not None:      # (disturbance['wrench'] = True; with or without a diagnosis)
             self._check(getattr(self.lib, pre + "wrench_disturbance_batch")(
                 self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
@@ -1197,6 +1270,13 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                                                          _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
                                                          C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
         return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
+    if be is not None:
+        self._check(getattr(self.lib, pre + "bias_batch")(
+            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
+            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
+            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
+            C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None, None, C.byref(be)))
+        return result(dict(x=x, u=uh, not_converged=bad))
     if db is not None:
         self._check(getattr(self.lib, pre + "disturbance_batch")(
             self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),

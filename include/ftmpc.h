@@ -1024,6 +1024,76 @@ int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t 
                                             const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                             int32_t* no_hull_step, const ftmpc_disturbance* disturbance);
 
+/* On-device estimation of the velocity and rate sensor bias.  The filter of ftmpc_estimator is augmented by six states per vehicle:
+ * b_v^ [3], a constant bias of the velocity measurement (m/s), and b_w^ [3], a constant bias of the rate measurement (rad/s): the
+ * channels 3..5 and 9..11 of ftmpc_sensor.bias.  Position tells the filter what the velocity is and attitude what the rate is, so both
+ * are observable from the kinematics alone; a constant position or attitude bias is not, and stays in the estimate.  The parameters
+ * are uniform over the call; the state and the outputs are per vehicle.
+ *   the filter (its definition): error coordinates (dp, dv, dtheta, dw, db_v, db_w), 18 in all;  y_v = v + b_v + n, y_w = w + b_w + n,
+ *     H = [I_12, HB], HB [12 x 6] with HB[3+r, r] = HB[9+r, 3+r] = 1;  Phi = diag(Phi_xx, I_6) with the estimator's Phi_xx, the mean
+ *     takes the estimator's RK4 step and b^ stays;  Q = diag(estimator.proc_sigma[g]^2, proc_sigma[0]^2 x 3, proc_sigma[1]^2 x 3), the
+ *     initial covariance likewise with p0;  the residual is the estimator's y [-] x~ with x~ = x^ with v^ + b_v^ and w^ + b_w^;  the
+ *     update is the estimator's twelve sequential scalar updates in channel order, each over all 18 coordinates with row h_j of H.
+ *   the form the device runs (exactly equivalent) and the arrays of this struct carry: the MEASURED coordinates
+ *     m = (dp, dv + db_v, dtheta, dw + db_w) with b unchanged, P^m = T P T', T = [[I, HB], [0, I]].  There H = [I 0];
+ *     Phi^m = [[Phi_xx, E], [0, I]] with E = (I - Phi_xx) HB, non-zero in (p, b_v) = -dt I, (theta, b_w) = -dt I, (w, b_w) = I - W;
+ *     Q^m = T Q T' (the v and w diagonals of Q_xx gain proc_sigma[0]^2, proc_sigma[1]^2; Q_xb = HB diag(q_b^2); Q_bb = diag(q_b^2));
+ *     after the twelve updates delta_x = delta_m - HB delta_b, x^ <- (x^ [+] delta_m) with HB delta_b taken off v^ and w^,
+ *     b^ += delta_b.  The covariance travels in three pieces: P_mm = ftmpc_estimator.cov (78 packed), P_mb = cross (12 x 6, row-major,
+ *     72) and P_bb = cov (packed upper triangle, row-major, 21), so that a continued run rounds nowhere on the way out or in.
+ *   priors: with cross handed, ftmpc_estimator.cov (diag(estimator.p0[g]^2) when NULL) is P_mm as it stands and cov, when NULL, is
+ *     diag(p0[0]^2 x 3, p0[1]^2 x 3).  Without cross the bias prior is independent of the state error: ftmpc_estimator.cov (or
+ *     diag(estimator.p0[g]^2)) is the covariance of (dp, dv, dtheta, dw) itself, P_bb = diag(p0^2), and the pieces are T P T':
+ *     the v and w diagonals of P_mm gain p0[0]^2 and p0[1]^2, P_mb = HB diag(p0^2).  On return ftmpc_estimator.cov is P_mm.
+ *   per loop step: as ftmpc_simulate_diagnosis_batch with ftmpc_filter_bias_kernel<0>, <1> in place of ftmpc_filter_kernel<0> and
+ *     <2>, <3> in place of <1>.  On the first step of a call that was not handed xhat: x^ = y_t with b^ (the handed values or 0) taken
+ *     off its velocity and rate, no update.  est_hist[t] = x^_{t|t}, bias_hist[t] = b^_{t|t}; err_sq as the estimator's; when the
+ *     sensor predicts, x^_{t|t} is propagated over the queued commands with the plain model (the bias does not enter the dynamics).
+ *     The estimate reaches the solve through x0 alone, so sqp_iters >= 0 is served on both forms.  The diagnosis kernels are
+ *     untouched: they read the raw y_t, and a constant bias cancels in their re-anchored residual.
+ * A handed bias / cross / cov are the priors of the call's first step; on return they hold the priors of step T, so that a continued
+ * run (with the estimator's xhat / cov, the sensor's pending / step0 and the diagnosis' carry-over) is the whole run bit for bit.
+ * Not served: a position or attitude bias, the bias states together with the disturbance states (24 states), per-vehicle filter
+ * parameters, ftmpc_multi_upload / _step.
+ * FTMPC_ERR_ARG, the message naming ftmpc_bias_estimate.<field> and, for an array, the first offending vehicle, the call's x
+ * untouched: a struct_size other than sizeof(ftmpc_bias_estimate); no estimator; a non-NULL disturbance in the same call; a p0 or
+ * proc_sigma negative or not finite; cross without bias or the estimator's xhat; cov without cross; a bias, cross or cov entry not
+ * finite; a diagonal entry of cov below zero.
+ */
+typedef struct ftmpc_bias_estimate {
+    int32_t struct_size;   /* sizeof(ftmpc_bias_estimate) */
+    int32_t reserved;      /* 0 */
+    double p0[2];          /* initial standard deviations: velocity bias (m/s), rate bias (rad/s), >= 0 */
+    double proc_sigma[2];  /* per step, >= 0 */
+    double* bias;          /* NULL (start at 0) or [B*6] in/out: b_v^, b_w^ */
+    double* cross;         /* NULL or [B*72] in/out; requires bias and estimator->xhat */
+    double* cov;           /* NULL or [B*21] in/out; requires cross */
+    double* bias_hist;     /* NULL or [T*B*6] out: b^_{t|t} */
+} ftmpc_bias_estimate;
+
+/* ftmpc_simulate_disturbance_batch with the bias estimate `bias_estimate` (NULL: exactly ftmpc_simulate_disturbance_batch, which IS
+ * this entry with NULL). */
+int ftmpc_simulate_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                              const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                              int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                              double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                              const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                              const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                              const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate);
+
+/* The bias estimate on the two-stage wrench form: ftmpc_simulate_wrench_disturbance_batch with `bias_estimate` (NULL: exactly that
+ * entry's kernels and bits).  The filter works on the applied thruster commands, so it is the thruster form's. */
+int ftmpc_simulate_wrench_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                     int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                     uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                     const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                     int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                     const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                     int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                     const ftmpc_bias_estimate* bias_estimate);
+
 /* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
  * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
  * after G / warmG; the rollout of the cost and of the linearisation sees tau + t^ at every RK4 stage and f^ / m added to the inertial
@@ -1306,6 +1376,18 @@ int ftmpc_multi_simulate_wrench_disturbance_batch(ftmpc_multi* m, int64_t B, int
                                                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                   const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                                   int32_t* no_hull_step, const ftmpc_disturbance* disturbance);
+/* ftmpc_multi_simulate_disturbance_batch with the bias estimate `bias_estimate` (ftmpc_bias_estimate; NULL: exactly that entry).
+ * The struct is checked once over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; bias + 6 lo,
+ * cross + 72 lo and cov + 21 lo are read and written per shard, bias_hist is copied row by row from the shard's staging.  The
+ * two-stage wrench form has no multi-GPU bias entry; ftmpc_multi_upload / _step take no bias estimate. */
+int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                    const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                    int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                    double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                    const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                    const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                    const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                    const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
