@@ -124,6 +124,17 @@ __global__ void __launch_bounds__(64) ftmpc_allocate_kernel(const DeviceConsts C
         tau[g] = P.tau[b * 6 + g];
         tmax = fmax(tmax, fabs(tau[g]));
     }
+    // a tau that is not finite (the wrench of a vehicle that has diverged) has no allocation: tmax, the residual and the multiplier norm
+    // below are fmax reductions, which drop a NaN -- with all six entries NaN the residual read 0 and the lane reported "solved"
+    bool tfin = true;
+#pragma unroll
+    for (int g = 0; g < 6; ++g) tfin = tfin && fabs(tau[g]) <= 1.7976931348623157e308;
+    if (!tfin) {
+        for (int i = 0; i < NT; ++i) P.out_u[b * NT + i] = 0.0;
+        if (P.status) P.status[b] = 2;
+        if (P.iters) P.iters[b] = 0;
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < MAX_NT; ++i) ubv[i] = (i < NT) ? P.ub[b * NT + i] : 0.0;
     // start: unconstrained least-norm multiplier (D D') lambda = tau over the healthy thrusters

@@ -175,4 +175,9 @@ struct SolveParams {
     float* dbg_vec;         // [484]: g | lo | hi at stride npad, [480] = n, [481] = npad
 };
 
+// FTMPC_STATUS_NUMERIC returns the linearisation point.  In the generalized-force form that point is D stuck (cold), which is not
+// finite itself where a stuck entry is not: such an entry of G / tau_0 is returned as 0 (the thruster form's clip does the same to a
+// NaN of its warm start), so that every output of a failed instance is finite.  Applied to failed instances only.
+__device__ __forceinline__ double finite_or_zero(double x) { return (fabs(x) <= 1.7976931348623157e308) ? x : 0.0; }
+
 }  // namespace ftmpc

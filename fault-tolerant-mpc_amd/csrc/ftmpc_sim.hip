@@ -259,7 +259,7 @@ __global__ void ftmpc_sqpw_init_kernel(const DeviceConsts C, const SqpState S, c
             const int g = (int)(i % 6);
             double t = 0.0;
             for (int k = 0; k < C.NT; ++k) t += C.D[g * MAX_NT + k] * stuck[b * C.NT + k];
-            S.U[i] = t;
+            S.U[i] = finite_or_zero(t);      // (a NaN stuck entry: the vehicle's first QP fails and this point is what comes back)
         }
     }
     if (i < S.B) {
@@ -311,6 +311,8 @@ __global__ void __launch_bounds__(64) ftmpc_sqpw_tau0_kernel(const DeviceConsts 
     hull_centre(C, ub + b * C.NT, stuck + b * C.NT, ctr);
     const int64_t set = hull_set ? hull_set[b] : 0;
     (void)hull_pull(t, ctr, hullA + set * hull_rows * 6, hullb + b * hull_rows, hull_rows, tau0 + b * 6);
+    // (a finite iterate and a finite centre give a finite tau_0: only a vehicle whose stuck entries are not finite has anything replaced)
+    for (int g = 0; g < 6; ++g) tau0[b * 6 + g] = finite_or_zero(tau0[b * 6 + g]);
 }
 
 // close the line search: Ut = U + alpha (Uq - U) where a trial point was accepted (the point ftmpc_cost_wrench_kernel evaluated), else U

@@ -1591,8 +1591,9 @@ __global__ void __launch_bounds__(f64k::WG, (SWEEP_ROWS == 4 && MODE == 0) ? 2 :
                     eps = fmin(wg_max(eps, red, tid), 1.0);
                 }
                 if (val) {
-                    const double tau = (status == 2) ? ubar0 : ubar0 + d;
-                    if (ek == 0) Q.out_tau0[inst * 6 + ea] = s_ctr[ea] + (1.0 - eps) * (tau - s_ctr[ea]);
+                    const double tau = (status == 2) ? finite_or_zero(ubar0) : ubar0 + d;
+                    const double t0 = s_ctr[ea] + (1.0 - eps) * (tau - s_ctr[ea]);
+                    if (ek == 0) Q.out_tau0[inst * 6 + ea] = (status == 2) ? finite_or_zero(t0) : t0;
                     if (Q.out_G) Q.out_G[(inst * N + ek) * 6 + ea] = tau;
                 }
             } else {

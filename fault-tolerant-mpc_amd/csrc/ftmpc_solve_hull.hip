@@ -1205,7 +1205,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
         for (int v = 0; v < NVW; ++v) {
             const int e = v * 64 + lane;
             if (e < n) {
-                const double tau = (status == 2) ? (double)ubar[v] : (double)ubar[v] + (double)d[v];
+                const double tau = (status == 2) ? finite_or_zero((double)ubar[v]) : (double)ubar[v] + (double)d[v];
                 if (e < 6) xv64[e] = tau;
                 if (Q.out_G) Q.out_G[inst * n + e] = tau;
             }
@@ -1230,7 +1230,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
                 eps = (st < 1e-8 * s0 && s0 > st) ? (float)need * 1.0001f : 0.f;
             }
             eps = wave_max(eps);
-            if (lane < 6) Q.out_tau0[inst * 6 + lane] = s_ctr64[lane] + (1.0 - (double)eps) * (xv64[lane] - s_ctr64[lane]);
+            if (lane < 6) {
+                const double t0 = s_ctr64[lane] + (1.0 - (double)eps) * (xv64[lane] - s_ctr64[lane]);
+                Q.out_tau0[inst * 6 + lane] = (status == 2) ? finite_or_zero(t0) : t0;
+            }
         }
         if (lane == 0) {
             if (P.status) P.status[inst] = status;

@@ -1030,7 +1030,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
         wave_lds_fence();
         for (int v = 0; v < nv; ++v) {
             const double dd = (status == 2) ? 0.0 : ((!SB && status == 0 && !verified) ? vref(V_D0, v) : vref(V_D, v));
-            const double tau = tbar_of(v) + dd;
+            double tau = tbar_of(v) + dd;
+            if (status == 2) tau = finite_or_zero(tau);
             if (4 * v + lq < NS) rvec[(4 * v + lq) * 16 + li] = wvalid(v) ? tau : 0.0;
             if (wvalid(v) && Q.out_G) Q.out_G[(inst * N + 4 * v + lq) * 6 + li] = tau;
         }
@@ -1053,7 +1054,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FTMPC_R
                 }
             }
             eps = fmin(wave_red<DMax>(eps), 1.0);
-            if (lane < 6) Q.out_tau0[inst * 6 + lane] = s_ctr[lane] + (1.0 - eps) * (rvec[lane] - s_ctr[lane]);
+            if (lane < 6) {
+                const double t0 = s_ctr[lane] + (1.0 - eps) * (rvec[lane] - s_ctr[lane]);
+                Q.out_tau0[inst * 6 + lane] = (status == 2) ? finite_or_zero(t0) : t0;
+            }
         }
         if (lane == 0) {
             if (P.status) P.status[inst] = status;

@@ -50,6 +50,35 @@ extern "C" {
 #define FTMPC_STATUS_NO_HULL 3     /* generalized-force formulation only: the healthy thrusters do not span R^6, the input hull
                                       is flat (the reference's Qhull call fails on such fault sets); set by the host front-end */
 
+/*
+ * A NON-FINITE VEHICLE (a NaN or Inf in its x0 or in a stuck entry of a broken thruster: a vehicle of a fault campaign that has
+ * diverged).  The solve entries do not validate x0 / stuck; such an instance is answered per instance and touches nothing else: every
+ * output of every other instance of the batch, and of every later call on the handle, has the bits it has without it
+ * (tests/test_gpu_poisoned_instances.py).  What comes back for the instance itself:
+ *   ftmpc_solve_batch          status FTMPC_STATUS_NUMERIC, iters >= 0; out_U = the linearisation point clip(warm start, 0, ub)
+ *                              (zeros on a cold start and on broken thrusters; the fp32 kernels return it rounded to float32), out_u0
+ *                              its first stage.  Always finite and inside [0, ub].
+ *   ftmpc_solve_wrench_batch   status FTMPC_STATUS_NUMERIC; out_G = the linearisation point (warmG; D stuck on a cold start), out_tau0
+ *                              its first stage pulled into the hull as for a solved instance, out_u0 the allocation of
+ *                              out_tau0 - D stuck with its own alloc_status (0 on a cold start: the point needs no thrust; 2 where a
+ *                              stuck entry is not finite, with out_u0 = 0).  An entry of that point that is not finite itself (D stuck
+ *                              of a NaN stuck entry; out_tau0 without a finite hull centre) is returned as 0: every output is finite,
+ *                              out_u0 inside [0, ub].
+ *   ftmpc_solve_sqp_batch / ftmpc_solve_sqp_wrench_batch   the first QP ends with FTMPC_STATUS_NUMERIC, so no line search opens:
+ *                              status 2, out_sqp_iters 0, the start point as out_U / out_G (as above), out_cost = out_cost0 = the
+ *                              cost there, which is NaN or +Inf (the wrench cost does not read stuck: finite for a NaN stuck entry).
+ *   ftmpc_eval_cost_batch / ftmpc_eval_cost_wrench_batch   out_cost NaN or +Inf, never a finite number; out_tviol sums max(0, .), which
+ *                              drops a NaN row: it is >= 0 and never NaN (+Inf for an infinite error).
+ *   ftmpc_allocate_batch       (a NaN or Inf in tau) status 2, iters 0, out_u = 0.
+ *   the closed loops           the vehicle counts in not_converged[t] and in the outcome `unsolved` at every step, status_hist shows
+ *                              its status 2; its own state, command history and error outcomes are not meaningful.
+ * A state that is huge but finite in the handle's arithmetic (1e30 on an fp32 handle, 1e200 in float64) is an ordinary instance: it
+ * ends with one of the three status values and finite outputs inside their bounds, status 0 only with the solution (at those two
+ * magnitudes, where intermediate products overflow, no kernel answers 0: FTMPC_STATUS_NUMERIC, on a long horizon of the two-stage
+ * form FTMPC_STATUS_MAXITER).
+ * Not covered: a non-finite warm start, reference, ub, or hull table.
+ */
+
 /* arithmetic of the solve path */
 #define FTMPC_DTYPE_F32 0
 #define FTMPC_DTYPE_F64 1
