@@ -2175,775 +2175,6 @@ int ftmpc_debug_struct_grad(ftmpc_handle* h, int64_t B, const double* x0, const 
     return FTMPC_OK;
 }
 
-int ftmpc_simulate_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                         double* u_hist, int32_t* not_converged) {
-    return ftmpc_simulate_batch_ex(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, 0, 0, 0.0, u_hist, not_converged);
-}
-
-struct WrenchLoop {      // the two-stage structure inside the closed loop: hull tables staged once, constant over the run
-    int32_t hull_rows;
-    bool has_set;
-    int32_t* alloc_failed;   // host [T] or null
-    double penalty;          // the wrench SQP's merit weight (sqp_iters > 0)
-    double* out_hull_b;      // host [B*hull_rows] or null: the controller's offsets after the last step
-    int32_t* no_hull_step;   // host [B] or null, in/out (under a diagnosis): the step of the first detection that left no hull
-};
-
-static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
-                         const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs = nullptr,
-                         double* x_hist = nullptr, const ftmpc_outcomes* oc = nullptr, const ftmpc_plant_model* pm = nullptr,
-                         const ftmpc_mission* ms = nullptr, const ftmpc_actuator* ac = nullptr, const ftmpc_sensor* se = nullptr,
-                         const ftmpc_estimator* es = nullptr, const ftmpc_diagnosis* dg = nullptr, const ftmpc_disturbance* db = nullptr,
-                         const ftmpc_bias_estimate* be = nullptr);
-
-// A plant model's layout and values (include/ftmpc.h, ftmpc_plant_model) over the vehicles [0, B): empty when it is acceptable, else the
-// message, which names the field and the first offending vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string plant_model_problem(const ftmpc_plant_model* pm, int64_t B, int NT, int64_t first = 0) {
-    if (!pm) return "";
-    if (pm->struct_size != (int32_t)sizeof(ftmpc_plant_model))
-        return "ftmpc_plant_model.struct_size is " + std::to_string(pm->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_plant_model));
-    auto at = [first](const char* field, int64_t b, const std::string& what) {
-        return std::string("ftmpc_plant_model.") + field + ": vehicle " + std::to_string(first + b) + " " + what;
-    };
-    if (pm->mass)
-        for (int64_t b = 0; b < B; ++b)
-            if (!std::isfinite(pm->mass[b]) || !(pm->mass[b] > 0.0)) return at("mass", b, "is not finite and positive");
-    if (pm->J)
-        for (int64_t b = 0; b < B; ++b) {
-            const double* J = pm->J + b * 9;
-            double big = 0.0;
-            for (int k = 0; k < 9; ++k) {
-                if (!std::isfinite(J[k])) return at("J", b, "has a non-finite entry");
-                big = std::max(big, std::fabs(J[k]));
-            }
-            for (int i = 0; i < 3; ++i)
-                for (int j = i + 1; j < 3; ++j)
-                    if (std::fabs(J[3 * i + j] - J[3 * j + i]) > 1e-12 * big) return at("J", b, "is not symmetric");
-            const double m2 = J[0] * J[4] - J[1] * J[3];
-            const double m3 = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
-            if (!(J[0] > 0.0) || !(m2 > 0.0) || !(m3 > 0.0)) return at("J", b, "is not positive definite");
-        }
-    const double* const arr[3] = {pm->D, pm->force, pm->torque};
-    const char* const name[3] = {"D", "force", "torque"};
-    const int64_t per[3] = {6 * (int64_t)NT, 3, 3};
-    for (int a = 0; a < 3; ++a)
-        if (arr[a])
-            for (int64_t i = 0; i < B * per[a]; ++i)
-                if (!std::isfinite(arr[a][i])) return at(name[a], i / per[a], "has a non-finite entry");
-    return "";
-}
-static int check_plant(ftmpc_handle* h, int64_t B, const ftmpc_plant_model* pm) {
-    const std::string msg = plant_model_problem(pm, B, h->cfg.NT);
-    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
-}
-
-// A mission's layout and values (include/ftmpc.h, ftmpc_mission) over the vehicles [0, B) of a loop of T steps with horizon N, together
-// with the call's own xref_traj / uref_traj: empty when acceptable, else the message, which names the field and, where there is one,
-// the first offending vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string mission_problem(const ftmpc_mission* ms, int64_t B, int32_t T, int N, const double* xref_traj, const double* uref_traj,
-                                   int64_t first = 0, int L = 0) {
-    if (!ms) return xref_traj ? "" : "null buffer or negative size";
-    if (ms->struct_size != (int32_t)sizeof(ftmpc_mission))
-        return "ftmpc_mission.struct_size is " + std::to_string(ms->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_mission));
-    if (ms->n_tables < 0) return "ftmpc_mission.n_tables is negative";
-    if (ms->n_tables == 0) {
-        if (!xref_traj) return "ftmpc_mission.n_tables = 0: every vehicle tracks the call's xref_traj, which is NULL";
-        if (ms->table) return "ftmpc_mission.table is given, but n_tables = 0 (no table to choose from)";
-        if (ms->offset) return "ftmpc_mission.offset is given, but n_tables = 0 (the call's xref_traj has no start column)";
-        return "";
-    }
-    // (L: the columns a predicting sensor shifts every window by, ftmpc_sensor)
-    const int64_t K = ms->n_tables, C = ms->n_cols, need = (int64_t)T + N + L;
-    const std::string sum = L > 0 ? "T + N + L = " : "T + N = ";
-    if (!ms->xref) return "ftmpc_mission.xref is NULL with n_tables = " + std::to_string(K);
-    if (C < need)
-        return "ftmpc_mission.n_cols = " + std::to_string(C) + " is below " + sum + std::to_string(need);
-    if (xref_traj) return "ftmpc_mission.n_tables > 0: the call's xref_traj must be NULL (the tables are the reference)";
-    if (uref_traj) return "ftmpc_mission.n_tables > 0: the call's uref_traj must be NULL (ftmpc_mission.uref holds the tables' uref)";
-    auto at = [first](const char* field, int64_t b, const std::string& what) {
-        return std::string("ftmpc_mission.") + field + ": vehicle " + std::to_string(first + b) + " " + what;
-    };
-    if (ms->table)
-        for (int64_t b = 0; b < B; ++b)
-            if (ms->table[b] < 0 || ms->table[b] >= K)
-                return at("table", b, "has table " + std::to_string(ms->table[b]) + ", outside [0, " + std::to_string(K) + ")");
-    if (ms->offset)
-        for (int64_t b = 0; b < B; ++b) {
-            if (ms->offset[b] < 0) return at("offset", b, "has a negative start column");
-            if ((int64_t)ms->offset[b] + need > C)
-                return at("offset", b, "has offset + " + sum + std::to_string((int64_t)ms->offset[b] + need) + " beyond n_cols = " +
-                                           std::to_string(C));
-        }
-    const double* const arr[2] = {ms->xref, ms->uref};
-    const char* const name[2] = {"xref", "uref"};
-    const int64_t rows[2] = {9, 6};
-    for (int a = 0; a < 2; ++a)
-        if (arr[a])
-            for (int64_t i = 0; i < K * rows[a] * C; ++i)
-                if (!std::isfinite(arr[a][i]))
-                    return std::string("ftmpc_mission.") + name[a] + ": table " + std::to_string(i / (rows[a] * C)) +
-                           " has a non-finite entry in column " + std::to_string(i % (rows[a] * C) / rows[a]);
-    return "";
-}
-static int check_mission(ftmpc_handle* h, int64_t B, int32_t T, const ftmpc_mission* ms, const double* xref_traj, const double* uref_traj,
-                         int L = 0) {
-    const std::string msg = mission_problem(ms, B, T, h->cfg.N, xref_traj, uref_traj, 0, L);
-    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
-}
-// cost of a loop without steps: zero
-static void zero_mission_cost(const ftmpc_mission* ms, int64_t B) {
-    if (ms && ms->cost && B > 0) std::fill(ms->cost, ms->cost + 3 * B, 0.0);
-}
-
-// An actuator's layout and values (include/ftmpc.h, ftmpc_actuator) over the vehicles [0, B): empty when acceptable, else the message,
-// which names the field and, where there is one, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string actuator_problem(const ftmpc_actuator* ac, int64_t B, int NT, int64_t first = 0) {
-    if (!ac) return "";
-    if (ac->struct_size != (int32_t)sizeof(ftmpc_actuator))
-        return "ftmpc_actuator.struct_size is " + std::to_string(ac->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_actuator));
-    if (ac->mode != 0 && ac->mode != 1) return "ftmpc_actuator.mode is " + std::to_string(ac->mode) + ", outside {0, 1}";
-    if (ac->substeps < 0 || ac->substeps > 64) return "ftmpc_actuator.substeps is " + std::to_string(ac->substeps) + ", outside [0, 64]";
-    const int S = ac->substeps > 0 ? ac->substeps : 1;
-    if (ac->min_on < 0 || ac->min_on > S)
-        return "ftmpc_actuator.min_on is " + std::to_string(ac->min_on) + ", outside [0, S = " + std::to_string(S) + "]";
-    if (ac->align < 0 || ac->align > 2) return "ftmpc_actuator.align is " + std::to_string(ac->align) + ", outside {0, 1, 2}";
-    if (!std::isfinite(ac->tau_on) || ac->tau_on < 0) return "ftmpc_actuator.tau_on is negative or not finite";
-    if (!std::isfinite(ac->tau_off) || ac->tau_off < 0) return "ftmpc_actuator.tau_off is negative or not finite";
-    if (ac->mode == 0) {
-        if (ac->min_on != 0) return "ftmpc_actuator.min_on is given, but mode = 0 (a proportional valve has no dead band)";
-        if (ac->align != 0) return "ftmpc_actuator.align is given, but mode = 0 (a proportional valve has no pulse to align)";
-        if (ac->pulses) return "ftmpc_actuator.pulses is given, but mode = 0 (a proportional valve has no pulses)";
-        if (ac->ticks_hist) return "ftmpc_actuator.ticks_hist is given, but mode = 0 (a proportional valve has no ticks)";
-    }
-    if (ac->state)
-        for (int64_t i = 0; i < B * NT; ++i)
-            if (!std::isfinite(ac->state[i]) || ac->state[i] < 0)
-                return "ftmpc_actuator.state: vehicle " + std::to_string(first + i / NT) + " has a negative or non-finite valve state (thruster " +
-                       std::to_string(i % NT) + ")";
-    return "";
-}
-static int check_actuator(ftmpc_handle* h, int64_t B, const ftmpc_actuator* ac) {
-    const std::string msg = actuator_problem(ac, B, h->cfg.NT);
-    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
-}
-// trivial: the loop launches the plant kernels it launches without the struct
-static bool actuator_trivial(const ftmpc_actuator* ac) {
-    return !ac || (ac->mode == 0 && ac->substeps <= 1 && ac->tau_on == 0 && ac->tau_off == 0 && !ac->delivered && !ac->pulses &&
-                   !ac->applied_hist && !ac->ticks_hist && !ac->state);
-}
-// the sums of a loop without steps: zero (the valve states stay as they are)
-static void zero_actuator_sums(const ftmpc_actuator* ac, int64_t B) {
-    if (ac && ac->delivered && B > 0) std::fill(ac->delivered, ac->delivered + B, 0.0);
-    if (ac && ac->pulses && B > 0) std::fill(ac->pulses, ac->pulses + B, 0);
-}
-
-// A sensor's layout and values (include/ftmpc.h, ftmpc_sensor) over the vehicles [0, B): empty when acceptable, else the message, which
-// names the field and, for an array, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string sensor_problem(const ftmpc_sensor* se, int64_t B, int NT, int64_t first = 0) {
-    if (!se) return "";
-    if (se->struct_size != (int32_t)sizeof(ftmpc_sensor))
-        return "ftmpc_sensor.struct_size is " + std::to_string(se->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_sensor));
-    if (se->latency < 0 || se->latency > FTMPC_MAX_LATENCY)
-        return "ftmpc_sensor.latency is " + std::to_string(se->latency) + ", outside [0, " + std::to_string(FTMPC_MAX_LATENCY) + "]";
-    if (se->predict != 0 && se->predict != 1) return "ftmpc_sensor.predict is " + std::to_string(se->predict) + ", outside {0, 1}";
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(se->sigma[k]) || se->sigma[k] < 0)
-            return "ftmpc_sensor.sigma[" + std::to_string(k) + "] is negative or not finite";
-    if (se->step0 < 0) return "ftmpc_sensor.step0 is negative";
-    if (se->pending && se->latency == 0) return "ftmpc_sensor.pending is given, but latency = 0 (no command waits)";
-    if (se->pred_hist && se->predict == 0) return "ftmpc_sensor.pred_hist is given, but predict = 0 (nothing is predicted)";
-    if (se->bias)
-        for (int64_t i = 0; i < B * 12; ++i)
-            if (!std::isfinite(se->bias[i]))
-                return "ftmpc_sensor.bias: vehicle " + std::to_string(first + i / 12) + " has a non-finite entry (channel " +
-                       std::to_string(i % 12) + ")";
-    if (se->pending) {
-        const int64_t per = (int64_t)se->latency * NT;
-        for (int64_t i = 0; i < B * per; ++i)
-            if (!std::isfinite(se->pending[i]))
-                return "ftmpc_sensor.pending: vehicle " + std::to_string(first + i / per) + " has a non-finite entry (row " +
-                       std::to_string(i % per / NT) + ")";
-    }
-    return "";
-}
-static int check_sensor(ftmpc_handle* h, int64_t B, const ftmpc_sensor* se) {
-    const std::string msg = sensor_problem(se, B, h->cfg.NT);
-    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
-}
-// trivial: the loop launches the kernels it launches without the struct
-static bool sensor_trivial(const ftmpc_sensor* se) {
-    return !se || (se->latency == 0 && se->predict == 0 && se->sigma[0] == 0 && se->sigma[1] == 0 && se->sigma[2] == 0 && se->sigma[3] == 0 &&
-                   !se->bias && !se->pending && !se->meas_hist && !se->pred_hist);
-}
-// columns a predicting sensor shifts every reference window by (0 for a struct that would be refused)
-static int sensor_shift(const ftmpc_sensor* se) {
-    return se && se->predict == 1 && se->latency > 0 && se->latency <= FTMPC_MAX_LATENCY ? se->latency : 0;
-}
-
-// An estimator's layout and values (include/ftmpc.h, ftmpc_estimator) over the vehicles [0, B): empty when acceptable, else the
-// message, which names the field and, for an array, the first offending vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string estimator_problem(const ftmpc_estimator* es, int64_t B, int64_t first = 0) {
-    if (!es) return "";
-    if (es->struct_size != (int32_t)sizeof(ftmpc_estimator))
-        return "ftmpc_estimator.struct_size is " + std::to_string(es->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_estimator));
-    if (es->every < 1) return "ftmpc_estimator.every is " + std::to_string(es->every) + ", below 1";
-    for (int k = 0; k < 4; ++k) {
-        if (!std::isfinite(es->p0[k]) || es->p0[k] < 0) return "ftmpc_estimator.p0[" + std::to_string(k) + "] is negative or not finite";
-        if (!std::isfinite(es->proc_sigma[k]) || es->proc_sigma[k] < 0)
-            return "ftmpc_estimator.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
-        if (!std::isfinite(es->meas_sigma[k]) || !(es->meas_sigma[k] > 0))
-            return "ftmpc_estimator.meas_sigma[" + std::to_string(k) + "] is not finite and > 0";
-    }
-    if (es->cov && !es->xhat) return "ftmpc_estimator.cov is given without xhat";
-    if (es->xhat)
-        for (int64_t i = 0; i < B * 13; ++i)
-            if (!std::isfinite(es->xhat[i]))
-                return "ftmpc_estimator.xhat: vehicle " + std::to_string(first + i / 13) + " has a non-finite entry (" + std::to_string(i % 13) + ")";
-    if (es->cov)
-        for (int64_t b = 0; b < B; ++b) {
-            const double* c = es->cov + b * 78;
-            for (int k = 0; k < 78; ++k)
-                if (!std::isfinite(c[k]))
-                    return "ftmpc_estimator.cov: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
-            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i)
-                if (c[k] < 0)
-                    return "ftmpc_estimator.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
-        }
-    return "";
-}
-// A disturbance estimate's layout and values (include/ftmpc.h, ftmpc_disturbance) over the vehicles [0, B), against the estimator and
-// the SQP count: empty when acceptable, else the message
-static std::string disturbance_problem(const ftmpc_disturbance* db, int64_t B, const ftmpc_estimator* es, int32_t sqp_iters, int64_t first = 0) {
-    if (!db) return "";
-    if (db->struct_size != (int32_t)sizeof(ftmpc_disturbance))
-        return "ftmpc_disturbance.struct_size is " + std::to_string(db->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_disturbance));
-    if (!es) return "ftmpc_disturbance needs an estimator (ftmpc_estimator): the disturbance states augment its filter";
-    if (sqp_iters > 0) return "ftmpc_disturbance: sqp_iters must be 0 (the cost kernels of the SQP do not know the estimate)";
-    if (db->compensate != 0 && db->compensate != 1) return "ftmpc_disturbance.compensate is " + std::to_string(db->compensate) + ", outside {0, 1}";
-    for (int k = 0; k < 2; ++k) {
-        if (!std::isfinite(db->p0[k]) || db->p0[k] < 0) return "ftmpc_disturbance.p0[" + std::to_string(k) + "] is negative or not finite";
-        if (!std::isfinite(db->proc_sigma[k]) || db->proc_sigma[k] < 0)
-            return "ftmpc_disturbance.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
-    }
-    if (db->cross && !db->force) return "ftmpc_disturbance.cross is given without force";
-    if (db->cross && !db->torque) return "ftmpc_disturbance.cross is given without torque";
-    if (db->cross && !es->xhat) return "ftmpc_disturbance.cross is given without ftmpc_estimator.xhat";
-    if (db->cov && !db->cross) return "ftmpc_disturbance.cov is given without cross";
-    const double* const arr[4] = {db->force, db->torque, db->cross, db->cov};
-    const char* const name[4] = {"force", "torque", "cross", "cov"};
-    const int64_t width[4] = {3, 3, 72, 21};
-    for (int a = 0; a < 4; ++a)
-        if (arr[a])
-            for (int64_t i = 0; i < B * width[a]; ++i)
-                if (!std::isfinite(arr[a][i]))
-                    return std::string("ftmpc_disturbance.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
-                           " has a non-finite entry (" + std::to_string(i % width[a]) + ")";
-    if (db->cov)
-        for (int64_t b = 0; b < B; ++b)
-            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
-                if (db->cov[b * 21 + k] < 0)
-                    return "ftmpc_disturbance.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
-    return "";
-}
-// A bias estimate's layout and values (include/ftmpc.h, ftmpc_bias_estimate) over the vehicles [0, B), against the estimator and the
-// disturbance estimate of the same call: empty when acceptable, else the message
-static std::string bias_problem(const ftmpc_bias_estimate* be, int64_t B, const ftmpc_estimator* es, const ftmpc_disturbance* db,
-                                int64_t first = 0) {
-    if (!be) return "";
-    if (be->struct_size != (int32_t)sizeof(ftmpc_bias_estimate))
-        return "ftmpc_bias_estimate.struct_size is " + std::to_string(be->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_bias_estimate));
-    if (!es) return "ftmpc_bias_estimate needs an estimator (ftmpc_estimator): the bias states augment its filter";
-    if (db) return "ftmpc_bias_estimate with a disturbance (ftmpc_disturbance) in the same call: 24 filter states are not served";
-    for (int k = 0; k < 2; ++k) {
-        if (!std::isfinite(be->p0[k]) || be->p0[k] < 0) return "ftmpc_bias_estimate.p0[" + std::to_string(k) + "] is negative or not finite";
-        if (!std::isfinite(be->proc_sigma[k]) || be->proc_sigma[k] < 0)
-            return "ftmpc_bias_estimate.proc_sigma[" + std::to_string(k) + "] is negative or not finite";
-    }
-    if (be->cross && !be->bias) return "ftmpc_bias_estimate.cross is given without bias";
-    if (be->cross && !es->xhat) return "ftmpc_bias_estimate.cross is given without ftmpc_estimator.xhat";
-    if (be->cov && !be->cross) return "ftmpc_bias_estimate.cov is given without cross";
-    const double* const arr[3] = {be->bias, be->cross, be->cov};
-    const char* const name[3] = {"bias", "cross", "cov"};
-    const int64_t width[3] = {6, 72, 21};
-    for (int a = 0; a < 3; ++a)
-        if (arr[a])
-            for (int64_t i = 0; i < B * width[a]; ++i)
-                if (!std::isfinite(arr[a][i]))
-                    return std::string("ftmpc_bias_estimate.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
-                           " has a non-finite entry (" + std::to_string(i % width[a]) + ")";
-    if (be->cov)
-        for (int64_t b = 0; b < B; ++b)
-            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
-                if (be->cov[b * 21 + k] < 0)
-                    return "ftmpc_bias_estimate.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
-    return "";
-}
-
-static int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
-    const std::string msg = estimator_problem(es, B);
-    return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
-}
-
-// A diagnosis' layout and values (include/ftmpc.h, ftmpc_diagnosis) over the vehicles [0, B), against the estimator, the schedule and
-// the sensor of the same call: empty when acceptable, else the message, which names the field and, for an array, the first offending
-// vehicle (first: number of vehicle 0 in the caller's batch)
-static std::string diagnosis_problem(const ftmpc_diagnosis* dg, int64_t B, int NT, const ftmpc_estimator* es, const ftmpc_fault_schedule* fs,
-                                     const ftmpc_sensor* se, int64_t first = 0) {
-    if (!dg) return "";
-    if (dg->struct_size != (int32_t)sizeof(ftmpc_diagnosis))
-        return "ftmpc_diagnosis.struct_size is " + std::to_string(dg->struct_size) + ", this library expects " +
-               std::to_string(sizeof(ftmpc_diagnosis));
-    if (dg->every < 1) return "ftmpc_diagnosis.every is " + std::to_string(dg->every) + ", below 1";
-    if (es && es->every != dg->every)
-        return "ftmpc_diagnosis.every is " + std::to_string(dg->every) + ", the estimator's every is " + std::to_string(es->every);
-    if (dg->n_levels < 1 || dg->n_levels > 4) return "ftmpc_diagnosis.n_levels is " + std::to_string(dg->n_levels) + ", outside [1, 4]";
-    if (dg->max_detect < 1 || dg->max_detect > FTMPC_MAX_FAULT_EVENTS)
-        return "ftmpc_diagnosis.max_detect is " + std::to_string(dg->max_detect) + ", outside [1, FTMPC_MAX_FAULT_EVENTS]";
-    for (int l = 0; l < dg->n_levels; ++l)
-        if (!std::isfinite(dg->levels[l]) || dg->levels[l] < 0 || (l > 0 && !(dg->levels[l] > dg->levels[l - 1])))
-            return "ftmpc_diagnosis.levels[" + std::to_string(l) + "] is negative, not finite or not above the level before";
-    for (int k = 0; k < 2; ++k) {
-        if (!std::isfinite(dg->resid_sigma[k]) || !(dg->resid_sigma[k] > 0))
-            return "ftmpc_diagnosis.resid_sigma[" + std::to_string(k) + "] is not finite and > 0";
-        if (!std::isfinite(dg->drift_sigma[k]) || dg->drift_sigma[k] < 0)
-            return "ftmpc_diagnosis.drift_sigma[" + std::to_string(k) + "] is negative or not finite";
-    }
-    if (!std::isfinite(dg->threshold) || !(dg->threshold > 0)) return "ftmpc_diagnosis.threshold is not finite and > 0";
-    if (dg->llr && !dg->state) return "ftmpc_diagnosis.llr is given without state";
-    if (!dg->state && dg->detect_step) return "ftmpc_diagnosis.detect_step is given without state";
-    if (!dg->state && dg->detect_thruster) return "ftmpc_diagnosis.detect_thruster is given without state";
-    if (!dg->state && dg->detect_level) return "ftmpc_diagnosis.detect_level is given without state";
-    if (dg->state) {
-        if (!dg->detect_step) return "ftmpc_diagnosis.detect_step is required with state";
-        if (!dg->detect_thruster) return "ftmpc_diagnosis.detect_thruster is required with state";
-        if (!dg->detect_level) return "ftmpc_diagnosis.detect_level is required with state";
-        const int64_t w = 14 + NT, H = (int64_t)NT * dg->n_levels, K = dg->max_detect;
-        for (int64_t b = 0; b < B; ++b) {
-            const double* st = dg->state + b * w;
-            for (int64_t k = 0; k < w; ++k)
-                if (!std::isfinite(st[k]))
-                    return "ftmpc_diagnosis.state: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
-            if (st[13] < 0) return "ftmpc_diagnosis.state: vehicle " + std::to_string(first + b) + " has n < 0";
-            if (dg->llr)
-                for (int64_t k = 0; k < H; ++k)
-                    if (!std::isfinite(dg->llr[b * H + k]))
-                        return "ftmpc_diagnosis.llr: vehicle " + std::to_string(first + b) + " has a non-finite entry (" + std::to_string(k) + ")";
-            bool unused = false;
-            for (int64_t k = 0; k < K; ++k) {
-                const int32_t ds = dg->detect_step[b * K + k], dt = dg->detect_thruster[b * K + k], dl = dg->detect_level[b * K + k];
-                if (ds == -1) {
-                    unused = true;
-                    continue;
-                }
-                if (ds < -1) return "ftmpc_diagnosis.detect_step: vehicle " + std::to_string(first + b) + " has an entry below -1";
-                if (unused) return "ftmpc_diagnosis.detect_step: vehicle " + std::to_string(first + b) + " has a used slot after an unused one";
-                if (dt < 0 || dt >= NT)
-                    return "ftmpc_diagnosis.detect_thruster: vehicle " + std::to_string(first + b) + " has an entry outside [0, NT)";
-                if (dl < 0 || dl >= dg->n_levels)
-                    return "ftmpc_diagnosis.detect_level: vehicle " + std::to_string(first + b) + " has an entry outside [0, n_levels)";
-            }
-        }
-    }
-    if (fs && fs->n_events > 0 && fs->detect)
-        return "ftmpc_diagnosis: ftmpc_fault_schedule.detect must be NULL (the schedule moves the plant only, the diagnosis detects)";
-    if (se && se->predict == 1 && !es)
-        return "ftmpc_diagnosis: ftmpc_sensor.predict = 1 needs an estimator (the sense kernel would predict with the pattern before the diagnosis)";
-    return "";
-}
-
-// What the wrench form adds to a diagnosis' refusals: the schedule of such a call moves the plant only, so it carries no hull tables,
-// and a handed no_hull_step entry is -1 or a step (first: number of vehicle 0 in the caller's batch)
-static std::string wrench_diagnosis_problem(const ftmpc_fault_schedule* fs, const int32_t* no_hull_step, int64_t B, int64_t first = 0) {
-    if (fs && fs->struct_size == (int32_t)sizeof(ftmpc_fault_schedule)) {
-        if (fs->hull_set) return "ftmpc_diagnosis: ftmpc_fault_schedule.hull_set must be NULL (the schedule moves the plant only, the diagnosis rebuilds the offsets)";
-        if (fs->hull_b) return "ftmpc_diagnosis: ftmpc_fault_schedule.hull_b must be NULL (the schedule moves the plant only, the diagnosis rebuilds the offsets)";
-    }
-    if (no_hull_step)
-        for (int64_t b = 0; b < B; ++b)
-            if (no_hull_step[b] < -1) return "no_hull_step: vehicle " + std::to_string(first + b) + " has an entry below -1";
-    return "";
-}
-
-// An outcomes struct's layout and values (include/ftmpc.h, ftmpc_outcomes); wrench: the form with an allocation
-static int check_outcomes(ftmpc_handle* h, int64_t B, const ftmpc_outcomes* oc, bool wrench) {
-    if (!oc) return FTMPC_OK;
-    if (oc->struct_size != (int32_t)sizeof(ftmpc_outcomes))
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.struct_size is " + std::to_string(oc->struct_size) + ", this library expects " +
-                                          std::to_string(sizeof(ftmpc_outcomes)));
-    if (oc->index0 < 0) return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index0 is negative");
-    if (oc->index_total == 0 && oc->index0 != 0)
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index_total = 0 (the call is the campaign) needs index0 = 0");
-    if (oc->index_total != 0 && (oc->index_total < 0 || oc->index0 > oc->index_total - B))
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.index_total: index0 + B = " + std::to_string(oc->index0) + " + " + std::to_string(B) +
-                                          " exceeds index_total = " + std::to_string(oc->index_total));
-    if (oc->settle_step) {
-        const double tol[3] = {oc->tol_pos, oc->tol_vel, oc->tol_rate};
-        const char* name[3] = {"tol_pos", "tol_vel", "tol_rate"};
-        for (int i = 0; i < 3; ++i)
-            if (!(tol[i] > 0.0) || !std::isfinite(tol[i]))
-                return fail(h, FTMPC_ERR_ARG, std::string("ftmpc_outcomes.") + name[i] + " must be positive and finite when settle_step is asked for");
-    }
-    if (oc->tset_step && (h->cfg.term_rows < 1 || h->cfg.term_rows > FTMPC_MAX_TERM_ROWS))
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.tset_step needs the terminal rows of the handle's config (term_rows in 1..80)");
-    if (oc->alloc_failed && !wrench)
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_outcomes.alloc_failed: the thruster form has no allocation (use ftmpc_simulate_wrench_outcomes_batch)");
-    return FTMPC_OK;
-}
-
-// A fault schedule's layout and values (include/ftmpc.h, ftmpc_fault_schedule).  wrench: the wrench form, whose call has n_sets hull
-// tables of hull_rows rows and its own hull_set (call_set) or not.
-static int check_schedule(ftmpc_handle* h, int64_t B, const ftmpc_fault_schedule* fs, bool wrench, int32_t n_sets, bool call_set) {
-    if (!fs) return FTMPC_OK;
-    if (fs->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: bad struct_size");
-    if (fs->n_events < 0 || fs->n_events > FTMPC_MAX_FAULT_EVENTS)
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: n_events outside [0, FTMPC_MAX_FAULT_EVENTS]");
-    const int E = fs->n_events, NT = h->cfg.NT;
-    if (E == 0) return FTMPC_OK;
-    if (!fs->onset || !fs->ub || !fs->stuck) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: null onset / ub / stuck");
-    if (wrench && !fs->hull_b) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: the wrench form needs hull_b");
-    if (wrench && fs->hull_set && !call_set)
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: per-event hull_set, but the call's hull_set is NULL (one table)");
-    if (wrench && !fs->hull_set && call_set)
-        return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: the call has a hull_set per instance, the schedule needs one per event");
-    for (int64_t b = 0; b < B; ++b) {
-        int32_t pon = -1, pde = -1;
-        bool unused = false;
-        for (int e = 0; e < E; ++e) {
-            const int64_t i = b * E + e;
-            const int32_t on = fs->onset[i];
-            if (on == -1) {
-                unused = true;
-                continue;
-            }
-            if (on < -1) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: onset below -1");
-            if (unused) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: a used slot after an unused one");
-            const int32_t de = fs->detect ? fs->detect[i] : on;
-            if (de < on) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: detect < onset");
-            if (on < pon || de < pde) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: slots not sorted by onset and detect");
-            pon = on;
-            pde = de;
-            for (int k = 0; k < NT; ++k) {
-                const double u = fs->ub[i * NT + k], st = fs->stuck[i * NT + k];
-                if (!std::isfinite(u) || u < 0.0) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: negative or non-finite ub");
-                if (!std::isfinite(st)) return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: non-finite stuck");
-            }
-            if (wrench && fs->hull_set && (fs->hull_set[i] < 0 || fs->hull_set[i] >= n_sets))
-                return fail(h, FTMPC_ERR_ARG, "ftmpc_fault_schedule: hull_set outside [0, n_sets)");
-        }
-    }
-    return FTMPC_OK;
-}
-
-int ftmpc_simulate_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                double* u_hist, double* x_hist, int32_t* not_converged) {
-    return ftmpc_simulate_outcomes_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                         x_hist, not_converged, nullptr);
-}
-
-int ftmpc_simulate_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
-    return ftmpc_simulate_plant_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                      x_hist, not_converged, out, nullptr);
-}
-
-int ftmpc_simulate_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                               const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                               int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                               double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                               const ftmpc_plant_model* plant) {
-    return ftmpc_simulate_mission_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                        x_hist, not_converged, out, plant, nullptr);
-}
-
-int ftmpc_simulate_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                 const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                 int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                 double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
-    return ftmpc_simulate_actuator_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                         x_hist, not_converged, out, plant, mission, nullptr);
-}
-
-int ftmpc_simulate_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                  const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                  int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                  double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                  const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
-    return ftmpc_simulate_sensor_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                       x_hist, not_converged, out, plant, mission, actuator, nullptr);
-}
-
-int ftmpc_simulate_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
-                                const ftmpc_sensor* sensor) {
-    return ftmpc_simulate_estimator_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                          x_hist, not_converged, out, plant, mission, actuator, sensor, nullptr);
-}
-
-int ftmpc_simulate_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
-                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
-    return ftmpc_simulate_diagnosis_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                          x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, nullptr);
-}
-
-int ftmpc_simulate_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
-                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis) {
-    return ftmpc_simulate_disturbance_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                            x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, nullptr);
-}
-
-int ftmpc_simulate_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                                     const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
-                                     const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
-                                     const ftmpc_disturbance* disturbance) {
-    return ftmpc_simulate_bias_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
-                                     x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, nullptr);
-}
-
-// the ABI guard of a bias estimate, before the handle is looked at (so that it needs no device): the message goes to the handle's
-// error, or to the one ftmpc_last_error(NULL) returns
-static int check_bias_size(ftmpc_handle* h, const ftmpc_bias_estimate* be) {
-    if (be && be->struct_size != (int32_t)sizeof(ftmpc_bias_estimate)) return fail(h, FTMPC_ERR_ARG, bias_problem(be, 0, nullptr, nullptr));
-    return FTMPC_OK;
-}
-
-int ftmpc_simulate_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                              const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                              int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
-                              double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
-                              const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
-                              const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
-                              const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
-    if (check_bias_size(h, bias_estimate) != FTMPC_OK) return FTMPC_ERR_ARG;
-    if (!h) return FTMPC_ERR_ARG;
-    if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    int rc = check_schedule(h, B, faults, false, 0, false);
-    if (rc != FTMPC_OK) return rc;
-    if ((rc = check_outcomes(h, B, out, false)) != FTMPC_OK) return rc;
-    if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
-    if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
-    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
-    if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
-    {
-        const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    {
-        const std::string msg = disturbance_problem(disturbance, B, estimator, sqp_iters);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    {     // (the estimate reaches the solve through x0 alone: sqp_iters >= 0 is served)
-        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    if (B == 0 || T == 0) {
-        zero_mission_cost(mission, B);
-        zero_actuator_sums(actuator, B);
-        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
-        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * h->cfg.NT, diagnosis->ub);
-        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * h->cfg.NT, diagnosis->stuck);
-        return FTMPC_OK;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = ftmpc_reserve(h, B)) != FTMPC_OK) return rc;
-    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged,
-                         faults, x_hist, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
-}
-
-int ftmpc_simulate_wrench_faults_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed) {
-    return ftmpc_simulate_wrench_outcomes_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                                seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                                nullptr);
-}
-
-int ftmpc_simulate_wrench_outcomes_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
-                                         const ftmpc_outcomes* out) {
-    return ftmpc_simulate_wrench_plant_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                             seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                             out, nullptr);
-}
-
-int ftmpc_simulate_wrench_plant_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                      const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                      int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                      double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
-                                      const ftmpc_outcomes* out, const ftmpc_plant_model* plant) {
-    return ftmpc_simulate_wrench_mission_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                               seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                               out, plant, nullptr);
-}
-
-int ftmpc_simulate_wrench_mission_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                        const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                        const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                        int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                        double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
-                                        const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
-    return ftmpc_simulate_wrench_actuator_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                                seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                                out, plant, mission, nullptr);
-}
-
-int ftmpc_simulate_wrench_actuator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                         const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                         int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                         double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
-                                         const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                                         const ftmpc_actuator* actuator) {
-    return ftmpc_simulate_wrench_sensor_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                              seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                              out, plant, mission, actuator, nullptr);
-}
-
-int ftmpc_simulate_wrench_sensor_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                       const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                       int32_t sqp_iters, int32_t backtracks, double tol, double penalty, const ftmpc_fault_schedule* faults,
-                                       double* u_hist, double* x_hist, int32_t* not_converged, int32_t* alloc_failed,
-                                       const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                                       const ftmpc_actuator* actuator, const ftmpc_sensor* sensor) {
-    return ftmpc_simulate_wrench_estimator_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                                 seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                                 out, plant, mission, actuator, sensor, nullptr);
-}
-
-int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
-                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
-                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
-                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
-                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
-                                          const ftmpc_estimator* estimator) {
-    return ftmpc_simulate_wrench_diagnosis_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                                 seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                                 out, plant, mission, actuator, sensor, estimator, nullptr, nullptr, nullptr);
-}
-
-int ftmpc_simulate_wrench_diagnosis_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
-                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
-                                          uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
-                                          const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                                          int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
-                                          const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
-                                          const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
-                                          int32_t* no_hull_step) {
-    return ftmpc_simulate_wrench_disturbance_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
-                                                   noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
-                                                   alloc_failed, out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b,
-                                                   no_hull_step, nullptr);
-}
-
-int ftmpc_simulate_wrench_disturbance_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
-                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
-                                            uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
-                                            const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                                            int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
-                                            const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
-                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
-                                            int32_t* no_hull_step, const ftmpc_disturbance* disturbance) {
-    return ftmpc_simulate_wrench_bias_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                            seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
-                                            out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b, no_hull_step,
-                                            disturbance, nullptr);
-}
-
-int ftmpc_simulate_wrench_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                     const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
-                                     int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
-                                     uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
-                                     const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                                     int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
-                                     const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
-                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
-                                     int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
-                                     const ftmpc_bias_estimate* bias_estimate) {
-    if (check_bias_size(h, bias_estimate) != FTMPC_OK) return FTMPC_ERR_ARG;
-    if (!h) return FTMPC_ERR_ARG;
-    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
-    if (rc != FTMPC_OK) return rc;
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    if (diagnosis) {     // the schedule moves the plant only: checked as the thruster form's, which has no hull fields
-        const std::string msg = wrench_diagnosis_problem(faults, no_hull_step, B);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    if ((rc = diagnosis ? check_schedule(h, B, faults, false, 0, false) : check_schedule(h, B, faults, true, n_sets, hull_set != nullptr)) != FTMPC_OK)
-        return rc;
-    if ((rc = check_outcomes(h, B, out, true)) != FTMPC_OK) return rc;
-    if ((rc = check_plant(h, B, plant)) != FTMPC_OK) return rc;
-    if ((rc = check_sensor(h, B, sensor)) != FTMPC_OK) return rc;
-    if ((rc = check_estimator(h, B, estimator)) != FTMPC_OK) return rc;
-    if ((rc = check_mission(h, B, T, mission, xref_traj, uref_traj, sensor_shift(sensor))) != FTMPC_OK) return rc;
-    if ((rc = check_actuator(h, B, actuator)) != FTMPC_OK) return rc;
-    {
-        const std::string msg = diagnosis_problem(diagnosis, B, h->cfg.NT, estimator, faults, sensor);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    {     // (the wrench SQP's cost kernel knows the estimate: sqp_iters > 0 is served here)
-        const std::string msg = disturbance_problem(disturbance, B, estimator, 0);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    {
-        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
-        if (!msg.empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    }
-    if (B == 0 || T == 0) {
-        zero_mission_cost(mission, B);
-        zero_actuator_sums(actuator, B);
-        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
-        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * h->cfg.NT, diagnosis->ub);
-        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * h->cfg.NT, diagnosis->stuck);
-        if (out_hull_b && B > 0 && hull_rows > 0) std::copy(hull_b, hull_b + B * hull_rows, out_hull_b);
-        return FTMPC_OK;
-    }
-    if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
-    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, sqp_iters > 0 ? (penalty > 0 ? penalty : FTMPC_SQPW_PENALTY) : 0.0,
-                  out_hull_b, diagnosis ? no_hull_step : nullptr};
-    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, sqp_iters > 0 ? backtracks : 0,
-                         sqp_iters > 0 ? tol : 0.0, &wl, u_hist, not_converged, faults, x_hist, out, plant, mission, actuator, sensor,
-                         estimator, diagnosis, disturbance, bias_estimate);
-}
-
 int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const double* stuck, const double* hull_A, int32_t n_sets,
                              const int32_t* hull_set, int32_t hull_rows, double* out_b, int32_t* out_flat) {
     if (!h) return FTMPC_ERR_ARG;
@@ -2985,1001 +2216,11 @@ int ftmpc_hull_offsets_batch(ftmpc_handle* h, int64_t B, const double* ub, const
     return FTMPC_OK;
 }
 
-int ftmpc_simulate_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                            const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                            int32_t sqp_iters, int32_t backtracks, double tol, double* u_hist, int32_t* not_converged) {
-    if (!h) return FTMPC_ERR_ARG;
-    if (sqp_iters < 0 || (sqp_iters > 0 && (backtracks < 1 || !(tol >= 0)))) return fail(h, FTMPC_ERR_ARG, "bad SQP iteration counts");
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    if (B == 0 || T == 0) return FTMPC_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ftmpc_reserve(h, B);
-    if (rc != FTMPC_OK) return rc;
-    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, nullptr, u_hist, not_converged);
-}
+}  // extern "C"
 
-int ftmpc_simulate_wrench_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                double* u_hist, int32_t* not_converged, int32_t* alloc_failed) {
-    if (!h) return FTMPC_ERR_ARG;
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    if (B == 0 || T == 0) return FTMPC_OK;
-    int rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows);
-    if (rc != FTMPC_OK) return rc;
-    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, 0.0};
-    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, 0, 0, 0.0, &wl, u_hist, not_converged);
-}
+#include "ftmpc_loop.hip"
 
-int ftmpc_simulate_wrench_batch_ex(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
-                                   const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows,
-                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
-                                   int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
-                                   double* u_hist, int32_t* not_converged, int32_t* alloc_failed) {
-    if (!h) return FTMPC_ERR_ARG;
-    int rc = sqpw_check(h, sqp_iters, backtracks, tol, penalty, sqp_iters > 0);
-    if (rc != FTMPC_OK) return rc;
-    if (sqp_iters == 0)
-        return ftmpc_simulate_wrench_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
-                                           seed, u_hist, not_converged, alloc_failed);
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !xref_traj || !noise || !hull_A || !hull_b) return fail(h, FTMPC_ERR_ARG, "null buffer or negative size");
-    if (B == 0 || T == 0) return FTMPC_OK;
-    if ((rc = wrench_prepare(h, B, hull_A, n_sets, hull_set, hull_b, hull_rows)) != FTMPC_OK) return rc;
-    WrenchLoop wl{hull_rows, hull_set != nullptr, alloc_failed, penalty > 0 ? penalty : FTMPC_SQPW_PENALTY};
-    return simulate_core(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, &wl, u_hist, not_converged);
-}
-
-static int simulate_core(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* xref_traj,
-                         const double* uref_traj, const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                         const WrenchLoop* wl, double* u_hist, int32_t* not_converged, const ftmpc_fault_schedule* fs, double* x_hist,
-                         const ftmpc_outcomes* oc, const ftmpc_plant_model* pm, const ftmpc_mission* ms, const ftmpc_actuator* ac,
-                         const ftmpc_sensor* se, const ftmpc_estimator* es, const ftmpc_diagnosis* dg, const ftmpc_disturbance* db,
-                         const ftmpc_bias_estimate* be) {
-    int rc;
-    const int N = h->cfg.N, NT = h->cfg.NT;
-    hipStream_t s = h->stream;
-    // estimator (checked by the entry): ftmpc_filter_kernel runs between the sense kernel and the solve (phase 0) and after the plant
-    // step (phase 1).  It takes the truth-buffer path of a sensor even when the sensor is trivial or NULL (se0: latency 0, step0 0,
-    // nothing drawn); the sense kernel then does not run and y_t is the truth
-    const bool est = es != nullptr;
-    // diagnosis (checked by the entry): ftmpc_diagnose_kernel runs before the filter's phase 0 (phase 0) and after the plant step
-    // (phase 1); it takes the same truth-buffer path.  On the wrench form ftmpc_hull_offsets_kernel and ftmpc_hull_switch_kernel follow
-    // phase 0: the offsets of the vehicles that switched, from the pattern the controller now holds
-    const bool diag = dg != nullptr;
-    const bool sensing = !sensor_trivial(se);      // ftmpc_sense_kernel runs
-    ftmpc_sensor se0{};
-    if ((est || diag) && !se) se = &se0;
-    // sensor (checked by the entry): not trivial, the truth lives in d_xtrue and ftmpc_sense_kernel writes h->d_x0 before every solve;
-    // lat commands wait in the ring d_ring ([lat + 1][B][NT]); a predicting sensor shifts every reference window by L = lat columns
-    const bool sense = sensing || est || diag;
-    const int lat = sense ? se->latency : 0, L = sense && se->predict ? lat : 0;
-    const int64_t ncol = (int64_t)T + N + L;   // windows t .. t+N for t < T (t+L .. t+L+N under a predicting sensor)
-    // (this call's own buffers: freed on every way out)
-    DevBuf<double> d_xr, d_ur, d_warmB, d_hist, d_xhist;
-    DevBuf<int32_t> d_bad, d_abad;
-    // fault schedule (E > 0): events [on | de | hull_set], patterns [ub | stuck], hull offsets, the plant's own pattern [ub | stuck]
-    const int E = fs ? fs->n_events : 0;
-    DevBuf<int32_t> d_fev;
-    DevBuf<double> d_fpat, d_fhb, d_plant;
-    // outcomes: records [err_int 3 | err_max 3 | impulse 2] x B and [settle | tset | unsolved | first_unsolved | alloc_failed] x B, the
-    // terminal rows of the config, the status history
-    const bool want_rec = oc && (oc->err_int || oc->err_max || oc->impulse || oc->settle_step || oc->tset_step || oc->unsolved ||
-                                 oc->first_unsolved || oc->alloc_failed);
-    // mission (checked by the entry): reference tables with a table number and a start column per vehicle, gathered into per-vehicle
-    // windows before every solve (ftmpc::RefWindow), and / or the closed-loop cost.  Without tables and without cost nothing below
-    // differs from a call without the struct.
-    const bool windows = ms && ms->n_tables > 0;
-    const bool want_cost = ms && ms->cost;
-    const bool has_uref = windows ? ms->uref != nullptr : uref_traj != nullptr;
-    DevBuf<double> d_mtab, d_mutab, d_xwin, d_uwin, d_qprev, d_cost;
-    DevBuf<int32_t> d_mtbl, d_moff;
-    const bool want_out = want_rec || (oc && oc->status_hist) || want_cost;
-    DevBuf<double> d_orec, d_oterm;
-    DevBuf<int32_t> d_oint, d_shist;
-    // plant model (checked by the entry): the arrays that are given, transposed to component-major [k][B] on the host (the layout of
-    // ftmpc::PlantVar), 1 / m_b and J_b^-1 computed here, once per call; the host copies live until the stream is drained
-    const bool var_plant = pm && (pm->mass || pm->J || pm->D || pm->force || pm->torque);
-    DevBuf<double> d_pim, d_pJ, d_pD, d_pf, d_pt;
-    std::vector<double> h_pim, h_pJ, h_pD, h_pf, h_pt;
-    ftmpc::PlantVar pv{};
-    if (var_plant) {
-        // dst [K][B] = src [B][K]^T, 64 vehicles at a time so that each of the K write streams fills whole cache lines
-        auto transpose = [B](const double* src, int64_t K, double* dst) {
-            for (int64_t b0 = 0; b0 < B; b0 += 64) {
-                const int64_t b1 = std::min(B, b0 + 64);
-                for (int64_t k = 0; k < K; ++k)
-                    for (int64_t b = b0; b < b1; ++b) dst[k * B + b] = src[b * K + k];
-            }
-        };
-        auto upload = [&](DevBuf<double>& d, const std::vector<double>& v) -> int {
-            HIP_TRY(h, hipMalloc(&d.p, v.size() * sizeof(double)));
-            HIP_TRY(h, hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            return FTMPC_OK;
-        };
-        try {
-            if (pm->mass) {
-                h_pim.resize((size_t)B);
-                for (int64_t b = 0; b < B; ++b) h_pim[b] = 1.0 / pm->mass[b];
-            }
-            if (pm->J) {
-                h_pJ.resize((size_t)B * 18);
-                for (int64_t b = 0; b < B; ++b) {
-                    const double* J = pm->J + b * 9;
-                    const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
-                    const double idet = 1.0 / (J[0] * c00 + J[1] * c01 + J[2] * c02);
-                    const double inv[9] = {c00 * idet, (J[2] * J[7] - J[1] * J[8]) * idet, (J[1] * J[5] - J[2] * J[4]) * idet,
-                                           c01 * idet, (J[0] * J[8] - J[2] * J[6]) * idet, (J[2] * J[3] - J[0] * J[5]) * idet,
-                                           c02 * idet, (J[1] * J[6] - J[0] * J[7]) * idet, (J[0] * J[4] - J[1] * J[3]) * idet};
-                    for (int k = 0; k < 9; ++k) {
-                        h_pJ[(size_t)k * B + b] = J[k];
-                        h_pJ[(size_t)(9 + k) * B + b] = inv[k];
-                    }
-                }
-            }
-            if (pm->D) {
-                h_pD.resize((size_t)B * 6 * NT);
-                transpose(pm->D, 6 * (int64_t)NT, h_pD.data());
-            }
-            if (pm->force) {
-                h_pf.resize((size_t)B * 3);
-                transpose(pm->force, 3, h_pf.data());
-            }
-            if (pm->torque) {
-                h_pt.resize((size_t)B * 3);
-                transpose(pm->torque, 3, h_pt.data());
-            }
-        } catch (const std::bad_alloc&) {
-            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the plant model's staging arrays");
-        }
-        if (pm->mass && (rc = upload(d_pim, h_pim)) != FTMPC_OK) return rc;
-        if (pm->J && (rc = upload(d_pJ, h_pJ)) != FTMPC_OK) return rc;
-        if (pm->D && (rc = upload(d_pD, h_pD)) != FTMPC_OK) return rc;
-        if (pm->force && (rc = upload(d_pf, h_pf)) != FTMPC_OK) return rc;
-        if (pm->torque && (rc = upload(d_pt, h_pt)) != FTMPC_OK) return rc;
-        pv.inv_mass = d_pim;
-        pv.J = d_pJ;
-        pv.D = d_pD;
-        pv.force = d_pf;
-        pv.torque = d_pt;
-    }
-    if (!windows) HIP_TRY(h, hipMalloc(&d_xr.p, (size_t)ncol * 9 * sizeof(double)));
-    if (uref_traj) HIP_TRY(h, hipMalloc(&d_ur.p, (size_t)ncol * 6 * sizeof(double)));
-    if (!wl) HIP_TRY(h, hipMalloc(&d_warmB.p, (size_t)B * N * NT * sizeof(double)));
-    if (wl && wl->alloc_failed) {
-        HIP_TRY(h, hipMalloc(&d_abad.p, (size_t)T * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetAsync(d_abad, 0, (size_t)T * sizeof(int32_t), s));
-    }
-    if (u_hist) HIP_TRY(h, hipMalloc(&d_hist.p, (size_t)T * B * NT * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&d_bad.p, (size_t)T * sizeof(int32_t)));
-    HIP_TRY(h, hipMemsetAsync(d_bad, 0, (size_t)T * sizeof(int32_t), s));
-    if (!windows) HIP_TRY(h, hipMemcpyAsync(d_xr, xref_traj, (size_t)ncol * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (uref_traj) HIP_TRY(h, hipMemcpyAsync(d_ur, uref_traj, (size_t)ncol * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = stage_inputs(h, B, x, ub, stuck)) != FTMPC_OK) return rc;
-    // actuator (checked by the entry): not trivial, the plant's step is ftmpc_plant_step_act_kernel's.  The four lag constants are
-    // computed here, once per call; the valve states are staged component-major [NT][B] (the caller's are vehicle-major), delivered and
-    // pulses start at zero
-    const bool act = !actuator_trivial(ac);
-    DevBuf<double> d_aval, d_adel, d_aapp;
-    DevBuf<int32_t> d_apul, d_atick;
-    std::vector<double> h_aval;
-    ftmpc::ActParams ap{};
-    if (act) {
-        const int S = ac->substeps > 0 ? ac->substeps : 1;
-        const double hs = h->cfg.dt / S;
-        ap.pwm = ac->mode == 1;
-        ap.substeps = S;
-        ap.min_on = ac->min_on;
-        ap.align = ac->align;
-        if (ac->tau_on > 0) {
-            ap.E_on = std::exp(-hs / ac->tau_on);
-            ap.K_on = -std::expm1(-hs / ac->tau_on) * ac->tau_on / hs;
-        }
-        if (ac->tau_off > 0) {
-            ap.E_off = std::exp(-hs / ac->tau_off);
-            ap.K_off = -std::expm1(-hs / ac->tau_off) * ac->tau_off / hs;
-        }
-        const size_t nv = (size_t)B * NT;
-        HIP_TRY(h, hipMalloc(&d_aval.p, nv * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_adel.p, (size_t)B * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_apul.p, (size_t)B * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetAsync(d_adel, 0, (size_t)B * sizeof(double), s));
-        HIP_TRY(h, hipMemsetAsync(d_apul, 0, (size_t)B * sizeof(int32_t), s));
-        if (ac->state) {
-            try {
-                h_aval.resize(nv);
-            } catch (const std::bad_alloc&) {
-                return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the actuator's staging array");
-            }
-            for (int64_t b = 0; b < B; ++b)
-                for (int i = 0; i < NT; ++i) h_aval[(size_t)i * B + b] = ac->state[b * NT + i];
-            HIP_TRY(h, hipMemcpyAsync(d_aval, h_aval.data(), nv * sizeof(double), hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(h, hipMemsetAsync(d_aval, 0, nv * sizeof(double), s));
-        }
-        if (ac->applied_hist) HIP_TRY(h, hipMalloc(&d_aapp.p, (size_t)T * nv * sizeof(double)));
-        if (ac->ticks_hist) HIP_TRY(h, hipMalloc(&d_atick.p, (size_t)T * nv * sizeof(int32_t)));
-        ap.state = d_aval;
-        ap.delivered = d_adel;
-        ap.pulses = d_apul;
-        ap.applied_hist = d_aapp;
-        ap.ticks_hist = d_atick;
-    }
-    DevBuf<double> d_xtrue, d_ring, d_sbias, d_mhist, d_phist;
-    std::vector<double> h_ring;
-    ftmpc::SenseParams sn{};
-    const size_t nu = (size_t)B * NT;       // doubles per ring slot
-    if (sense) {
-        HIP_TRY(h, hipMalloc(&d_xtrue.p, (size_t)B * 13 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_xtrue, h->d_x0, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToDevice, s));
-        if (lat > 0) {      // slots 0 .. lat-1: the pending commands, oldest first (the caller's are vehicle-major [B][lat][NT])
-            HIP_TRY(h, hipMalloc(&d_ring.p, (size_t)(lat + 1) * nu * sizeof(double)));
-            if (se->pending) {
-                try {
-                    h_ring.resize((size_t)lat * nu);
-                } catch (const std::bad_alloc&) {
-                    return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the sensor's staging array");
-                }
-                for (int64_t b = 0; b < B; ++b)
-                    for (int j = 0; j < lat; ++j)
-                        for (int i = 0; i < NT; ++i) h_ring[(size_t)j * nu + b * NT + i] = se->pending[(b * lat + j) * NT + i];
-                HIP_TRY(h, hipMemcpyAsync(d_ring, h_ring.data(), (size_t)lat * nu * sizeof(double), hipMemcpyHostToDevice, s));
-            } else {
-                HIP_TRY(h, hipMemsetAsync(d_ring, 0, (size_t)lat * nu * sizeof(double), s));
-            }
-        }
-        if (se->bias) {
-            HIP_TRY(h, hipMalloc(&d_sbias.p, (size_t)B * 12 * sizeof(double)));
-            HIP_TRY(h, hipMemcpyAsync(d_sbias, se->bias, (size_t)B * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        if (se->meas_hist) HIP_TRY(h, hipMalloc(&d_mhist.p, (size_t)T * B * 13 * sizeof(double)));
-        if (se->pred_hist) HIP_TRY(h, hipMalloc(&d_phist.p, (size_t)T * B * 13 * sizeof(double)));
-        sn.B = B;
-        sn.x = d_xtrue;
-        sn.y = h->d_x0;
-        sn.ub = h->d_ub;
-        sn.stuck = h->d_stuck;
-        sn.ring = d_ring;
-        sn.nslots = lat + 1;
-        sn.latency = lat;
-        sn.predict = se->predict;
-        for (int i = 0; i < 4; ++i) sn.sigma[i] = se->sigma[i];
-        sn.bias = d_sbias;
-        sn.seed = se->seed;
-        sn.index0 = oc ? oc->index0 : 0;
-        sn.index_total = oc && oc->index_total != 0 ? oc->index_total : B;
-        sn.meas_hist = d_mhist;
-        sn.pred_hist = d_phist;
-    }
-    // the filter's state: the mean [B][13] and the packed covariance, component-major [78][B] (the caller's is vehicle-major),
-    // diag(p0^2) when none is handed over; err_sq [B][4] starts at zero
-    DevBuf<double> d_xhat, d_cov, d_ehist, d_esq;
-    std::vector<double> h_cov;
-    ftmpc::FilterParams fp{};
-    if (est) {
-        const size_t nc = (size_t)B * 78;
-        try {
-            h_cov.assign(nc, 0.0);
-        } catch (const std::bad_alloc&) {
-            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the estimator's staging array");
-        }
-        if (es->cov) {
-            for (int64_t b0 = 0; b0 < B; b0 += 64) {
-                const int64_t b1 = std::min(B, b0 + 64);
-                for (int64_t k = 0; k < 78; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_cov[(size_t)k * B + b] = es->cov[b * 78 + k];
-            }
-        } else {
-            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i) std::fill(h_cov.begin() + (size_t)k * B, h_cov.begin() + (size_t)(k + 1) * B, es->p0[i / 3] * es->p0[i / 3]);
-        }
-        if (be && !be->cross)     // a bias estimate without handed pieces: P_mm = P_xx + HB diag(p0_b^2) HB' (see the bias block below)
-            for (int i = 0, k = 0; i < 12; k += 12 - i, ++i)
-                if ((i >= 3 && i < 6) || i >= 9)
-                    for (int64_t b = 0; b < B; ++b) h_cov[(size_t)k * B + b] += be->p0[i >= 9] * be->p0[i >= 9];
-        HIP_TRY(h, hipMalloc(&d_cov.p, nc * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_cov, h_cov.data(), nc * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMalloc(&d_xhat.p, (size_t)B * 13 * sizeof(double)));
-        if (es->xhat) HIP_TRY(h, hipMemcpyAsync(d_xhat, es->xhat, (size_t)B * 13 * sizeof(double), hipMemcpyHostToDevice, s));
-        if (es->est_hist) HIP_TRY(h, hipMalloc(&d_ehist.p, (size_t)T * B * 13 * sizeof(double)));
-        if (es->err_sq) {
-            HIP_TRY(h, hipMalloc(&d_esq.p, (size_t)B * 4 * sizeof(double)));
-            HIP_TRY(h, hipMemsetAsync(d_esq, 0, (size_t)B * 4 * sizeof(double), s));
-        }
-        sn.predict = 0;             // the filter propagates its own estimate over the queue, and writes pred_hist
-        sn.pred_hist = nullptr;
-        fp.B = B;
-        fp.latency = lat;
-        fp.predict = se->predict;
-        fp.nslots = lat + 1;
-        fp.y = sensing ? h->d_x0.p : d_xtrue.p;
-        fp.truth = d_xtrue;
-        fp.x0 = h->d_x0;
-        fp.xhat = d_xhat;
-        fp.cov = d_cov;
-        fp.ub = h->d_ub;
-        fp.stuck = h->d_stuck;
-        fp.ring = d_ring;
-        for (int i = 0; i < 4; ++i) {
-            fp.rsq[i] = es->meas_sigma[i] * es->meas_sigma[i];
-            fp.qsq[i] = es->proc_sigma[i] * es->proc_sigma[i];
-        }
-        fp.est_hist = d_ehist;
-        fp.pred_hist = d_phist;
-        fp.err_sq = d_esq;
-    }
-    // disturbance estimate (checked by the entry; it needs the estimator): P_xd [72][B] and P_dd [21][B] component-major (the caller's
-    // are vehicle-major), 0 and diag(p0^2) when none is handed over; the estimate itself [B][6] = (f^, t^), what the linearise
-    // kernel's DIST instantiations and ftmpc_diagnose_dist_kernel read; the gain slot [168][B] between the two passes of the update
-    const bool dist = db != nullptr;
-    DevBuf<double> d_dcross, d_dcovd, d_dest, d_dgain, d_dfh, d_dth;
-    std::vector<double> h_dcross, h_dcovd, h_dest;
-    ftmpc::DistParams dq{};
-    if (dist) {
-        try {
-            h_dcross.assign((size_t)B * 72, 0.0);
-            h_dcovd.assign((size_t)B * 21, 0.0);
-            h_dest.assign((size_t)B * 6, 0.0);
-        } catch (const std::bad_alloc&) {
-            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the disturbance estimate's staging arrays");
-        }
-        for (int64_t b0 = 0; b0 < B; b0 += 64) {
-            const int64_t b1 = std::min(B, b0 + 64);
-            if (db->cross)
-                for (int64_t k = 0; k < 72; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_dcross[(size_t)k * B + b] = db->cross[b * 72 + k];
-            if (db->cov)
-                for (int64_t k = 0; k < 21; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_dcovd[(size_t)k * B + b] = db->cov[b * 21 + k];
-        }
-        if (!db->cov)
-            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i)
-                std::fill(h_dcovd.begin() + (size_t)k * B, h_dcovd.begin() + (size_t)(k + 1) * B, db->p0[i / 3] * db->p0[i / 3]);
-        for (int64_t b = 0; b < B; ++b)
-            for (int k = 0; k < 3; ++k) {
-                if (db->force) h_dest[(size_t)b * 6 + k] = db->force[b * 3 + k];
-                if (db->torque) h_dest[(size_t)b * 6 + 3 + k] = db->torque[b * 3 + k];
-            }
-        HIP_TRY(h, hipMalloc(&d_dcross.p, (size_t)B * 72 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_dcovd.p, (size_t)B * 21 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_dest.p, (size_t)B * 6 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_dgain.p, (size_t)B * 168 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_dcross, h_dcross.data(), (size_t)B * 72 * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_dcovd, h_dcovd.data(), (size_t)B * 21 * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_dest, h_dest.data(), (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-        if (db->force_hist) HIP_TRY(h, hipMalloc(&d_dfh.p, (size_t)T * B * 3 * sizeof(double)));
-        if (db->torque_hist) HIP_TRY(h, hipMalloc(&d_dth.p, (size_t)T * B * 3 * sizeof(double)));
-        dq.cross = d_dcross;
-        dq.covd = d_dcovd;
-        dq.dist = d_dest;
-        dq.gain = d_dgain;
-        for (int k = 0; k < 2; ++k) dq.qdsq[k] = db->proc_sigma[k] * db->proc_sigma[k];
-        dq.force_hist = d_dfh;
-        dq.torque_hist = d_dth;
-    }
-    // bias estimate (checked by the entry; it needs the estimator and excludes the disturbance estimate): the pieces in measured
-    // coordinates, P_mb [72][B] and P_bb [21][B] component-major with P_mm in d_cov; b^ [B][6]; the gain slot [168][B].  Without a
-    // handed cross the bias prior is independent of the state error, and the pieces are T diag(P_xx, P_bb) T'
-    const bool bias = be != nullptr;
-    DevBuf<double> d_bcross, d_bcovb, d_best, d_bgain, d_bhist;
-    std::vector<double> h_bcross, h_bcovb;
-    ftmpc::BiasParams bq{};
-    if (bias) {
-        try {
-            h_bcross.assign((size_t)B * 72, 0.0);
-            h_bcovb.assign((size_t)B * 21, 0.0);
-        } catch (const std::bad_alloc&) {
-            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the bias estimate's staging arrays");
-        }
-        const double pb[2] = {be->p0[0] * be->p0[0], be->p0[1] * be->p0[1]};
-        for (int64_t b0 = 0; b0 < B; b0 += 64) {
-            const int64_t b1 = std::min(B, b0 + 64);
-            if (be->cross)
-                for (int64_t k = 0; k < 72; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_bcross[(size_t)k * B + b] = be->cross[b * 72 + k];
-            if (be->cov)
-                for (int64_t k = 0; k < 21; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_bcovb[(size_t)k * B + b] = be->cov[b * 21 + k];
-        }
-        if (!be->cov)
-            for (int i = 0, k = 0; i < 6; k += 6 - i, ++i) std::fill(h_bcovb.begin() + (size_t)k * B, h_bcovb.begin() + (size_t)(k + 1) * B, pb[i / 3]);
-        if (!be->cross) {
-            for (int r = 0; r < 3; ++r) {
-                const int kv = 6 * (3 + r) + r, kw = 6 * (9 + r) + 3 + r;      // HB's ones
-                std::fill(h_bcross.begin() + (size_t)kv * B, h_bcross.begin() + (size_t)(kv + 1) * B, pb[0]);
-                std::fill(h_bcross.begin() + (size_t)kw * B, h_bcross.begin() + (size_t)(kw + 1) * B, pb[1]);
-            }
-        }
-        HIP_TRY(h, hipMalloc(&d_bcross.p, (size_t)B * 72 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_bcovb.p, (size_t)B * 21 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_best.p, (size_t)B * 6 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_bgain.p, (size_t)B * 168 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_bcross, h_bcross.data(), (size_t)B * 72 * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_bcovb, h_bcovb.data(), (size_t)B * 21 * sizeof(double), hipMemcpyHostToDevice, s));
-        if (be->bias)
-            HIP_TRY(h, hipMemcpyAsync(d_best, be->bias, (size_t)B * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-        else
-            HIP_TRY(h, hipMemsetAsync(d_best, 0, (size_t)B * 6 * sizeof(double), s));
-        if (be->bias_hist) HIP_TRY(h, hipMalloc(&d_bhist.p, (size_t)T * B * 6 * sizeof(double)));
-        bq.cross = d_bcross;
-        bq.covb = d_bcovb;
-        bq.bias = d_best;
-        bq.gain = d_bgain;
-        for (int k = 0; k < 2; ++k) bq.qbsq[k] = be->proc_sigma[k] * be->proc_sigma[k];
-        bq.bias_hist = d_bhist;
-    }
-    // the diagnosis' state: xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (the caller's are vehicle-major;
-    // the statistics are filled on the device when none are handed over), the detect arrays [B][K] with the count per vehicle, the
-    // flag the repair kernel reads
-    DevBuf<double> d_dxt, d_dacc, d_dllr, d_dhist;
-    DevBuf<int32_t> d_ddet;      // [count B | switched B | step BK | thruster BK | level BK]
-    std::vector<double> h_dxt, h_dacc, h_dllr;
-    std::vector<int32_t> h_ddet;
-    ftmpc::DiagParams dp{};
-    const int dL = diag ? dg->n_levels : 0, dK = diag ? dg->max_detect : 0;
-    const int64_t dH = (int64_t)NT * dL;
-    if (diag) {
-        const size_t nd = (size_t)B * (2 + 3 * (size_t)dK);
-        try {
-            h_dxt.assign((size_t)B * 14, 0.0);
-            h_dacc.assign((size_t)B * NT, 0.0);
-            if (dg->state && dg->llr) h_dllr.assign((size_t)(B * dH), 0.0);
-            h_ddet.assign(nd, -1);
-        } catch (const std::bad_alloc&) {
-            return fail(h, FTMPC_ERR_ALLOC, "out of host memory for the diagnosis' staging arrays");
-        }
-        std::fill(h_ddet.begin(), h_ddet.begin() + 2 * B, 0);
-        HIP_TRY(h, hipMalloc(&d_dxt.p, (size_t)B * 14 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_dacc.p, (size_t)B * NT * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_dllr.p, (size_t)(B * dH) * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_ddet.p, nd * sizeof(int32_t)));
-        if (dg->state) {
-            const int64_t w = 14 + NT;
-            for (int64_t b = 0; b < B; ++b) {
-                for (int k = 0; k < 14; ++k) h_dxt[(size_t)b * 14 + k] = dg->state[b * w + k];
-                for (int i = 0; i < NT; ++i) h_dacc[(size_t)i * B + b] = dg->state[b * w + 14 + i];
-                int32_t cnt = 0;
-                for (int k = 0; k < dK; ++k) {
-                    const int32_t ds = dg->detect_step[b * dK + k];
-                    h_ddet[(size_t)(2 * B + b * dK + k)] = ds;
-                    h_ddet[(size_t)(2 * B + (B + b) * dK + k)] = ds < 0 ? -1 : dg->detect_thruster[b * dK + k];
-                    h_ddet[(size_t)(2 * B + (2 * B + b) * dK + k)] = ds < 0 ? -1 : dg->detect_level[b * dK + k];
-                    cnt += ds >= 0;
-                }
-                h_ddet[(size_t)b] = cnt;
-            }
-            HIP_TRY(h, hipMemcpyAsync(d_dxt, h_dxt.data(), h_dxt.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(d_dacc, h_dacc.data(), h_dacc.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        } else {      // (the first step's phase 0 initialises both)
-            HIP_TRY(h, hipMemsetAsync(d_dxt, 0, (size_t)B * 14 * sizeof(double), s));
-            HIP_TRY(h, hipMemsetAsync(d_dacc, 0, (size_t)B * NT * sizeof(double), s));
-        }
-        if (dg->state && dg->llr) {
-            for (int64_t b0 = 0; b0 < B; b0 += 64) {
-                const int64_t b1 = std::min(B, b0 + 64);
-                for (int64_t k = 0; k < dH; ++k)
-                    for (int64_t b = b0; b < b1; ++b) h_dllr[(size_t)(k * B + b)] = dg->llr[b * dH + k];
-            }
-            HIP_TRY(h, hipMemcpyAsync(d_dllr, h_dllr.data(), h_dllr.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(h, hipMemsetAsync(d_dllr, 0, (size_t)(B * dH) * sizeof(double), s));
-        }
-        HIP_TRY(h, hipMemcpyAsync(d_ddet, h_ddet.data(), nd * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (dg->llr_hist) HIP_TRY(h, hipMalloc(&d_dhist.p, (size_t)(T * B * dH) * sizeof(double)));
-        dp.B = B;
-        dp.L = dL;
-        dp.K = dK;
-        dp.y = sensing ? h->d_x0.p : d_xtrue.p;
-        dp.xt = d_dxt;
-        dp.acc = d_dacc;
-        dp.llr = d_dllr;
-        for (int l = 0; l < dL; ++l) dp.levels[l] = dg->levels[l];
-        for (int k = 0; k < 2; ++k) {
-            dp.rsq[k] = dg->resid_sigma[k] * dg->resid_sigma[k];
-            dp.dsq[k] = dg->drift_sigma[k] * dg->drift_sigma[k];
-        }
-        dp.threshold = dg->threshold;
-        dp.ub = h->d_ub;
-        dp.stuck = h->d_stuck;
-        dp.count = d_ddet;
-        dp.switched = d_ddet + B;
-        dp.det_step = d_ddet + 2 * B;
-        dp.det_thruster = d_ddet + 2 * B + B * dK;
-        dp.det_level = d_ddet + 2 * B + 2 * B * dK;
-        dp.llr_hist = d_dhist;
-    }
-    // ... on the wrench form: the new offsets [B][hull_rows] and [flat B | no_hull B]
-    DevBuf<double> d_hbnew;
-    DevBuf<int32_t> d_hflat;
-    ftmpc::HullOffsets ho{};
-    ftmpc::HullSwitch hw{};
-    if (diag && wl) {
-        const int R = wl->hull_rows;
-        HIP_TRY(h, hipMalloc(&d_hbnew.p, (size_t)B * R * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_hflat.p, 2 * (size_t)B * sizeof(int32_t)));
-        if (wl->no_hull_step)
-            HIP_TRY(h, hipMemcpyAsync(d_hflat + B, wl->no_hull_step, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        else
-            HIP_TRY(h, hipMemsetAsync(d_hflat + B, 0xFF, (size_t)B * sizeof(int32_t), s));
-        ho.B = B;
-        ho.hull_rows = R;
-        ho.switched = dp.switched;
-        ho.ub = h->d_ub;
-        ho.stuck = h->d_stuck;
-        ho.hullA = h->d_hullA;
-        ho.hullset = wl->has_set ? h->d_hullset.p : nullptr;
-        ho.out_b = d_hbnew;
-        ho.flat = d_hflat;
-        hw.B = B;
-        hw.hull_rows = R;
-        hw.switched = dp.switched;
-        hw.flat = d_hflat;
-        hw.ub = h->d_ub;
-        hw.stuck = h->d_stuck;
-        hw.hullA = h->d_hullA;
-        hw.hullset = ho.hullset;
-        hw.new_b = d_hbnew;
-        hw.hullb = h->d_hullb;
-        hw.warmG = h->d_warmG;
-        hw.no_hull = d_hflat + B;
-    }
-    double* const d_truth = sense ? d_xtrue.p : h->d_x0.p;      // what the plant integrates and the outcomes measure
-    // a continued run (step0 > 0, and the handle's last loop with a sensor ended at that step, on this batch and form, in this x):
-    // its first solve is warm-started as the whole run's would be, from what the handle kept; otherwise it starts cold
-    const int64_t nkeep = B * (int64_t)N * (wl ? 6 : NT);
-    bool resume = false;
-    if (sense) {
-        resume = se->step0 > 0 && h->keep_step == se->step0 && h->keep_B == B && h->keep_wrench == (wl != nullptr) &&
-                 h->keep_x.size() == (size_t)B * 13 && std::memcmp(h->keep_x.data(), x, (size_t)B * 13 * sizeof(double)) == 0;
-        h->keep_step = -1;      // valid again only when this call ends well
-        if (resume)
-            HIP_TRY(h, hipMemcpyAsync(wl ? h->d_warmG.p : d_warmB.p, h->d_keep_warm, (size_t)nkeep * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    const int64_t xw = 9 * (int64_t)(N + 1 + L), uw = 6 * (int64_t)(N + 1 + L);     // doubles per window
-    ftmpc::RefWindow rw{};
-    if (windows) {
-        const size_t KC = (size_t)ms->n_tables * (size_t)ms->n_cols;
-        HIP_TRY(h, hipMalloc(&d_mtab.p, KC * 9 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_mtab, ms->xref, KC * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMalloc(&d_xwin.p, (size_t)(B * xw) * sizeof(double)));
-        if (ms->uref) {
-            HIP_TRY(h, hipMalloc(&d_mutab.p, KC * 6 * sizeof(double)));
-            HIP_TRY(h, hipMemcpyAsync(d_mutab, ms->uref, KC * 6 * sizeof(double), hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMalloc(&d_uwin.p, (size_t)(B * uw) * sizeof(double)));
-        }
-        if (ms->table) {
-            HIP_TRY(h, hipMalloc(&d_mtbl.p, (size_t)B * sizeof(int32_t)));
-            HIP_TRY(h, hipMemcpyAsync(d_mtbl, ms->table, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        if (ms->offset) {
-            HIP_TRY(h, hipMalloc(&d_moff.p, (size_t)B * sizeof(int32_t)));
-            HIP_TRY(h, hipMemcpyAsync(d_moff, ms->offset, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        rw.B = B;
-        rw.C = ms->n_cols;
-        rw.N1 = N + 1 + L;
-        rw.xtab = d_mtab;
-        rw.utab = d_mutab;
-        rw.table = d_mtbl;
-        rw.offset = d_moff;
-        rw.xwin = d_xwin;
-        rw.uwin = d_uwin;
-    }
-    ftmpc::MissionOut mo{};
-    if (want_cost) {     // the three sums, and q_0 of every vehicle from the staged x (pitch 13 -> 4 doubles)
-        HIP_TRY(h, hipMalloc(&d_cost.p, (size_t)B * 3 * sizeof(double)));
-        HIP_TRY(h, hipMemsetAsync(d_cost, 0, (size_t)B * 3 * sizeof(double), s));
-        HIP_TRY(h, hipMalloc(&d_qprev.p, (size_t)B * 4 * sizeof(double)));
-        HIP_TRY(h, hipMemcpy2DAsync(d_qprev, 4 * sizeof(double), h->d_x0 + 6, 13 * sizeof(double), 4 * sizeof(double), (size_t)B,
-                                 hipMemcpyDeviceToDevice, s));
-        mo.cost = d_cost;
-        mo.qprev = d_qprev;
-        mo.tcost = h->d_tcost;
-    }
-    ftmpc::SimParams sp;
-    sp.B = B;
-    sp.x = d_truth;
-    sp.u0 = h->d_u0;
-    sp.ub = h->d_ub;
-    sp.stuck = h->d_stuck;
-    for (int i = 0; i < 4; ++i) sp.noise[i] = noise[i];
-    sp.seed = seed;
-    sp.u_hist = d_hist;
-    sp.status = h->d_status;
-    sp.bad_count = d_bad;
-    sp.index0 = oc ? oc->index0 : 0;
-    sp.index_total = oc && oc->index_total != 0 ? oc->index_total : B;
-    if (x_hist) {
-        HIP_TRY(h, hipMalloc(&d_xhist.p, (size_t)T * B * 13 * sizeof(double)));
-        sp.x_hist = d_xhist;
-    }
-    ftmpc::OutcomeParams op{};
-    if (want_out) {
-        HIP_TRY(h, hipMalloc(&d_orec.p, (size_t)B * 8 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_oint.p, (size_t)B * 5 * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetAsync(d_orec, 0, (size_t)B * 8 * sizeof(double), s));
-        HIP_TRY(h, hipMemsetAsync(d_oint, 0, (size_t)B * 5 * sizeof(int32_t), s));
-        HIP_TRY(h, hipMemsetAsync(d_oint + B, 0xFF, (size_t)B * sizeof(int32_t), s));          // tset_step = -1
-        HIP_TRY(h, hipMemsetAsync(d_oint + 3 * B, 0xFF, (size_t)B * sizeof(int32_t), s));      // first_unsolved = -1
-        op.B = B;
-        op.x = d_truth;
-        op.u0 = h->d_u0;
-        op.astatus = wl ? h->d_ast2.p : nullptr;
-        op.err_int = d_orec;
-        op.err_max = d_orec + 3 * B;
-        op.impulse = d_orec + 6 * B;
-        op.settle = d_oint;
-        op.tset = d_oint + B;
-        op.unsolved = d_oint + 2 * B;
-        op.first_unsolved = d_oint + 3 * B;
-        op.alloc_failed = d_oint + 4 * B;
-        if (oc && oc->settle_step) {
-            op.tol[0] = oc->tol_pos;
-            op.tol[1] = oc->tol_vel;
-            op.tol[2] = oc->tol_rate;
-        }
-        if (oc && oc->tset_step) {
-            const int R = h->cfg.term_rows;
-            HIP_TRY(h, hipMalloc(&d_oterm.p, (size_t)R * 10 * sizeof(double)));
-            HIP_TRY(h, hipMemcpyAsync(d_oterm, h->cfg.term_A, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, s));
-            HIP_TRY(h, hipMemcpyAsync(d_oterm + R * 9, h->cfg.term_b, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
-            op.term = d_oterm;
-            op.term_rows = R;
-        }
-        if (oc && oc->status_hist) {
-            HIP_TRY(h, hipMalloc(&d_shist.p, (size_t)T * B * sizeof(int32_t)));
-            op.status_hist = d_shist;
-        }
-    }
-    const int64_t nw = B * (int64_t)N * NT;
-    std::vector<char> ev_step;         // steps at which some instance switches its plant or controller pattern
-    ftmpc::FaultEvents fe{};
-    if (E > 0) {
-        const int64_t BE = B * E;
-        std::vector<int32_t> ev((size_t)BE * 3, 0);
-        ev_step.assign((size_t)T, 0);
-        for (int64_t i = 0; i < BE; ++i) {
-            ev[i] = fs->onset[i];
-            // (under a diagnosis the schedule moves the plant only: no event is ever detected, and only onset steps launch the kernel)
-            ev[BE + i] = diag ? INT32_MAX : (fs->detect ? fs->detect[i] : fs->onset[i]);
-            if (wl && fs->hull_set) ev[2 * BE + i] = fs->hull_set[i];
-            if (ev[i] >= 0 && ev[i] < T) ev_step[ev[i]] = 1;
-            if (ev[i] >= 0 && ev[BE + i] < T) ev_step[ev[BE + i]] = 1;
-        }
-        HIP_TRY(h, hipMalloc(&d_fev.p, ev.size() * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc(&d_fpat.p, (size_t)BE * NT * 2 * sizeof(double)));
-        HIP_TRY(h, hipMalloc(&d_plant.p, (size_t)B * NT * 2 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_fev, ev.data(), ev.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_fpat, fs->ub, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_fpat + BE * NT, fs->stuck, (size_t)BE * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        if (wl && !diag) {     // (under a diagnosis no event is detected: the schedule carries no hull tables)
-            HIP_TRY(h, hipMalloc(&d_fhb.p, (size_t)BE * wl->hull_rows * sizeof(double)));
-            HIP_TRY(h, hipMemcpyAsync(d_fhb, fs->hull_b, (size_t)BE * wl->hull_rows * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        fe.B = B;
-        fe.E = E;
-        fe.onset = d_fev;
-        fe.detect = d_fev + BE;
-        fe.ev_ub = d_fpat;
-        fe.ev_stuck = d_fpat + BE * NT;
-        fe.plant_ub = d_plant;
-        fe.plant_stuck = d_plant + B * NT;
-        fe.ub = h->d_ub;
-        fe.stuck = h->d_stuck;
-        fe.warmU = wl ? nullptr : d_warmB.p;
-        if (wl) {
-            fe.warmG = h->d_warmG;
-            fe.hullA = h->d_hullA;
-            fe.ev_hullset = fs->hull_set ? d_fev + 2 * BE : nullptr;
-            fe.ev_hullb = d_fhb;
-            fe.hullset = wl->has_set ? h->d_hullset.p : nullptr;
-            fe.hullb = h->d_hullb;
-            fe.hull_rows = wl->hull_rows;
-        }
-        sp.ub = d_plant;
-        sp.stuck = d_plant + B * NT;
-    } else if (diag) {     // the plant keeps the call's pattern whatever the diagnosis makes of the controller's
-        HIP_TRY(h, hipMalloc(&d_plant.p, (size_t)B * NT * 2 * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(d_plant, ub, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d_plant + B * NT, stuck, (size_t)B * NT * sizeof(double), hipMemcpyHostToDevice, s));
-        sp.ub = d_plant;
-        sp.stuck = d_plant + B * NT;
-    }
-    for (int t = 0; t < T; ++t) {
-        if (E > 0 && ev_step[t]) {     // some instance switches its pattern at this step: before the solve
-            fe.t = t;
-            fe.repair = t > 0 || resume;
-            hipLaunchKernelGGL(ftmpc::ftmpc_fault_event_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, fe);
-            HIP_TRY(h, hipGetLastError());
-            // the work lists follow the new patterns: no small grid for a list that was empty the step before
-            h->qcnt_valid = false;
-            h->qcnt_pending = false;
-        }
-        // window t..t+N of the reference (column-major, so a plain pointer offset; under a mission with tables: every vehicle's own
-        // window, gathered here); warm start from step 1 on
-        if (windows) {
-            rw.t = t;
-            const int64_t nwin = B * (xw + (rw.utab ? uw : 0));
-            hipLaunchKernelGGL(ftmpc::ftmpc_ref_window_kernel, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, s, rw);
-            HIP_TRY(h, hipGetLastError());
-        }
-        // (under a predicting sensor the solve's window starts L columns later; xo_t / uo_t: the step's own columns, for the outcomes)
-        const double* const xo_t = windows ? d_xwin.p : d_xr + (int64_t)9 * t;
-        const double* const uo_t = !has_uref ? nullptr : (windows ? d_uwin.p : d_ur + (int64_t)6 * t);
-        const double* const xr_t = xo_t + (int64_t)9 * L;
-        const double* const ur_t = uo_t ? uo_t + (int64_t)6 * L : nullptr;
-        if (sensing) {     // y_t (and its propagation over the queue) into h->d_x0; slot t mod (lat + 1) holds a_t
-            sn.cstep = se->step0 + t;
-            sn.step = t;
-            sn.slot0 = t % (lat + 1);
-            hipLaunchKernelGGL(ftmpc::ftmpc_sense_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sn);
-            HIP_TRY(h, hipGetLastError());
-        }
-        if (diag) {     // test, decision and re-anchor on y_t; a vehicle that switched has its shifted warm start clipped to the new bounds
-            dp.init = t == 0 && !dg->state;
-            dp.anchor = (se->step0 + t) % dg->every == 0;
-            dp.cstep = (int32_t)(se->step0 + t);
-            dp.step = t;
-            hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
-            if (wl) {     // two launches: the switch kernel's lanes read the offsets the first one wrote
-                hw.repair = t > 0 || resume;
-                hw.cstep = dp.cstep;
-                hipLaunchKernelGGL(ftmpc::ftmpc_hull_offsets_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, ho);
-                hipLaunchKernelGGL(ftmpc::ftmpc_hull_switch_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, h->dc, hw);
-            } else if (t > 0 || resume)
-                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_repair_kernel, dim3((unsigned)((B * N + 63) / 64)), dim3(64), 0, s, B, N, NT,
-                                   (const int32_t*)dp.switched, (const double*)h->d_ub, d_warmB.p);
-            HIP_TRY(h, hipGetLastError());
-            // a pattern can change at any step without the host knowing: no small grid for a list that was empty the step before
-            h->qcnt_valid = false;
-            h->qcnt_pending = false;
-            if (!sensing && !est)     // nobody else writes the solve's x0: it is the truth
-                HIP_TRY(h, hipMemcpyAsync(h->d_x0, d_xtrue, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        if (est) {     // the update on y_t, the estimate (propagated over the queue when the sensor predicts) into h->d_x0
-            fp.init = t == 0 && !es->xhat;
-            fp.update = (se->step0 + t) % es->every == 0;
-            fp.step = t;
-            fp.slot0 = t % (lat + 1);
-            if (dist) {     // the x pass and the d pass of the augmented update; the d pass writes the solve's x0
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
-            } else if (bias) {     // the x pass in measured coordinates and the bias pass, which completes x^ and writes the solve's x0
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
-            } else
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
-            HIP_TRY(h, hipGetLastError());
-        }
-        const int64_t xr_s = windows ? xw : 0, ur_s = windows ? uw : 0;
-        const double* Ufin = h->d_U;
-        const double* Gfin = h->d_G;
-        if (wl && sqp_iters > 0) {     // the two-stage structure with the nonlinear program of this step solved by the wrench SQP
-            ftmpc::SqpState S;
-            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into every linearisation and cost launch
-            rc = sqpw_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
-                              (t > 0 || resume) ? h->d_warmG.p : nullptr, sqp_iters, backtracks, tol, wl->penalty, false, S);
-            h->lin_dist = nullptr;
-            if (rc == FTMPC_OK) {
-                Gfin = S.U;
-                sp.status = S.status;
-                if (d_abad)
-                    hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B,
-                                       (const int32_t*)h->d_ast2, d_abad + t);
-            }
-        } else if (sqp_iters > 0) {     // the nonlinear program of this step by the line-search SQP, started from the shifted previous solution
-            ftmpc::SqpState S;
-            double* J0 = nullptr;
-            rc = sqp_enqueue(h, B, xr_t, xr_s, ur_t, ur_s, (t > 0 || resume) ? d_warmB.p : nullptr, sqp_iters, backtracks, tol, S, &J0);
-            if (rc == FTMPC_OK) {
-                Ufin = S.U;
-                sp.status = S.status;
-                HIP_TRY(h, hipMemcpy2DAsync(h->d_u0, NT * sizeof(double), S.U, (size_t)N * NT * sizeof(double), NT * sizeof(double), (size_t)B,
-                                         hipMemcpyDeviceToDevice, s));
-            }
-        } else if (wl) {         // the reference's two-stage structure: wrench MPC with the hull rows, then allocation
-            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into the linearisation
-            rc = wrench_enqueue(h, B, wl->hull_rows, wl->has_set, xr_t, xr_s, ur_t, ur_s,
-                                (t > 0 || resume) ? h->d_warmG.p : nullptr);
-            h->lin_dist = nullptr;
-            if (rc == FTMPC_OK && d_abad)
-                hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, (const int32_t*)h->d_ast2,
-                                   d_abad + t);
-        } else {
-            h->lin_dist = dist && db->compensate ? d_dest.p : nullptr;      // d^_{t|t} into the linearisation
-            rc = enqueue(h, B, h->d_x0, h->d_ub, h->d_stuck, xr_t, xr_s, ur_t, ur_s,
-                         (t > 0 || resume) ? d_warmB.p : nullptr, h->d_u0, h->d_U, h->d_status, h->d_iters, s, -1);
-            h->lin_dist = nullptr;
-        }
-        if (rc != FTMPC_OK) return rc;
-        if (lat > 0) {     // u_t waits lat steps: into the slot behind the newest; the plant and the outcomes get the slot of a_t
-            HIP_TRY(h, hipMemcpyAsync(d_ring + (size_t)((t + lat) % (lat + 1)) * nu, h->d_u0, nu * sizeof(double), hipMemcpyDeviceToDevice, s));
-            sp.u0 = op.u0 = d_ring + (size_t)(t % (lat + 1)) * nu;
-        }
-        sp.step = t;
-        if (act)
-            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_act_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv, ap);
-        else if (var_plant)
-            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_var_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp, pv);
-        else
-            hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, sp);
-        if (est) {     // the time update under a_t and the controller's pattern of this step
-            fp.u = sp.u0;
-            if (dist) {     // P_xx, then P_xd, P_dd, the cross terms of P_xx and the mean
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<2>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_dist_kernel<3>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, dq);
-            } else if (bias) {     // P_mm, then P_mb, P_bb, the cross terms of P_mm and the mean
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<2>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<3>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp, bq);
-            } else
-                hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, fp);
-        }
-        if (diag) {     // the model's step under a_t and the controller's pattern of this step (with the estimate: d^_{t|t})
-            dp.u = sp.u0;
-            if (dist)
-                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_dist_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp,
-                                   (const double*)d_dest.p);
-            else
-                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<1>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, dp);
-        }
-        if (want_out) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
-            op.step = t;
-            op.ub = sp.ub;
-            op.stuck = sp.stuck;
-            op.status = sp.status;
-            if (windows || want_cost) {     // a column per vehicle (column 1 of its window, column 0 of its uref window) and / or the cost
-                mo.xref = xo_t + 9;
-                mo.xref_stride = xr_s;
-                mo.uref = uo_t;
-                mo.uref_stride = ur_s;
-                hipLaunchKernelGGL(ftmpc::ftmpc_outcome_mission_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op, mo);
-            } else {
-                op.xref = d_xr + (int64_t)9 * (t + 1);
-                hipLaunchKernelGGL(ftmpc::ftmpc_outcome_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, h->dc, op);
-            }
-        }
-        if (wl)     // wrench warm start: shifted by one stage, the last stage repeats
-            hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((B * N * 6 + 255) / 256)), dim3(256), 0, s, B, N, 6,
-                               Gfin, h->d_warmG, 1);
-        else
-            hipLaunchKernelGGL(ftmpc::ftmpc_shift_warm_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, B, N, NT, Ufin, d_warmB, 0);
-        HIP_TRY(h, hipGetLastError());
-    }
-    HIP_TRY(h, hipMemcpyAsync(x, d_truth, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (sense) {
-        if ((rc = h->d_keep_warm.ensure(h, nkeep)) != FTMPC_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_keep_warm, wl ? h->d_warmG.p : d_warmB.p, (size_t)nkeep * sizeof(double), hipMemcpyDeviceToDevice, s));
-        if (se->meas_hist) HIP_TRY(h, hipMemcpyAsync(se->meas_hist, d_mhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (se->pred_hist) HIP_TRY(h, hipMemcpyAsync(se->pred_hist, d_phist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (se->pending)      // c_T .. c_{T+lat-1}: the slots from T mod (lat + 1) on, oldest first
-            for (int j = 0; j < lat; ++j)
-                HIP_TRY(h, hipMemcpyAsync(h_ring.data() + (size_t)j * nu, d_ring + (size_t)((T + j) % (lat + 1)) * nu, nu * sizeof(double),
-                                          hipMemcpyDeviceToHost, s));
-    }
-    if (est) {
-        if (es->est_hist) HIP_TRY(h, hipMemcpyAsync(es->est_hist, d_ehist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (es->err_sq) HIP_TRY(h, hipMemcpyAsync(es->err_sq, d_esq, (size_t)B * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (es->xhat) HIP_TRY(h, hipMemcpyAsync(es->xhat, d_xhat, (size_t)B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (es->cov) HIP_TRY(h, hipMemcpyAsync(h_cov.data(), d_cov, (size_t)B * 78 * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    if (dist) {
-        if (db->force_hist) HIP_TRY(h, hipMemcpyAsync(db->force_hist, d_dfh, (size_t)T * B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (db->torque_hist) HIP_TRY(h, hipMemcpyAsync(db->torque_hist, d_dth, (size_t)T * B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (db->force || db->torque) HIP_TRY(h, hipMemcpyAsync(h_dest.data(), d_dest, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (db->cross) HIP_TRY(h, hipMemcpyAsync(h_dcross.data(), d_dcross, (size_t)B * 72 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (db->cov) HIP_TRY(h, hipMemcpyAsync(h_dcovd.data(), d_dcovd, (size_t)B * 21 * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    if (bias) {
-        if (be->bias_hist) HIP_TRY(h, hipMemcpyAsync(be->bias_hist, d_bhist, (size_t)T * B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (be->bias) HIP_TRY(h, hipMemcpyAsync(be->bias, d_best, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (be->cross) HIP_TRY(h, hipMemcpyAsync(h_bcross.data(), d_bcross, (size_t)B * 72 * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (be->cov) HIP_TRY(h, hipMemcpyAsync(h_bcovb.data(), d_bcovb, (size_t)B * 21 * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    if (diag) {
-        if (dg->llr_hist) HIP_TRY(h, hipMemcpyAsync(dg->llr_hist, d_dhist, (size_t)(T * B * dH) * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (dg->ub) HIP_TRY(h, hipMemcpyAsync(dg->ub, h->d_ub, (size_t)B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (dg->stuck) HIP_TRY(h, hipMemcpyAsync(dg->stuck, h->d_stuck, (size_t)B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (dg->state) {
-            HIP_TRY(h, hipMemcpyAsync(h_dxt.data(), d_dxt, h_dxt.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipMemcpyAsync(h_dacc.data(), d_dacc, h_dacc.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipMemcpyAsync(h_ddet.data(), d_ddet, h_ddet.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            if (dg->llr) HIP_TRY(h, hipMemcpyAsync(h_dllr.data(), d_dllr, h_dllr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        }
-    }
-    if (wl && wl->out_hull_b)
-        HIP_TRY(h, hipMemcpyAsync(wl->out_hull_b, h->d_hullb, (size_t)B * wl->hull_rows * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (diag && wl && wl->no_hull_step)
-        HIP_TRY(h, hipMemcpyAsync(wl->no_hull_step, d_hflat + B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (u_hist) HIP_TRY(h, hipMemcpyAsync(u_hist, d_hist, (size_t)T * B * NT * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xhist, (size_t)T * B * 13 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (not_converged) HIP_TRY(h, hipMemcpyAsync(not_converged, d_bad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (d_abad) HIP_TRY(h, hipMemcpyAsync(wl->alloc_failed, d_abad, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (want_cost) HIP_TRY(h, hipMemcpyAsync(ms->cost, d_cost, (size_t)B * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (want_out && oc) {
-        double* const rec[3] = {oc->err_int, oc->err_max, oc->impulse};
-        const int64_t rec_off[3] = {0, 3 * B, 6 * B}, rec_n[3] = {3 * B, 3 * B, 2 * B};
-        for (int i = 0; i < 3; ++i)
-            if (rec[i]) HIP_TRY(h, hipMemcpyAsync(rec[i], d_orec + rec_off[i], (size_t)rec_n[i] * sizeof(double), hipMemcpyDeviceToHost, s));
-        int32_t* const cnt[5] = {oc->settle_step, oc->tset_step, oc->unsolved, oc->first_unsolved, oc->alloc_failed};
-        for (int i = 0; i < 5; ++i)
-            if (cnt[i]) HIP_TRY(h, hipMemcpyAsync(cnt[i], d_oint + i * B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (oc->status_hist)
-            HIP_TRY(h, hipMemcpyAsync(oc->status_hist, d_shist, (size_t)T * B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (act) {
-        const size_t nv = (size_t)B * NT;
-        if (ac->delivered) HIP_TRY(h, hipMemcpyAsync(ac->delivered, d_adel, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (ac->pulses) HIP_TRY(h, hipMemcpyAsync(ac->pulses, d_apul, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (ac->applied_hist) HIP_TRY(h, hipMemcpyAsync(ac->applied_hist, d_aapp, (size_t)T * nv * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (ac->ticks_hist) HIP_TRY(h, hipMemcpyAsync(ac->ticks_hist, d_atick, (size_t)T * nv * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (ac->state) HIP_TRY(h, hipMemcpyAsync(h_aval.data(), d_aval, nv * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (act && ac->state)
-        for (int64_t b = 0; b < B; ++b)
-            for (int i = 0; i < NT; ++i) ac->state[b * NT + i] = h_aval[(size_t)i * B + b];
-    if (diag && dg->state) {
-        const int64_t w = 14 + NT;
-        for (int64_t b = 0; b < B; ++b) {
-            for (int k = 0; k < 14; ++k) dg->state[b * w + k] = h_dxt[(size_t)b * 14 + k];
-            for (int i = 0; i < NT; ++i) dg->state[b * w + 14 + i] = h_dacc[(size_t)i * B + b];
-            for (int k = 0; k < dK; ++k) {
-                dg->detect_step[b * dK + k] = h_ddet[(size_t)(2 * B + b * dK + k)];
-                dg->detect_thruster[b * dK + k] = h_ddet[(size_t)(2 * B + (B + b) * dK + k)];
-                dg->detect_level[b * dK + k] = h_ddet[(size_t)(2 * B + (2 * B + b) * dK + k)];
-            }
-            if (dg->llr)
-                for (int64_t k = 0; k < dH; ++k) dg->llr[b * dH + k] = h_dllr[(size_t)(k * B + b)];
-        }
-    }
-    if (dist) {
-        for (int64_t b = 0; b < B; ++b)
-            for (int k = 0; k < 3; ++k) {
-                if (db->force) db->force[b * 3 + k] = h_dest[(size_t)b * 6 + k];
-                if (db->torque) db->torque[b * 3 + k] = h_dest[(size_t)b * 6 + 3 + k];
-            }
-        for (int64_t b0 = 0; b0 < B; b0 += 64) {
-            const int64_t b1 = std::min(B, b0 + 64);
-            if (db->cross)
-                for (int64_t k = 0; k < 72; ++k)
-                    for (int64_t b = b0; b < b1; ++b) db->cross[b * 72 + k] = h_dcross[(size_t)k * B + b];
-            if (db->cov)
-                for (int64_t k = 0; k < 21; ++k)
-                    for (int64_t b = b0; b < b1; ++b) db->cov[b * 21 + k] = h_dcovd[(size_t)k * B + b];
-        }
-    }
-    if (bias)
-        for (int64_t b0 = 0; b0 < B; b0 += 64) {
-            const int64_t b1 = std::min(B, b0 + 64);
-            if (be->cross)
-                for (int64_t k = 0; k < 72; ++k)
-                    for (int64_t b = b0; b < b1; ++b) be->cross[b * 72 + k] = h_bcross[(size_t)k * B + b];
-            if (be->cov)
-                for (int64_t k = 0; k < 21; ++k)
-                    for (int64_t b = b0; b < b1; ++b) be->cov[b * 21 + k] = h_bcovb[(size_t)k * B + b];
-        }
-    if (est && es->cov)
-        for (int64_t b0 = 0; b0 < B; b0 += 64) {
-            const int64_t b1 = std::min(B, b0 + 64);
-            for (int64_t k = 0; k < 78; ++k)
-                for (int64_t b = b0; b < b1; ++b) es->cov[b * 78 + k] = h_cov[(size_t)k * B + b];
-        }
-    if (sense) {
-        try {
-            h->keep_x.assign(x, x + B * 13);
-            h->keep_B = B;
-            h->keep_wrench = wl != nullptr;
-            h->keep_step = se->step0 + T;
-        } catch (const std::bad_alloc&) {
-            h->keep_step = -1;      // nothing kept: the next call starts cold
-        }
-    }
-    if (sense && se->pending)
-        for (int64_t b = 0; b < B; ++b)
-            for (int j = 0; j < lat; ++j)
-                for (int i = 0; i < NT; ++i) se->pending[(b * lat + j) * NT + i] = h_ring[(size_t)j * nu + b * NT + i];
-    return FTMPC_OK;
-}
+extern "C" {
 
 #ifdef FTMPC_STAMPS
 /* diagnostic build only: copies the per-instance phase cycle totals (12 u64 per instance, first

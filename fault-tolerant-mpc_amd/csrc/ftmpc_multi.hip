@@ -208,74 +208,64 @@ void scatter_rows(V* dst, const V* src, int64_t T, int64_t B, int64_t lo, int64_
 // form): slot g runs its shard [lo, hi) through the single-handle entry as the slice index0 = lo of a campaign of B, reading the
 // caller's per-vehicle arrays at the shard's offset and writing the per-vehicle outputs there; a history goes through a shard-sized
 // staging array and is copied row by row (one slot: straight into the caller's), the per-step counts are summed afterwards.
-int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck, const double* hull_A,
-                   int32_t n_sets, const int32_t* hull_set, const double* hull_b, int32_t hull_rows, const double* xref_traj,
-                   const double* uref_traj, const double* noise, uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
-                   double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
-                   int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant, const ftmpc_mission* mission,
-                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, bool wrench,
-                   const ftmpc_diagnosis* diagnosis = nullptr, double* out_hull_b = nullptr, int32_t* no_hull_step = nullptr,
-                   const ftmpc_disturbance* disturbance = nullptr, const ftmpc_bias_estimate* bias_estimate = nullptr) {
+int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
     if (!m) return FTMPC_ERR_ARG;
+    const int64_t B = c.B;
+    const int32_t T = c.T;
     auto refuse = [m](const std::string& msg) {
         m->err = msg;
         return FTMPC_ERR_ARG;
     };
-    if (B < 0 || T < 0 || !x || !ub || !stuck || !noise || (wrench && (!hull_A || !hull_b || hull_rows < 1)))
+    if (B < 0 || T < 0 || !c.x || !c.ub || !c.stuck || !c.noise || (c.wrench && (!c.hull_A || !c.hull_b || c.hull_rows < 1)))
         return refuse("null buffer or negative size");
-    if (out && out->struct_size != (int32_t)sizeof(ftmpc_outcomes))
-        return refuse("ftmpc_outcomes.struct_size is " + std::to_string(out->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_outcomes)));
-    if (out && (out->index0 != 0 || (out->index_total != 0 && out->index_total != B)))
+    if (c.oc && c.oc->struct_size != (int32_t)sizeof(ftmpc_outcomes))
+        return refuse("ftmpc_outcomes.struct_size is " + std::to_string(c.oc->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_outcomes)));
+    if (c.oc && (c.oc->index0 != 0 || (c.oc->index_total != 0 && c.oc->index_total != B)))
         return refuse("ftmpc_outcomes.index0 / index_total are set per device slot by the multi-GPU driver: pass 0 / 0 or 0 / B");
-    if (faults && faults->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return refuse("ftmpc_fault_schedule: bad struct_size");
-    if (faults && (faults->n_events < 0 || faults->n_events > FTMPC_MAX_FAULT_EVENTS))
+    if (c.fs && c.fs->struct_size != (int32_t)sizeof(ftmpc_fault_schedule)) return refuse("ftmpc_fault_schedule: bad struct_size");
+    if (c.fs && (c.fs->n_events < 0 || c.fs->n_events > FTMPC_MAX_FAULT_EVENTS))
         return refuse("ftmpc_fault_schedule: n_events outside [0, FTMPC_MAX_FAULT_EVENTS]");
     {     // the plant model over the whole batch, so that a refusal names the vehicle by its number in the caller's arrays
-        const std::string msg = plant_model_problem(plant, B, m->cfg.NT);
+        const std::string msg = plant_model_problem(c.pm, B, m->cfg.NT);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the sensor likewise: the parameters are uniform, bias / pending and the two histories are per vehicle
-        const std::string msg = sensor_problem(sensor, B, m->cfg.NT);
+        const std::string msg = sensor_problem(c.se, B, m->cfg.NT);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the estimator likewise: the parameters are uniform, xhat / cov, est_hist and err_sq are per vehicle
-        const std::string msg = estimator_problem(estimator, B);
+        const std::string msg = estimator_problem(c.es, B);
         if (!msg.empty()) return refuse(msg);
     }
-    if (diagnosis) {     // the diagnosis likewise: the parameters are uniform, the state and the outputs per vehicle
-        if (wrench) {
-            const std::string msg = wrench_diagnosis_problem(faults, no_hull_step, B);
+    if (c.dg) {     // the diagnosis likewise: the parameters are uniform, the state and the outputs per vehicle
+        if (c.wrench) {
+            const std::string msg = wrench_diagnosis_problem(c.fs, c.no_hull_step, B);
             if (!msg.empty()) return refuse(msg);
         }
-        if (faults && faults->n_events > 0 && (!faults->onset || !faults->ub || !faults->stuck))
+        if (c.fs && c.fs->n_events > 0 && (!c.fs->onset || !c.fs->ub || !c.fs->stuck))
             return refuse("ftmpc_fault_schedule: null onset / ub / stuck");
-        const std::string msg = diagnosis_problem(diagnosis, B, m->cfg.NT, estimator, faults, sensor);
+        const std::string msg = diagnosis_problem(c.dg, B, m->cfg.NT, c.es, c.fs, c.se);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the disturbance estimate likewise: the parameters are uniform, force / torque / cross / cov and the histories per vehicle
-        const std::string msg = disturbance_problem(disturbance, B, estimator, wrench ? 0 : sqp_iters);      // (the wrench SQP is served)
+        const std::string msg = disturbance_problem(c.db, B, c.es, c.wrench ? 0 : c.sqp_iters);      // (the wrench SQP is served)
         if (!msg.empty()) return refuse(msg);
     }
     {     // the bias estimate likewise (thruster form only): the parameters are uniform, bias / cross / cov and the history per vehicle
-        const std::string msg = bias_problem(bias_estimate, B, estimator, disturbance);
+        const std::string msg = bias_problem(c.be, B, c.es, c.db);
         if (!msg.empty()) return refuse(msg);
     }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
-        const std::string msg = mission_problem(mission, B, T, m->cfg.N, xref_traj, uref_traj, 0, sensor_shift(sensor));
+        const std::string msg = mission_problem(c.ms, B, T, m->cfg.N, c.xref_traj, c.uref_traj, 0, sensor_shift(c.se));
         if (!msg.empty()) return refuse(msg);
     }
     {     // the actuator likewise: the parameters are uniform, delivered / pulses / state and the two histories are per vehicle.  (The
           // handle entry checks each shard's struct again, state included: what passed here cannot fail there.)
-        const std::string msg = actuator_problem(actuator, B, m->cfg.NT);
+        const std::string msg = actuator_problem(c.ac, B, m->cfg.NT);
         if (!msg.empty()) return refuse(msg);
     }
     if (B == 0 || T == 0) {
-        zero_mission_cost(mission, B);
-        zero_actuator_sums(actuator, B);
-        if (estimator && estimator->err_sq && B > 0) std::fill(estimator->err_sq, estimator->err_sq + B * 4, 0.0);
-        if (diagnosis && diagnosis->ub && B > 0) std::copy(ub, ub + B * m->cfg.NT, diagnosis->ub);
-        if (diagnosis && diagnosis->stuck && B > 0) std::copy(stuck, stuck + B * m->cfg.NT, diagnosis->stuck);
-        if (wrench && out_hull_b && B > 0) std::copy(hull_b, hull_b + B * hull_rows, out_hull_b);
+        loop_empty(c, m->cfg.NT);
         return FTMPC_OK;
     }
     const int G = (int)m->dev.size();
@@ -288,19 +278,19 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         shard(B, G, g, lo, hi);
         const int64_t n = hi - lo;
         ftmpc_fault_schedule fs{};
-        if (faults) {
-            fs = *faults;
+        if (c.fs) {
+            fs = *c.fs;
             const int64_t E = fs.n_events;
             if (fs.onset) fs.onset += lo * E;
             if (fs.detect) fs.detect += lo * E;
             if (fs.ub) fs.ub += lo * E * NT;
             if (fs.stuck) fs.stuck += lo * E * NT;
             if (fs.hull_set) fs.hull_set += lo * E;
-            if (fs.hull_b) fs.hull_b += lo * E * hull_rows;
+            if (fs.hull_b) fs.hull_b += lo * E * c.hull_rows;
         }
         ftmpc_plant_model pl{};
-        if (plant) {
-            pl = *plant;
+        if (c.pm) {
+            pl = *c.pm;
             if (pl.mass) pl.mass += lo;
             if (pl.J) pl.J += lo * 9;
             if (pl.D) pl.D += lo * 6 * NT;
@@ -308,8 +298,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (pl.torque) pl.torque += lo * 3;
         }
         ftmpc_mission mi{};
-        if (mission) {
-            mi = *mission;
+        if (c.ms) {
+            mi = *c.ms;
             if (mi.table) mi.table += lo;
             if (mi.offset) mi.offset += lo;
             if (mi.cost) mi.cost += lo * 3;
@@ -322,31 +312,31 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         std::vector<double> uh, xh, ah;
         std::vector<int32_t> sh, kh;
         ftmpc_actuator at{};
-        if (actuator) {
-            at = *actuator;
+        if (c.ac) {
+            at = *c.ac;
             if (at.delivered) at.delivered += lo;
             if (at.pulses) at.pulses += lo;
             if (at.state) at.state += lo * NT;
         }
         std::vector<double> mh, ph;
         ftmpc_sensor sv{};
-        if (sensor) {
-            sv = *sensor;
+        if (c.se) {
+            sv = *c.se;
             if (sv.bias) sv.bias += lo * 12;
             if (sv.pending) sv.pending += lo * sv.latency * NT;
         }
         std::vector<double> eh;
         ftmpc_estimator ev{};
-        if (estimator) {
-            ev = *estimator;
+        if (c.es) {
+            ev = *c.es;
             if (ev.xhat) ev.xhat += lo * 13;
             if (ev.cov) ev.cov += lo * 78;
             if (ev.err_sq) ev.err_sq += lo * 4;
         }
         std::vector<double> lh;
         ftmpc_diagnosis dv{};
-        if (diagnosis) {
-            dv = *diagnosis;
+        if (c.dg) {
+            dv = *c.dg;
             const int64_t K = dv.max_detect, H = (int64_t)NT * dv.n_levels;
             if (dv.state) dv.state += lo * (14 + NT);
             if (dv.llr) dv.llr += lo * H;
@@ -358,8 +348,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         }
         std::vector<double> fh, th;
         ftmpc_disturbance bv{};
-        if (disturbance) {
-            bv = *disturbance;
+        if (c.db) {
+            bv = *c.db;
             if (bv.force) bv.force += lo * 3;
             if (bv.torque) bv.torque += lo * 3;
             if (bv.cross) bv.cross += lo * 72;
@@ -367,8 +357,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
         }
         std::vector<double> bh;
         ftmpc_bias_estimate sb{};
-        if (bias_estimate) {
-            sb = *bias_estimate;
+        if (c.be) {
+            sb = *c.be;
             if (sb.bias) sb.bias += lo * 6;
             if (sb.cross) sb.cross += lo * 72;
             if (sb.cov) sb.cov += lo * 21;
@@ -383,30 +373,30 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (sv.pred_hist && !whole) ph.resize((size_t)T * n * 13);
             bad[g].assign((size_t)T, 0);
             abad[g].assign((size_t)T, 0);
-            if (u_hist && !whole) uh.resize((size_t)T * n * NT);
-            if (x_hist && !whole) xh.resize((size_t)T * n * 13);
-            if (out && out->status_hist && !whole) sh.resize((size_t)T * n);
+            if (c.u_hist && !whole) uh.resize((size_t)T * n * NT);
+            if (c.x_hist && !whole) xh.resize((size_t)T * n * 13);
+            if (c.oc && c.oc->status_hist && !whole) sh.resize((size_t)T * n);
             if (at.applied_hist && !whole) ah.resize((size_t)T * n * NT);
             if (at.ticks_hist && !whole) kh.resize((size_t)T * n * NT);
         } catch (const std::bad_alloc&) {
             return dev_fail(d, FTMPC_ERR_ALLOC, "out of host memory for the shard's histories");
         }
-        if (out) {
-            oc.tol_pos = out->tol_pos;
-            oc.tol_vel = out->tol_vel;
-            oc.tol_rate = out->tol_rate;
-            oc.err_int = out->err_int ? out->err_int + lo * 3 : nullptr;
-            oc.err_max = out->err_max ? out->err_max + lo * 3 : nullptr;
-            oc.impulse = out->impulse ? out->impulse + lo * 2 : nullptr;
-            oc.settle_step = out->settle_step ? out->settle_step + lo : nullptr;
-            oc.tset_step = out->tset_step ? out->tset_step + lo : nullptr;
-            oc.unsolved = out->unsolved ? out->unsolved + lo : nullptr;
-            oc.first_unsolved = out->first_unsolved ? out->first_unsolved + lo : nullptr;
-            oc.alloc_failed = out->alloc_failed ? out->alloc_failed + lo : nullptr;
-            oc.status_hist = !out->status_hist ? nullptr : (whole ? out->status_hist : sh.data());
+        if (c.oc) {
+            oc.tol_pos = c.oc->tol_pos;
+            oc.tol_vel = c.oc->tol_vel;
+            oc.tol_rate = c.oc->tol_rate;
+            oc.err_int = c.oc->err_int ? c.oc->err_int + lo * 3 : nullptr;
+            oc.err_max = c.oc->err_max ? c.oc->err_max + lo * 3 : nullptr;
+            oc.impulse = c.oc->impulse ? c.oc->impulse + lo * 2 : nullptr;
+            oc.settle_step = c.oc->settle_step ? c.oc->settle_step + lo : nullptr;
+            oc.tset_step = c.oc->tset_step ? c.oc->tset_step + lo : nullptr;
+            oc.unsolved = c.oc->unsolved ? c.oc->unsolved + lo : nullptr;
+            oc.first_unsolved = c.oc->first_unsolved ? c.oc->first_unsolved + lo : nullptr;
+            oc.alloc_failed = c.oc->alloc_failed ? c.oc->alloc_failed + lo : nullptr;
+            oc.status_hist = !c.oc->status_hist ? nullptr : (whole ? c.oc->status_hist : sh.data());
         }
-        double* const uh_p = !u_hist ? nullptr : (whole ? u_hist : uh.data());
-        double* const xh_p = !x_hist ? nullptr : (whole ? x_hist : xh.data());
+        double* const uh_p = !c.u_hist ? nullptr : (whole ? c.u_hist : uh.data());
+        double* const xh_p = !c.x_hist ? nullptr : (whole ? c.x_hist : xh.data());
         if (!whole) {
             if (at.applied_hist) at.applied_hist = ah.data();
             if (at.ticks_hist) at.ticks_hist = kh.data();
@@ -418,37 +408,35 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             if (bv.torque_hist) bv.torque_hist = th.data();
             if (sb.bias_hist) sb.bias_hist = bh.data();
         }
-        const int rc2 = wrench ? ftmpc_simulate_wrench_disturbance_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, hull_A, n_sets,
-                                                                       hull_set ? hull_set + lo : nullptr, hull_b + lo * hull_rows, hull_rows,
-                                                                       xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty,
-                                                                       faults ? &fs : nullptr, uh_p, xh_p, bad[g].data(),
-                                                                       alloc_failed ? abad[g].data() : nullptr, &oc, plant ? &pl : nullptr,
-                                                                       mission ? &mi : nullptr, actuator ? &at : nullptr,
-                                                                       sensor ? &sv : nullptr, estimator ? &ev : nullptr,
-                                                                       diagnosis ? &dv : nullptr,
-                                                                       out_hull_b ? out_hull_b + lo * hull_rows : nullptr,
-                                                                       no_hull_step ? no_hull_step + lo : nullptr,
-                                                                       disturbance ? &bv : nullptr)
-                               : ftmpc_simulate_bias_batch(d.h, n, T, x + lo * 13, ub + lo * NT, stuck + lo * NT, xref_traj, uref_traj, noise,
-                                                          seed, sqp_iters, backtracks, tol, faults ? &fs : nullptr, uh_p, xh_p,
-                                                          bad[g].data(), &oc, plant ? &pl : nullptr, mission ? &mi : nullptr,
-                                                          actuator ? &at : nullptr, sensor ? &sv : nullptr, estimator ? &ev : nullptr,
-                                                          diagnosis ? &dv : nullptr, disturbance ? &bv : nullptr,
-                                                          bias_estimate ? &sb : nullptr);
+        LoopCall sc = c;      // the shard as a call of its own: the path of the single-handle entry
+        sc.B = n;
+        sc.x = c.x + lo * 13, sc.ub = c.ub + lo * NT, sc.stuck = c.stuck + lo * NT;
+        if (c.wrench) {
+            sc.hull_set = c.hull_set ? c.hull_set + lo : nullptr;
+            sc.hull_b = c.hull_b + lo * c.hull_rows;
+            sc.alloc_failed = c.alloc_failed ? abad[g].data() : nullptr;
+            sc.out_hull_b = c.out_hull_b ? c.out_hull_b + lo * c.hull_rows : nullptr;
+            sc.no_hull_step = c.no_hull_step ? c.no_hull_step + lo : nullptr;
+        }
+        sc.u_hist = uh_p, sc.x_hist = xh_p, sc.not_converged = bad[g].data();
+        sc.fs = c.fs ? &fs : nullptr, sc.oc = &oc, sc.pm = c.pm ? &pl : nullptr, sc.ms = c.ms ? &mi : nullptr, sc.ac = c.ac ? &at : nullptr;
+        sc.se = c.se ? &sv : nullptr, sc.es = c.es ? &ev : nullptr, sc.dg = c.dg ? &dv : nullptr, sc.db = c.db ? &bv : nullptr;
+        sc.be = c.be ? &sb : nullptr;
+        const int rc2 = loop_run(d.h, sc);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
-            if (u_hist) scatter_rows(u_hist, uh.data(), T, B, lo, n, NT);
-            if (x_hist) scatter_rows(x_hist, xh.data(), T, B, lo, n, 13);
-            if (out && out->status_hist) scatter_rows(out->status_hist, sh.data(), T, B, lo, n, 1);
-            if (actuator && actuator->applied_hist) scatter_rows(actuator->applied_hist, ah.data(), T, B, lo, n, NT);
-            if (actuator && actuator->ticks_hist) scatter_rows(actuator->ticks_hist, kh.data(), T, B, lo, n, NT);
-            if (sensor && sensor->meas_hist) scatter_rows(sensor->meas_hist, mh.data(), T, B, lo, n, 13);
-            if (sensor && sensor->pred_hist) scatter_rows(sensor->pred_hist, ph.data(), T, B, lo, n, 13);
-            if (estimator && estimator->est_hist) scatter_rows(estimator->est_hist, eh.data(), T, B, lo, n, 13);
-            if (diagnosis && diagnosis->llr_hist) scatter_rows(diagnosis->llr_hist, lh.data(), T, B, lo, n, (int64_t)NT * dv.n_levels);
-            if (disturbance && disturbance->force_hist) scatter_rows(disturbance->force_hist, fh.data(), T, B, lo, n, 3);
-            if (disturbance && disturbance->torque_hist) scatter_rows(disturbance->torque_hist, th.data(), T, B, lo, n, 3);
-            if (bias_estimate && bias_estimate->bias_hist) scatter_rows(bias_estimate->bias_hist, bh.data(), T, B, lo, n, 6);
+            if (c.u_hist) scatter_rows(c.u_hist, uh.data(), T, B, lo, n, NT);
+            if (c.x_hist) scatter_rows(c.x_hist, xh.data(), T, B, lo, n, 13);
+            if (c.oc && c.oc->status_hist) scatter_rows(c.oc->status_hist, sh.data(), T, B, lo, n, 1);
+            if (c.ac && c.ac->applied_hist) scatter_rows(c.ac->applied_hist, ah.data(), T, B, lo, n, NT);
+            if (c.ac && c.ac->ticks_hist) scatter_rows(c.ac->ticks_hist, kh.data(), T, B, lo, n, NT);
+            if (c.se && c.se->meas_hist) scatter_rows(c.se->meas_hist, mh.data(), T, B, lo, n, 13);
+            if (c.se && c.se->pred_hist) scatter_rows(c.se->pred_hist, ph.data(), T, B, lo, n, 13);
+            if (c.es && c.es->est_hist) scatter_rows(c.es->est_hist, eh.data(), T, B, lo, n, 13);
+            if (c.dg && c.dg->llr_hist) scatter_rows(c.dg->llr_hist, lh.data(), T, B, lo, n, (int64_t)NT * dv.n_levels);
+            if (c.db && c.db->force_hist) scatter_rows(c.db->force_hist, fh.data(), T, B, lo, n, 3);
+            if (c.db && c.db->torque_hist) scatter_rows(c.db->torque_hist, th.data(), T, B, lo, n, 3);
+            if (c.be && c.be->bias_hist) scatter_rows(c.be->bias_hist, bh.data(), T, B, lo, n, 6);
         }
         return FTMPC_OK;
     });
@@ -459,8 +447,8 @@ int multi_simulate(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double
             nb += bad[g][t];
             na += abad[g][t];
         }
-        if (not_converged) not_converged[t] = nb;
-        if (alloc_failed) alloc_failed[t] = na;
+        if (c.not_converged) c.not_converged[t] = nb;
+        if (c.alloc_failed) c.alloc_failed[t] = na;
     }
     return FTMPC_OK;
 }
@@ -686,8 +674,8 @@ int ftmpc_multi_simulate_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+    return ftmpc_multi_simulate_plant_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                            u_hist, x_hist, not_converged, out, nullptr);
 }
 
 int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -695,8 +683,8 @@ int ftmpc_multi_simulate_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, doubl
                                      int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                      const ftmpc_plant_model* plant) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, nullptr, nullptr, nullptr, nullptr, false);
+    return ftmpc_multi_simulate_mission_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                              u_hist, x_hist, not_converged, out, plant, nullptr);
 }
 
 int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -704,8 +692,8 @@ int ftmpc_multi_simulate_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, dou
                                        int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                        double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                        const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, nullptr, nullptr, nullptr, false);
+    return ftmpc_multi_simulate_actuator_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                               u_hist, x_hist, not_converged, out, plant, mission, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -714,8 +702,9 @@ int ftmpc_multi_simulate_wrench_outcomes_batch(ftmpc_multi* m, int64_t B, int32_
                                                uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
                                                const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+    return ftmpc_multi_simulate_wrench_plant_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
+                                                   noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
+                                                   alloc_failed, out, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -725,8 +714,9 @@ int ftmpc_multi_simulate_wrench_plant_batch(ftmpc_multi* m, int64_t B, int32_t T
                                             const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                             int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                             const ftmpc_plant_model* plant) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, nullptr, nullptr, nullptr, nullptr, true);
+    return ftmpc_multi_simulate_wrench_mission_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                     uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist,
+                                                     not_converged, alloc_failed, out, plant, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -736,8 +726,9 @@ int ftmpc_multi_simulate_wrench_mission_batch(ftmpc_multi* m, int64_t B, int32_t
                                               const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
                                               int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                               const ftmpc_plant_model* plant, const ftmpc_mission* mission) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, nullptr, nullptr, nullptr, true);
+    return ftmpc_multi_simulate_wrench_actuator_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                      uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist,
+                                                      not_converged, alloc_failed, out, plant, mission, nullptr);
 }
 
 int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -745,8 +736,8 @@ int ftmpc_multi_simulate_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, do
                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, nullptr, nullptr, false);
+    return ftmpc_multi_simulate_sensor_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                             u_hist, x_hist, not_converged, out, plant, mission, actuator, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -757,8 +748,9 @@ int ftmpc_multi_simulate_wrench_actuator_batch(ftmpc_multi* m, int64_t B, int32_
                                                int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                                const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                                const ftmpc_actuator* actuator) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, nullptr, nullptr, true);
+    return ftmpc_multi_simulate_wrench_sensor_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                    uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist,
+                                                    not_converged, alloc_failed, out, plant, mission, actuator, nullptr);
 }
 
 int ftmpc_multi_simulate_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -767,8 +759,8 @@ int ftmpc_multi_simulate_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, doub
                                       double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                       const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                       const ftmpc_sensor* sensor) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, nullptr, false);
+    return ftmpc_multi_simulate_estimator_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                                                faults, u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -779,8 +771,9 @@ int ftmpc_multi_simulate_wrench_sensor_batch(ftmpc_multi* m, int64_t B, int32_t 
                                              int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
                                              const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                              const ftmpc_actuator* actuator, const ftmpc_sensor* sensor) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor, nullptr, true);
+    return ftmpc_multi_simulate_wrench_estimator_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                       uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist,
+                                                       not_converged, alloc_failed, out, plant, mission, actuator, sensor, nullptr);
 }
 
 int ftmpc_multi_simulate_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -789,8 +782,9 @@ int ftmpc_multi_simulate_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, d
                                          double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
                                          const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                          const ftmpc_sensor* sensor, const ftmpc_estimator* estimator) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false);
+    return ftmpc_multi_simulate_diagnosis_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                                                faults, u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator,
+                                                nullptr);
 }
 
 int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -800,8 +794,9 @@ int ftmpc_multi_simulate_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, d
                                          const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                                          const ftmpc_sensor* sensor, const ftmpc_estimator* estimator,
                                          const ftmpc_diagnosis* diagnosis) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis);
+    return ftmpc_multi_simulate_disturbance_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                                                  faults, u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator,
+                                                  diagnosis, nullptr);
 }
 
 int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -812,9 +807,9 @@ int ftmpc_multi_simulate_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T,
                                            const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                            const ftmpc_disturbance* disturbance) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis,
-                          nullptr, nullptr, disturbance);
+    return ftmpc_multi_simulate_bias_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                           u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis,
+                                           disturbance, nullptr);
 }
 
 int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -825,9 +820,9 @@ int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double
                                     const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                     const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
-    return multi_simulate(m, B, T, x, ub, stuck, nullptr, 0, nullptr, nullptr, 0, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
-                          0.0, faults, u_hist, x_hist, not_converged, nullptr, out, plant, mission, actuator, sensor, estimator, false, diagnosis,
-                          nullptr, nullptr, disturbance, bias_estimate);
+    LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
+    return multi_simulate(m, c);
 }
 
 int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -839,9 +834,10 @@ int ftmpc_multi_simulate_wrench_estimator_batch(ftmpc_multi* m, int64_t B, int32
                                                 const ftmpc_plant_model* plant, const ftmpc_mission* mission,
                                                 const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                 const ftmpc_estimator* estimator) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
-                          estimator, true);
+    return ftmpc_multi_simulate_wrench_diagnosis_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                       uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist,
+                                                       not_converged, alloc_failed, out, plant, mission, actuator, sensor, estimator,
+                                                       nullptr, nullptr, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -854,9 +850,10 @@ int ftmpc_multi_simulate_wrench_diagnosis_batch(ftmpc_multi* m, int64_t B, int32
                                                 const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                 const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                                 int32_t* no_hull_step) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
-                          estimator, true, diagnosis, out_hull_b, no_hull_step);
+    return ftmpc_multi_simulate_wrench_disturbance_batch(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj,
+                                                         uref_traj, noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist,
+                                                         x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
+                                                         estimator, diagnosis, out_hull_b, no_hull_step, nullptr);
 }
 
 int ftmpc_multi_simulate_wrench_disturbance_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
@@ -869,9 +866,12 @@ int ftmpc_multi_simulate_wrench_disturbance_batch(ftmpc_multi* m, int64_t B, int
                                                   const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                                   const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                                   int32_t* no_hull_step, const ftmpc_disturbance* disturbance) {
-    return multi_simulate(m, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise, seed, sqp_iters,
-                          backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed, out, plant, mission, actuator, sensor,
-                          estimator, true, diagnosis, out_hull_b, no_hull_step, disturbance);
+    LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
+    loop_call_wrench(c, hull_A, n_sets, hull_set, hull_b, hull_rows, penalty, alloc_failed);
+    c.out_hull_b = out_hull_b;
+    c.no_hull_step = no_hull_step;
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, nullptr);
+    return multi_simulate(m, c);
 }
 
 const char* ftmpc_multi_routed_kernel_name(const ftmpc_multi* m, int32_t slot) {

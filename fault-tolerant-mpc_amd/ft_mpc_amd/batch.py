@@ -1146,8 +1146,6 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     if cost is not None:
         orec = {} if orec is None else orec
         orec["cost"] = cost
-    pmp = C.byref(pm) if pm is not None else None
-
     def result(out):
         if return_states:
             out["x_hist"] = xh
@@ -1168,9 +1166,16 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         if beout is not None:
             out["bias_estimate"] = beout
         return out
-    msp = C.byref(ms) if ms is not None else None
-    pre = "ftmpc_multi_simulate_" if multi else "ftmpc_simulate_"
-    if formulation == "wrench":
+    # One argument list, built once: the lead-in of the form, then the feature structs in the order every entry takes them.  The entry
+    # is the narrowest one that carries every feature present, so that each ABI level keeps being exercised from here.
+    ref = lambda st: C.byref(st) if st is not None else None
+    wrench = formulation == "wrench"
+    lead = [self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck)]
+    sqp = [int(sqp_iters), int(backtracks), float(tol)]
+    counts = [_ptr(bad, C.c_int32)]
+    out = dict(x=x, u=uh, not_converged=bad)
+    dgx = []      # what the wrench form's entries take behind the diagnosis
+    if wrench:
         from .controllers.tools.input_bounds import hull_tables
         if hull is None:
             hull = hull_tables(self.D, ub, stuck)
@@ -1186,155 +1191,36 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
                 if hb.shape != (B, int(hull["rows"])) or not np.isfinite(hb).all():
                     raise ValueError(f"diagnosis['hull_b'] must be finite with shape {(B, int(hull['rows']))}")
             dout["hull_b"], dout["no_hull"] = np.empty((B, int(hull["rows"]))), d_nh
-        if be is not None:      # (with or without a diagnosis; a disturbance in the same call has been refused)
-            self._check(self.lib.ftmpc_simulate_wrench_bias_batch(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-                C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None,
-                _ptr(dout["hull_b"]) if dg is not None else None, _ptr(d_nh, C.c_int32) if dg is not None else None, None, C.byref(be)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if db is not None:      # (disturbance['wrench'] = True; with or without a diagnosis)
-            self._check(getattr(self.lib, pre + "wrench_disturbance_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-                C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None,
-                _ptr(dout["hull_b"]) if dg is not None else None, _ptr(d_nh, C.c_int32) if dg is not None else None, C.byref(db)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if dg is not None:
-            self._check(getattr(self.lib, pre + "wrench_diagnosis_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-                C.byref(es) if es is not None else None, C.byref(dg), _ptr(dout["hull_b"]), _ptr(d_nh, C.c_int32)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if es is not None:
-            self._check(getattr(self.lib, pre + "wrench_estimator_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None, C.byref(es)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if se is not None:
-            self._check(getattr(self.lib, pre + "wrench_sensor_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac) if ac is not None else None, C.byref(se)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if ac is not None:
-            self._check(getattr(self.lib, pre + "wrench_actuator_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, msp,
-                C.byref(ac)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if ms is not None:
-            self._check(getattr(self.lib, pre + "wrench_mission_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), pmp, C.byref(ms)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if pm is not None:
-            self._check(getattr(self.lib, pre + "wrench_plant_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc), C.byref(pm)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if new:
-            self._check(getattr(self.lib, pre + "wrench_outcomes_batch")(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32), C.byref(oc)))
-            return result(dict(x=x, u=uh, not_converged=bad, alloc_failed=abad))
-        if ext:
-            self._check(self.lib.ftmpc_simulate_wrench_faults_batch(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-            out = dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-            if return_states:
-                out["x_hist"] = xh
-            return out
-        if sqp_iters:
-            self._check(self.lib.ftmpc_simulate_wrench_batch_ex(
-                self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb),
-                int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                float(penalty), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-            return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-        self._check(self.lib.ftmpc_simulate_wrench_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(A), A.shape[0],
-                                                         _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"]), _ptr(xr), _ptr(ur), _ptr(nz),
-                                                         C.c_uint64(int(seed)), _ptr(uh), _ptr(bad, C.c_int32), _ptr(abad, C.c_int32)))
-        return dict(x=x, u=uh, not_converged=bad, alloc_failed=abad)
-    if be is not None:
-        self._check(getattr(self.lib, pre + "bias_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
-            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-            C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None, None, C.byref(be)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if db is not None:
-        self._check(getattr(self.lib, pre + "disturbance_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
-            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-            C.byref(es) if es is not None else None, C.byref(dg) if dg is not None else None, C.byref(db)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if dg is not None:
-        self._check(getattr(self.lib, pre + "diagnosis_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
-            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None,
-            C.byref(es) if es is not None else None, C.byref(dg)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if es is not None:
-        self._check(getattr(self.lib, pre + "estimator_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
-            C.byref(ac) if ac is not None else None, C.byref(se) if se is not None else None, C.byref(es)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if se is not None:
-        self._check(getattr(self.lib, pre + "sensor_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp,
-            C.byref(ac) if ac is not None else None, C.byref(se)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if ac is not None:
-        self._check(getattr(self.lib, pre + "actuator_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, msp, C.byref(ac)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if ms is not None:
-        self._check(getattr(self.lib, pre + "mission_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), pmp, C.byref(ms)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if pm is not None:
-        self._check(getattr(self.lib, pre + "plant_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc), C.byref(pm)))
-        return result(dict(x=x, u=uh, not_converged=bad))
-    if new:
-        self._check(getattr(self.lib, pre + "outcomes_batch")(
-            self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters),
-            int(backtracks), float(tol), sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32), C.byref(oc)))
-        return result(dict(x=x, u=uh, not_converged=bad))
+        lead += [_ptr(A), A.shape[0], _ptr(hs, C.c_int32), _ptr(hb), int(hull["rows"])]
+        sqp += [float(penalty)]
+        counts += [_ptr(abad, C.c_int32)]
+        out["alloc_failed"] = abad
+        dgx = [_ptr(dout["hull_b"]), _ptr(d_nh, C.c_int32)] if dg is not None else [None, None]
+    lead += [_ptr(xr), _ptr(ur), _ptr(nz), C.c_uint64(int(seed))]
+    form = "wrench_" if wrench else ""
+    # (name of the entry, the feature is present, what the entry appends to the narrower one's arguments)
+    tail = [("outcomes", new, [ref(oc)]), ("plant", pm is not None, [ref(pm)]), ("mission", ms is not None, [ref(ms)]),
+            ("actuator", ac is not None, [ref(ac)]), ("sensor", se is not None, [ref(se)]), ("estimator", es is not None, [ref(es)]),
+            ("diagnosis", dg is not None, [ref(dg)] + dgx), ("disturbance", db is not None, [ref(db)]),
+            ("bias", be is not None, [ref(be)])]
+    last = max((i for i, (_, present, _) in enumerate(tail) if present), default=-1)
+    if last >= 0:
+        name = tail[last][0]
+        # (the wrench form's bias entry exists on the single handle only: the multi-GPU request has been refused above)
+        pre = "ftmpc_simulate_" if (not multi or (wrench and name == "bias")) else "ftmpc_multi_simulate_"
+        args = lead + sqp + [sp, _ptr(uh), _ptr(xh)] + counts + [a for _, _, extra in tail[:last + 1] for a in extra]
+        self._check(getattr(self.lib, pre + form + name + "_batch")(*args))
+        return result(out)
     if ext:
-        self._check(self.lib.ftmpc_simulate_faults_batch(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
-                                                         _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                                                         sp, _ptr(uh), _ptr(xh), _ptr(bad, C.c_int32)))
-        out = dict(x=x, u=uh, not_converged=bad)
+        self._check(getattr(self.lib, "ftmpc_simulate_" + form + "faults_batch")(*lead, *sqp, sp, _ptr(uh), _ptr(xh), *counts))
         if return_states:
             out["x_hist"] = xh
         return out
-    self._check(self.lib.ftmpc_simulate_batch_ex(self._h, B, int(T), _ptr(x), _ptr(ub), _ptr(stuck), _ptr(xr), _ptr(ur),
-                                                 _ptr(nz), C.c_uint64(int(seed)), int(sqp_iters), int(backtracks), float(tol),
-                                                 _ptr(uh), _ptr(bad, C.c_int32)))
-    return dict(x=x, u=uh, not_converged=bad)
+    if wrench and not sqp_iters:
+        self._check(self.lib.ftmpc_simulate_wrench_batch(*lead, _ptr(uh), *counts))
+        return out
+    self._check(getattr(self.lib, "ftmpc_simulate_" + form + "batch_ex")(*lead, *sqp, _ptr(uh), *counts))
+    return out
 
 
 def make_synthetic_batch(B, N, NT, nfault, seed, f_max=F_MAX, omega_des=(0.0, 0.0, 0.6)):
