@@ -42,6 +42,7 @@ struct LoopCall {
     const ftmpc_diagnosis* dg = nullptr;
     const ftmpc_disturbance* db = nullptr;
     const ftmpc_bias_estimate* be = nullptr;
+    const ftmpc_outage* og = nullptr;
 };
 
 // the thruster lead-in and the wrench lead-in of the public entries, which differ in nothing else
@@ -347,6 +348,43 @@ std::string bias_problem(const ftmpc_bias_estimate* be, int64_t B, const ftmpc_e
                 if (be->cov[b * 21 + k] < 0)
                     return "ftmpc_bias_estimate.cov: vehicle " + std::to_string(first + b) + " has a negative diagonal entry (" + std::to_string(i) + ")";
     return "";
+}
+
+// An outage's layout and values (include/ftmpc.h, ftmpc_outage) over the vehicles [0, B), against the estimator and the two estimates of
+// the same call: empty when acceptable, else the message, which names the field and, for an array, the first offending vehicle
+std::string outage_problem(const ftmpc_outage* og, int64_t B, const ftmpc_estimator* es, const ftmpc_disturbance* db,
+                           const ftmpc_bias_estimate* be, int64_t first = 0) {
+    if (!og) return "";
+    if (og->struct_size != (int32_t)sizeof(ftmpc_outage))
+        return "ftmpc_outage.struct_size is " + std::to_string(og->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_outage));
+    if (og->reserved != 0) return "ftmpc_outage.reserved is " + std::to_string(og->reserved) + ", not 0";
+    if (!es) return "ftmpc_outage needs an estimator (ftmpc_estimator): the availability and the gate act on its filter";
+    if (db) return "ftmpc_outage with a disturbance (ftmpc_disturbance) in the same call: ftmpc_filter_dist_kernel has no gated form";
+    if (be) return "ftmpc_outage with a bias estimate (ftmpc_bias_estimate) in the same call: ftmpc_filter_bias_kernel has no gated form";
+    if (!(og->p_loss >= 0.0 && og->p_loss < 1.0)) return "ftmpc_outage.p_loss is outside [0, 1)";
+    if (!(og->p_recover > 0.0 && og->p_recover <= 1.0)) return "ftmpc_outage.p_recover is outside (0, 1]";
+    for (int k = 0; k < 4; ++k) {
+        if (!(og->p_outlier[k] >= 0.0 && og->p_outlier[k] <= 1.0)) return "ftmpc_outage.p_outlier[" + std::to_string(k) + "] is outside [0, 1]";
+        if (!std::isfinite(og->outlier_sigma[k]) || og->outlier_sigma[k] < 0)
+            return "ftmpc_outage.outlier_sigma[" + std::to_string(k) + "] is negative or not finite";
+    }
+    if (!std::isfinite(og->gate) || og->gate < 0) return "ftmpc_outage.gate is negative or not finite";
+    const int32_t* const arr[3] = {og->state, og->rejected, og->outliers};
+    const char* const name[3] = {"state", "rejected", "outliers"};
+    const int64_t width[3] = {3, 4, 4};
+    for (int a = 0; a < 3; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < B * width[a]; ++i)
+                if (arr[a][i] < 0)
+                    return std::string("ftmpc_outage.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
+                           " has a negative entry (" + std::to_string(i % width[a]) + ")";
+    return "";
+}
+// trivial: the loop launches the kernels it launches without the struct
+bool outage_trivial(const ftmpc_outage* og) {
+    return !og || (og->p_loss == 0 && og->p_outlier[0] == 0 && og->p_outlier[1] == 0 && og->p_outlier[2] == 0 && og->p_outlier[3] == 0 &&
+                   og->gate == 0 && !og->window && !og->state && !og->rejected && !og->outliers && !og->avail_hist && !og->outlier_hist &&
+                   !og->gate_hist && !og->meas_hist);
 }
 
 int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
@@ -1015,6 +1053,75 @@ struct BiasStage {
     }
 };
 
+// Outage (checked by the entry; it needs the estimator and excludes both estimates): the chain's state [B][3], the counters [B][4]
+// and the scripted window [B][2] in the caller's layout (a lane reads and writes its own few words once per step), zeros when none are
+// handed over; the availability word [B] between ftmpc_outage_kernel and its two consumers; the four histories.  Nothing is converted
+// on the way out, so there is no unpack
+struct OutageStage {
+    bool on = false;
+    DevBuf<int32_t> d_avail, d_state, d_rej, d_out, d_win, d_ahist, d_ohist, d_ghist;
+    DevBuf<double> d_mhist;
+    ftmpc::OutageParams oq{};
+    ftmpc::GateParams gq{};
+
+    int stage(const Loop& q, const ftmpc_outage* og) {
+        on = !outage_trivial(og);
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        auto counters = [&](DevBuf<int32_t>& d, const int32_t* host, size_t n) -> int {
+            LOOP_TRY(dev_alloc(q, d, n));
+            return host ? dev_put(q, d.p, host, n) : dev_fill(q, d.p, 0, n);
+        };
+        LOOP_TRY(dev_alloc(q, d_avail, B));
+        LOOP_TRY(counters(d_state, og->state, B * 3));
+        LOOP_TRY(counters(d_rej, og->rejected, B * 4));
+        LOOP_TRY(counters(d_out, og->outliers, B * 4));
+        if (og->window) {
+            LOOP_TRY(dev_alloc(q, d_win, B * 2));
+            LOOP_TRY(dev_put(q, d_win.p, og->window, B * 2));
+        }
+        LOOP_TRY(hist_alloc(q, d_ahist, (const int32_t*)og->avail_hist, T * B));
+        LOOP_TRY(hist_alloc(q, d_ohist, (const int32_t*)og->outlier_hist, T * B));
+        LOOP_TRY(hist_alloc(q, d_ghist, (const int32_t*)og->gate_hist, T * B));
+        LOOP_TRY(hist_alloc(q, d_mhist, (const double*)og->meas_hist, T * B * 13));
+        oq.B = q.B;
+        oq.y = q.h->d_x0;
+        oq.seed = og->seed;
+        oq.p_loss = og->p_loss;
+        oq.p_recover = og->p_recover;
+        for (int k = 0; k < 4; ++k) {
+            oq.p_outlier[k] = og->p_outlier[k];
+            oq.outlier_sigma[k] = og->outlier_sigma[k];
+        }
+        oq.index0 = q.index0;
+        oq.index_total = q.index_total;
+        oq.window = d_win;
+        oq.state = d_state;
+        oq.outliers = d_out;
+        oq.avail = d_avail;
+        oq.avail_hist = d_ahist;
+        oq.outlier_hist = d_ohist;
+        oq.meas_hist = d_mhist;
+        gq.avail = d_avail;
+        gq.gate_sq = og->gate * og->gate;
+        gq.rejected = d_rej;
+        gq.gate_hist = d_ghist;
+        return FTMPC_OK;
+    }
+    int fetch(const Loop& q, const ftmpc_outage* og) {
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        LOOP_TRY(hist_get(q, og->state, d_state, B * 3));
+        LOOP_TRY(hist_get(q, og->rejected, d_rej, B * 4));
+        LOOP_TRY(hist_get(q, og->outliers, d_out, B * 4));
+        LOOP_TRY(hist_get(q, og->avail_hist, d_ahist, T * B));
+        LOOP_TRY(hist_get(q, og->outlier_hist, d_ohist, T * B));
+        LOOP_TRY(hist_get(q, og->gate_hist, d_ghist, T * B));
+        LOOP_TRY(hist_get(q, og->meas_hist, d_mhist, T * B * 13));
+        return FTMPC_OK;
+    }
+};
+
 // Diagnosis (checked by the entry): xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (filled on the device when
 // none are handed over), the detect arrays [B][K] with the count per vehicle, the flag the repair kernel reads.  On the wrench form
 // also the hull rebuild: the new offsets [B][hull_rows] and [flat B | no_hull B]
@@ -1394,6 +1501,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     FilterStage fil;
     DistStage dst;
     BiasStage bia;
+    OutageStage oge;
     DiagStage dia;
     MissionStage mis;
     OutcomeStage out;
@@ -1405,6 +1513,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(fil.stage(q, es, c.be, se));
     LOOP_TRY(dst.stage(q, db));
     LOOP_TRY(bia.stage(q, c.be));
+    LOOP_TRY(oge.stage(q, c.og));
     LOOP_TRY(dia.stage(q, dg, c));
     LOOP_TRY(mis.stage(q, c.ms, windows, want_cost, xw, uw, L));
     LOOP_TRY(out.stage(q, c.oc, want_cost, wrench));
@@ -1444,6 +1553,11 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
         fp.pred_hist = sen.d_phist;
     }
     if (diag) dp.y = sensing ? h->d_x0.p : sen.d_xtrue.p;
+    if (oge.on) {     // ftmpc_outage_kernel rewrites y_t into the handle's x0 (from there, or from the truth): both consumers read it there
+        oge.oq.src = fp.y;
+        fp.y = h->d_x0;
+        if (diag) dp.y = h->d_x0;
+    }
     if (flt.E > 0) fe.warmU = wrench ? nullptr : d_warmB;
     ftmpc::SimParams sp;
     sp.B = B;
@@ -1497,12 +1611,22 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
             hipLaunchKernelGGL(ftmpc::ftmpc_sense_kernel, per_vehicle, wave, 0, s, h->dc, sn);
             HIP_TRY(h, hipGetLastError());
         }
+        if (oge.on) {     // availability, outliers into y_t, the availability word for the diagnosis' and the filter's phase 0
+            oge.oq.init = t == 0 && !es->xhat;
+            oge.oq.cstep = se->step0 + t;
+            oge.oq.step = t;
+            hipLaunchKernelGGL(ftmpc::ftmpc_outage_kernel, per_vehicle, wave, 0, s, oge.oq);
+            HIP_TRY(h, hipGetLastError());
+        }
         if (diag) {     // test, decision and re-anchor on y_t; a vehicle that switched has its shifted warm start clipped to the new bounds
             dp.init = t == 0 && !dg->state;
             dp.anchor = (se->step0 + t) % dg->every == 0;
             dp.cstep = (int32_t)(se->step0 + t);
             dp.step = t;
-            hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, per_vehicle, wave, 0, s, h->dc, dp);
+            if (oge.on)
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_gated_kernel, per_vehicle, wave, 0, s, h->dc, dp, (const int32_t*)oge.d_avail.p);
+            else
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, per_vehicle, wave, 0, s, h->dc, dp);
             if (wrench) {     // two launches: the switch kernel's lanes read the offsets the first one wrote
                 hw.repair = t > 0 || resume;
                 hw.cstep = dp.cstep;
@@ -1529,7 +1653,9 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
             } else if (bias) {     // the x pass in measured coordinates and the bias pass, which completes x^ and writes the solve's x0
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<0>, per_vehicle, wave, 0, s, h->dc, fp, bia.bq);
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_bias_kernel<1>, per_vehicle, wave, 0, s, h->dc, fp, bia.bq);
-            } else
+            } else if (oge.on)     // (an outage excludes both estimates)
+                hipLaunchKernelGGL(ftmpc::ftmpc_filter_gated_kernel, per_vehicle, wave, 0, s, h->dc, fp, oge.gq);
+            else
                 hipLaunchKernelGGL(ftmpc::ftmpc_filter_kernel<0>, per_vehicle, wave, 0, s, h->dc, fp);
             HIP_TRY(h, hipGetLastError());
         }
@@ -1629,6 +1755,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(fil.fetch(q, es));
     LOOP_TRY(dst.fetch(q, db));
     LOOP_TRY(bia.fetch(q, c.be));
+    LOOP_TRY(oge.fetch(q, c.og));
     LOOP_TRY(dia.fetch(q, dg, c));
     LOOP_TRY(run.fetch(q, c));
     LOOP_TRY(mis.fetch(q, c.ms, want_cost));
@@ -1658,9 +1785,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
 
 void loop_call_features(LoopCall& c, double* x_hist, const ftmpc_fault_schedule* fs, const ftmpc_outcomes* oc, const ftmpc_plant_model* pm,
                         const ftmpc_mission* ms, const ftmpc_actuator* ac, const ftmpc_sensor* se, const ftmpc_estimator* es,
-                        const ftmpc_diagnosis* dg, const ftmpc_disturbance* db, const ftmpc_bias_estimate* be) {
+                        const ftmpc_diagnosis* dg, const ftmpc_disturbance* db, const ftmpc_bias_estimate* be,
+                        const ftmpc_outage* og = nullptr) {
     c.x_hist = x_hist;
-    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be;
+    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og;
 }
 
 // the argument checks, in the order the entries have always made them (a bad call keeps its message)
@@ -1688,6 +1816,7 @@ int loop_check(ftmpc_handle* h, const LoopCall& c) {
     if (!(msg = disturbance_problem(c.db, B, c.es, c.wrench ? 0 : c.sqp_iters)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     // (a bias estimate reaches the solve through x0 alone: sqp_iters >= 0 is served)
     if (!(msg = bias_problem(c.be, B, c.es, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    if (!(msg = outage_problem(c.og, B, c.es, c.db, c.be)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     return FTMPC_OK;
 }
 
@@ -1826,8 +1955,21 @@ int ftmpc_simulate_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, 
                               const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
                               const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                               const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
+    return ftmpc_simulate_outage_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                       x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance,
+                                       bias_estimate, nullptr);
+}
+
+int ftmpc_simulate_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                const ftmpc_outage* outage) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
     return loop_run(h, c);
 }
 
@@ -1951,11 +2093,27 @@ int ftmpc_simulate_wrench_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
                                      const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                      int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                      const ftmpc_bias_estimate* bias_estimate) {
+    return ftmpc_simulate_wrench_outage_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj, noise,
+                                              seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged, alloc_failed,
+                                              out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b, no_hull_step,
+                                              disturbance, bias_estimate, nullptr);
+}
+
+int ftmpc_simulate_wrench_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                       int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                       uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                       const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                       int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                       const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                       const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                       int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                       const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_wrench(c, hull_A, n_sets, hull_set, hull_b, hull_rows, penalty, alloc_failed);
     c.out_hull_b = out_hull_b;
     c.no_hull_step = no_hull_step;
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
     return loop_run(h, c);
 }
 

@@ -255,6 +255,10 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         const std::string msg = bias_problem(c.be, B, c.es, c.db);
         if (!msg.empty()) return refuse(msg);
     }
+    {     // the outage likewise: the parameters are uniform, window / state / rejected / outliers and the four histories per vehicle
+        const std::string msg = outage_problem(c.og, B, c.es, c.db, c.be);
+        if (!msg.empty()) return refuse(msg);
+    }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
         const std::string msg = mission_problem(c.ms, B, T, m->cfg.N, c.xref_traj, c.uref_traj, 0, sensor_shift(c.se));
         if (!msg.empty()) return refuse(msg);
@@ -363,7 +367,21 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (sb.cross) sb.cross += lo * 72;
             if (sb.cov) sb.cov += lo * 21;
         }
+        std::vector<int32_t> oah, ooh, ogh;
+        std::vector<double> omh;
+        ftmpc_outage ov{};
+        if (c.og) {
+            ov = *c.og;
+            if (ov.window) ov.window += lo * 2;
+            if (ov.state) ov.state += lo * 3;
+            if (ov.rejected) ov.rejected += lo * 4;
+            if (ov.outliers) ov.outliers += lo * 4;
+        }
         try {
+            if (ov.avail_hist && !whole) oah.resize((size_t)T * n);
+            if (ov.outlier_hist && !whole) ooh.resize((size_t)T * n);
+            if (ov.gate_hist && !whole) ogh.resize((size_t)T * n);
+            if (ov.meas_hist && !whole) omh.resize((size_t)T * n * 13);
             if (sb.bias_hist && !whole) bh.resize((size_t)T * n * 6);
             if (bv.force_hist && !whole) fh.resize((size_t)T * n * 3);
             if (bv.torque_hist && !whole) th.resize((size_t)T * n * 3);
@@ -407,6 +425,10 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (bv.force_hist) bv.force_hist = fh.data();
             if (bv.torque_hist) bv.torque_hist = th.data();
             if (sb.bias_hist) sb.bias_hist = bh.data();
+            if (ov.avail_hist) ov.avail_hist = oah.data();
+            if (ov.outlier_hist) ov.outlier_hist = ooh.data();
+            if (ov.gate_hist) ov.gate_hist = ogh.data();
+            if (ov.meas_hist) ov.meas_hist = omh.data();
         }
         LoopCall sc = c;      // the shard as a call of its own: the path of the single-handle entry
         sc.B = n;
@@ -422,6 +444,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         sc.fs = c.fs ? &fs : nullptr, sc.oc = &oc, sc.pm = c.pm ? &pl : nullptr, sc.ms = c.ms ? &mi : nullptr, sc.ac = c.ac ? &at : nullptr;
         sc.se = c.se ? &sv : nullptr, sc.es = c.es ? &ev : nullptr, sc.dg = c.dg ? &dv : nullptr, sc.db = c.db ? &bv : nullptr;
         sc.be = c.be ? &sb : nullptr;
+        sc.og = c.og ? &ov : nullptr;
         const int rc2 = loop_run(d.h, sc);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
@@ -437,6 +460,10 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (c.db && c.db->force_hist) scatter_rows(c.db->force_hist, fh.data(), T, B, lo, n, 3);
             if (c.db && c.db->torque_hist) scatter_rows(c.db->torque_hist, th.data(), T, B, lo, n, 3);
             if (c.be && c.be->bias_hist) scatter_rows(c.be->bias_hist, bh.data(), T, B, lo, n, 6);
+            if (c.og && c.og->avail_hist) scatter_rows(c.og->avail_hist, oah.data(), T, B, lo, n, 1);
+            if (c.og && c.og->outlier_hist) scatter_rows(c.og->outlier_hist, ooh.data(), T, B, lo, n, 1);
+            if (c.og && c.og->gate_hist) scatter_rows(c.og->gate_hist, ogh.data(), T, B, lo, n, 1);
+            if (c.og && c.og->meas_hist) scatter_rows(c.og->meas_hist, omh.data(), T, B, lo, n, 13);
         }
         return FTMPC_OK;
     });
@@ -820,8 +847,22 @@ int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double
                                     const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                     const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate) {
+    return ftmpc_multi_simulate_outage_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                             u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis,
+                                             disturbance, bias_estimate, nullptr);
+}
+
+int ftmpc_multi_simulate_outage_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                      int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                      const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                      const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                      const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                      const ftmpc_outage* outage) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
     return multi_simulate(m, c);
 }
 

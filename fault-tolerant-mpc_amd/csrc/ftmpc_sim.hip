@@ -2195,4 +2195,294 @@ template __global__ void ftmpc_filter_bias_kernel<1>(const DeviceConsts, const F
 template __global__ void ftmpc_filter_bias_kernel<2>(const DeviceConsts, const FilterParams, const BiasParams);
 template __global__ void ftmpc_filter_bias_kernel<3>(const DeviceConsts, const FilterParams, const BiasParams);
 
+// ---------------------------------------------------------------------------------------------------------
+// Measurement dropouts, outliers and the gated filter (ftmpc_simulate_outage_batch / ftmpc_simulate_wrench_outage_batch;
+// include/ftmpc.h, ftmpc_outage).  Three kernels, a lane per vehicle each, all between ftmpc_sense_kernel and the solve:
+//   ftmpc_outage_kernel          the availability chain (a two-state Markov chain per vehicle, overridden inside the scripted
+//                                window), the outlier draws of an available step and their application to y_t, the counters, the
+//                                histories, and the availability word avail[b] the two kernels below read
+//   ftmpc_diagnose_gated_kernel  ftmpc_diagnose_kernel<0> with the per-vehicle skip: a lost vehicle neither tests nor re-anchors,
+//                                its statistics carry over (llr_hist holds them) and phase 1 keeps counting n
+//   ftmpc_filter_gated_kernel    ftmpc_filter_kernel<0> with availability and the innovation gate per vehicle: the update runs where
+//                                !init && update && avail[b]; inside it channel j is left out (d and P as they are) when
+//                                e^2 > gate^2 s_j.  The gate is two selects per channel (a gain and an innovation of exactly zero), not
+//                                a branch around the unrolled channel body (which cost 100 more AGPRs and 36 bytes of scratch), so the
+//                                78 packed entries of P stay in registers at compile-time indices, as in the plain kernel
+// The plain kernels are siblings, not instantiations of these: their code is what it was.
+// Counters: k = cstep * index_total + index0 + b, u_s = u01(seed, 32 k + s); s = 0 the chain, s = 1 + g the outlier of group g,
+// s = 8 + 2 j, 9 + 2 j the Box-Muller pair of channel j.
+// ---------------------------------------------------------------------------------------------------------
+struct OutageParams {
+    int64_t B;
+    int32_t init, pad0;       // first step of a call without estimator.xhat: available, nothing drawn, y_t untouched
+    const double* src;        // [B*13] y_t as the sense kernel left it (the handle's x0), or the truth when the sensor is trivial
+    double* y;                // [B*13] the handle's x0: y_t as the filter and the diagnosis see it
+    unsigned long long seed;
+    double p_loss, p_recover;
+    double p_outlier[4], outlier_sigma[4];
+    int64_t cstep, step, index0, index_total;   // step0 + t (the counter's step, the window's clock), t (the histories' row)
+    const int32_t* window;    // nullptr or [B*2]
+    int32_t* state;           // [B*3] run, lost_steps, longest
+    int32_t* outliers;        // [B*4]
+    int32_t* avail;           // [B] 1 available, 0 lost: what the two consumers read
+    int32_t* avail_hist;      // nullptr or [T*B]
+    int32_t* outlier_hist;    // nullptr or [T*B]
+    double* meas_hist;        // nullptr or [T*B*13]
+};
+
+struct GateParams {
+    const int32_t* avail;     // [B]
+    double gate_sq;           // 0: no gate
+    int32_t* rejected;        // [B*4]
+    int32_t* gate_hist;       // nullptr or [T*B]
+};
+
+__global__ void __launch_bounds__(64) ftmpc_outage_kernel(const OutageParams O) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= O.B) return;
+    double y[13];
+    for (int i = 0; i < 13; ++i) y[i] = O.src[b * 13 + i];
+    int32_t run = 0, obits = 0;
+    if (!O.init) {
+        const unsigned long long k0 = (unsigned long long)(O.cstep * O.index_total + O.index0 + b) * 32ull;
+        const int32_t run_prev = O.state[b * 3];
+        const double u0 = u01(O.seed, k0);
+        bool lost = run_prev > 0 ? !(u0 < O.p_recover) : (u0 < O.p_loss);
+        if (O.window) {
+            const int64_t from = O.window[b * 2], to = O.window[b * 2 + 1];
+            if (from <= O.cstep && O.cstep < to) lost = true;
+        }
+        if (lost) {
+            run = run_prev + 1;
+            O.state[b * 3 + 1] += 1;
+            if (run > O.state[b * 3 + 2]) O.state[b * 3 + 2] = run;
+        } else {
+            double e[12];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const bool hit = O.p_outlier[g] > 0.0 && u01(O.seed, k0 + 1ull + g) < O.p_outlier[g];
+                if (hit) {
+                    obits |= 1 << g;
+                    O.outliers[b * 4 + g] += 1;
+                }
+#pragma unroll
+                for (int j = 3 * g; j < 3 * g + 3; ++j)
+                    e[j] = hit ? O.outlier_sigma[g] * sqrt(-2.0 * log(1.0 - u01(O.seed, k0 + 8ull + 2 * j))) *
+                                     cos(6.283185307179586 * u01(O.seed, k0 + 9ull + 2 * j))
+                               : 0.0;
+            }
+            for (int i = 0; i < 3; ++i) {
+                if (obits & 1) y[i] += e[i];
+                if (obits & 2) y[3 + i] += e[3 + i];
+                if (obits & 8) y[10 + i] += e[9 + i];
+            }
+            if (obits & 4) filter_rotate(y + 6, e[6], e[7], e[8]);
+        }
+        O.state[b * 3] = run;
+    } else {
+        O.state[b * 3] = 0;
+    }
+    O.avail[b] = run == 0;
+    if (O.avail_hist) O.avail_hist[O.step * O.B + b] = run == 0;
+    if (O.outlier_hist) O.outlier_hist[O.step * O.B + b] = obits;
+    if (O.meas_hist)
+        for (int i = 0; i < 13; ++i) O.meas_hist[(O.step * O.B + b) * 13 + i] = y[i];
+    for (int i = 0; i < 13; ++i) O.y[b * 13 + i] = y[i];
+}
+
+// phase 0 of ftmpc_diagnose_kernel with the per-vehicle skip (the diagnosis' own first step anchors on y_t whatever avail says)
+__global__ void __launch_bounds__(64) ftmpc_diagnose_gated_kernel(const DeviceConsts C, const DiagParams P, const int32_t* avail) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int64_t B = P.B;
+    const int NT = C.NT, L = P.L, H = NT * L;
+    double x[13], y[13];
+    double* const hist = P.llr_hist ? P.llr_hist + (P.step * B + b) * H : nullptr;
+    if (!P.init && !avail[b]) {     // lost: no test, no re-anchor; xt, n, acc and llr carry over
+        if (hist) {
+#pragma unroll 1
+            for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+        }
+        P.switched[b] = 0;
+        return;
+    }
+    for (int i = 0; i < 13; ++i) y[i] = P.y[b * 13 + i];
+    int32_t sw = 0;
+    bool tested = false;
+    if (P.init) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+    } else {
+        const double n = P.xt[b * 14 + 13];
+        const int32_t cnt = P.count[b];
+        if (P.anchor && n >= 1.0 && cnt < P.K) {
+            tested = true;
+            for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+            const double qx = x[6], qy = x[7], qz = x[8], qw = x[9];
+            const double R00 = qx * qx - qy * qy - qz * qz + qw * qw, R01 = 2 * (qx * qy + qz * qw), R02 = 2 * (qx * qz - qy * qw);
+            const double R10 = 2 * (qx * qy - qz * qw), R11 = -qx * qx + qy * qy - qz * qz + qw * qw, R12 = 2 * (qy * qz + qx * qw);
+            const double R20 = 2 * (qx * qz + qy * qw), R21 = 2 * (qy * qz - qx * qw), R22 = -qx * qx - qy * qy + qz * qz + qw * qw;
+            const double e0 = y[3] - x[3], e1 = y[4] - x[4], e2 = y[5] - x[5];
+            const double rv0 = R00 * e0 + R01 * e1 + R02 * e2;
+            const double rv1 = R10 * e0 + R11 * e1 + R12 * e2;
+            const double rv2 = R20 * e0 + R21 * e1 + R22 * e2;
+            const double rw0 = y[10] - x[10], rw1 = y[11] - x[11], rw2 = y[12] - x[12];
+            const double isv = 1.0 / (P.rsq[0] + n * P.dsq[0]), isw = 1.0 / (P.rsq[1] + n * P.dsq[1]);
+            const double kv = C.dt * C.inv_mass, dt = C.dt;
+            double best = P.threshold;
+            int besth = -1;
+#pragma unroll 1
+            for (int i = 0; i < NT; ++i) {
+                const bool live = P.ub[b * NT + i] > 0.0;
+                const double acci = P.acc[(int64_t)i * B + b];
+                const double d0 = C.D[i], d1 = C.D[MAX_NT + i], d2 = C.D[2 * MAX_NT + i];
+                const double t0 = C.D[3 * MAX_NT + i], t1 = C.D[4 * MAX_NT + i], t2 = C.D[5 * MAX_NT + i];
+                const double g0 = kv * d0, g1 = kv * d1, g2 = kv * d2;
+                const double h0 = dt * (C.Jinv[0] * t0 + C.Jinv[1] * t1 + C.Jinv[2] * t2);
+                const double h1 = dt * (C.Jinv[3] * t0 + C.Jinv[4] * t1 + C.Jinv[5] * t2);
+                const double h2 = dt * (C.Jinv[6] * t0 + C.Jinv[7] * t1 + C.Jinv[8] * t2);
+#pragma unroll
+                for (int l = 0; l < 4; ++l) {
+                    if (l < L) {
+                        const int64_t k = (int64_t)(i * L + l);
+                        double v = 0.0;
+                        if (live) {
+                            const double delta = n * P.levels[l] - acci;
+                            const double a0 = g0 * delta, a1 = g1 * delta, a2 = g2 * delta;
+                            const double w0 = h0 * delta, w1 = h1 * delta, w2 = h2 * delta;
+                            const double z = ((a0 * rv0 + a1 * rv1 + a2 * rv2) - 0.5 * (a0 * a0 + a1 * a1 + a2 * a2)) * isv +
+                                             ((w0 * rw0 + w1 * rw1 + w2 * rw2) - 0.5 * (w0 * w0 + w1 * w1 + w2 * w2)) * isw;
+                            v = fmax(0.0, P.llr[k * B + b] + z);
+                        }
+                        P.llr[k * B + b] = v;
+                        if (hist) hist[k] = v;
+                        if (v > best) {      // (strictly: a tie stays with the lowest index)
+                            best = v;
+                            besth = (int)k;
+                        }
+                    }
+                }
+            }
+            if (besth >= 0) {
+                const int i = besth / L, l = besth - i * L;
+                const double lv = l == 0 ? P.levels[0] : (l == 1 ? P.levels[1] : (l == 2 ? P.levels[2] : P.levels[3]));
+                P.det_step[b * P.K + cnt] = P.cstep;
+                P.det_thruster[b * P.K + cnt] = i;
+                P.det_level[b * P.K + cnt] = l;
+                P.count[b] = cnt + 1;
+                P.ub[b * NT + i] = 0.0;
+                P.stuck[b * NT + i] = lv;
+#pragma unroll 1
+                for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+                sw = 1;
+            }
+        }
+    }
+    if (hist && !tested) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+    }
+    P.switched[b] = sw;
+    if (P.init || P.anchor) {
+        for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = y[i];
+        P.xt[b * 14 + 13] = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) P.acc[(int64_t)i * B + b] = 0.0;
+    }
+}
+
+// phase 0 of ftmpc_filter_kernel with availability and the innovation gate per vehicle
+__global__ void __launch_bounds__(64) ftmpc_filter_gated_kernel(const DeviceConsts C, const FilterParams F, const GateParams Gt) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= F.B) return;
+    const int64_t B = F.B;
+    double* const covb = F.cov + (int64_t)blockIdx.x * blockDim.x;
+    const unsigned lane = threadIdx.x;
+    double x[13], P[78];
+    int32_t mask = 0;      // bit j: channel j was rejected
+    double y[13];
+    for (int i = 0; i < 13; ++i) y[i] = F.y[b * 13 + i];
+    if (F.init) {
+        for (int i = 0; i < 13; ++i) x[i] = y[i];
+    } else {
+        for (int i = 0; i < 13; ++i) x[i] = F.xhat[b * 13 + i];
+    }
+    if (!F.init && F.update && Gt.avail[b]) {
+        // A rejected channel runs the channel's straight-line code with a gain of exactly zero and an innovation of exactly zero:
+        // d + 0 and P - 0 are d and P, so the 78 entries need no merge across a branch and stay where the plain kernel keeps them
+        double th[3], d[12];
+        filter_att_residual(x + 6, y + 6, th);
+        const double gsq = Gt.gate_sq;
+#pragma unroll
+        for (int k = 0; k < 78; ++k) P[k] = cov_row(covb + (int64_t)k * B)[lane];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) d[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            const int jx = j < 6 ? j : j + 1;      // channel j's entry of x (rate: past the quaternion)
+            const double rj = (j >= 6 && j < 9) ? th[j - 6] : F.y[b * 13 + jx] - F.xhat[b * 13 + jx];
+            const double sj = P[tri(j, j)] + F.rsq[j / 3];
+            const double ej = rj - d[j];
+            const bool rej = gsq > 0.0 && ej * ej > gsq * sj;
+            if (rej) mask |= 1 << j;
+            const double inv = rej ? 0.0 : 1.0 / sj;
+            const double e = rej ? 0.0 : ej;
+            double k[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) k[i] = P[tri(i, j)] * inv;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) d[i] += k[i] * e;
+#pragma unroll
+            for (int a = 0; a < 12; ++a) {
+                const double ska = sj * k[a];
+#pragma unroll
+                for (int c = a; c < 12; ++c) P[tri(a, c)] -= ska * k[c];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 78; ++k) cov_row(covb + (int64_t)k * B)[lane] = P[k];
+        {     // (a volatile read, as in ftmpc_filter_kernel<0>: x^ is not held across the covariance)
+            const volatile double* const xh = F.xhat + b * 13;
+            for (int i = 0; i < 13; ++i) x[i] = xh[i];
+        }
+        for (int i = 0; i < 3; ++i) {
+            x[i] += d[i];
+            x[3 + i] += d[3 + i];
+            x[10 + i] += d[9 + i];
+        }
+        filter_rotate(x + 6, d[6], d[7], d[8]);
+        if (mask)
+            for (int g = 0; g < 4; ++g) Gt.rejected[b * 4 + g] += __popc((unsigned)(mask >> (3 * g)) & 7u);
+    }
+    if (Gt.gate_hist) Gt.gate_hist[F.step * B + b] = mask;
+    for (int i = 0; i < 13; ++i) F.xhat[b * 13 + i] = x[i];
+    if (F.est_hist)
+        for (int i = 0; i < 13; ++i) F.est_hist[(F.step * B + b) * 13 + i] = x[i];
+    if (F.err_sq) {     // against the truth: position, velocity, attitude (the residual's theta), rate
+        double xt[13], th[3], e[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 13; ++i) xt[i] = F.truth[b * 13 + i];
+        filter_att_residual(x + 6, xt + 6, th);
+        for (int i = 0; i < 3; ++i) {
+            e[0] += (x[i] - xt[i]) * (x[i] - xt[i]);
+            e[1] += (x[3 + i] - xt[3 + i]) * (x[3 + i] - xt[3 + i]);
+            e[2] += th[i] * th[i];
+            e[3] += (x[10 + i] - xt[10 + i]) * (x[10 + i] - xt[10 + i]);
+        }
+        for (int i = 0; i < 4; ++i) F.err_sq[b * 4 + i] += e[i];
+    }
+    if (F.predict) {
+        int32_t slot = F.slot0;
+#pragma unroll 1
+        for (int j = 0; j < F.latency; ++j) {
+            double gen[6];
+            filter_gen(C, F.ring + (int64_t)slot * B * C.NT, F.ub, F.stuck, b, gen);
+            slot = slot + 1 == F.nslots ? 0 : slot + 1;
+            filter_rk4(C, x, gen);
+        }
+        if (F.pred_hist)
+            for (int i = 0; i < 13; ++i) F.pred_hist[(F.step * B + b) * 13 + i] = x[i];
+    }
+    for (int i = 0; i < 13; ++i) F.x0[b * 13 + i] = x[i];
+}
+
 }  // namespace ftmpc

@@ -43,6 +43,7 @@ SYMBOLS = (
     "ftmpc_simulate_wrench_disturbance_batch", "ftmpc_multi_simulate_wrench_disturbance_batch",
     "ftmpc_eval_cost_wrench_disturbance_batch", "ftmpc_solve_wrench_disturbance_batch", "ftmpc_solve_sqp_wrench_disturbance_batch",
     "ftmpc_simulate_bias_batch", "ftmpc_simulate_wrench_bias_batch", "ftmpc_multi_simulate_bias_batch",
+    "ftmpc_simulate_outage_batch", "ftmpc_simulate_wrench_outage_batch", "ftmpc_multi_simulate_outage_batch",
 )
 
 
@@ -159,6 +160,16 @@ class ftmpc_bias_estimate(C.Structure):
     ]
 
 
+class ftmpc_outage(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("p_loss", C.c_double), ("p_recover", C.c_double),
+        ("p_outlier", C.c_double * 4), ("outlier_sigma", C.c_double * 4), ("gate", C.c_double),
+        ("window", C.POINTER(C.c_int32)), ("state", C.POINTER(C.c_int32)), ("rejected", C.POINTER(C.c_int32)),
+        ("outliers", C.POINTER(C.c_int32)), ("avail_hist", C.POINTER(C.c_int32)), ("outlier_hist", C.POINTER(C.c_int32)),
+        ("gate_hist", C.POINTER(C.c_int32)), ("meas_hist", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -251,6 +262,9 @@ def load_library() -> C.CDLL:
     lib.ftmpc_simulate_bias_batch.argtypes = lib.ftmpc_simulate_disturbance_batch.argtypes + [C.POINTER(ftmpc_bias_estimate)]
     lib.ftmpc_multi_simulate_bias_batch.argtypes = lib.ftmpc_simulate_bias_batch.argtypes
     lib.ftmpc_simulate_wrench_bias_batch.argtypes = lib.ftmpc_simulate_wrench_disturbance_batch.argtypes + [C.POINTER(ftmpc_bias_estimate)]
+    lib.ftmpc_simulate_outage_batch.argtypes = lib.ftmpc_simulate_bias_batch.argtypes + [C.POINTER(ftmpc_outage)]
+    lib.ftmpc_multi_simulate_outage_batch.argtypes = lib.ftmpc_simulate_outage_batch.argtypes
+    lib.ftmpc_simulate_wrench_outage_batch.argtypes = lib.ftmpc_simulate_wrench_bias_batch.argtypes + [C.POINTER(ftmpc_outage)]
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,

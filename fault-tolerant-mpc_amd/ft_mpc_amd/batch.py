@@ -468,7 +468,7 @@ class BatchedMPC:
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
                  plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None,
-                 bias_estimate=None):
+                 bias_estimate=None, outage=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -554,11 +554,20 @@ class BatchedMPC:
         run: the pieces travel in the measured coordinates of ft_mpc_amd.biases, and estimator["cov"] is then P_mm -- and
         fields=(...) among bias_hist [T,B,6] (the estimates of each step) and state (bias [B,6], cross [B,72], cov [B,21]: the
         priors of step T); they come back as out["bias_estimate"].
+        outage: measurement dropouts, outliers and an innovation gate in the estimator's filter, decided per vehicle on the device
+        (include/ftmpc.h, ftmpc_outage; ft_mpc_amd.outages restates it in NumPy; both formulations, needs `estimator`, not together
+        with `disturbance` or `bias_estimate`): a dict with seed=0, p_loss=0.0 and p_recover=1.0 (the availability chain:
+        outages.chain_params converts a loss fraction and a mean outage length), p_outlier=0.0 and outlier_sigma=0.0 (one value or 4,
+        by group: position, velocity, attitude, rate), gate=0.0 (standard deviations of the scalar innovation; 0: no gate), window=None
+        ([B,2] int: a scripted outage [from, to) in campaign steps), state=None ([B,3]: run, lost_steps, longest), rejected=None
+        ([B,4]) and outliers=None ([B,4]) -- what a previous call returned, for a continued run -- and fields=(...) among avail,
+        outlier, gate [T,B] int, meas [T,B,13] (y_t as the filter and the diagnosis saw it), state, rejected, outliers; they come
+        back as out["outage"].  A lost vehicle's filter propagates and its diagnosis waits; outliers reach the diagnosis ungated.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate)
+                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -1045,9 +1054,41 @@ def _bias_request(bias_estimate, B, T, estimator, disturbance, es, ekeep):
     return be, keep, out
 
 
+def _outage_request(outage, B, T, estimator, disturbance, bias_estimate):
+    """The ftmpc_outage struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .outages import request
+    r = request(outage, B, T, estimator, disturbance, bias_estimate)
+    og = _lib.ftmpc_outage(struct_size=C.sizeof(_lib.ftmpc_outage), seed=r["seed"] & ((1 << 64) - 1), p_loss=r["p_loss"],
+                           p_recover=r["p_recover"], gate=r["gate"])
+    for k in range(4):
+        og.p_outlier[k], og.outlier_sigma[k] = float(r["p_outlier"][k]), float(r["outlier_sigma"][k])
+    keep, out = [], {}
+    if r["window"] is not None:
+        keep.append(r["window"])
+        og.window = _ptr(r["window"], C.c_int32)
+    # state, rejected and outliers are in/out: asked back without being handed over, they start as the library's defaults (zeros)
+    for name, width in (("state", 3), ("rejected", 4), ("outliers", 4)):
+        a = r[name]
+        if a is None and name in r["fields"]:
+            a = np.zeros((B, width), np.int32)
+        if a is not None:
+            keep.append(a)
+            setattr(og, name, _ptr(a, C.c_int32))
+            if name in r["fields"]:
+                out[name] = a
+    for name, field in (("avail", "avail_hist"), ("outlier", "outlier_hist"), ("gate", "gate_hist")):
+        if name in r["fields"]:
+            out[name] = np.zeros((T, B), np.int32)
+            setattr(og, field, _ptr(out[name], C.c_int32))
+    if "meas" in r["fields"]:
+        out["meas"] = np.zeros((T, B, 13))
+        og.meas_hist = _ptr(out["meas"])
+    return og, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -1090,6 +1131,10 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     if bias_estimate is not None and multi and formulation == "wrench":
         raise ValueError("bias_estimate: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
     be, bekeep, beout = (_bias_request(bias_estimate, B, T, estimator, disturbance, es, ekeep) if bias_estimate is not None
+                         else (None, None, None))
+    if outage is not None and multi and formulation == "wrench":
+        raise ValueError("outage: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
+    og, ogkeep, ogout = (_outage_request(outage, B, T, estimator, disturbance, bias_estimate) if outage is not None
                          else (None, None, None))
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
@@ -1140,7 +1185,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
            or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
-           or db is not None or be is not None)
+           or db is not None or be is not None or og is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1165,6 +1210,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["disturbance"] = bout
         if beout is not None:
             out["bias_estimate"] = beout
+        if ogout is not None:
+            out["outage"] = ogout
         return out
     # One argument list, built once: the lead-in of the form, then the feature structs in the order every entry takes them.  The entry
     # is the narrowest one that carries every feature present, so that each ABI level keeps being exercised from here.
@@ -1202,12 +1249,12 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     tail = [("outcomes", new, [ref(oc)]), ("plant", pm is not None, [ref(pm)]), ("mission", ms is not None, [ref(ms)]),
             ("actuator", ac is not None, [ref(ac)]), ("sensor", se is not None, [ref(se)]), ("estimator", es is not None, [ref(es)]),
             ("diagnosis", dg is not None, [ref(dg)] + dgx), ("disturbance", db is not None, [ref(db)]),
-            ("bias", be is not None, [ref(be)])]
+            ("bias", be is not None, [ref(be)]), ("outage", og is not None, [ref(og)])]
     last = max((i for i, (_, present, _) in enumerate(tail) if present), default=-1)
     if last >= 0:
         name = tail[last][0]
-        # (the wrench form's bias entry exists on the single handle only: the multi-GPU request has been refused above)
-        pre = "ftmpc_simulate_" if (not multi or (wrench and name == "bias")) else "ftmpc_multi_simulate_"
+        # (the wrench form's bias and outage entries exist on the single handle only: the multi-GPU request has been refused above)
+        pre = "ftmpc_simulate_" if (not multi or (wrench and name in ("bias", "outage"))) else "ftmpc_multi_simulate_"
         args = lead + sqp + [sp, _ptr(uh), _ptr(xh)] + counts + [a for _, _, extra in tail[:last + 1] for a in extra]
         self._check(getattr(self.lib, pre + form + name + "_batch")(*args))
         return result(out)

@@ -80,11 +80,13 @@ def propagate(xt, n, acc, u, ub, stuck, cfg, force=None, torque=None):
     return xn, n + 1, np.asarray(acc, dtype=np.float64) + c
 
 
-def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None):
+def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None, avail=None):
     """The loop's diagnosis for ONE vehicle.  meas [T,13]: the y_t; applied_u [T,NT]: the a_t (u_hist); ub, stuck [NT]: the
     controller's pattern at the call's start; spec: dict(every, levels, resid_sigma, drift_sigma, threshold, max_detect); state
     [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned; force / torque [T,3]: the
-    estimated disturbance of each step (simulate(disturbance=...): force_hist / torque_hist) for the propagation, None: without.
+    estimated disturbance of each step (simulate(disturbance=...): force_hist / torque_hist) for the propagation, None: without;
+    avail [T] (simulate(outage=...): the avail history; None: always available): on a step where the vehicle is lost there is no test
+    and no re-anchor, the statistics carry over and n keeps counting (the first step of a replay without state anchors regardless).
     Returns dict(llr_hist [T,NT*L], detections [(step, thruster, level)], ub [T,NT], stuck [T,NT] (the pattern each solve saw),
     ub_end, stuck_end, state [14+NT], llr [NT*L], peak [T] (the largest statistic of every step that tested, else nan))."""
     meas = np.asarray(meas, dtype=np.float64).reshape(-1, 13)
@@ -110,6 +112,8 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
         if xt is None:
             xt, n, acc, s = meas[t].copy(), 0, np.zeros(NT), np.zeros((NT, L))
             hist[t] = 0.0
+        elif avail is not None and not avail[t]:
+            hist[t] = s.reshape(-1)
         else:
             if c % every == 0 and n >= 1 and len(det) < K:
                 s = test_step(s, meas[t], xt, n, acc, ub, spec, cfg)

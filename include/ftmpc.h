@@ -1123,6 +1123,88 @@ int ftmpc_simulate_wrench_bias_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
                                      int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                      const ftmpc_bias_estimate* bias_estimate);
 
+/* Measurement dropouts, outliers and a gated filter.  The fix a vehicle navigates by drops out for stretches and sometimes returns a
+ * wild sample; per vehicle and step the device decides whether y_t is available, whether it carries an outlier, and which channels of
+ * it the filter accepts.  The parameters are uniform over the call; the state, the counters and the histories are per vehicle.
+ *   notation: campaign step c = step0 + t (step0 the sensor's, 0 without one); vehicle number g = index0 + b and index_total as in
+ *     ftmpc_outcomes; counter k = c * index_total + g; u_s = u01(seed, 32 k + s), the splitmix counter function of the plant noise
+ *     and the sensor, under this struct's own seed.
+ *   per loop step, right after ftmpc_sense_kernel has formed y_t (the truth when the sensor is trivial) and before the diagnosis' and
+ *     the filter's phase 0 (ftmpc_outage_kernel):
+ *     init step (the first step of a call that was not handed ftmpc_estimator.xhat): available, run = 0, no outlier is drawn and
+ *       y_t is untouched, whatever the chain or the window say.
+ *     otherwise lost = run_prev > 0 ? !(u_0 < p_recover) : (u_0 < p_loss), and inside the window (from <= c < to) lost regardless.
+ *     a lost step: run = run_prev + 1, lost_steps += 1, longest = max(longest, run); y_t stays as the sense kernel left it and
+ *       nobody reads it.
+ *     an available step: run = 0; for each group k (position, velocity, attitude, rate) with p_outlier[k] > 0 an outlier is drawn
+ *       when u_{1+k} < p_outlier[k]; its three channels j = 3k .. 3k+2 get e_j = outlier_sigma[k] sqrt(-2 log(1 - u_{8+2j}))
+ *       cos(2 pi u_{9+2j}), added to y_t for position, velocity and rate, and y_q <- rotate(y_q, e_{6:9}) for attitude (the
+ *       sensor's closed form, renormalised); outliers[b][k] += 1.
+ *     meas_hist[t] is y_t after this step, on lost steps too; ftmpc_sensor.meas_hist stays the sense kernel's sample.
+ *   the filter (ftmpc_filter_gated_kernel in place of ftmpc_filter_kernel<0>): the measurement update of step c runs for a vehicle
+ *     when !init && c % every == 0 && available; otherwise the solve starts from the propagated estimate, as between two updates.
+ *     Inside the update, at channel j, e = r_j - d_j and s_j = P_jj + R_j; with gate > 0 and e e > (gate gate) s_j the channel is
+ *     rejected: d and P stay as they are, rejected[b][j / 3] += 1 and bit j of gate_hist[t] is set; otherwise the channel is
+ *     processed as ftmpc_filter_kernel<0> does.  The time update, est_hist, err_sq and the queue prediction are unchanged.
+ *   the diagnosis, when the call has one (ftmpc_diagnose_gated_kernel in place of ftmpc_diagnose_kernel<0>): on a step where the
+ *     vehicle is lost phase 0 does nothing for it: no test, no re-anchor; xt, n, acc and llr carry over and llr_hist[t] holds the
+ *     carried values.  Phase 1 is unchanged, so n keeps counting and the first test after reacquisition covers the whole outage (the
+ *     n >= 1 window of the signature).  The first step of a call without ftmpc_diagnosis.state anchors on y_t whatever the
+ *     availability.  On the wrench form the hull step runs off `switched` and is unchanged.
+ * A handed state / rejected / outliers are the values at the call's first step; on return they hold those of step T, so that a
+ * continued run (with the sensor's pending / step0, the estimator's xhat / cov and the diagnosis' carry-over) is the whole run bit
+ * for bit; without them the chain starts available and the counters at zero.  outage == NULL, or a trivial struct (p_loss = 0, every
+ * p_outlier = 0, gate = 0, window and every array NULL), launches exactly the kernels of the _bias_ entries and returns their bits.
+ * Limits: outliers reach the diagnosis ungated (the gate lives in the filter alone); ftmpc_filter_dist_kernel and
+ * ftmpc_filter_bias_kernel have no gated form, so ftmpc_disturbance and ftmpc_bias_estimate are refused; the parameters are uniform
+ * over the call; the whole 12-channel measurement is lost or present (no per-group availability); ftmpc_multi_upload / _step take
+ * no outage.
+ * FTMPC_ERR_ARG, the message naming ftmpc_outage.<field> and, for an array, the first offending vehicle, the call's x untouched: a
+ * struct_size other than sizeof(ftmpc_outage); reserved != 0; no estimator; a non-NULL disturbance or bias_estimate in the same call;
+ * p_loss outside [0, 1); p_recover outside (0, 1]; a p_outlier outside [0, 1]; an outlier_sigma or gate negative or not finite; a
+ * negative state, rejected or outliers entry.
+ */
+typedef struct ftmpc_outage {
+    int32_t struct_size, reserved;      /* sizeof(ftmpc_outage), 0 */
+    uint64_t seed;                      /* its own stream */
+    double p_loss;                      /* P(lost at c | available at c-1), in [0, 1) */
+    double p_recover;                   /* P(available at c | lost at c-1), in (0, 1] */
+    double p_outlier[4];                /* per group (position, velocity, attitude, rate), in [0, 1] */
+    double outlier_sigma[4];            /* >= 0, the group's units */
+    double gate;                        /* 0: no gate; > 0: in standard deviations of the scalar innovation */
+    const int32_t* window;              /* NULL or [B*2]: a scripted outage [from, to) in campaign steps; to <= from: none */
+    int32_t* state;                     /* NULL or [B*3] in/out: run (length of the current outage, 0 = available), lost_steps, longest */
+    int32_t* rejected;                  /* NULL or [B*4] in/out: gated channel-steps per group */
+    int32_t* outliers;                  /* NULL or [B*4] in/out: outlier draws per group */
+    int32_t* avail_hist;                /* NULL or [T*B] out: 1 available, 0 lost */
+    int32_t* outlier_hist;              /* NULL or [T*B] out: bit k = group k carried an outlier */
+    int32_t* gate_hist;                 /* NULL or [T*B] out: bit j = channel j was rejected */
+    double* meas_hist;                  /* NULL or [T*B*13] out: y_t as the filter and the diagnosis saw it */
+} ftmpc_outage;
+
+/* ftmpc_simulate_bias_batch with the outage `outage` (NULL: exactly ftmpc_simulate_bias_batch, which IS this entry with NULL). */
+int ftmpc_simulate_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                const ftmpc_outage* outage);
+
+/* The outage on the two-stage wrench form: ftmpc_simulate_wrench_bias_batch with `outage` (NULL: exactly that entry's kernels and
+ * bits).  The three kernels are the thruster form's. */
+int ftmpc_simulate_wrench_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                       const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                       int32_t hull_rows, const double* xref_traj, const double* uref_traj, const double noise[4],
+                                       uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol, double penalty,
+                                       const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist, int32_t* not_converged,
+                                       int32_t* alloc_failed, const ftmpc_outcomes* out, const ftmpc_plant_model* plant,
+                                       const ftmpc_mission* mission, const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                       const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                       int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                       const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage);
+
 /* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
  * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
  * after G / warmG; the rollout of the cost and of the linearisation sees tau + t^ at every RK4 stage and f^ / m added to the inertial
@@ -1417,6 +1499,19 @@ int ftmpc_multi_simulate_bias_batch(ftmpc_multi* m, int64_t B, int32_t T, double
                                     const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
                                     const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                     const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate);
+/* ftmpc_multi_simulate_bias_batch with the outage `outage` (ftmpc_outage; NULL: exactly that entry).  The struct is checked once
+ * over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; window + 2 lo, state + 3 lo,
+ * rejected + 4 lo and outliers + 4 lo are read and written per shard, the four histories are copied row by row from the shard's
+ * staging.  The two-stage wrench form has no multi-GPU bias entry to extend, so it has no multi-GPU outage entry either. */
+int ftmpc_multi_simulate_outage_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                      int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                      double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                      const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                      const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                      const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                      const ftmpc_outage* outage);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
