@@ -43,6 +43,7 @@ struct LoopCall {
     const ftmpc_disturbance* db = nullptr;
     const ftmpc_bias_estimate* be = nullptr;
     const ftmpc_outage* og = nullptr;
+    const ftmpc_environment* ev = nullptr;
 };
 
 // the thruster lead-in and the wrench lead-in of the public entries, which differ in nothing else
@@ -385,6 +386,52 @@ bool outage_trivial(const ftmpc_outage* og) {
     return !og || (og->p_loss == 0 && og->p_outlier[0] == 0 && og->p_outlier[1] == 0 && og->p_outlier[2] == 0 && og->p_outlier[3] == 0 &&
                    og->gate == 0 && !og->window && !og->state && !og->rejected && !og->outliers && !og->avail_hist && !og->outlier_hist &&
                    !og->gate_hist && !og->meas_hist);
+}
+
+// An environment's layout and values (include/ftmpc.h, ftmpc_environment) over the vehicles [0, B), against the sensor and the
+// disturbance estimate of the same call: empty when acceptable, else the message, which names the field and, for an array, the first
+// offending vehicle
+std::string environment_problem(const ftmpc_environment* ev, int64_t B, const ftmpc_sensor* se, const ftmpc_disturbance* db,
+                                int64_t first = 0) {
+    if (!ev) return "";
+    if (ev->struct_size != (int32_t)sizeof(ftmpc_environment))
+        return "ftmpc_environment.struct_size is " + std::to_string(ev->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_environment));
+    if (ev->reserved != 0) return "ftmpc_environment.reserved is " + std::to_string(ev->reserved) + ", not 0";
+    if (ev->step0 < 0) return "ftmpc_environment.step0 is negative";
+    if (se && se->step0 != ev->step0)
+        return "ftmpc_environment.step0 is " + std::to_string(ev->step0) + ", the sensor's (ftmpc_sensor.step0) is " +
+               std::to_string(se->step0) + ": one campaign clock per call";
+    for (int a = 0; a < 2; ++a) {
+        if (!std::isfinite(ev->sigma[a]) || ev->sigma[a] < 0)
+            return "ftmpc_environment.sigma[" + std::to_string(a) + "] is negative or not finite";
+        if (ev->sigma[a] > 0 && !(std::isfinite(ev->tau[a]) && ev->tau[a] > 0))
+            return "ftmpc_environment.tau[" + std::to_string(a) + "] is not positive and finite (sigma[" + std::to_string(a) + "] > 0)";
+    }
+    if ((ev->amp_force || ev->amp_torque) && !(std::isfinite(ev->period) && ev->period > 0))
+        return "ftmpc_environment.period is not positive and finite (an amplitude is given)";
+    if (ev->kick && !ev->window) return "ftmpc_environment.kick without ftmpc_environment.window";
+    if (ev->est_err_sq && !db)
+        return "ftmpc_environment.est_err_sq needs a disturbance estimate (ftmpc_disturbance) in the same call";
+    const double* const arr[6] = {ev->amp_force, ev->amp_torque, ev->phase, ev->kick, ev->state, ev->est_err_sq};
+    const char* const name[6] = {"amp_force", "amp_torque", "phase", "kick", "state", "est_err_sq"};
+    const int64_t width[6] = {3, 3, 1, 6, 6, 2};
+    for (int a = 0; a < 6; ++a)
+        if (arr[a])
+            for (int64_t i = 0; i < B * width[a]; ++i) {
+                if (!std::isfinite(arr[a][i]))
+                    return std::string("ftmpc_environment.") + name[a] + ": vehicle " + std::to_string(first + i / width[a]) +
+                           " has a non-finite entry (" + std::to_string(i % width[a]) + ")";
+                if (a == 5 && arr[a][i] < 0)
+                    return std::string("ftmpc_environment.est_err_sq: vehicle ") + std::to_string(first + i / 2) + " has a negative entry (" +
+                           std::to_string(i % 2) + ")";
+            }
+    return "";
+}
+// trivial: the loop launches the kernels it launches without the struct
+bool environment_trivial(const ftmpc_environment* ev) {
+    return !ev || (ev->sigma[0] == 0 && ev->sigma[1] == 0 && !ev->amp_force && !ev->amp_torque && !ev->phase && !ev->kick && !ev->window &&
+                   !ev->state && !ev->wrench_hist && !ev->est_err_sq);
 }
 
 int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
@@ -1122,6 +1169,86 @@ struct OutageStage {
     }
 };
 
+// Environment (checked by the entry): the wrench of the step, force [3][B] and torque [3][B], which simulate_core wires into the plant's
+// PlantVar in place of PlantStage's constant arrays (those become the kernel's base); the Gauss-Markov state [6][B], the amplitudes
+// [3][B] each and the kick [6][B] component-major, vehicle-major at the ABI; the phase [B], the window [B][2] and the error sums [B][2]
+// in the caller's layout; phi and the innovation scale computed here, once per call
+struct EnvironmentStage {
+    bool on = false;
+    DevBuf<double> d_force, d_torque, d_g, d_af, d_at, d_ph, d_kick, d_whist, d_err;
+    DevBuf<int32_t> d_win;
+    std::vector<double> h_g, h_af, h_at, h_kick;
+    ftmpc::EnvParams eq{};
+
+    int stage(const Loop& q, const ftmpc_environment* ev) {
+        on = !environment_trivial(ev);
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        auto packed = [&](DevBuf<double>& d, const double* src, int64_t K, std::vector<double>& v) -> int {
+            if (!src) return FTMPC_OK;
+            v.resize(B * (size_t)K);
+            ftmpc::pack_kb(src, q.B, K, v.data());
+            LOOP_TRY(dev_alloc(q, d, v.size()));
+            return dev_put(q, d.p, v.data(), v.size());
+        };
+        try {
+            h_g.assign(B * 6, 0.0);      // (also the landing place of the state's read-back)
+            LOOP_TRY(packed(d_af, ev->amp_force, 3, h_af));
+            LOOP_TRY(packed(d_at, ev->amp_torque, 3, h_at));
+            LOOP_TRY(packed(d_kick, ev->kick, 6, h_kick));
+        } catch (const std::bad_alloc&) {
+            return fail(q.h, FTMPC_ERR_ALLOC, "out of host memory for the environment's staging arrays");
+        }
+        LOOP_TRY(dev_alloc(q, d_force, B * 3));
+        LOOP_TRY(dev_alloc(q, d_torque, B * 3));
+        LOOP_TRY(dev_alloc(q, d_g, B * 6));
+        if (ev->state) {
+            ftmpc::pack_kb(ev->state, q.B, 6, h_g.data());
+            LOOP_TRY(dev_put(q, d_g.p, h_g.data(), B * 6));
+        }
+        if (ev->phase) {
+            LOOP_TRY(dev_alloc(q, d_ph, B));
+            LOOP_TRY(dev_put(q, d_ph.p, ev->phase, B));
+        }
+        if (ev->window) {
+            LOOP_TRY(dev_alloc(q, d_win, B * 2));
+            LOOP_TRY(dev_put(q, d_win.p, ev->window, B * 2));
+        }
+        if (ev->est_err_sq) {
+            LOOP_TRY(dev_alloc(q, d_err, B * 2));
+            LOOP_TRY(dev_put(q, d_err.p, (const double*)ev->est_err_sq, B * 2));
+        }
+        LOOP_TRY(hist_alloc(q, d_whist, (const double*)ev->wrench_hist, T * B * 6));
+        eq.B = q.B;
+        eq.seed = ev->seed;
+        eq.index0 = q.index0;
+        eq.index_total = q.index_total;
+        ftmpc_env::process(ev->sigma, ev->tau, q.h->cfg.dt, ev->period, eq.proc);
+        eq.amp_f = d_af;
+        eq.amp_t = d_at;
+        eq.phase = d_ph;
+        eq.kick = d_kick;
+        eq.window = d_win;
+        eq.g = d_g;
+        eq.force = d_force;
+        eq.torque = d_torque;
+        eq.wrench_hist = d_whist;
+        eq.err_sq = d_err;
+        return FTMPC_OK;
+    }
+    int fetch(const Loop& q, const ftmpc_environment* ev) {
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        if (ev->state) LOOP_TRY(dev_get(q, h_g.data(), d_g.p, B * 6));
+        LOOP_TRY(hist_get(q, ev->est_err_sq, d_err, B * 2));
+        LOOP_TRY(hist_get(q, ev->wrench_hist, d_whist, T * B * 6));
+        return FTMPC_OK;
+    }
+    void unpack(const Loop& q, const ftmpc_environment* ev) {
+        if (on && ev->state) ftmpc::unpack_kb(h_g.data(), q.B, 6, ev->state);
+    }
+};
+
 // Diagnosis (checked by the entry): xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (filled on the device when
 // none are handed over), the detect arrays [B][K] with the count per vehicle, the flag the repair kernel reads.  On the wrench form
 // also the hull rebuild: the new offsets [B][hull_rows] and [flat B | no_hull B]
@@ -1502,6 +1629,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     DistStage dst;
     BiasStage bia;
     OutageStage oge;
+    EnvironmentStage env;
     DiagStage dia;
     MissionStage mis;
     OutcomeStage out;
@@ -1514,6 +1642,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(dst.stage(q, db));
     LOOP_TRY(bia.stage(q, c.be));
     LOOP_TRY(oge.stage(q, c.og));
+    LOOP_TRY(env.stage(q, c.ev));
     LOOP_TRY(dia.stage(q, dg, c));
     LOOP_TRY(mis.stage(q, c.ms, windows, want_cost, xw, uw, L));
     LOOP_TRY(out.stage(q, c.oc, want_cost, wrench));
@@ -1557,6 +1686,14 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
         oge.oq.src = fp.y;
         fp.y = h->d_x0;
         if (diag) dp.y = h->d_x0;
+    }
+    if (env.on) {     // ftmpc_environment_kernel writes the step's wrench where the plant reads its disturbance; the call's constant is its base
+        env.eq.base_f = pla.pv.force;
+        env.eq.base_t = pla.pv.torque;
+        pla.pv.force = env.d_force;
+        pla.pv.torque = env.d_torque;
+        pla.var = true;
+        env.eq.est = dist ? d_dest : nullptr;
     }
     if (flt.E > 0) fe.warmU = wrench ? nullptr : d_warmB;
     ftmpc::SimParams sp;
@@ -1697,6 +1834,12 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
             sp.u0 = op.u0 = d_ring + (size_t)(t % (lat + 1)) * nu;
         }
         sp.step = t;
+        if (env.on) {     // w_c into the plant's force and torque; the estimate's error against it while d^ is the one the solve saw
+            env.eq.init = t == 0 && !c.ev->state;
+            env.eq.cstep = c.ev->step0 + t;
+            env.eq.step = t;
+            hipLaunchKernelGGL(ftmpc::ftmpc_environment_kernel, per_vehicle, wave, 0, s, env.eq);
+        }
         if (act.on)
             hipLaunchKernelGGL(ftmpc::ftmpc_plant_step_act_kernel, per_vehicle, wave, 0, s, h->dc, sp, pla.pv, act.ap);
         else if (pla.var)
@@ -1756,6 +1899,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(dst.fetch(q, db));
     LOOP_TRY(bia.fetch(q, c.be));
     LOOP_TRY(oge.fetch(q, c.og));
+    LOOP_TRY(env.fetch(q, c.ev));
     LOOP_TRY(dia.fetch(q, dg, c));
     LOOP_TRY(run.fetch(q, c));
     LOOP_TRY(mis.fetch(q, c.ms, want_cost));
@@ -1766,6 +1910,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     dia.unpack(q, dg);
     dst.unpack(q, db);
     bia.unpack(q, c.be);
+    env.unpack(q, c.ev);
     fil.unpack(q, es);
     sen.unpack(q, se);
     if (sense) {
@@ -1786,9 +1931,9 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
 void loop_call_features(LoopCall& c, double* x_hist, const ftmpc_fault_schedule* fs, const ftmpc_outcomes* oc, const ftmpc_plant_model* pm,
                         const ftmpc_mission* ms, const ftmpc_actuator* ac, const ftmpc_sensor* se, const ftmpc_estimator* es,
                         const ftmpc_diagnosis* dg, const ftmpc_disturbance* db, const ftmpc_bias_estimate* be,
-                        const ftmpc_outage* og = nullptr) {
+                        const ftmpc_outage* og = nullptr, const ftmpc_environment* ev = nullptr) {
     c.x_hist = x_hist;
-    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og;
+    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og, c.ev = ev;
 }
 
 // the argument checks, in the order the entries have always made them (a bad call keeps its message)
@@ -1817,6 +1962,7 @@ int loop_check(ftmpc_handle* h, const LoopCall& c) {
     // (a bias estimate reaches the solve through x0 alone: sqp_iters >= 0 is served)
     if (!(msg = bias_problem(c.be, B, c.es, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     if (!(msg = outage_problem(c.og, B, c.es, c.db, c.be)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    if (!(msg = environment_problem(c.ev, B, c.se, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     return FTMPC_OK;
 }
 
@@ -1968,8 +2114,22 @@ int ftmpc_simulate_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x
                                 const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                 const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                 const ftmpc_outage* outage) {
+    return ftmpc_simulate_environment_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                            u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis,
+                                            disturbance, bias_estimate, outage, nullptr);
+}
+
+int ftmpc_simulate_environment_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                     const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                     const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                     const ftmpc_outage* outage, const ftmpc_environment* environment) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
+                       environment);
     return loop_run(h, c);
 }
 
@@ -2109,11 +2269,30 @@ int ftmpc_simulate_wrench_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
                                        int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                        const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage) {
+    return ftmpc_simulate_wrench_environment_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
+                                                   noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
+                                                   alloc_failed, out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b,
+                                                   no_hull_step, disturbance, bias_estimate, outage, nullptr);
+}
+
+int ftmpc_simulate_wrench_environment_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                            const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                            double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                            int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                            const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                            const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                            int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                            const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                            const ftmpc_environment* environment) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_wrench(c, hull_A, n_sets, hull_set, hull_b, hull_rows, penalty, alloc_failed);
     c.out_hull_b = out_hull_b;
     c.no_hull_step = no_hull_step;
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
+                       environment);
     return loop_run(h, c);
 }
 

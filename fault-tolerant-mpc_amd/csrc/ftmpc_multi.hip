@@ -259,6 +259,10 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         const std::string msg = outage_problem(c.og, B, c.es, c.db, c.be);
         if (!msg.empty()) return refuse(msg);
     }
+    {     // the environment likewise: sigma, tau and period are uniform, every array is per vehicle
+        const std::string msg = environment_problem(c.ev, B, c.se, c.db);
+        if (!msg.empty()) return refuse(msg);
+    }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
         const std::string msg = mission_problem(c.ms, B, T, m->cfg.N, c.xref_traj, c.uref_traj, 0, sensor_shift(c.se));
         if (!msg.empty()) return refuse(msg);
@@ -377,7 +381,20 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (ov.rejected) ov.rejected += lo * 4;
             if (ov.outliers) ov.outliers += lo * 4;
         }
+        std::vector<double> ewh;
+        ftmpc_environment nv{};
+        if (c.ev) {
+            nv = *c.ev;
+            if (nv.amp_force) nv.amp_force += lo * 3;
+            if (nv.amp_torque) nv.amp_torque += lo * 3;
+            if (nv.phase) nv.phase += lo;
+            if (nv.kick) nv.kick += lo * 6;
+            if (nv.window) nv.window += lo * 2;
+            if (nv.state) nv.state += lo * 6;
+            if (nv.est_err_sq) nv.est_err_sq += lo * 2;
+        }
         try {
+            if (nv.wrench_hist && !whole) ewh.resize((size_t)T * n * 6);
             if (ov.avail_hist && !whole) oah.resize((size_t)T * n);
             if (ov.outlier_hist && !whole) ooh.resize((size_t)T * n);
             if (ov.gate_hist && !whole) ogh.resize((size_t)T * n);
@@ -429,6 +446,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (ov.outlier_hist) ov.outlier_hist = ooh.data();
             if (ov.gate_hist) ov.gate_hist = ogh.data();
             if (ov.meas_hist) ov.meas_hist = omh.data();
+            if (nv.wrench_hist) nv.wrench_hist = ewh.data();
         }
         LoopCall sc = c;      // the shard as a call of its own: the path of the single-handle entry
         sc.B = n;
@@ -445,6 +463,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         sc.se = c.se ? &sv : nullptr, sc.es = c.es ? &ev : nullptr, sc.dg = c.dg ? &dv : nullptr, sc.db = c.db ? &bv : nullptr;
         sc.be = c.be ? &sb : nullptr;
         sc.og = c.og ? &ov : nullptr;
+        sc.ev = c.ev ? &nv : nullptr;
         const int rc2 = loop_run(d.h, sc);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
@@ -464,6 +483,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (c.og && c.og->outlier_hist) scatter_rows(c.og->outlier_hist, ooh.data(), T, B, lo, n, 1);
             if (c.og && c.og->gate_hist) scatter_rows(c.og->gate_hist, ogh.data(), T, B, lo, n, 1);
             if (c.og && c.og->meas_hist) scatter_rows(c.og->meas_hist, omh.data(), T, B, lo, n, 13);
+            if (c.ev && c.ev->wrench_hist) scatter_rows(c.ev->wrench_hist, ewh.data(), T, B, lo, n, 6);
         }
         return FTMPC_OK;
     });
@@ -861,8 +881,23 @@ int ftmpc_multi_simulate_outage_batch(ftmpc_multi* m, int64_t B, int32_t T, doub
                                       const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                       const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                       const ftmpc_outage* outage) {
+    return ftmpc_multi_simulate_environment_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                                                  faults, u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator,
+                                                  diagnosis, disturbance, bias_estimate, outage, nullptr);
+}
+
+int ftmpc_multi_simulate_environment_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                           const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                           int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                           double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                           const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                           const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                           const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                           const ftmpc_outage* outage, const ftmpc_environment* environment) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
-    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage);
+    loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
+                       environment);
     return multi_simulate(m, c);
 }
 

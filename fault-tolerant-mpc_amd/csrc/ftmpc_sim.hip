@@ -2485,4 +2485,92 @@ __global__ void __launch_bounds__(64) ftmpc_filter_gated_kernel(const DeviceCons
     for (int i = 0; i < 13; ++i) F.x0[b * 13 + i] = x[i];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// A disturbance that varies over the run (ftmpc_simulate_environment_batch / ftmpc_simulate_wrench_environment_batch;
+// include/ftmpc.h, ftmpc_environment).  One kernel, a lane per vehicle, launched after the step's solve and right before the plant
+// step: it forms the wrench w_c = base + g_c + p_c + k_c held over plant step c (csrc/ftmpc_env.h: the Gauss-Markov draws and
+// recursion, the periodic term, the kick, the sum) and writes it into the [3][B] force and [3][B] torque arrays that
+// ftmpc_plant_step_var_kernel and ftmpc_plant_step_act_kernel read as PlantVar.force / .torque.  Neither plant kernel changes: what
+// was a constant per call is rewritten between two of their launches.  The base is the call's own ftmpc_plant_model.force / .torque
+// (PlantStage's arrays, which the plant no longer reads directly), the Gauss-Markov state is [6][B] in / out, the amplitudes, the
+// kick and every output are component-major as well, so a wave's load or store covers 512 contiguous bytes; the window and the
+// error sums keep the caller's layout (two words per lane).  The estimate error is taken against DistStage's estimate [B][6] as it
+// stands at this point of the step: the value the step's solve saw.
+// Counters: k = cstep * index_total + index0 + b, u_s = u01(seed, 32 k + s); s = 2 j, 2 j + 1 the innovation of component j,
+// s = 16 + 2 j, 17 + 2 j its stationary start.
+// ---------------------------------------------------------------------------------------------------------
+}  // namespace ftmpc
+#include "ftmpc_env.h"      // (included here, not at the top: the build logs keep the source lines of every kernel above)
+namespace ftmpc {
+struct EnvParams {
+    int64_t B;
+    int32_t init, pad0;       // first step of a call without a handed state: g_c is the stationary draw
+    unsigned long long seed;
+    int64_t cstep, step, index0, index_total;   // step0 + t (the counter's step, the periodic term's and the window's clock), t
+    ftmpc_env::Process proc;
+    const double* base_f;     // nullptr or [3][B] ftmpc_plant_model.force
+    const double* base_t;     // nullptr or [3][B] ftmpc_plant_model.torque
+    const double* amp_f;      // nullptr or [3][B]
+    const double* amp_t;      // nullptr or [3][B]
+    const double* phase;      // nullptr or [B]
+    const double* kick;       // nullptr or [6][B]
+    const int32_t* window;    // nullptr or [B*2] (with a kick: never nullptr)
+    double* g;                // [6][B] g_c in, g_{c+1} out
+    double* force;            // [3][B] out: PlantVar.force
+    double* torque;           // [3][B] out: PlantVar.torque
+    double* wrench_hist;      // nullptr or [T*B*6]
+    const double* est;        // nullptr or [B*6] f^, t^ (with err_sq: never nullptr)
+    double* err_sq;           // nullptr or [B*2] in/out
+};
+
+__global__ void __launch_bounds__(64) ftmpc_environment_kernel(const EnvParams E) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t B = E.B;
+    if (b >= B) return;
+    double base[6], amp[6], kick[6], g[6], w[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        base[k] = E.base_f ? E.base_f[k * B + b] : 0.0;
+        base[3 + k] = E.base_t ? E.base_t[k * B + b] : 0.0;
+        amp[k] = E.amp_f ? E.amp_f[k * B + b] : 0.0;
+        amp[3 + k] = E.amp_t ? E.amp_t[k * B + b] : 0.0;
+    }
+    const bool periodic = E.amp_f || E.amp_t;
+    const double phase = E.phase ? E.phase[b] : 0.0;
+    bool kicked = false;
+    if (E.kick) {
+        const int64_t from = E.window[b * 2], to = E.window[b * 2 + 1];
+        kicked = from <= E.cstep && E.cstep < to;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        kick[j] = kicked ? E.kick[j * B + b] : 0.0;
+        g[j] = E.init ? 0.0 : E.g[j * B + b];
+    }
+    const unsigned long long k = (unsigned long long)(E.cstep * E.index_total + E.index0 + b);
+    ftmpc_env::step(E.proc, E.seed, E.cstep, k, E.init != 0, periodic, kicked, base, amp, phase, kick, g, w);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) E.g[j * B + b] = g[j];
+#pragma unroll
+    for (int k3 = 0; k3 < 3; ++k3) {
+        E.force[k3 * B + b] = w[k3];
+        E.torque[k3 * B + b] = w[3 + k3];
+    }
+    if (E.wrench_hist) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) E.wrench_hist[(E.step * B + b) * 6 + j] = w[j];
+    }
+    if (E.err_sq) {
+        double ef = 0.0, et = 0.0;
+#pragma unroll
+        for (int k3 = 0; k3 < 3; ++k3) {
+            const double df = E.est[b * 6 + k3] - w[k3], dt = E.est[b * 6 + 3 + k3] - w[3 + k3];
+            ef += df * df;
+            et += dt * dt;
+        }
+        E.err_sq[b * 2] += ef;
+        E.err_sq[b * 2 + 1] += et;
+    }
+}
+
 }  // namespace ftmpc

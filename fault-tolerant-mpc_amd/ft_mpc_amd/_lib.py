@@ -44,6 +44,7 @@ SYMBOLS = (
     "ftmpc_eval_cost_wrench_disturbance_batch", "ftmpc_solve_wrench_disturbance_batch", "ftmpc_solve_sqp_wrench_disturbance_batch",
     "ftmpc_simulate_bias_batch", "ftmpc_simulate_wrench_bias_batch", "ftmpc_multi_simulate_bias_batch",
     "ftmpc_simulate_outage_batch", "ftmpc_simulate_wrench_outage_batch", "ftmpc_multi_simulate_outage_batch",
+    "ftmpc_simulate_environment_batch", "ftmpc_simulate_wrench_environment_batch", "ftmpc_multi_simulate_environment_batch",
 )
 
 
@@ -170,6 +171,16 @@ class ftmpc_outage(C.Structure):
     ]
 
 
+class ftmpc_environment(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("step0", C.c_int64),
+        ("sigma", C.c_double * 2), ("tau", C.c_double * 2), ("period", C.c_double),
+        ("amp_force", C.POINTER(C.c_double)), ("amp_torque", C.POINTER(C.c_double)), ("phase", C.POINTER(C.c_double)),
+        ("kick", C.POINTER(C.c_double)), ("window", C.POINTER(C.c_int32)), ("state", C.POINTER(C.c_double)),
+        ("wrench_hist", C.POINTER(C.c_double)), ("est_err_sq", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -265,6 +276,10 @@ def load_library() -> C.CDLL:
     lib.ftmpc_simulate_outage_batch.argtypes = lib.ftmpc_simulate_bias_batch.argtypes + [C.POINTER(ftmpc_outage)]
     lib.ftmpc_multi_simulate_outage_batch.argtypes = lib.ftmpc_simulate_outage_batch.argtypes
     lib.ftmpc_simulate_wrench_outage_batch.argtypes = lib.ftmpc_simulate_wrench_bias_batch.argtypes + [C.POINTER(ftmpc_outage)]
+    lib.ftmpc_simulate_environment_batch.argtypes = lib.ftmpc_simulate_outage_batch.argtypes + [C.POINTER(ftmpc_environment)]
+    lib.ftmpc_multi_simulate_environment_batch.argtypes = lib.ftmpc_simulate_environment_batch.argtypes
+    lib.ftmpc_simulate_wrench_environment_batch.argtypes = (lib.ftmpc_simulate_wrench_outage_batch.argtypes
+                                                            + [C.POINTER(ftmpc_environment)])
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,

@@ -468,7 +468,7 @@ class BatchedMPC:
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
                  plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None,
-                 bias_estimate=None, outage=None):
+                 bias_estimate=None, outage=None, environment=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -563,11 +563,20 @@ class BatchedMPC:
         ([B,4]) and outliers=None ([B,4]) -- what a previous call returned, for a continued run -- and fields=(...) among avail,
         outlier, gate [T,B] int, meas [T,B,13] (y_t as the filter and the diagnosis saw it), state, rejected, outliers; they come
         back as out["outage"].  A lost vehicle's filter propagates and its diagnosis waits; outliers reach the diagnosis ungated.
+        environment: a disturbance wrench that varies over the run, drawn per vehicle on the device and handed to the plant before every
+        plant step (include/ftmpc.h, ftmpc_environment; ft_mpc_amd.environments restates it in NumPy; both formulations): on top of
+        plant["force"] / ["torque"], a Gauss-Markov process (sigma=0.0 and tau=1.0, one value or 2: force in N, torque in N m; s), a
+        periodic term (amp_force=None, amp_torque=None [B,3], phase=None [B] rad, period=1.0 s) and a kick (kick=None [B,6] while
+        window [B,2] int holds: from <= c < to in campaign steps c = step0 + t); seed=0, step0=0 (the sensor's, where the call has
+        one), state=None ([B,6]: what a previous call returned, for a continued run; without it the process starts from a stationary
+        draw), est_err_sq=None ([B,2], continued likewise; needs `disturbance`) and fields=(...) among wrench [T,B,6] (the wrench of
+        every plant step), state, est_err_sq (summed squared error of the disturbance estimate against the wrench, force and
+        torque); they come back as out["environment"].  environments.sample draws a campaign's amplitudes, phases and kicks.
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage][, environment])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage)
+                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage, environment)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -1086,9 +1095,42 @@ def _outage_request(outage, B, T, estimator, disturbance, bias_estimate):
     return og, keep, out
 
 
+def _environment_request(environment, B, T, sensor, disturbance, index0, index_total):
+    """The ftmpc_environment struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .environments import request, stationary
+    r = request(environment, B, T, sensor, disturbance)
+    ev = _lib.ftmpc_environment(struct_size=C.sizeof(_lib.ftmpc_environment), seed=r["seed"] & ((1 << 64) - 1), step0=r["step0"],
+                                period=r["period"])
+    for a in range(2):
+        ev.sigma[a], ev.tau[a] = float(r["sigma"][a]), float(r["tau"][a])
+    keep, out = [], {}
+    for name in ("amp_force", "amp_torque", "phase", "kick"):
+        if r[name] is not None:
+            keep.append(r[name])
+            setattr(ev, name, _ptr(r[name]))
+    if r["window"] is not None:
+        keep.append(r["window"])
+        ev.window = _ptr(r["window"], C.c_int32)
+    # state and est_err_sq are in/out.  At the ABI a state pointer means "handed over", so a state asked back from a run that starts
+    # stationary needs the stationary draw made here (environments.stationary restates the library's) and handed over
+    for name, width in (("state", 6), ("est_err_sq", 2)):
+        a = r[name]
+        if a is None and name in r["fields"]:
+            a = (stationary(B, r["sigma"], r["seed"], r["step0"], index0, index_total) if name == "state" else np.zeros((B, width)))
+        if a is not None:
+            keep.append(a)
+            setattr(ev, name, _ptr(a))
+            if name in r["fields"]:
+                out[name] = a
+    if "wrench" in r["fields"]:
+        out["wrench"] = np.zeros((T, B, 6))
+        ev.wrench_hist = _ptr(out["wrench"])
+    return ev, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -1135,6 +1177,10 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     if outage is not None and multi and formulation == "wrench":
         raise ValueError("outage: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
     og, ogkeep, ogout = (_outage_request(outage, B, T, estimator, disturbance, bias_estimate) if outage is not None
+                         else (None, None, None))
+    if environment is not None and multi and formulation == "wrench":
+        raise ValueError("environment: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
+    ev, evkeep, evout = (_environment_request(environment, B, T, sensor, disturbance, index0, index_total) if environment is not None
                          else (None, None, None))
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
@@ -1185,7 +1231,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
            or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
-           or db is not None or be is not None or og is not None)
+           or db is not None or be is not None or og is not None or environment is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1212,6 +1258,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["bias_estimate"] = beout
         if ogout is not None:
             out["outage"] = ogout
+        if evout is not None:
+            out["environment"] = evout
         return out
     # One argument list, built once: the lead-in of the form, then the feature structs in the order every entry takes them.  The entry
     # is the narrowest one that carries every feature present, so that each ABI level keeps being exercised from here.
@@ -1249,12 +1297,14 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     tail = [("outcomes", new, [ref(oc)]), ("plant", pm is not None, [ref(pm)]), ("mission", ms is not None, [ref(ms)]),
             ("actuator", ac is not None, [ref(ac)]), ("sensor", se is not None, [ref(se)]), ("estimator", es is not None, [ref(es)]),
             ("diagnosis", dg is not None, [ref(dg)] + dgx), ("disturbance", db is not None, [ref(db)]),
-            ("bias", be is not None, [ref(be)]), ("outage", og is not None, [ref(og)])]
+            ("bias", be is not None, [ref(be)]), ("outage", og is not None, [ref(og)]),
+            ("environment", ev is not None, [ref(ev)])]
     last = max((i for i, (_, present, _) in enumerate(tail) if present), default=-1)
     if last >= 0:
         name = tail[last][0]
-        # (the wrench form's bias and outage entries exist on the single handle only: the multi-GPU request has been refused above)
-        pre = "ftmpc_simulate_" if (not multi or (wrench and name in ("bias", "outage"))) else "ftmpc_multi_simulate_"
+        # (the wrench form's bias, outage and environment entries exist on the single handle only: the multi-GPU request has been
+        # refused above)
+        pre = "ftmpc_simulate_" if (not multi or (wrench and name in ("bias", "outage", "environment"))) else "ftmpc_multi_simulate_"
         args = lead + sqp + [sp, _ptr(uh), _ptr(xh)] + counts + [a for _, _, extra in tail[:last + 1] for a in extra]
         self._check(getattr(self.lib, pre + form + name + "_batch")(*args))
         return result(out)

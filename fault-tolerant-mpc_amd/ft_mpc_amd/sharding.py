@@ -126,7 +126,7 @@ class MultiGPUMPC:
     def simulate(self, x0, ub, stuck, xref_traj, T, uref_traj=None, noise=(1e-3, 1e-3, 1e-3, 1e-3), seed=0, return_inputs=False,
                  sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0, faults=None, detect_delay=0,
                  return_states=False, outcomes=None, return_status=False, plant=None, mission=None, actuator=None, sensor=None,
-                 estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None):
+                 estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None):
         """BatchedMPC.simulate over the device slots (ftmpc_multi_simulate_outcomes_batch / _wrench_outcomes_batch): slot g runs its
         shard as the slice [lo, hi) of the campaign, so the noise -- and wherever a vehicle's solve does not depend on its batch, every
         output -- is what one handle computes for the whole batch.  Same arguments and result, without index0 / index_total; the
@@ -142,12 +142,15 @@ class MultiGPUMPC:
         sqp_iters >= 0: ftmpc_multi_simulate_wrench_disturbance_batch); the parameters of `bias_estimate` are uniform, its estimates,
         covariance pieces and history per vehicle (ftmpc_multi_simulate_bias_batch; thruster formulation: the wrench form is not
         built on this driver and raises); the parameters of `outage` are uniform, its window, chain state, counters and histories per
-        vehicle (ftmpc_multi_simulate_outage_batch; thruster formulation: the wrench form is not built on this driver and raises)."""
+        vehicle (ftmpc_multi_simulate_outage_batch; thruster formulation: the wrench form is not built on this driver and raises); sigma,
+        tau and period of `environment` are uniform, its amplitudes, phase, kick, window, state, error sums and wrench history per
+        vehicle (ftmpc_multi_simulate_environment_batch; thruster formulation: the wrench form is not built on this driver and
+        raises)."""
         from .batch import _simulate
         return _simulate(self, True, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, 0, None, plant,
                          mission, actuator, sensor, estimator, diagnosis, disturbance,
-                         bias_estimate, outage)
+                         bias_estimate, outage, environment)
 
     # -- shards resident in HBM between steps ---------------------------------------------------
     def upload(self, x0, ub, stuck, xref, uref=None, warmU=None):

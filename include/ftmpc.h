@@ -1205,6 +1205,87 @@ int ftmpc_simulate_wrench_outage_batch(ftmpc_handle* h, int64_t B, int32_t T, do
                                        int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                        const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage);
 
+/* A disturbance that varies over the run.  ftmpc_plant_model.force / .torque are one constant wrench per vehicle for the whole call;
+ * here the wrench the plant integrates under is rewritten on the device before every plant step: a Gauss-Markov process, a periodic
+ * term and a kick on top of that constant.  The parameters sigma, tau and period are uniform over the call; the amplitudes, the
+ * phase, the kick, its window, the process state and the outputs are per vehicle.
+ *   notation: campaign step c = step0 + t (step0 this struct's own; a sensor in the same call has to carry the same value);
+ *     vehicle number g = index0 + b and index_total as in ftmpc_outcomes; counter k = c * index_total + g; u_s = u01(seed, 32 k + s),
+ *     the splitmix counter function of the plant noise and the sensor, under this struct's own seed; the Gaussian of the slot pair
+ *     (s, s + 1) is sqrt(-2 log(1 - u_s)) cos(6.283185307179586 u_{s+1}).
+ *   per loop step, after the step's solve and right before the plant step (ftmpc_environment_kernel), the wrench held over plant
+ *     step t (zero-order hold, as the constant one is) is  w_c = base + g_c + p_c + k_c,  six components: force in the inertial frame
+ *     [0:3] (N), torque in the body frame [3:6] (N m), the frames and units of ftmpc_plant_model.
+ *     base: plant.force / plant.torque of the call, zero where they are NULL (or the call has no plant model).
+ *     g_c: six independent first-order Gauss-Markov processes, exactly discretised: with phi_a = exp(-dt / tau[a]), a = 0 for the
+ *       force and 1 for the torque, g_{c+1,j} = phi_a g_{c,j} + sigma[a] sqrt(1 - phi_a^2) n_{c,j}, n_{c,j} the Gaussian of the
+ *       slots 2j, 2j+1 of counter k; phi and the innovation scale are computed on the host once per call.  With `state` handed
+ *       over, g of the call's first step is that state; otherwise it is a stationary draw, sigma[a] times the Gaussian of the slots
+ *       16+2j, 17+2j of that step's counter.  On return `state` holds g of step step0 + T, so that a continued run (with step0
+ *       moved on) is the whole run bit for bit.  A non-NULL state always counts as handed over: a caller who wants the end state of
+ *       a run that starts stationary makes that draw itself (ft_mpc_amd.environments.stationary restates it).  sigma[a] = 0 switches the process off: tau[a] is not looked at, nothing is drawn
+ *       and phi_a = 0.
+ *     p_c = amp sin(6.283185307179586 (c dt / period) + phase_b), amp the vehicle's amp_force / amp_torque (a NULL array: zero).
+ *     k_c = kick_b while from_b <= c < to_b (window, in campaign steps); to <= from: no kick.
+ *   the plant: ftmpc_plant_step_var_kernel (with an actuator: ftmpc_plant_step_act_kernel) reads w_c where it read the constant
+ *     wrench; neither kernel changes.  A call without a plant model gets the nominal mass, J and D, as a plant model with every
+ *     array NULL would.
+ *   est_err_sq, in step order: [b][0] += |f^ - w_c[0:3]|^2, [b][1] += |t^ - w_c[3:6]|^2, with (f^, t^) the disturbance estimate
+ *     the step's solve saw (what ftmpc_disturbance.force_hist[t] / torque_hist[t] record).  A handed array is continued.
+ * environment == NULL, or a trivial struct (both sigma zero, every array NULL and no output), launches exactly the kernels of the
+ * _outage_ entries and returns their bits.
+ * Limits: sigma, tau and period are uniform over the call; the force is in the inertial frame only (no body-frame force such as a
+ * leaking valve's, no inertial torque); one kick per vehicle; neither the controller nor the disturbance filter is told the
+ * process's tau (the filter's model stays a random walk with proc_sigma); ftmpc_multi_upload / _step take no environment.
+ * FTMPC_ERR_ARG, the message naming ftmpc_environment.<field> and, for an array, the first offending vehicle, the call's x
+ * untouched: a struct_size other than sizeof(ftmpc_environment); reserved != 0; step0 < 0; a sensor in the call whose step0
+ * differs; a sigma that is negative or not finite; sigma[a] > 0 with a tau[a] that is not positive and finite; an amplitude array
+ * given with a period that is not positive and finite; a non-finite entry of any array; kick without window; est_err_sq without a
+ * disturbance estimate (ftmpc_disturbance) in the call, or with a negative entry.
+ */
+typedef struct ftmpc_environment {
+    int32_t struct_size, reserved;      /* sizeof(ftmpc_environment), 0 */
+    uint64_t seed;                      /* its own stream */
+    int64_t step0;                      /* campaign step of the call's first loop step, >= 0 */
+    double sigma[2];                    /* stationary standard deviation of the Gauss-Markov force (N) and torque (N m); 0: off */
+    double tau[2];                      /* its correlation time (s), > 0 where sigma > 0 */
+    double period;                      /* of the periodic term (s), > 0 where an amplitude is given */
+    const double* amp_force;            /* NULL or [B*3]: amplitude of the periodic force (N, inertial frame) */
+    const double* amp_torque;           /* NULL or [B*3]: amplitude of the periodic torque (N m, body frame) */
+    const double* phase;                /* NULL (0) or [B]: rad */
+    const double* kick;                 /* NULL or [B*6]: force, then torque; needs window */
+    const int32_t* window;              /* NULL or [B*2]: the kick acts while from <= c < to, in campaign steps; to <= from: none */
+    double* state;                      /* NULL or [B*6] in/out: g of the call's first step; on return g of step step0 + T */
+    double* wrench_hist;                /* NULL or [T*B*6] out: w_c of every step */
+    double* est_err_sq;                 /* NULL or [B*2] in/out: summed squared error of f^ and of t^ against w_c; needs a disturbance */
+} ftmpc_environment;
+
+/* ftmpc_simulate_outage_batch with the environment `environment` (NULL: exactly ftmpc_simulate_outage_batch, which IS this entry
+ * with NULL). */
+int ftmpc_simulate_environment_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                     const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                     int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                     double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                     const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                     const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                     const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                     const ftmpc_outage* outage, const ftmpc_environment* environment);
+
+/* The environment on the two-stage wrench form: ftmpc_simulate_wrench_outage_batch with `environment` (NULL: exactly that entry's
+ * kernels and bits).  The kernel is the thruster form's. */
+int ftmpc_simulate_wrench_environment_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                            const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                            int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                            const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                            double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                            int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                            const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                            const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                            int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                            const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                            const ftmpc_environment* environment);
+
 /* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
  * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
  * after G / warmG; the rollout of the cost and of the linearisation sees tau + t^ at every RK4 stage and f^ / m added to the inertial
@@ -1512,6 +1593,20 @@ int ftmpc_multi_simulate_outage_batch(ftmpc_multi* m, int64_t B, int32_t T, doub
                                       const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                       const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                       const ftmpc_outage* outage);
+/* ftmpc_multi_simulate_outage_batch with the environment `environment` (ftmpc_environment; NULL: exactly that entry).  The struct
+ * is checked once over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; amp_force + 3 lo,
+ * amp_torque + 3 lo, phase + lo, kick + 6 lo, window + 2 lo, state + 6 lo and est_err_sq + 2 lo are read and written per shard,
+ * wrench_hist is copied row by row from the shard's staging; the shard's index0 keys its draws, so the bits are the single handle's.
+ * The two-stage wrench form has no multi-GPU outage entry to extend, so it has no multi-GPU environment entry either. */
+int ftmpc_multi_simulate_environment_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                           const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                           int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                           double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                           const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                           const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                           const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                           const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                           const ftmpc_outage* outage, const ftmpc_environment* environment);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
