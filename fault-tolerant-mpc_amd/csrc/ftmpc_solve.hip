@@ -229,18 +229,20 @@ __device__ __forceinline__ double quad_sum_d(double x) {
 
 // ---- 16x16 Cholesky + inverse of the diagonal tile, in the accumulator layout ---------------
 // c[rr] = A[4q+rr][col] (full symmetric tile) on entry; on exit w[rr] = (L^-1)[4q+rr][col].
-// Right-looking elimination WITHOUT scaling the pivot column: after step j column j of the tile is
-// a_j = sqrt(d_j) L[:,j] and is never touched again by anything that matters, so the step is
-//     c[r][col] += bcast_j(c[r]) * nm[col],   nm = -c[j][col] / d_j            (one v_fmac_f32_dpp per register)
-// applied to EVERY lane: the lanes of the columns <= j are dead from here on (they are read only by
-// the row_newbcast of their own step, which is over) and may hold anything, NaN included.
-// The inverse is built alongside: E starts as I, row j of W is E[j]/sqrt(d_j), and
-//     E[r][col] += bcast_j(c[r]) * nw[col],   nw = -E[j][col] / d_j            (c still unscaled -> 1/d, not 1/sqrt d)
-// again on every lane (rows <= j of E are dead once row j has been copied out).  Per step: one
-// v_readlane (pivot), one v_rsq, two row broadcasts through the LDS crossbar (ds_bpermute), 8 fused DPP FMAs,
-// one select.  No barrier, no compare: a non-positive pivot d makes rsq(d) NaN or inf, every
-// later nw = -E[j][col]/d has a 0 * inf in it, and W[15][15] (lane 63, register 3) ends up NaN (inf
-// when only the last pivot is bad).
+// Right-looking elimination WITHOUT scaling the pivot column: at step j column j of the tile is
+// a_j = sqrt(d_j) L[:,j], and the step is
+//     c[r][col] += bcast_j(c[r]) * nm[col],   nm = -c[j][col] / d_j  (0 in the pivot column)   (one v_fmac_f32_dpp per register)
+// applied to EVERY lane, the columns already eliminated included.  Those columns carry the inverse: with E the
+// matrix that starts as I and receives the same row operations (row j of W = L^-1 is E[j] / sqrt(d_j)), Y = E diag(-d_col)
+// obeys  Y[r] += c[r][j] (-1/d_j) Y[j]  with  Y[r][j] = c[r][j] at step j, which IS the update above on the columns < j.
+// So when row r is the pivot row,
+//     W[r][col] = c[r][col] * (-1/d_col) / sqrt(d_r)   (col < r),     W[r][r] = 1/sqrt(d_r),     W[r][col] = 0   (col > r)
+// and no second tile is kept: the step copies row j out scaled by 1/sqrt(d_j) and remembers 1/sqrt(d_j) in the lanes
+// of column j; the column scale and the diagonal / zero selects are applied once per tile (potrf_inv_tail).  Per step:
+// one v_readlane (pivot), one v_rsq, one row broadcast through the LDS crossbar (ds_bpermute), 4 fused DPP FMAs, two
+// multiplies, one masked DPP multiply, two selects.  No barrier, no compare: a non-positive pivot d makes rsq(d) NaN or
+// inf, the update of that step puts NaN or -inf into every later pivot, and W[15][15] = 1/sqrt(d_15) (lane 63,
+// register 3) ends up NaN (inf when only the last pivot is zero).
 template <class F>
 constexpr unsigned long long lane_mask(F f) {
     unsigned long long m = 0;
@@ -279,38 +281,54 @@ struct StepMasks {
     static constexpr unsigned long long piv = lane_mask([](int, int col) { return col == J; });
 };
 template <int J, class Work>
-__device__ __forceinline__ void potrf_inv_step(float (&c)[4], float (&e)[4], float (&w)[4], int bperm_base, const Work& work) {
+__device__ __forceinline__ void potrf_inv_step(float (&c)[4], float (&w)[4], float& icol, int bperm_base, const Work& work) {
     constexpr int QJ = J >> 2, RJ = J & 3;
-    // row J of E to every row-group through the LDS crossbar (ds_bpermute: no VALU slot, ~100 cycles of latency that
-    // the pivot chain below covers).  Row J of the tile itself, which IS on the pivot chain, goes the same way: through the
-    // v_permlane16/32_swap pair it took five VALU issues (two swaps, three copies, as a swap overwrites both of its registers)
-    // against the one readlane + rsq it runs beside, and the pipe the two resident waves share is the bound, not this
-    // chain (12.24 -> 11.85 ms on the headline batch, the same bits)
-    const float ej = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, e[RJ])));
+    // row J of the tile, A[J][col], to every row-group through the LDS crossbar (ds_bpermute: no VALU slot, ~100 cycles of
+    // latency beside the readlane + rsq of the pivot).  Through the v_permlane16/32_swap pair it took five VALU issues (two
+    // swaps, three copies, as a swap overwrites both of its registers), and the pipe the two resident waves share is the
+    // bound, not this chain (12.24 -> 11.85 ms on the headline batch, the same bits)
+    const float rowj = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, c[RJ])));
     const float d = readlane_f(c[RJ], 16 * QJ + J);
     const float inv = __builtin_amdgcn_rsqf(d);
-    const float nrd = -inv * inv;
     work.template run<5 * J + 0>();
     if constexpr (J < 15) {
-        const float rowj = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, c[RJ])));   // A[J][col] in every row-group
+        const float nrd = -inv * inv;
         work.template run<5 * J + 1>();
-        // the pivot column itself stays as it is (multiplier 0): the inverse below still needs it unscaled
+        // the pivot column itself stays as it is (multiplier 0): the columns < J take the update like the ones > J
         fmac4_rowbcast<J>(c, c, sel<StepMasks<J>::piv>(rowj * nrd, 0.f));
         work.template run<5 * J + 2>();
     } else {
         work.template run<5 * J + 1>();
         work.template run<5 * J + 2>();
     }
-    // W[J][col] = E[J][col] / sqrt(d) into row-group QJ only: a DPP multiply with the identity lane pattern whose
-    // row_mask enables just that row-group (multiply and select in one instruction; ej comes from the LDS
-    // crossbar, not from a VALU write, so the DPP read hazard does not apply)
+    // row J of W before its column scale, A[J][col] / sqrt(d), into row-group QJ only: a DPP multiply with the identity
+    // lane pattern whose row_mask enables just that row-group (multiply and select in one instruction; rowj comes from
+    // the LDS crossbar, not from a VALU write, so the DPP read hazard does not apply)
     // (the s_nop covers the wait state a VALU read needs after the transcendental v_rsq that produced `inv`, and the
-    // two a DPP read needs should the compiler have copied `ej` with a VALU move: the hazard recognizer does not
+    // two a DPP read needs should the compiler have copied `rowj` with a VALU move: the hazard recognizer does not
     // look inside inline asm)
-    asm("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 quad_perm:[0,1,2,3] row_mask:%3 bank_mask:0xf" : "+v"(w[RJ]) : "v"(ej), "v"(inv), "n"(1 << QJ));
+    asm("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 quad_perm:[0,1,2,3] row_mask:%3 bank_mask:0xf" : "+v"(w[RJ]) : "v"(rowj), "v"(inv), "n"(1 << QJ));
     work.template run<5 * J + 3>();
-    if constexpr (J < 15) fmac4_rowbcast<J>(e, c, ej * nrd);
+    icol = sel<StepMasks<J>::piv>(icol, inv);      // 1/sqrt(d_J) stays in the lanes of column J (the two s_mov of the select stand after the v_rsq)
     work.template run<5 * J + 4>();
+}
+// Once per tile, after the last step: the column scale -1/d_col below the diagonal, 1/sqrt(d_row) on it, exact zeros above.
+// ROWS: the rows that were eliminated; the rows from there on are identity padding and get the rows of I.
+template <int RR>
+struct TailMasks {
+    static constexpr unsigned long long low = lane_mask([](int q, int col) { return col < 4 * q + RR; });
+    static constexpr unsigned long long dia = lane_mask([](int q, int col) { return col == 4 * q + RR; });
+    static constexpr unsigned long long low8 = lane_mask([](int q, int col) { return q < 2 && col < 4 * q + RR; });
+};
+template <int ROWS>
+__device__ __forceinline__ void potrf_inv_tail(float (&w)[4], float icol) {
+    static_assert(ROWS == 16 || ROWS == 8, "full tile or half tile");
+    const float ncol = -icol * icol;
+    // half tile: icol is still 1 in the columns 8..15, which is their diagonal; `low8` zeroes the rest of those rows
+    w[0] = sel<TailMasks<0>::dia>(sel<(ROWS == 16 ? TailMasks<0>::low : TailMasks<0>::low8)>(0.f, w[0] * ncol), icol);
+    w[1] = sel<TailMasks<1>::dia>(sel<(ROWS == 16 ? TailMasks<1>::low : TailMasks<1>::low8)>(0.f, w[1] * ncol), icol);
+    w[2] = sel<TailMasks<2>::dia>(sel<(ROWS == 16 ? TailMasks<2>::low : TailMasks<2>::low8)>(0.f, w[2] * ncol), icol);
+    w[3] = sel<TailMasks<3>::dia>(sel<(ROWS == 16 ? TailMasks<3>::low : TailMasks<3>::low8)>(0.f, w[3] * ncol), icol);
 }
 struct NoWork {
     template <int S>
@@ -318,13 +336,10 @@ struct NoWork {
 };
 template <class Work>
 __device__ __forceinline__ void potrf_inv16(float (&c)[4], float (&w)[4], int lane, const Work& work) {
-    const int q = lane >> 4, col = lane & 15;
-    float e[4];
+    const int col = lane & 15;
+    float icol = 1.f;
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        e[rr] = (4 * q + rr == col) ? 1.f : 0.f;
-        w[rr] = 0.f;
-    }
+    for (int rr = 0; rr < 4; ++rr) w[rr] = 0.f;
     const int bb = 4 * col;   // ds_bpermute byte address of lane `col` of row-group 0
 #ifndef FTMPC_POTRF_PRIO
 #define FTMPC_POTRF_PRIO 1    // measured at two waves per SIMD: 13.96 -> 13.80 ms on the headline batch (0: off)
@@ -332,46 +347,85 @@ __device__ __forceinline__ void potrf_inv16(float (&c)[4], float (&w)[4], int la
 #if FTMPC_POTRF_PRIO
     __builtin_amdgcn_s_setprio(FTMPC_POTRF_PRIO);   // the pivot chain is dependency-bound: let it issue whenever it can, the partner wave's MFMA stream fills the rest
 #endif
-    potrf_inv_step<0>(c, e, w, bb, work);   potrf_inv_step<1>(c, e, w, bb, work);
-    potrf_inv_step<2>(c, e, w, bb, work);   potrf_inv_step<3>(c, e, w, bb, work);
-    potrf_inv_step<4>(c, e, w, bb, work);   potrf_inv_step<5>(c, e, w, bb, work);
-    potrf_inv_step<6>(c, e, w, bb, work);   potrf_inv_step<7>(c, e, w, bb, work);
-    potrf_inv_step<8>(c, e, w, bb, work);   potrf_inv_step<9>(c, e, w, bb, work);
-    potrf_inv_step<10>(c, e, w, bb, work);  potrf_inv_step<11>(c, e, w, bb, work);
-    potrf_inv_step<12>(c, e, w, bb, work);  potrf_inv_step<13>(c, e, w, bb, work);
-    potrf_inv_step<14>(c, e, w, bb, work);  potrf_inv_step<15>(c, e, w, bb, work);
+    potrf_inv_step<0>(c, w, icol, bb, work);   potrf_inv_step<1>(c, w, icol, bb, work);
+    potrf_inv_step<2>(c, w, icol, bb, work);   potrf_inv_step<3>(c, w, icol, bb, work);
+    potrf_inv_step<4>(c, w, icol, bb, work);   potrf_inv_step<5>(c, w, icol, bb, work);
+    potrf_inv_step<6>(c, w, icol, bb, work);   potrf_inv_step<7>(c, w, icol, bb, work);
+    potrf_inv_step<8>(c, w, icol, bb, work);   potrf_inv_step<9>(c, w, icol, bb, work);
+    potrf_inv_step<10>(c, w, icol, bb, work);  potrf_inv_step<11>(c, w, icol, bb, work);
+    potrf_inv_step<12>(c, w, icol, bb, work);  potrf_inv_step<13>(c, w, icol, bb, work);
+    potrf_inv_step<14>(c, w, icol, bb, work);  potrf_inv_step<15>(c, w, icol, bb, work);
 #if FTMPC_POTRF_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
+    potrf_inv_tail<16>(w, icol);
 }
 __device__ __forceinline__ void potrf_inv16(float (&c)[4], float (&w)[4], int lane) {
     potrf_inv16(c, w, lane, NoWork{});
 }
 // The same for a diagonal tile whose rows 8..15 are identity padding (the last block of n = 16 (NB - 1) + 8 .. : the headline
 // shape, n = 120): pivots 8..15 are 1 and their columns zero, so the elimination stops after eight steps and rows 8..15 of W
-// are the untouched rows of E.  A bad pivot among the first eight shows as NaN / inf in W[7][7] (lane 23, register 3).
+// are rows of the identity, written by the tail.  A bad pivot among the first eight shows as NaN / inf in W[7][7] (lane 23, register 3).
 __device__ __forceinline__ void potrf_inv16_half(float (&c)[4], float (&w)[4], int lane) {
+    const int col = lane & 15;
+    float icol = 1.f;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) w[rr] = 0.f;
+    const int bb = 4 * col;
+    const NoWork work{};
+#if FTMPC_POTRF_PRIO
+    __builtin_amdgcn_s_setprio(FTMPC_POTRF_PRIO);
+#endif
+    potrf_inv_step<0>(c, w, icol, bb, work);   potrf_inv_step<1>(c, w, icol, bb, work);
+    potrf_inv_step<2>(c, w, icol, bb, work);   potrf_inv_step<3>(c, w, icol, bb, work);
+    potrf_inv_step<4>(c, w, icol, bb, work);   potrf_inv_step<5>(c, w, icol, bb, work);
+    potrf_inv_step<6>(c, w, icol, bb, work);   potrf_inv_step<7>(c, w, icol, bb, work);
+#if FTMPC_POTRF_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
+    potrf_inv_tail<8>(w, icol);
+}
+// The form with a second tile, kept for kernel 8 (ftmpc_solve_ws.hip) alone: E starts as I, takes the row operations of the
+// tile ( E[r][col] += bcast_j(c[r]) * nw[col],  nw = -E[j][col] / d_j ), and row j of W is E[j] / sqrt(d_j).  Same W up to
+// rounding for four more DPP FMAs, a multiply and a second ds_bpermute per step.  Kernel 8's interior-point iteration on the
+// synthetic vehicles of its parity test (cond(H) ~ 1e7 in fp32) has instances that end at the iteration cap or a few
+// iterations short of it depending on that rounding, with either form; it keeps the bits it was tuned and tested with.
+template <int J>
+__device__ __forceinline__ void potrf_inv_step_e(float (&c)[4], float (&e)[4], float (&w)[4], int bperm_base) {
+    constexpr int QJ = J >> 2, RJ = J & 3;
+    const float ej = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, e[RJ])));
+    const float d = readlane_f(c[RJ], 16 * QJ + J);
+    const float inv = __builtin_amdgcn_rsqf(d);
+    const float nrd = -inv * inv;
+    if constexpr (J < 15) {
+        const float rowj = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(bperm_base + 64 * QJ, __builtin_bit_cast(int, c[RJ])));   // A[J][col] in every row-group
+        fmac4_rowbcast<J>(c, c, sel<StepMasks<J>::piv>(rowj * nrd, 0.f));
+    }
+    // (s_nop: the wait state after the transcendental v_rsq, and the two a DPP read needs should `ej` have been copied by a VALU move)
+    asm("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 quad_perm:[0,1,2,3] row_mask:%3 bank_mask:0xf" : "+v"(w[RJ]) : "v"(ej), "v"(inv), "n"(1 << QJ));
+    if constexpr (J < 15) fmac4_rowbcast<J>(e, c, ej * nrd);
+}
+__device__ __forceinline__ f32x4 potrf_inv16_e_call(f32x4 cin, int lane) {
     const int q = lane >> 4, col = lane & 15;
-    float e[4];
+    float c[4] = {cin.x, cin.y, cin.z, cin.w}, e[4], w[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
         e[rr] = (4 * q + rr == col) ? 1.f : 0.f;
         w[rr] = 0.f;
     }
     const int bb = 4 * col;
-    const NoWork work{};
 #if FTMPC_POTRF_PRIO
     __builtin_amdgcn_s_setprio(FTMPC_POTRF_PRIO);
 #endif
-    potrf_inv_step<0>(c, e, w, bb, work);   potrf_inv_step<1>(c, e, w, bb, work);
-    potrf_inv_step<2>(c, e, w, bb, work);   potrf_inv_step<3>(c, e, w, bb, work);
-    potrf_inv_step<4>(c, e, w, bb, work);   potrf_inv_step<5>(c, e, w, bb, work);
-    potrf_inv_step<6>(c, e, w, bb, work);   potrf_inv_step<7>(c, e, w, bb, work);
+    potrf_inv_step_e<0>(c, e, w, bb);   potrf_inv_step_e<1>(c, e, w, bb);   potrf_inv_step_e<2>(c, e, w, bb);   potrf_inv_step_e<3>(c, e, w, bb);
+    potrf_inv_step_e<4>(c, e, w, bb);   potrf_inv_step_e<5>(c, e, w, bb);   potrf_inv_step_e<6>(c, e, w, bb);   potrf_inv_step_e<7>(c, e, w, bb);
+    potrf_inv_step_e<8>(c, e, w, bb);   potrf_inv_step_e<9>(c, e, w, bb);   potrf_inv_step_e<10>(c, e, w, bb);  potrf_inv_step_e<11>(c, e, w, bb);
+    potrf_inv_step_e<12>(c, e, w, bb);  potrf_inv_step_e<13>(c, e, w, bb);  potrf_inv_step_e<14>(c, e, w, bb);  potrf_inv_step_e<15>(c, e, w, bb);
 #if FTMPC_POTRF_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) w[rr] = (q >= 2) ? e[rr] : w[rr];
+    const f32x4 r = {w[0], w[1], w[2], w[3]};
+    return r;
 }
 
 // =============================================================================================

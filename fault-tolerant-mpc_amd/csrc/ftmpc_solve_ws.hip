@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(wsk::WG) __attribute__((amdgpu_waves_per_eu((N
                 f32x4 cd;
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) cd[rr] = ((4 * lq + rr == li) ? sg : 0.f) - dsum[rr];
-                const f32x4 w = potrf_inv16_call(cd, lane, NoWork{});
+                const f32x4 w = potrf_inv16_e_call(cd, lane);      // the form with the E tile: see there
                 if (!(fabsf(w.w) <= 3.0e38f) && lane == 63) s_flag = 0;
                 *reinterpret_cast<f32x4*>(Wdl + D * 256 + 4 * lane) = w;
 #pragma unroll
