@@ -44,6 +44,7 @@ struct LoopCall {
     const ftmpc_bias_estimate* be = nullptr;
     const ftmpc_outage* og = nullptr;
     const ftmpc_environment* ev = nullptr;
+    const ftmpc_isolation* is = nullptr;
 };
 
 // the thruster lead-in and the wrench lead-in of the public entries, which differ in nothing else
@@ -432,6 +433,43 @@ std::string environment_problem(const ftmpc_environment* ev, int64_t B, const ft
 bool environment_trivial(const ftmpc_environment* ev) {
     return !ev || (ev->sigma[0] == 0 && ev->sigma[1] == 0 && !ev->amp_force && !ev->amp_torque && !ev->phase && !ev->kick && !ev->window &&
                    !ev->state && !ev->wrench_hist && !ev->est_err_sq);
+}
+
+// trivial: the loop launches the kernels it launches without the struct
+bool isolation_trivial(const ftmpc_isolation* is) {
+    return !is || (is->consist == 0 && is->persist == 1 && is->revise == 0 && !is->lead && !is->voided && !is->revised && !is->fit_hist);
+}
+// An isolation's layout and values (include/ftmpc.h, ftmpc_isolation) over the vehicles [0, B), against the diagnosis of the same
+// call: empty when acceptable, else the message, which names the field and, for an array, the first offending vehicle
+std::string isolation_problem(const ftmpc_isolation* is, int64_t B, int NT, const ftmpc_diagnosis* dg, int64_t first = 0) {
+    if (!is) return "";
+    if (is->struct_size != (int32_t)sizeof(ftmpc_isolation))
+        return "ftmpc_isolation.struct_size is " + std::to_string(is->struct_size) + ", this library expects " +
+               std::to_string(sizeof(ftmpc_isolation));
+    if (is->reserved != 0) return "ftmpc_isolation.reserved is " + std::to_string(is->reserved) + ", not 0";
+    if (!std::isfinite(is->consist) || is->consist < 0) return "ftmpc_isolation.consist is negative or not finite";
+    if (is->persist < 1) return "ftmpc_isolation.persist is " + std::to_string(is->persist) + ", not >= 1";
+    if (is->revise != 0 && is->revise != 1) return "ftmpc_isolation.revise is " + std::to_string(is->revise) + ", not 0 or 1";
+    if (!isolation_trivial(is) && !dg)
+        return "ftmpc_isolation: consist, persist, revise or an array is set, but the call has no diagnosis (ftmpc_diagnosis) whose "
+               "rule they could change";
+    if (is->lead && !dg->state) return "ftmpc_isolation.lead without ftmpc_diagnosis.state";
+    if (is->lead) {
+        const int64_t H = (int64_t)NT * dg->n_levels;
+        for (int64_t b = 0; b < B; ++b) {
+            if (is->lead[b * 2] < -1 || is->lead[b * 2] >= H)
+                return "ftmpc_isolation.lead: vehicle " + std::to_string(first + b) + " has a leader outside [-1, NT * n_levels)";
+            if (is->lead[b * 2 + 1] < 0) return "ftmpc_isolation.lead: vehicle " + std::to_string(first + b) + " has a negative run";
+        }
+    }
+    const int32_t* const arr[2] = {is->voided, is->revised};
+    const char* const name[2] = {"voided", "revised"};
+    for (int a = 0; a < 2; ++a)
+        if (arr[a])
+            for (int64_t b = 0; b < B; ++b)
+                if (arr[a][b] < 0)
+                    return std::string("ftmpc_isolation.") + name[a] + ": vehicle " + std::to_string(first + b) + " has a negative entry";
+    return "";
 }
 
 int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
@@ -1249,6 +1287,59 @@ struct EnvironmentStage {
     }
 };
 
+// Isolation (checked by the entry; it needs the diagnosis): the leader and its run [B][2], the void and the revision counts [B] in
+// the caller's layout (a lane reads and writes its own few words once per step), (-1, 0) and zeros when none are handed over; the
+// fit history.  Nothing is converted on the way out, so there is no unpack
+struct IsolationStage {
+    bool on = false;
+    DevBuf<int32_t> d_lead, d_void, d_rev;
+    DevBuf<double> d_fit;
+    std::vector<int32_t> h_lead;
+    ftmpc::IsoParams iq{};
+
+    int stage(const Loop& q, const ftmpc_isolation* is) {
+        on = !isolation_trivial(is);
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        LOOP_TRY(dev_alloc(q, d_lead, B * 2));
+        if (is->lead) {
+            LOOP_TRY(dev_put(q, d_lead.p, (const int32_t*)is->lead, B * 2));
+        } else {
+            try {
+                h_lead.assign(B * 2, 0);
+            } catch (const std::bad_alloc&) {
+                return fail(q.h, FTMPC_ERR_ALLOC, "out of host memory for the isolation's staging array");
+            }
+            for (size_t b = 0; b < B; ++b) h_lead[b * 2] = -1;
+            LOOP_TRY(dev_put(q, d_lead.p, (const int32_t*)h_lead.data(), B * 2));
+        }
+        auto counters = [&](DevBuf<int32_t>& d, const int32_t* host) -> int {
+            LOOP_TRY(dev_alloc(q, d, B));
+            return host ? dev_put(q, d.p, host, B) : dev_fill(q, d.p, 0, B);
+        };
+        LOOP_TRY(counters(d_void, is->voided));
+        LOOP_TRY(counters(d_rev, is->revised));
+        LOOP_TRY(hist_alloc(q, d_fit, (const double*)is->fit_hist, T * B * 2));
+        iq.consist_sq = is->consist * is->consist;
+        iq.persist = is->persist;
+        iq.revise = is->revise;
+        iq.lead = d_lead;
+        iq.voided = d_void;
+        iq.revised = d_rev;
+        iq.fit_hist = d_fit;
+        return FTMPC_OK;
+    }
+    int fetch(const Loop& q, const ftmpc_isolation* is) {
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B;
+        LOOP_TRY(hist_get(q, is->lead, d_lead, B * 2));
+        LOOP_TRY(hist_get(q, is->voided, d_void, B));
+        LOOP_TRY(hist_get(q, is->revised, d_rev, B));
+        LOOP_TRY(hist_get(q, is->fit_hist, d_fit, T * B * 2));
+        return FTMPC_OK;
+    }
+};
+
 // Diagnosis (checked by the entry): xt and n [B][14], acc [NT][B] and the statistics [H][B] component-major (filled on the device when
 // none are handed over), the detect arrays [B][K] with the count per vehicle, the flag the repair kernel reads.  On the wrench form
 // also the hull rebuild: the new offsets [B][hull_rows] and [flat B | no_hull B]
@@ -1630,6 +1721,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     BiasStage bia;
     OutageStage oge;
     EnvironmentStage env;
+    IsolationStage iso;
     DiagStage dia;
     MissionStage mis;
     OutcomeStage out;
@@ -1643,6 +1735,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(bia.stage(q, c.be));
     LOOP_TRY(oge.stage(q, c.og));
     LOOP_TRY(env.stage(q, c.ev));
+    LOOP_TRY(iso.stage(q, c.is));
     LOOP_TRY(dia.stage(q, dg, c));
     LOOP_TRY(mis.stage(q, c.ms, windows, want_cost, xw, uw, L));
     LOOP_TRY(out.stage(q, c.oc, want_cost, wrench));
@@ -1760,7 +1853,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
             dp.anchor = (se->step0 + t) % dg->every == 0;
             dp.cstep = (int32_t)(se->step0 + t);
             dp.step = t;
-            if (oge.on)
+            if (iso.on)     // the test with the gate, confirmation and revision, in place of either phase-0 kernel
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_iso_kernel, per_vehicle, wave, 0, s, h->dc, dp, iso.iq,
+                                   oge.on ? (const int32_t*)oge.d_avail.p : (const int32_t*)nullptr);
+            else if (oge.on)
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_gated_kernel, per_vehicle, wave, 0, s, h->dc, dp, (const int32_t*)oge.d_avail.p);
             else
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<0>, per_vehicle, wave, 0, s, h->dc, dp);
@@ -1900,6 +1996,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(bia.fetch(q, c.be));
     LOOP_TRY(oge.fetch(q, c.og));
     LOOP_TRY(env.fetch(q, c.ev));
+    LOOP_TRY(iso.fetch(q, c.is));
     LOOP_TRY(dia.fetch(q, dg, c));
     LOOP_TRY(run.fetch(q, c));
     LOOP_TRY(mis.fetch(q, c.ms, want_cost));
@@ -1931,9 +2028,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
 void loop_call_features(LoopCall& c, double* x_hist, const ftmpc_fault_schedule* fs, const ftmpc_outcomes* oc, const ftmpc_plant_model* pm,
                         const ftmpc_mission* ms, const ftmpc_actuator* ac, const ftmpc_sensor* se, const ftmpc_estimator* es,
                         const ftmpc_diagnosis* dg, const ftmpc_disturbance* db, const ftmpc_bias_estimate* be,
-                        const ftmpc_outage* og = nullptr, const ftmpc_environment* ev = nullptr) {
+                        const ftmpc_outage* og = nullptr, const ftmpc_environment* ev = nullptr,
+                        const ftmpc_isolation* is = nullptr) {
     c.x_hist = x_hist;
-    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og, c.ev = ev;
+    c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og, c.ev = ev, c.is = is;
 }
 
 // the argument checks, in the order the entries have always made them (a bad call keeps its message)
@@ -1963,6 +2061,7 @@ int loop_check(ftmpc_handle* h, const LoopCall& c) {
     if (!(msg = bias_problem(c.be, B, c.es, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     if (!(msg = outage_problem(c.og, B, c.es, c.db, c.be)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     if (!(msg = environment_problem(c.ev, B, c.se, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    if (!(msg = isolation_problem(c.is, B, h->cfg.NT, c.dg)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     return FTMPC_OK;
 }
 
@@ -2127,9 +2226,23 @@ int ftmpc_simulate_environment_batch(ftmpc_handle* h, int64_t B, int32_t T, doub
                                      const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                      const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                      const ftmpc_outage* outage, const ftmpc_environment* environment) {
+    return ftmpc_simulate_isolation_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults,
+                                          u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis,
+                                          disturbance, bias_estimate, outage, environment, nullptr);
+}
+
+int ftmpc_simulate_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                   const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                   const ftmpc_outage* outage, const ftmpc_environment* environment,
+                                   const ftmpc_isolation* isolation) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
-                       environment);
+                       environment, isolation);
     return loop_run(h, c);
 }
 
@@ -2287,12 +2400,30 @@ int ftmpc_simulate_wrench_environment_batch(ftmpc_handle* h, int64_t B, int32_t 
                                             int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                             const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
                                             const ftmpc_environment* environment) {
+    return ftmpc_simulate_wrench_isolation_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
+                                                 noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
+                                                 alloc_failed, out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b,
+                                                 no_hull_step, disturbance, bias_estimate, outage, environment, nullptr);
+}
+
+int ftmpc_simulate_wrench_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                          const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                          double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                          int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                          const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                          const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                          int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                          const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                          const ftmpc_environment* environment, const ftmpc_isolation* isolation) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_wrench(c, hull_A, n_sets, hull_set, hull_b, hull_rows, penalty, alloc_failed);
     c.out_hull_b = out_hull_b;
     c.no_hull_step = no_hull_step;
     loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
-                       environment);
+                       environment, isolation);
     return loop_run(h, c);
 }
 

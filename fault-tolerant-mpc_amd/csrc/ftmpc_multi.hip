@@ -263,6 +263,10 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         const std::string msg = environment_problem(c.ev, B, c.se, c.db);
         if (!msg.empty()) return refuse(msg);
     }
+    {     // the isolation likewise: consist, persist and revise are uniform, lead, the two counters and fit_hist per vehicle
+        const std::string msg = isolation_problem(c.is, B, m->cfg.NT, c.dg);
+        if (!msg.empty()) return refuse(msg);
+    }
     {     // the mission likewise: tables are shared, table / offset / cost are per vehicle
         const std::string msg = mission_problem(c.ms, B, T, m->cfg.N, c.xref_traj, c.uref_traj, 0, sensor_shift(c.se));
         if (!msg.empty()) return refuse(msg);
@@ -393,7 +397,16 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (nv.state) nv.state += lo * 6;
             if (nv.est_err_sq) nv.est_err_sq += lo * 2;
         }
+        std::vector<double> ifh;
+        ftmpc_isolation iv{};
+        if (c.is) {
+            iv = *c.is;
+            if (iv.lead) iv.lead += lo * 2;
+            if (iv.voided) iv.voided += lo;
+            if (iv.revised) iv.revised += lo;
+        }
         try {
+            if (iv.fit_hist && !whole) ifh.resize((size_t)T * n * 2);
             if (nv.wrench_hist && !whole) ewh.resize((size_t)T * n * 6);
             if (ov.avail_hist && !whole) oah.resize((size_t)T * n);
             if (ov.outlier_hist && !whole) ooh.resize((size_t)T * n);
@@ -447,6 +460,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (ov.gate_hist) ov.gate_hist = ogh.data();
             if (ov.meas_hist) ov.meas_hist = omh.data();
             if (nv.wrench_hist) nv.wrench_hist = ewh.data();
+            if (iv.fit_hist) iv.fit_hist = ifh.data();
         }
         LoopCall sc = c;      // the shard as a call of its own: the path of the single-handle entry
         sc.B = n;
@@ -464,6 +478,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
         sc.be = c.be ? &sb : nullptr;
         sc.og = c.og ? &ov : nullptr;
         sc.ev = c.ev ? &nv : nullptr;
+        sc.is = c.is ? &iv : nullptr;
         const int rc2 = loop_run(d.h, sc);
         if (rc2 != FTMPC_OK) return dev_fail(d, rc2, ftmpc_last_error(d.h));
         if (!whole) {
@@ -484,6 +499,7 @@ int multi_simulate(ftmpc_multi* m, const LoopCall& c) {
             if (c.og && c.og->gate_hist) scatter_rows(c.og->gate_hist, ogh.data(), T, B, lo, n, 1);
             if (c.og && c.og->meas_hist) scatter_rows(c.og->meas_hist, omh.data(), T, B, lo, n, 13);
             if (c.ev && c.ev->wrench_hist) scatter_rows(c.ev->wrench_hist, ewh.data(), T, B, lo, n, 6);
+            if (c.is && c.is->fit_hist) scatter_rows(c.is->fit_hist, ifh.data(), T, B, lo, n, 2);
         }
         return FTMPC_OK;
     });
@@ -895,9 +911,24 @@ int ftmpc_multi_simulate_environment_batch(ftmpc_multi* m, int64_t B, int32_t T,
                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                            const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                            const ftmpc_outage* outage, const ftmpc_environment* environment) {
+    return ftmpc_multi_simulate_isolation_batch(m, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol,
+                                                faults, u_hist, x_hist, not_converged, out, plant, mission, actuator, sensor, estimator,
+                                                diagnosis, disturbance, bias_estimate, outage, environment, nullptr);
+}
+
+int ftmpc_multi_simulate_isolation_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                         const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                         const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                         const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                         const ftmpc_outage* outage, const ftmpc_environment* environment,
+                                         const ftmpc_isolation* isolation) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
-                       environment);
+                       environment, isolation);
     return multi_simulate(m, c);
 }
 

@@ -2573,4 +2573,110 @@ __global__ void __launch_bounds__(64) ftmpc_environment_kernel(const EnvParams E
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The diagnosis' test with a consistency gate, confirmation and level revision (ftmpc_simulate_isolation_batch /
+// ftmpc_simulate_wrench_isolation_batch; include/ftmpc.h, ftmpc_isolation).  One kernel, a lane per vehicle, launched in place of
+// ftmpc_diagnose_kernel<0> or ftmpc_diagnose_gated_kernel (avail == nullptr: the call has no outage); phase 1, the repair and the hull
+// kernels are the ones every diagnosis runs.  The per-vehicle test is csrc/ftmpc_isolate.h: the residual and q_0 once, then the rolled
+// thruster loop with the levels unrolled, which carries the arg-max, the smallest q_h and the counts; the scan of the vehicle's
+// detection list (revise: is this off thruster one of the vehicle's own detections?) is a rolled loop of at most max_detect <= 8
+// compares, entered for an off thruster only.  The plain kernels are siblings, not instantiations of this one: their code is what
+// it was.  lead [B][2] (leader, run), voided [B] and revised [B] keep the caller's layout (a lane reads and writes its own few words
+// once per step), fit_hist is [T][B][2].
+// ---------------------------------------------------------------------------------------------------------
+}  // namespace ftmpc
+#include "ftmpc_isolate.h"      // (included here, not at the top: the build logs keep the source lines of every kernel above)
+namespace ftmpc {
+struct IsoParams {
+    double consist_sq;        // 0: no gate
+    int32_t persist, revise;
+    int32_t* lead;            // [B*2] leader, run: in/out
+    int32_t* voided;          // [B] in/out
+    int32_t* revised;         // [B] in/out
+    double* fit_hist;         // nullptr or [T*B*2]
+};
+
+__global__ void __launch_bounds__(64) ftmpc_diagnose_iso_kernel(const DeviceConsts C, const DiagParams P, const IsoParams I,
+                                                                const int32_t* avail) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int64_t B = P.B;
+    const int NT = C.NT, L = P.L, H = NT * L;
+    double x[13], y[13];
+    double* const hist = P.llr_hist ? P.llr_hist + (P.step * B + b) * H : nullptr;
+    double* const fit = I.fit_hist ? I.fit_hist + (P.step * B + b) * 2 : nullptr;
+    if (!P.init && avail && !avail[b]) {     // lost: no test, no re-anchor; xt, n, acc, llr, lead and the counters carry over
+        if (hist) {
+#pragma unroll 1
+            for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+        }
+        if (fit) fit[0] = fit[1] = -1.0;
+        P.switched[b] = 0;
+        return;
+    }
+    for (int i = 0; i < 13; ++i) y[i] = P.y[b * 13 + i];
+    int32_t sw = 0;
+    bool tested = false;
+    double f0 = -1.0, f1 = -1.0;
+    if (P.init) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+    } else {
+        const double n = P.xt[b * 14 + 13];
+        const int32_t cnt = P.count[b];
+        if (P.anchor && n >= 1.0 && cnt < P.K) {
+            tested = true;
+            for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+            ftmpc_iso::Rule R;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) R.levels[l] = P.levels[l];
+            R.threshold = P.threshold;
+            R.consist_sq = I.consist_sq;
+            R.L = L, R.persist = I.persist, R.revise = I.revise, R.pad0 = 0;
+            ftmpc_iso::Resid r;
+            ftmpc_iso::residual(x, y, n, P.rsq, P.dsq, r);
+            ftmpc_iso::Scan s;
+            ftmpc_iso::scan_start(R, s);
+#pragma unroll 1
+            for (int i = 0; i < NT; ++i) {
+                const bool live = P.ub[b * NT + i] > 0.0;
+                bool listed = false;
+                if (!live && I.revise) {
+#pragma unroll 1
+                    for (int k = 0; k < cnt; ++k) listed = listed || P.det_thruster[b * P.K + k] == i;
+                }
+                const double d[6] = {C.D[i], C.D[MAX_NT + i], C.D[2 * MAX_NT + i], C.D[3 * MAX_NT + i], C.D[4 * MAX_NT + i], C.D[5 * MAX_NT + i]};
+                double gh[6];
+                ftmpc_iso::unit_signature(C.dt, C.inv_mass, C.Jinv, d, gh);
+                ftmpc_iso::thruster(R, r, n, i, live, listed, P.acc[(int64_t)i * B + b], P.stuck[b * NT + i], gh,
+                                    P.llr + (int64_t)i * L * B + b, B, hist ? hist + i * L : nullptr, s);
+            }
+            if (s.eligible > 0) f0 = r.q0, f1 = s.qmin;
+            if (ftmpc_iso::is_void(R, r, s)) I.voided[b] += 1;
+            int lead = I.lead[b * 2], run = I.lead[b * 2 + 1];
+            if (ftmpc_iso::confirm(R, s, lead, run)) {
+                const int rev = ftmpc_iso::decide(R, s.besth, P.cstep, cnt, H, P.ub + b * NT, P.stuck + b * NT, P.det_step + b * P.K,
+                                                  P.det_thruster + b * P.K, P.det_level + b * P.K, P.llr + b, B, lead, run);
+                P.count[b] = cnt + 1;
+                if (rev) I.revised[b] += 1;
+                sw = 1;
+            }
+            I.lead[b * 2] = lead;
+            I.lead[b * 2 + 1] = run;
+        }
+    }
+    if (hist && !tested) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+    }
+    if (fit) fit[0] = f0, fit[1] = f1;
+    P.switched[b] = sw;
+    if (P.init || P.anchor) {
+        for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = y[i];
+        P.xt[b * 14 + 13] = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) P.acc[(int64_t)i * B + b] = 0.0;
+    }
+}
+
 }  // namespace ftmpc

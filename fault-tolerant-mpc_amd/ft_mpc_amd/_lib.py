@@ -45,6 +45,7 @@ SYMBOLS = (
     "ftmpc_simulate_bias_batch", "ftmpc_simulate_wrench_bias_batch", "ftmpc_multi_simulate_bias_batch",
     "ftmpc_simulate_outage_batch", "ftmpc_simulate_wrench_outage_batch", "ftmpc_multi_simulate_outage_batch",
     "ftmpc_simulate_environment_batch", "ftmpc_simulate_wrench_environment_batch", "ftmpc_multi_simulate_environment_batch",
+    "ftmpc_simulate_isolation_batch", "ftmpc_simulate_wrench_isolation_batch", "ftmpc_multi_simulate_isolation_batch",
 )
 
 
@@ -181,6 +182,14 @@ class ftmpc_environment(C.Structure):
     ]
 
 
+class ftmpc_isolation(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("consist", C.c_double), ("persist", C.c_int32), ("revise", C.c_int32),
+        ("lead", C.POINTER(C.c_int32)), ("voided", C.POINTER(C.c_int32)), ("revised", C.POINTER(C.c_int32)),
+        ("fit_hist", C.POINTER(C.c_double)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -280,6 +289,10 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_environment_batch.argtypes = lib.ftmpc_simulate_environment_batch.argtypes
     lib.ftmpc_simulate_wrench_environment_batch.argtypes = (lib.ftmpc_simulate_wrench_outage_batch.argtypes
                                                             + [C.POINTER(ftmpc_environment)])
+    lib.ftmpc_simulate_isolation_batch.argtypes = lib.ftmpc_simulate_environment_batch.argtypes + [C.POINTER(ftmpc_isolation)]
+    lib.ftmpc_multi_simulate_isolation_batch.argtypes = lib.ftmpc_simulate_isolation_batch.argtypes
+    lib.ftmpc_simulate_wrench_isolation_batch.argtypes = (lib.ftmpc_simulate_wrench_environment_batch.argtypes
+                                                          + [C.POINTER(ftmpc_isolation)])
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,

@@ -468,7 +468,7 @@ class BatchedMPC:
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
                  plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None,
-                 bias_estimate=None, outage=None, environment=None):
+                 bias_estimate=None, outage=None, environment=None, isolation=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -572,11 +572,19 @@ class BatchedMPC:
         draw), est_err_sq=None ([B,2], continued likewise; needs `disturbance`) and fields=(...) among wrench [T,B,6] (the wrench of
         every plant step), state, est_err_sq (summed squared error of the disturbance estimate against the wrench, force and
         torque); they come back as out["environment"].  environments.sample draws a campaign's amplitudes, phases and kicks.
+        isolation: three safeguards for the diagnosis' decision rule (include/ftmpc.h, ftmpc_isolation; ft_mpc_amd.diagnosis.replay
+        with isolation= restates them in NumPy; both formulations; needs `diagnosis`): consist=0.0 (the gate on the fit q_h of a
+        hypothesis, in standard deviations: diagnosis.consist_for(p); 0: no gate), persist=1 (tests in a row with the same leader
+        before the decision), revise=False (the level of a detected thruster is tested on and may be revised), lead=None ([B,2] int:
+        leader and run, what a previous call returned; needs diagnosis['state']), voided=None ([B]) and revised=None ([B]),
+        continued likewise, and fields=(...) among lead, voided, revised, fit [T,B,2] (q_0 and the smallest q_h of every tested
+        step, else -1); they come back as out["isolation"].
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage][, environment])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage][, environment][, isolation])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
-                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage, environment)
+                         plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage, environment,
+                         isolation)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -1128,9 +1136,35 @@ def _environment_request(environment, B, T, sensor, disturbance, index0, index_t
     return ev, keep, out
 
 
+def _isolation_request(isolation, B, T, NT, diagnosis):
+    """The ftmpc_isolation struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .diagnosis import isolation_request
+    r = isolation_request(isolation, B, NT, diagnosis)
+    iso = _lib.ftmpc_isolation(struct_size=C.sizeof(_lib.ftmpc_isolation), consist=r["consist"], persist=r["persist"],
+                               revise=int(r["revise"]))
+    keep, out = [], {}
+    # lead, voided and revised are in/out: asked back without being handed over, they start as the library's defaults
+    for name, shape in (("lead", (B, 2)), ("voided", (B,)), ("revised", (B,))):
+        a = r[name]
+        if a is None and name in r["fields"]:
+            a = np.zeros(shape, np.int32)
+            if name == "lead":
+                a[:, 0] = -1
+        if a is not None:
+            keep.append(a)
+            setattr(iso, name, _ptr(a, C.c_int32))
+            if name in r["fields"]:
+                out[name] = a
+    if "fit" in r["fields"]:
+        out["fit"] = np.zeros((T, B, 2))
+        iso.fit_hist = _ptr(out["fit"])
+    return iso, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
-              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None):
+              actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None,
+              isolation=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -1182,6 +1216,15 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         raise ValueError("environment: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
     ev, evkeep, evout = (_environment_request(environment, B, T, sensor, disturbance, index0, index_total) if environment is not None
                          else (None, None, None))
+    if isolation is not None and multi and formulation == "wrench":
+        raise ValueError("isolation: the two-stage wrench form on MultiGPUMPC is not built (use BatchedMPC, or the thruster formulation)")
+    iso, isokeep, isoout = (None, None, None)
+    if isolation is not None:
+        # lead needs a state at the ABI: asked back (or handed over) on a run whose diagnosis carries no state, the call is refused here
+        iso, isokeep, isoout = _isolation_request(isolation, B, T, NT, diagnosis)
+        if iso.lead and dg is not None and not dg.state:
+            raise ValueError("isolation['lead'] (handed over or among fields) needs the diagnosis' state: put 'state' into "
+                             "diagnosis['fields'] or hand diagnosis['state'] over")
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -1231,7 +1274,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     ac, akeep, aout = _actuator_request(actuator, B, T, NT) if actuator is not None else (None, None, None)
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
            or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
-           or db is not None or be is not None or og is not None or environment is not None)
+           or db is not None or be is not None or og is not None or environment is not None
+           or isolation is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1260,6 +1304,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["outage"] = ogout
         if evout is not None:
             out["environment"] = evout
+        if isoout is not None:
+            out["isolation"] = isoout
         return out
     # One argument list, built once: the lead-in of the form, then the feature structs in the order every entry takes them.  The entry
     # is the narrowest one that carries every feature present, so that each ABI level keeps being exercised from here.
@@ -1298,13 +1344,14 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             ("actuator", ac is not None, [ref(ac)]), ("sensor", se is not None, [ref(se)]), ("estimator", es is not None, [ref(es)]),
             ("diagnosis", dg is not None, [ref(dg)] + dgx), ("disturbance", db is not None, [ref(db)]),
             ("bias", be is not None, [ref(be)]), ("outage", og is not None, [ref(og)]),
-            ("environment", ev is not None, [ref(ev)])]
+            ("environment", ev is not None, [ref(ev)]), ("isolation", iso is not None, [ref(iso)])]
     last = max((i for i, (_, present, _) in enumerate(tail) if present), default=-1)
     if last >= 0:
         name = tail[last][0]
-        # (the wrench form's bias, outage and environment entries exist on the single handle only: the multi-GPU request has been
-        # refused above)
-        pre = "ftmpc_simulate_" if (not multi or (wrench and name in ("bias", "outage", "environment"))) else "ftmpc_multi_simulate_"
+        # (the wrench form's bias, outage, environment and isolation entries exist on the single handle only: the multi-GPU request
+        # has been refused above)
+        pre = ("ftmpc_simulate_" if (not multi or (wrench and name in ("bias", "outage", "environment", "isolation")))
+               else "ftmpc_multi_simulate_")
         args = lead + sqp + [sp, _ptr(uh), _ptr(xh)] + counts + [a for _, _, extra in tail[:last + 1] for a in extra]
         self._check(getattr(self.lib, pre + form + name + "_batch")(*args))
         return result(out)

@@ -13,7 +13,8 @@ measurement.  With n the model steps since that measurement and acc_i the sum ov
 replay runs the loop's diagnosis for one vehicle from the recorded measurements and applied commands.
 
 The signature is first order in dt; a dead thruster that is not commanded has none, and neither has a thruster stuck at the level it
-is commanded at; a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's test; a
+is commanded at; with isolation= (include/ftmpc.h, ftmpc_isolation; csrc/ftmpc_isolate.h) the decision gets a consistency gate on the
+fit q_h = q_0 - 2 z_h, confirmation over `persist` tests and the revision of a detected thruster's level; a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's test; a
 detection is never withdrawn; position and attitude are not used; the diagnosis is told neither the plant's dispersion nor the
 actuator."""
 from __future__ import annotations
@@ -26,6 +27,7 @@ from .sensors import predict
 MAX_LEVELS = 4
 MAX_DETECT = 8          # FTMPC_MAX_FAULT_EVENTS
 FIELDS = ("detect", "pattern", "llr_hist", "state")
+ISO_FIELDS = ("lead", "voided", "revised", "fit")
 
 
 def default_sigma(sensor_sigma, noise=(0.0, 0.0, 0.0, 0.0)):
@@ -47,8 +49,35 @@ def signature(n, acc, levels, cfg):
     return gv[:, None, :] * delta[:, :, None], gw[:, None, :] * delta[:, :, None]
 
 
-def test_step(llr, y, xt, n, acc, ub, spec, cfg):
-    """The statistics [NT,L] after the test of one step (after the max(0, .), before a detection's reset)."""
+def consist_for(p):
+    """The gate `consist` that a residual which fits its hypothesis passes with probability p: the square root of the chi-square(6)
+    quantile, the root x of 1 - exp(-x / 2) (1 + x / 2 + x^2 / 8) = p (bisection on a function that rises with x)."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError("consist_for: p must lie strictly between 0 and 1")
+    cdf = lambda x: 1.0 - np.exp(-0.5 * x) * (1.0 + 0.5 * x + 0.125 * x * x)
+    lo, hi = 0.0, 16.0
+    while cdf(hi) < p:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if cdf(mid) < p else (lo, mid)
+    return float(np.sqrt(0.5 * (lo + hi)))
+
+
+def _isolation(isolation):
+    """(consist, persist, revise) of an isolation dict"""
+    return float(isolation.get("consist", 0.0)), int(isolation.get("persist", 1)), bool(isolation.get("revise", False))
+
+
+def test_step(llr, y, xt, n, acc, ub, spec, cfg, isolation=None, lead=None, stuck=None, listed=()):
+    """The statistics [NT,L] after the test of one step (after the max(0, .), before a detection's reset).
+    isolation = dict(consist, persist, revise): the test under ftmpc_isolation's rule, with lead = (leader, run) as the last test left
+    it (None: (-1, 0)), stuck [NT] the controller's levels and listed the thrusters of the vehicle's detection list (both looked at
+    with revise only).  It then returns dict(llr [NT,L], q0, q [NT,L] (nan where the hypothesis is not eligible), qmin (nan without an
+    eligible hypothesis), void, leader (-1: none), lead (leader, run) after the confirmation and before a decision's reset, decide
+    (the leader is decided now), margin (the smallest |q_h - consist^2|, inf without a gate), gap (the leader's statistic minus the
+    runner-up's, inf without a leader))."""
     lv = np.asarray(spec["levels"], dtype=np.float64).reshape(-1)
     rs = np.asarray(spec["resid_sigma"], dtype=np.float64).reshape(2)
     ds = np.asarray(spec.get("drift_sigma", (0.0, 0.0)), dtype=np.float64).reshape(2)
@@ -60,8 +89,45 @@ def test_step(llr, y, xt, n, acc, ub, spec, cfg):
     a_v, a_w = signature(n, acc, lv, cfg)
     z = (a_v @ rho_v - 0.5 * (a_v * a_v).sum(-1)) / s_v + (a_w @ r_w - 0.5 * (a_w * a_w).sum(-1)) / s_w
     out = np.maximum(0.0, np.asarray(llr, dtype=np.float64).reshape(z.shape) + z)
-    out[np.asarray(ub).reshape(-1) <= 0] = 0.0
-    return out
+    live = np.asarray(ub).reshape(-1) > 0
+    if isolation is None:
+        out[~live] = 0.0
+        return out
+    consist, persist, revise = _isolation(isolation)
+    old = np.asarray(llr, dtype=np.float64).reshape(z.shape)
+    NT, L = z.shape
+    off = np.zeros(NT, bool)
+    if revise:
+        off[[i for i in set(int(i) for i in listed) if not live[i]]] = True
+        if off.any():      # the signature of a revised level against the model's stuck level: delta = n (levels[l] - stuck_i)
+            D, m, J = _cfg_model(cfg)
+            delta = float(n) * (lv[None, :] - np.asarray(stuck, dtype=np.float64).reshape(-1, 1))
+            b_v = ((float(cfg.dt) / m) * D[0:3].T)[:, None, :] * delta[:, :, None]
+            b_w = (float(cfg.dt) * np.linalg.solve(J, D[3:6]).T)[:, None, :] * delta[:, :, None]
+            zr = (b_v @ rho_v - 0.5 * (b_v * b_v).sum(-1)) / s_v + (b_w @ r_w - 0.5 * (b_w * b_w).sum(-1)) / s_w
+            z = np.where(off[:, None], zr, z)
+    eligible = live | off
+    q0 = float(rho_v @ rho_v / s_v + r_w @ r_w / s_w)
+    q = np.where(eligible[:, None], q0 - 2.0 * z, np.nan)
+    counted = eligible[:, None] & ((q <= consist * consist) if consist > 0 else np.ones_like(z, bool))
+    new = np.where(counted, np.maximum(0.0, old + z), np.where(eligible[:, None], old, 0.0))
+    flat = new.reshape(-1)
+    thr = float(spec["threshold"])
+    leader = int(np.argmax(flat)) if flat.max() > thr else -1      # (the first of equal maxima)
+    gap = np.inf
+    if leader >= 0 and flat.size > 1:
+        gap = float(flat[leader] - np.delete(flat, leader).max())
+    ld, run = (-1, 0) if lead is None else (int(lead[0]), int(lead[1]))
+    if leader < 0:
+        ld, run = -1, 0
+    elif leader == ld:
+        run += 1
+    else:
+        ld, run = leader, 1
+    margin = float(np.abs(q[eligible] - consist * consist).min()) if consist > 0 and eligible.any() else np.inf
+    return dict(llr=new, q0=q0, q=q, qmin=float(np.min(q[eligible])) if eligible.any() else np.nan,
+                void=bool(consist > 0 and q0 > consist * consist and not counted.any()), leader=leader, lead=(ld, run),
+                decide=leader >= 0 and run >= persist, margin=margin, gap=gap)
 
 
 test_step.__test__ = False      # (not a test of the suite, whatever its name)
@@ -80,13 +146,18 @@ def propagate(xt, n, acc, u, ub, stuck, cfg, force=None, torque=None):
     return xn, n + 1, np.asarray(acc, dtype=np.float64) + c
 
 
-def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None, avail=None):
+def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None, avail=None,
+           isolation=None, lead=None, voided=0, revised=0):
     """The loop's diagnosis for ONE vehicle.  meas [T,13]: the y_t; applied_u [T,NT]: the a_t (u_hist); ub, stuck [NT]: the
     controller's pattern at the call's start; spec: dict(every, levels, resid_sigma, drift_sigma, threshold, max_detect); state
     [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned; force / torque [T,3]: the
     estimated disturbance of each step (simulate(disturbance=...): force_hist / torque_hist) for the propagation, None: without;
     avail [T] (simulate(outage=...): the avail history; None: always available): on a step where the vehicle is lost there is no test
     and no re-anchor, the statistics carry over and n keeps counting (the first step of a replay without state anchors regardless).
+    isolation = dict(consist, persist, revise): ftmpc_isolation's rule (test_step), with lead (leader, run), voided and revised what a
+    previous call returned; a lost vehicle's lead and counters do not move.  The result then also holds lead, voided, revised,
+    fit_hist [T,2] (q_0 and the smallest q_h of a tested step with an eligible hypothesis, else -1, -1), gate_margin (the smallest
+    |q_h - consist^2| met, inf without a gate) and lead_gap (the smallest distance of a leader to its runner-up).
     Returns dict(llr_hist [T,NT*L], detections [(step, thruster, level)], ub [T,NT], stuck [T,NT] (the pattern each solve saw),
     ub_end, stuck_end, state [14+NT], llr [NT*L], peak [T] (the largest statistic of every step that tested, else nan))."""
     meas = np.asarray(meas, dtype=np.float64).reshape(-1, 13)
@@ -107,6 +178,9 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
     s = np.zeros((NT, L)) if llr is None else np.array(llr, dtype=np.float64).reshape(NT, L)
     hist, peak = np.empty((T, NT * L)), np.full(T, np.nan)
     ubh, sth = np.empty((T, NT)), np.empty((T, NT))
+    ld = (-1, 0) if lead is None else (int(lead[0]), int(lead[1]))
+    voided, revised = int(voided), int(revised)
+    fit, gate_margin, lead_gap = np.full((T, 2), -1.0), np.inf, np.inf
     for t in range(T):
         c = int(step0) + t
         if xt is None:
@@ -115,7 +189,23 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
         elif avail is not None and not avail[t]:
             hist[t] = s.reshape(-1)
         else:
-            if c % every == 0 and n >= 1 and len(det) < K:
+            if c % every == 0 and n >= 1 and len(det) < K and isolation is not None:
+                r = test_step(s, meas[t], xt, n, acc, ub, spec, cfg, isolation=isolation, lead=ld, stuck=stuck,
+                              listed=[d[1] for d in det])
+                s, ld = r["llr"], r["lead"]
+                hist[t] = s.reshape(-1)
+                peak[t] = hist[t].max()
+                if not np.isnan(r["qmin"]):
+                    fit[t] = r["q0"], r["qmin"]
+                voided += int(r["void"])
+                gate_margin, lead_gap = min(gate_margin, r["margin"]), min(lead_gap, r["gap"])
+                if r["decide"]:
+                    i, l = divmod(r["leader"], L)
+                    det.append((c, i, l))
+                    revised += int(not ub[i] > 0)
+                    ub[i], stuck[i] = 0.0, lv[l]
+                    s, ld = np.zeros((NT, L)), (-1, 0)
+            elif c % every == 0 and n >= 1 and len(det) < K:
                 s = test_step(s, meas[t], xt, n, acc, ub, spec, cfg)
                 hist[t] = s.reshape(-1)
                 peak[t] = hist[t].max()
@@ -132,7 +222,8 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
         xt, n, acc = propagate(xt, n, acc, u[t], ub, stuck, cfg, None if force is None else np.asarray(force)[t],
                                None if torque is None else np.asarray(torque)[t])
     return dict(llr_hist=hist, detections=det, ub=ubh, stuck=sth, ub_end=ub, stuck_end=stuck,
-                state=np.concatenate([xt, [float(n)], acc]), llr=s.reshape(-1), peak=peak)
+                state=np.concatenate([xt, [float(n)], acc]), llr=s.reshape(-1), peak=peak,
+                lead=ld, voided=voided, revised=revised, fit_hist=fit, gate_margin=gate_margin, lead_gap=lead_gap)
 
 
 def pattern(ub, stuck, detections, levels):
@@ -152,28 +243,36 @@ def detections_of(step, thruster, level):
             for b in range(step.shape[0])]
 
 
-def score(faults, detections):
+def score(faults, detections, final=False):
     """faults: per vehicle a list of (onset, thruster, level) events that happened; detections: per vehicle a list of
     (step, thruster, level).  An event is matched to the first unmatched detection of its thruster at or after its onset; an event
     left over is matched to the first unmatched detection at or after its onset, which then blames the wrong thruster; what is left
     of the events was missed, what is left of the detections are false alarms.
+    final=True: an event is matched to the LAST detection of its thruster at or after its onset, so that a revised level counts as
+    right; the earlier detections of that thruster from the onset on belong to the same match (they are no false alarms) and the
+    delay is taken from the first of them.
     Returns dict(delay [per event: detect_step - onset, or None when missed], missed, wrong_thruster, wrong_level, false_alarms)."""
     delay, missed, wrong_t, wrong_l, false_alarms = [], 0, 0, 0, 0
     for ev, det in zip(faults, detections):
         ev, det = sorted(ev), sorted(det)
-        used, hit = [False] * len(det), [None] * len(ev)
+        used, hit, first = [False] * len(det), [None] * len(ev), [None] * len(ev)
         for same in (True, False):
             for j, (onset, thr, _) in enumerate(ev):
                 if hit[j] is None:
-                    hit[j] = next((k for k, d in enumerate(det) if not used[k] and d[0] >= onset and (d[1] == thr) == same), None)
-                    if hit[j] is not None:
+                    cand = [k for k, d in enumerate(det) if not used[k] and d[0] >= onset and (d[1] == thr) == same]
+                    if cand and final and same:
+                        hit[j], first[j] = cand[-1], cand[0]
+                        for k in cand:
+                            used[k] = True
+                    elif cand:
+                        hit[j] = first[j] = cand[0]
                         used[hit[j]] = True
         for j, (onset, thr, lvl) in enumerate(ev):
             if hit[j] is None:
                 delay.append(None)
                 missed += 1
                 continue
-            delay.append(det[hit[j]][0] - onset)
+            delay.append(det[first[j]][0] - onset)
             if det[hit[j]][1] != thr:
                 wrong_t += 1
             elif det[hit[j]][2] != lvl:
@@ -250,4 +349,58 @@ def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None):
     if sensor is not None and sensor.get("predict") and estimator is None:
         raise ValueError("diagnosis: a predicting sensor needs an estimator (the sensor alone would predict with the pattern "
                          "before the diagnosis)")
+    return out
+
+
+def isolation_request(isolation, B, NT, diagnosis):
+    """The checks BatchedMPC.simulate makes on an isolation dict before the call reaches the library (the library's own refusals, raised
+    from Python too); diagnosis: the call's diagnosis dict or None.  Returns the dict with defaults filled in: consist, persist,
+    revise, lead [B,2] | None, voided [B] | None, revised [B] | None (int32 copies: the call writes into them), fields."""
+    spec = dict(isolation)
+    out = dict(consist=spec.pop("consist", 0.0), persist=spec.pop("persist", 1), revise=spec.pop("revise", False),
+               lead=spec.pop("lead", None), voided=spec.pop("voided", None), revised=spec.pop("revised", None),
+               fields=spec.pop("fields", None))
+    if spec:
+        raise ValueError(f"isolation: unknown keys {sorted(spec)}")
+    has_state = diagnosis is not None and (diagnosis.get("state") is not None
+                                           or any(f in ("detect", "state") for f in diagnosis.get("fields", FIELDS)))
+    if out["fields"] is None:
+        out["fields"] = tuple(f for f in ISO_FIELDS if f != "lead" or has_state)
+    out["fields"] = tuple(out["fields"])
+    if any(f not in ISO_FIELDS for f in out["fields"]):
+        raise ValueError(f"isolation['fields'] must be among {list(ISO_FIELDS)}")
+    try:
+        out["consist"] = float(out["consist"])
+    except (TypeError, ValueError):
+        raise ValueError("isolation['consist'] must be one number") from None
+    if not (np.isfinite(out["consist"]) and out["consist"] >= 0):
+        raise ValueError("isolation['consist'] must be 0 or finite and positive")
+    if isinstance(out["persist"], bool) or int(out["persist"]) != out["persist"] or int(out["persist"]) < 1:
+        raise ValueError(f"isolation['persist'] must be an integer >= 1, not {out['persist']}")
+    out["persist"] = int(out["persist"])
+    if out["revise"] not in (0, 1, False, True):
+        raise ValueError(f"isolation['revise'] must be 0 or 1 (False or True), not {out['revise']}")
+    out["revise"] = bool(out["revise"])
+    trivial = (out["consist"] == 0 and out["persist"] == 1 and not out["revise"] and out["lead"] is None and out["voided"] is None
+               and out["revised"] is None and not out["fields"])
+    if diagnosis is None and not trivial:
+        raise ValueError("isolation: the call has no diagnosis whose rule it could change")
+    if out["lead"] is not None or "lead" in out["fields"]:
+        if not has_state:
+            raise ValueError("isolation['lead'] requires the diagnosis' state (diagnosis['state'], or 'state' or 'detect' among its fields)")
+    if out["lead"] is not None:
+        lv = diagnosis.get("levels")
+        H = NT * (2 if lv is None else np.asarray(lv).size)
+        ld = out["lead"] = np.array(out["lead"], dtype=np.int32)
+        if ld.shape != (B, 2):
+            raise ValueError(f"isolation['lead'] must have shape {(B, 2)}")
+        if ((ld[:, 0] < -1) | (ld[:, 0] >= H)).any():
+            raise ValueError(f"isolation['lead']: a leader outside [-1, NT * n_levels) = [-1, {H})")
+        if (ld[:, 1] < 0).any():
+            raise ValueError("isolation['lead']: a negative run")
+    for name in ("voided", "revised"):
+        if out[name] is not None:
+            a = out[name] = np.array(out[name], dtype=np.int32)
+            if a.shape != (B,) or (a < 0).any():
+                raise ValueError(f"isolation[{name!r}] must have shape {(B,)} and no negative entry")
     return out

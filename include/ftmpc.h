@@ -1286,6 +1286,79 @@ int ftmpc_simulate_wrench_environment_batch(ftmpc_handle* h, int64_t B, int32_t 
                                             const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
                                             const ftmpc_environment* environment);
 
+/* Three safeguards for the diagnosis' decision rule (ftmpc_diagnosis), as an opt-in: a consistency gate, confirmation and level
+ * revision.  The plain rule switches the controller's pattern on the first test whose largest statistic crosses the threshold and
+ * never looks back; a short unmodelled push is then taken for a stuck thruster, a fault that starts inside a window is named at
+ * the neighbour, and a wrong level stays wrong.  The parameters are uniform over the call; lead, the counters and fit_hist are per
+ * vehicle.  A test happens under exactly the plain rule's condition (c % every == 0, n >= 1, fewer than max_detect entries, and
+ * the vehicle available when the call has an outage); rho_v, r_w, s_v, s_w, a_v(h), a_w(h) and z_h are ftmpc_diagnosis'.
+ *   fit: q_0 = |rho_v|^2 / s_v + |r_w|^2 / s_w and, for hypothesis h, q_h = q_0 - 2 z_h, the normalised energy left once h's
+ *     signature is subtracted (under h chi-square with 6 degrees of freedom).  With consist > 0, h is counted in this test only if
+ *     q_h <= consist^2: llr_h = max(0, llr_h + z_h); a statistic that is not counted keeps its value.  The test is void, and adds 1
+ *     to voided[b], when q_0 > consist^2 and no eligible hypothesis was counted.  consist = 0: every eligible hypothesis is counted
+ *     and no test is void.  (ft_mpc_amd.diagnosis.consist_for(p) gives the square root of the chi-square(6) quantile.)
+ *   eligible: (i, l) with ub_c,i > 0, delta = n levels[l] - acc_i, as in the plain rule.  With revise also (i, l) of a thruster
+ *     with ub_c,i == 0 that stands in the vehicle's own detection list (of this call, or carried in through
+ *     ftmpc_diagnosis.detect_*), delta = n (levels[l] - stuck_c,i); the hypothesis at its current level has delta = 0 and z = 0
+ *     and stays where it is.  A thruster that is off in the call's pattern but not in the list stays the caller's: it is never
+ *     revised and its statistics are 0.
+ *   confirmation: the leader is the largest statistic strictly above the threshold (the lowest index on a tie).  The same leader
+ *     as lead[b][0] gives run + 1, another one lead = h, run = 1, none lead = -1, run = 0.  The decision is taken when
+ *     run >= persist; until then the statistics keep accumulating.  persist = 1 is the plain rule.
+ *   decision: for a live thruster the plain rule's (a detection entry, ub_c,i = 0, stuck_c,i = levels[l], every statistic 0).
+ *     For a revision the entry (c, i, l), which uses a slot of max_detect, stuck_c,i = levels[l], ub_c,i stays 0, revised[b] += 1,
+ *     every statistic 0.  Either resets lead and run and flags the vehicle as switched, so the warm-start repair, the hull offsets
+ *     (wrench form) and the linearisation follow as after any detection.
+ * Re-anchoring, the model's step, llr_hist and an outage's carry-over of a lost vehicle (lead and the counters included) are
+ * unchanged.  ftmpc_diagnose_iso_kernel runs in place of the call's phase-0 diagnosis kernel.
+ * isolation == NULL, or a trivial struct (consist = 0, persist = 1, revise = 0, every array NULL), launches exactly the kernels
+ * of the _environment_ entries and returns their bits.
+ * Limits: a detection is never withdrawn back to healthy (a thruster the controller no longer commands has no signature);
+ * consist and persist are uniform over the call; the innovation gate of the filters is ftmpc_outage's, not this one.
+ * FTMPC_ERR_ARG, the message naming ftmpc_isolation.<field> and, for an array, the first offending vehicle, the call's x
+ * untouched: a struct_size other than sizeof(ftmpc_isolation); reserved != 0; a non-trivial struct without an ftmpc_diagnosis in
+ * the call; consist negative or not finite; persist < 1; revise outside {0, 1}; a lead entry with a hypothesis outside
+ * [-1, NT * n_levels) or a negative run; lead without ftmpc_diagnosis.state; a negative voided or revised entry.
+ */
+typedef struct ftmpc_isolation {
+    int32_t struct_size, reserved;      /* sizeof(ftmpc_isolation), 0 */
+    double consist;                     /* the gate on q_h (its square root); 0: no gate */
+    int32_t persist;                    /* consecutive tests with the same leader before the decision, >= 1 */
+    int32_t revise;                     /* 1: the level of a detected thruster is tested on, 0: not */
+    int32_t* lead;                      /* NULL or [B*2] in/out: the leader (-1: none) and its run length; needs diagnosis.state */
+    int32_t* voided;                    /* NULL or [B] in/out: void tests */
+    int32_t* revised;                   /* NULL or [B] in/out: revisions */
+    double* fit_hist;                   /* NULL or [T*B*2] out: q_0 and the smallest q_h over the eligible hypotheses of a tested step;
+                                           -1, -1 on a step without a test or without an eligible hypothesis */
+} ftmpc_isolation;
+
+/* ftmpc_simulate_environment_batch with the decision rule `isolation` (NULL: exactly ftmpc_simulate_environment_batch, which IS
+ * this entry with NULL). */
+int ftmpc_simulate_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                   const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                   int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                   double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                   const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                                   const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                   const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                   const ftmpc_outage* outage, const ftmpc_environment* environment,
+                                   const ftmpc_isolation* isolation);
+
+/* The decision rule on the two-stage wrench form: ftmpc_simulate_wrench_environment_batch with `isolation` (NULL: exactly that
+ * entry's kernels and bits).  The kernel is the thruster form's; a revision recomputes the hull offsets as any detection does. */
+int ftmpc_simulate_wrench_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                          const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                          int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                          const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                          double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                          int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                          const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                          const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                          const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                          int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                          const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                          const ftmpc_environment* environment, const ftmpc_isolation* isolation);
+
 /* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
  * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
  * after G / warmG; the rollout of the cost and of the linearisation sees tau + t^ at every RK4 stage and f^ / m added to the inertial
@@ -1607,6 +1680,20 @@ int ftmpc_multi_simulate_environment_batch(ftmpc_multi* m, int64_t B, int32_t T,
                                            const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
                                            const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                            const ftmpc_outage* outage, const ftmpc_environment* environment);
+/* ftmpc_multi_simulate_environment_batch with the decision rule `isolation` (ftmpc_isolation; NULL: exactly that entry).  The
+ * struct is checked once over the whole batch, so a refusal names the vehicle by its number in the caller's arrays; lead + 2 lo,
+ * voided + lo and revised + lo are read and written per shard, fit_hist is copied row by row from the shard's staging.  The
+ * two-stage wrench form has no multi-GPU environment entry to extend, so it has no multi-GPU isolation entry either. */
+int ftmpc_multi_simulate_isolation_batch(ftmpc_multi* m, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                         const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                                         int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                                         double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                                         const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                         const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                         const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                                         const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                                         const ftmpc_outage* outage, const ftmpc_environment* environment,
+                                         const ftmpc_isolation* isolation);
 /* per-kernel device timing of device slot `slot` (see ftmpc_set_profiling / ftmpc_last_kernel_ms) */
 int ftmpc_multi_set_profiling(ftmpc_multi* m, int32_t enabled);
 int ftmpc_multi_last_kernel_ms(ftmpc_multi* m, int32_t slot, float* ms, int32_t n_slots);
