@@ -45,6 +45,7 @@ struct LoopCall {
     const ftmpc_outage* og = nullptr;
     const ftmpc_environment* ev = nullptr;
     const ftmpc_isolation* is = nullptr;
+    const ftmpc_probe* pb = nullptr;
 };
 
 // the thruster lead-in and the wrench lead-in of the public entries, which differ in nothing else
@@ -441,7 +442,8 @@ bool isolation_trivial(const ftmpc_isolation* is) {
 }
 // An isolation's layout and values (include/ftmpc.h, ftmpc_isolation) over the vehicles [0, B), against the diagnosis of the same
 // call: empty when acceptable, else the message, which names the field and, for an array, the first offending vehicle
-std::string isolation_problem(const ftmpc_isolation* is, int64_t B, int NT, const ftmpc_diagnosis* dg, int64_t first = 0) {
+std::string isolation_problem(const ftmpc_isolation* is, int64_t B, int NT, const ftmpc_diagnosis* dg, int64_t first = 0,
+                              bool reinstating = false) {
     if (!is) return "";
     if (is->struct_size != (int32_t)sizeof(ftmpc_isolation))
         return "ftmpc_isolation.struct_size is " + std::to_string(is->struct_size) + ", this library expects " +
@@ -455,7 +457,8 @@ std::string isolation_problem(const ftmpc_isolation* is, int64_t B, int NT, cons
                "rule they could change";
     if (is->lead && !dg->state) return "ftmpc_isolation.lead without ftmpc_diagnosis.state";
     if (is->lead) {
-        const int64_t H = (int64_t)NT * dg->n_levels;
+        // (under a reinstating probe the leader may be H + i, "thruster i is healthy")
+        const int64_t H = (int64_t)NT * dg->n_levels + (reinstating ? NT : 0);
         for (int64_t b = 0; b < B; ++b) {
             if (is->lead[b * 2] < -1 || is->lead[b * 2] >= H)
                 return "ftmpc_isolation.lead: vehicle " + std::to_string(first + b) + " has a leader outside [-1, NT * n_levels)";
@@ -472,6 +475,47 @@ std::string isolation_problem(const ftmpc_isolation* is, int64_t B, int NT, cons
     return "";
 }
 
+// a probe that replaces the phase-0 diagnosis kernel and widens the detect_level and lead checks
+bool probe_reinstates(const ftmpc_probe* pb) {
+    return pb && pb->struct_size == (int32_t)sizeof(ftmpc_probe) && pb->reinstate == 1;
+}
+// A probe's layout and values (include/ftmpc.h, ftmpc_probe) over the vehicles [0, B), against the diagnosis of the same call: empty
+// when acceptable, else the message, which names the field and, for an array, the first offending vehicle
+std::string probe_problem(const ftmpc_probe* pb, int64_t B, int NT, const ftmpc_diagnosis* dg, int64_t first = 0) {
+    if (!pb) return "";
+    if (pb->struct_size != (int32_t)sizeof(ftmpc_probe))
+        return "ftmpc_probe.struct_size is " + std::to_string(pb->struct_size) + ", this library expects " + std::to_string(sizeof(ftmpc_probe));
+    if (pb->reserved != 0) return "ftmpc_probe.reserved is " + std::to_string(pb->reserved) + ", not 0";
+    if (!dg) return "ftmpc_probe: the call has no diagnosis (ftmpc_diagnosis) whose pattern and detection list the probe reads";
+    if (!std::isfinite(pb->amp) || !(pb->amp > 0)) return "ftmpc_probe.amp is not finite and > 0";
+    if (!(pb->quiet >= 0 && pb->quiet < pb->amp)) return "ftmpc_probe.quiet is outside [0, amp)";
+    if (pb->idle_steps < 1) return "ftmpc_probe.idle_steps is " + std::to_string(pb->idle_steps) + ", not >= 1";
+    if (pb->max_pulses < 0) return "ftmpc_probe.max_pulses is negative";
+    if (pb->reinstate != 0 && pb->reinstate != 1) return "ftmpc_probe.reinstate is " + std::to_string(pb->reinstate) + ", not 0 or 1";
+    if (pb->reinstate == 1 && (!std::isfinite(pb->restore_ub) || !(pb->restore_ub > 0)))
+        return "ftmpc_probe.restore_ub is not finite and > 0 (reinstate = 1)";
+    if (pb->pacc && !dg->state) return "ftmpc_probe.pacc without ftmpc_diagnosis.state";
+    if (pb->health && !dg->state) return "ftmpc_probe.health without ftmpc_diagnosis.state";
+    const int32_t* const iarr[3] = {pb->idle, pb->pulses, pb->reinstated};
+    const char* const iname[3] = {"idle", "pulses", "reinstated"};
+    const int64_t iwidth[3] = {NT, NT, 1};
+    for (int a = 0; a < 3; ++a)
+        if (iarr[a])
+            for (int64_t i = 0; i < B * iwidth[a]; ++i)
+                if (iarr[a][i] < 0)
+                    return std::string("ftmpc_probe.") + iname[a] + ": vehicle " + std::to_string(first + i / iwidth[a]) + " has a negative entry";
+    const double* const darr[3] = {pb->impulse, pb->pacc, pb->health};
+    const char* const dname[3] = {"impulse", "pacc", "health"};
+    const int64_t dwidth[3] = {1, NT, NT};
+    for (int a = 0; a < 3; ++a)
+        if (darr[a])
+            for (int64_t i = 0; i < B * dwidth[a]; ++i)
+                if (!std::isfinite(darr[a][i]) || darr[a][i] < 0)
+                    return std::string("ftmpc_probe.") + dname[a] + ": vehicle " + std::to_string(first + i / dwidth[a]) +
+                           " has a negative or non-finite entry";
+    return "";
+}
+
 int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
     const std::string msg = estimator_problem(es, B);
     return msg.empty() ? FTMPC_OK : fail(h, FTMPC_ERR_ARG, msg);
@@ -481,7 +525,7 @@ int check_estimator(ftmpc_handle* h, int64_t B, const ftmpc_estimator* es) {
 // the sensor of the same call: empty when acceptable, else the message, which names the field and, for an array, the first offending
 // vehicle (first: number of vehicle 0 in the caller's batch)
 std::string diagnosis_problem(const ftmpc_diagnosis* dg, int64_t B, int NT, const ftmpc_estimator* es, const ftmpc_fault_schedule* fs,
-                                     const ftmpc_sensor* se, int64_t first = 0) {
+                                     const ftmpc_sensor* se, int64_t first = 0, bool reinstating = false) {
     if (!dg) return "";
     if (dg->struct_size != (int32_t)sizeof(ftmpc_diagnosis))
         return "ftmpc_diagnosis.struct_size is " + std::to_string(dg->struct_size) + ", this library expects " +
@@ -532,7 +576,8 @@ std::string diagnosis_problem(const ftmpc_diagnosis* dg, int64_t B, int NT, cons
                 if (unused) return "ftmpc_diagnosis.detect_step: vehicle " + std::to_string(first + b) + " has a used slot after an unused one";
                 if (dt < 0 || dt >= NT)
                     return "ftmpc_diagnosis.detect_thruster: vehicle " + std::to_string(first + b) + " has an entry outside [0, NT)";
-                if (dl < 0 || dl >= dg->n_levels)
+                // (under a reinstating probe an entry at n_levels is a reinstatement)
+                if (dl < 0 || dl >= dg->n_levels + (reinstating ? 1 : 0))
                     return "ftmpc_diagnosis.detect_level: vehicle " + std::to_string(first + b) + " has an entry outside [0, n_levels)";
             }
         }
@@ -1297,9 +1342,13 @@ struct IsolationStage {
     std::vector<int32_t> h_lead;
     ftmpc::IsoParams iq{};
 
-    int stage(const Loop& q, const ftmpc_isolation* is) {
-        on = !isolation_trivial(is);
+    // force: a reinstating probe runs the rule's kernel whatever the struct says (NULL: the trivial rule)
+    int stage(const Loop& q, const ftmpc_isolation* is, bool force) {
+        on = !isolation_trivial(is) || force;
         if (!on) return FTMPC_OK;
+        ftmpc_isolation none{};
+        none.persist = 1;
+        if (!is) is = &none;
         const size_t T = (size_t)q.T, B = (size_t)q.B;
         LOOP_TRY(dev_alloc(q, d_lead, B * 2));
         if (is->lead) {
@@ -1330,13 +1379,88 @@ struct IsolationStage {
         return FTMPC_OK;
     }
     int fetch(const Loop& q, const ftmpc_isolation* is) {
-        if (!on) return FTMPC_OK;
+        if (!on || !is) return FTMPC_OK;
         const size_t T = (size_t)q.T, B = (size_t)q.B;
         LOOP_TRY(hist_get(q, is->lead, d_lead, B * 2));
         LOOP_TRY(hist_get(q, is->voided, d_void, B));
         LOOP_TRY(hist_get(q, is->revised, d_rev, B));
         LOOP_TRY(hist_get(q, is->fit_hist, d_fit, T * B * 2));
         return FTMPC_OK;
+    }
+};
+
+// Probe (checked by the entry; it needs the diagnosis): the counters idle and pulses [B][NT] and reinstated [B] in the caller's layout,
+// impulse [B], pacc and health component-major [NT][B] as the diagnosis' acc and llr are (zeros when none are handed over), the
+// pulsed thruster of every step [T][B].  The pointers into the diagnosis' pattern and detection list are set by the wiring
+struct ProbeStage {
+    bool on = false;
+    DevBuf<int32_t> d_idle, d_pulses, d_rein, d_hist;
+    DevBuf<double> d_impulse, d_pacc, d_health;
+    std::vector<double> h_pacc, h_health;
+    ftmpc::ProbeParams pq{};
+
+    int stage(const Loop& q, const ftmpc_probe* pb, const ftmpc_diagnosis* dg) {
+        on = pb != nullptr;
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B, NT = (size_t)q.NT;
+        try {
+            if (pb->pacc) h_pacc.assign(B * NT, 0.0);
+            if (pb->health) h_health.assign(B * NT, 0.0);
+        } catch (const std::bad_alloc&) {
+            return fail(q.h, FTMPC_ERR_ALLOC, "out of host memory for the probe's staging arrays");
+        }
+        auto counters = [&](DevBuf<int32_t>& d, const int32_t* host, size_t n) -> int {
+            LOOP_TRY(dev_alloc(q, d, n));
+            return host ? dev_put(q, d.p, host, n) : dev_fill(q, d.p, 0, n);
+        };
+        auto sums = [&](DevBuf<double>& d, const double* host, std::vector<double>& packed) -> int {
+            LOOP_TRY(dev_alloc(q, d, B * NT));
+            if (!host) return dev_fill(q, d.p, 0, B * NT);
+            ftmpc::pack_kb(host, q.B, q.NT, packed.data());
+            return dev_put(q, d.p, (const double*)packed.data(), B * NT);
+        };
+        LOOP_TRY(counters(d_idle, pb->idle, B * NT));
+        LOOP_TRY(counters(d_pulses, pb->pulses, B * NT));
+        LOOP_TRY(counters(d_rein, pb->reinstated, B));
+        LOOP_TRY(dev_alloc(q, d_impulse, B));
+        if (pb->impulse)
+            LOOP_TRY(dev_put(q, d_impulse.p, (const double*)pb->impulse, B));
+        else
+            LOOP_TRY(dev_fill(q, d_impulse.p, 0, B));
+        LOOP_TRY(sums(d_pacc, pb->pacc, h_pacc));
+        LOOP_TRY(sums(d_health, pb->health, h_health));
+        LOOP_TRY(hist_alloc(q, d_hist, (const int32_t*)pb->thruster_hist, T * B));
+        pq.B = q.B;
+        pq.amp = pb->amp, pq.quiet = pb->quiet, pq.restore_ub = pb->reinstate ? pb->restore_ub : 0.0, pq.dt = q.h->cfg.dt;
+        pq.idle_steps = pb->idle_steps, pq.max_pulses = pb->max_pulses, pq.reinstate = pb->reinstate, pq.n_levels = dg->n_levels;
+        pq.K = dg->max_detect;
+        pq.u0 = q.h->d_u0;
+        pq.ub = q.h->d_ub;
+        pq.idle = d_idle;
+        pq.pulses = d_pulses;
+        pq.impulse = d_impulse;
+        pq.pacc = d_pacc;
+        pq.health = d_health;
+        pq.reinstated = d_rein;
+        pq.hist = d_hist;
+        return FTMPC_OK;
+    }
+    int fetch(const Loop& q, const ftmpc_probe* pb) {
+        if (!on) return FTMPC_OK;
+        const size_t T = (size_t)q.T, B = (size_t)q.B, NT = (size_t)q.NT;
+        LOOP_TRY(hist_get(q, pb->idle, d_idle, B * NT));
+        LOOP_TRY(hist_get(q, pb->pulses, d_pulses, B * NT));
+        LOOP_TRY(hist_get(q, pb->reinstated, d_rein, B));
+        LOOP_TRY(hist_get(q, pb->impulse, d_impulse, B));
+        if (pb->pacc) LOOP_TRY(dev_get(q, h_pacc.data(), (const double*)d_pacc.p, B * NT));
+        if (pb->health) LOOP_TRY(dev_get(q, h_health.data(), (const double*)d_health.p, B * NT));
+        LOOP_TRY(hist_get(q, pb->thruster_hist, d_hist, T * B));
+        return FTMPC_OK;
+    }
+    void unpack(const Loop& q, const ftmpc_probe* pb) {
+        if (!on) return;
+        if (pb->pacc) ftmpc::unpack_kb(h_pacc.data(), q.B, q.NT, pb->pacc);
+        if (pb->health) ftmpc::unpack_kb(h_health.data(), q.B, q.NT, pb->health);
     }
 };
 
@@ -1722,6 +1846,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     OutageStage oge;
     EnvironmentStage env;
     IsolationStage iso;
+    ProbeStage prb;
     DiagStage dia;
     MissionStage mis;
     OutcomeStage out;
@@ -1735,7 +1860,9 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(bia.stage(q, c.be));
     LOOP_TRY(oge.stage(q, c.og));
     LOOP_TRY(env.stage(q, c.ev));
-    LOOP_TRY(iso.stage(q, c.is));
+    const bool reinstating = c.pb && c.pb->reinstate == 1;      // ftmpc_diagnose_probe_kernel is the call's phase-0 diagnosis kernel
+    LOOP_TRY(iso.stage(q, c.is, reinstating));
+    LOOP_TRY(prb.stage(q, c.pb, dg));
     LOOP_TRY(dia.stage(q, dg, c));
     LOOP_TRY(mis.stage(q, c.ms, windows, want_cost, xw, uw, L));
     LOOP_TRY(out.stage(q, c.oc, want_cost, wrench));
@@ -1787,6 +1914,11 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
         pla.pv.torque = env.d_torque;
         pla.var = true;
         env.eq.est = dist ? d_dest : nullptr;
+    }
+    if (prb.on) {     // the probe reads the controller's pattern and the diagnosis' detection list
+        prb.pq.count = dp.count;
+        prb.pq.det_thruster = dp.det_thruster;
+        prb.pq.det_level = dp.det_level;
     }
     if (flt.E > 0) fe.warmU = wrench ? nullptr : d_warmB;
     ftmpc::SimParams sp;
@@ -1853,7 +1985,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
             dp.anchor = (se->step0 + t) % dg->every == 0;
             dp.cstep = (int32_t)(se->step0 + t);
             dp.step = t;
-            if (iso.on)     // the test with the gate, confirmation and revision, in place of either phase-0 kernel
+            if (reinstating)     // the rule's test with the hypotheses "listed thruster i is healthy", in place of any phase-0 kernel
+                hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_probe_kernel, per_vehicle, wave, 0, s, h->dc, dp, iso.iq, prb.pq,
+                                   oge.on ? (const int32_t*)oge.d_avail.p : (const int32_t*)nullptr);
+            else if (iso.on)     // the test with the gate, confirmation and revision, in place of either phase-0 kernel
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_iso_kernel, per_vehicle, wave, 0, s, h->dc, dp, iso.iq,
                                    oge.on ? (const int32_t*)oge.d_avail.p : (const int32_t*)nullptr);
             else if (oge.on)
@@ -1925,6 +2060,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
         if (wrench && run.d_abad)
             hipLaunchKernelGGL(ftmpc::ftmpc_count_nonzero_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B,
                                (const int32_t*)h->d_ast2, run.d_abad + t);
+        if (prb.on) {     // at most one quiet thruster per vehicle is pulsed in u_t, before the command enters the ring
+            prb.pq.step = t;
+            hipLaunchKernelGGL(ftmpc::ftmpc_probe_kernel<0>, per_vehicle, wave, 0, s, h->dc, prb.pq);
+        }
         if (lat > 0) {     // u_t waits lat steps: into the slot behind the newest; the plant and the outcomes get the slot of a_t
             HIP_TRY(h, hipMemcpyAsync(d_ring + (size_t)((t + lat) % (lat + 1)) * nu, h->d_u0, nu * sizeof(double), hipMemcpyDeviceToDevice, s));
             sp.u0 = op.u0 = d_ring + (size_t)(t % (lat + 1)) * nu;
@@ -1959,6 +2098,10 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_dist_kernel, per_vehicle, wave, 0, s, h->dc, dp, (const double*)d_dest);
             else
                 hipLaunchKernelGGL(ftmpc::ftmpc_diagnose_kernel<1>, per_vehicle, wave, 0, s, h->dc, dp);
+            if (reinstating) {     // a_t of the listed thrusters, which the model's acc leaves out
+                prb.pq.u = sp.u0;
+                hipLaunchKernelGGL(ftmpc::ftmpc_probe_kernel<1>, per_vehicle, wave, 0, s, h->dc, prb.pq);
+            }
         }
         if (out.on) {     // the plant's pattern and the status the plant kernel read; x_{t+1} against column t + 1 of the reference
             op.step = t;
@@ -1997,6 +2140,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     LOOP_TRY(oge.fetch(q, c.og));
     LOOP_TRY(env.fetch(q, c.ev));
     LOOP_TRY(iso.fetch(q, c.is));
+    LOOP_TRY(prb.fetch(q, c.pb));
     LOOP_TRY(dia.fetch(q, dg, c));
     LOOP_TRY(run.fetch(q, c));
     LOOP_TRY(mis.fetch(q, c.ms, want_cost));
@@ -2005,6 +2149,7 @@ int simulate_core(ftmpc_handle* h, const LoopCall& c) {
     HIP_TRY(h, hipStreamSynchronize(s));
     act.unpack(q, c.ac);
     dia.unpack(q, dg);
+    prb.unpack(q, c.pb);
     dst.unpack(q, db);
     bia.unpack(q, c.be);
     env.unpack(q, c.ev);
@@ -2029,7 +2174,8 @@ void loop_call_features(LoopCall& c, double* x_hist, const ftmpc_fault_schedule*
                         const ftmpc_mission* ms, const ftmpc_actuator* ac, const ftmpc_sensor* se, const ftmpc_estimator* es,
                         const ftmpc_diagnosis* dg, const ftmpc_disturbance* db, const ftmpc_bias_estimate* be,
                         const ftmpc_outage* og = nullptr, const ftmpc_environment* ev = nullptr,
-                        const ftmpc_isolation* is = nullptr) {
+                        const ftmpc_isolation* is = nullptr, const ftmpc_probe* pb = nullptr) {
+    c.pb = pb;
     c.x_hist = x_hist;
     c.fs = fs, c.oc = oc, c.pm = pm, c.ms = ms, c.ac = ac, c.se = se, c.es = es, c.dg = dg, c.db = db, c.be = be, c.og = og, c.ev = ev, c.is = is;
 }
@@ -2054,14 +2200,16 @@ int loop_check(ftmpc_handle* h, const LoopCall& c) {
     if ((rc = check_estimator(h, B, c.es)) != FTMPC_OK) return rc;
     if ((rc = check_mission(h, B, c.T, c.ms, c.xref_traj, c.uref_traj, sensor_shift(c.se))) != FTMPC_OK) return rc;
     if ((rc = check_actuator(h, B, c.ac)) != FTMPC_OK) return rc;
-    if (!(msg = diagnosis_problem(c.dg, B, h->cfg.NT, c.es, c.fs, c.se)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    const bool reinstating = probe_reinstates(c.pb);      // widens the detect_level and lead checks
+    if (!(msg = diagnosis_problem(c.dg, B, h->cfg.NT, c.es, c.fs, c.se, 0, reinstating)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     // (the thruster SQP does not know a disturbance estimate; the wrench SQP's cost kernel does: sqp_iters > 0 is served there)
     if (!(msg = disturbance_problem(c.db, B, c.es, c.wrench ? 0 : c.sqp_iters)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     // (a bias estimate reaches the solve through x0 alone: sqp_iters >= 0 is served)
     if (!(msg = bias_problem(c.be, B, c.es, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     if (!(msg = outage_problem(c.og, B, c.es, c.db, c.be)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     if (!(msg = environment_problem(c.ev, B, c.se, c.db)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
-    if (!(msg = isolation_problem(c.is, B, h->cfg.NT, c.dg)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    if (!(msg = isolation_problem(c.is, B, h->cfg.NT, c.dg, 0, reinstating)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
+    if (!(msg = probe_problem(c.pb, B, h->cfg.NT, c.dg)).empty()) return fail(h, FTMPC_ERR_ARG, msg);
     return FTMPC_OK;
 }
 
@@ -2240,9 +2388,23 @@ int ftmpc_simulate_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T, double
                                    const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
                                    const ftmpc_outage* outage, const ftmpc_environment* environment,
                                    const ftmpc_isolation* isolation) {
+    return ftmpc_simulate_probe_batch(h, B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, faults, u_hist,
+                                      x_hist, not_converged, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance,
+                                      bias_estimate, outage, environment, isolation, nullptr);
+}
+
+int ftmpc_simulate_probe_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                               const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                               int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                               double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                               const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                               const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                               const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                               const ftmpc_outage* outage, const ftmpc_environment* environment,
+                               const ftmpc_isolation* isolation, const ftmpc_probe* probe) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
-                       environment, isolation);
+                       environment, isolation, probe);
     return loop_run(h, c);
 }
 
@@ -2418,12 +2580,31 @@ int ftmpc_simulate_wrench_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                           const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
                                           const ftmpc_environment* environment, const ftmpc_isolation* isolation) {
+    return ftmpc_simulate_wrench_probe_batch(h, B, T, x, ub, stuck, hull_A, n_sets, hull_set, hull_b, hull_rows, xref_traj, uref_traj,
+                                             noise, seed, sqp_iters, backtracks, tol, penalty, faults, u_hist, x_hist, not_converged,
+                                             alloc_failed, out, plant, mission, actuator, sensor, estimator, diagnosis, out_hull_b,
+                                             no_hull_step, disturbance, bias_estimate, outage, environment, isolation, nullptr);
+}
+
+int ftmpc_simulate_wrench_probe_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                      int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                      const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                      double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                      int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                      const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                      const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                      int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                      const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                      const ftmpc_environment* environment, const ftmpc_isolation* isolation,
+                                      const ftmpc_probe* probe) {
     LoopCall c = loop_call(B, T, x, ub, stuck, xref_traj, uref_traj, noise, seed, sqp_iters, backtracks, tol, u_hist, not_converged);
     loop_call_wrench(c, hull_A, n_sets, hull_set, hull_b, hull_rows, penalty, alloc_failed);
     c.out_hull_b = out_hull_b;
     c.no_hull_step = no_hull_step;
     loop_call_features(c, x_hist, faults, out, plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage,
-                       environment, isolation);
+                       environment, isolation, probe);
     return loop_run(h, c);
 }
 

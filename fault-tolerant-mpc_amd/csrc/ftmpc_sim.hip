@@ -2679,4 +2679,194 @@ __global__ void __launch_bounds__(64) ftmpc_diagnose_iso_kernel(const DeviceCons
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Probe pulses (ftmpc_simulate_probe_batch / ftmpc_simulate_wrench_probe_batch; include/ftmpc.h, ftmpc_probe).  A lane per vehicle,
+// the per-vehicle rule is csrc/ftmpc_probe.h.
+//   ftmpc_probe_kernel<0>         after the step's solve (and the allocation) and before the command enters the latency ring: the
+//                                 idle counters move, at most one thruster per vehicle is pulsed in the handle's u0, in place
+//   ftmpc_probe_kernel<1>         after the plant step, beside the diagnosis' phase 1, under reinstate only: pacc_i += a_t,i for the
+//                                 listed thrusters (the model's c_i is 0 for a thruster that is off)
+//   ftmpc_diagnose_probe_kernel   under reinstate, in place of the call's phase-0 diagnosis kernel: ftmpc_diagnose_iso_kernel's test
+//                                 (the call's ftmpc_isolation, or the trivial rule) with the NT further hypotheses H + i "listed
+//                                 thruster i is healthy" and their decision.  A sibling of that kernel, whose code is what it was
+// idle and pulses keep the caller's layout [B][NT] beside ub and u0, which have it; pacc and health are component-major ([NT][B]) as
+// acc and llr are.  `listed` scans the vehicle's detection list (at most max_detect <= 8 entries), for an off thruster only.
+// ---------------------------------------------------------------------------------------------------------
+}  // namespace ftmpc
+#include "ftmpc_probe.h"
+namespace ftmpc {
+struct ProbeParams {
+    int64_t B;
+    int64_t step;             // t (the history's row)
+    double amp, quiet, restore_ub, dt;
+    int32_t idle_steps, max_pulses, reinstate, n_levels;
+    int32_t K, pad0;          // max_detect
+    double* u0;               // [B*NT] phase 0: the step's command, edited in place
+    const double* u;          // [B*NT] phase 1: a_t, the command the plant applied in this step
+    const double* ub;         // [B*NT] the controller's pattern
+    const int32_t* count;     // [B] the diagnosis' detection list
+    const int32_t* det_thruster;      // [B*K]
+    const int32_t* det_level;
+    int32_t* idle;            // [B*NT] in/out
+    int32_t* pulses;          // [B*NT] in/out
+    double* impulse;          // [B] in/out
+    double* pacc;             // [NT][B]
+    double* health;           // [NT][B]
+    int32_t* reinstated;      // [B] in/out
+    int32_t* hist;            // nullptr or [T*B]
+};
+
+__device__ __forceinline__ ftmpc_prb::Rule probe_rule(const ProbeParams& Q) {
+    ftmpc_prb::Rule R;
+    R.amp = Q.amp, R.quiet = Q.quiet, R.restore_ub = Q.restore_ub, R.dt = Q.dt;
+    R.idle_steps = Q.idle_steps, R.max_pulses = Q.max_pulses, R.reinstate = Q.reinstate, R.n_levels = Q.n_levels;
+    return R;
+}
+
+template <int PHASE>
+__global__ void __launch_bounds__(64) ftmpc_probe_kernel(const DeviceConsts C, const ProbeParams Q) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Q.B) return;
+    const int64_t B = Q.B;
+    const int NT = C.NT;
+    const ftmpc_prb::Rule R = probe_rule(Q);
+    const int32_t cnt = Q.count[b];
+    const int32_t* const dth = Q.det_thruster + b * Q.K;
+    const int32_t* const dlv = Q.det_level + b * Q.K;
+    if constexpr (PHASE == 0) {
+        ftmpc_prb::Pick p;
+        ftmpc_prb::pick_start(p);
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) {
+            const bool live = Q.ub[b * NT + i] > 0.0;
+            const bool lst = R.reinstate != 0 && ftmpc_prb::listed(i, live, cnt, dth, dlv, R.n_levels);
+            int idle = Q.idle[b * NT + i];
+            ftmpc_prb::thruster(R, i, live, lst, Q.u0[b * NT + i], Q.pulses[b * NT + i], idle, p);
+            Q.idle[b * NT + i] = idle;
+        }
+        if (p.cand >= 0) {
+            const int64_t k = b * NT + p.cand;
+            const double ubi = Q.ub[k];
+            double u = Q.u0[k];
+            int pulses = Q.pulses[k], idle = p.idle;
+            Q.impulse[b] += ftmpc_prb::pulse(R, ubi > 0.0, ubi, u, pulses, idle);
+            Q.u0[k] = u;
+            Q.pulses[k] = pulses;
+            Q.idle[k] = idle;
+        }
+        if (Q.hist) Q.hist[Q.step * B + b] = p.cand;
+        return;
+    }
+    // PHASE 1: the applied command of the listed thrusters, which the model's acc leaves out
+#pragma unroll 1
+    for (int i = 0; i < NT; ++i) {
+        const bool live = Q.ub[b * NT + i] > 0.0;
+        if (ftmpc_prb::listed(i, live, cnt, dth, dlv, R.n_levels)) Q.pacc[(int64_t)i * B + b] += Q.u[b * NT + i];
+    }
+}
+template __global__ void ftmpc_probe_kernel<0>(const DeviceConsts, const ProbeParams);
+template __global__ void ftmpc_probe_kernel<1>(const DeviceConsts, const ProbeParams);
+
+__global__ void __launch_bounds__(64) ftmpc_diagnose_probe_kernel(const DeviceConsts C, const DiagParams P, const IsoParams I,
+                                                                  const ProbeParams Q, const int32_t* avail) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const int64_t B = P.B;
+    const int NT = C.NT, L = P.L, H = NT * L;
+    double x[13], y[13];
+    double* const hist = P.llr_hist ? P.llr_hist + (P.step * B + b) * H : nullptr;
+    double* const fit = I.fit_hist ? I.fit_hist + (P.step * B + b) * 2 : nullptr;
+    if (!P.init && avail && !avail[b]) {     // lost: no test, no re-anchor; every statistic, pacc, lead and the counters carry over
+        if (hist) {
+#pragma unroll 1
+            for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+        }
+        if (fit) fit[0] = fit[1] = -1.0;
+        P.switched[b] = 0;
+        return;
+    }
+    for (int i = 0; i < 13; ++i) y[i] = P.y[b * 13 + i];
+    int32_t sw = 0;
+    bool tested = false;
+    double f0 = -1.0, f1 = -1.0;
+    if (P.init) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) Q.health[(int64_t)i * B + b] = 0.0;
+    } else {
+        const double n = P.xt[b * 14 + 13];
+        const int32_t cnt = P.count[b];
+        if (P.anchor && n >= 1.0 && cnt < P.K) {
+            tested = true;
+            for (int i = 0; i < 13; ++i) x[i] = P.xt[b * 14 + i];
+            ftmpc_iso::Rule R;
+#pragma unroll
+            for (int l = 0; l < 4; ++l) R.levels[l] = P.levels[l];
+            R.threshold = P.threshold;
+            R.consist_sq = I.consist_sq;
+            R.L = L, R.persist = I.persist, R.revise = I.revise, R.pad0 = 0;
+            const ftmpc_prb::Rule PR = probe_rule(Q);
+            ftmpc_iso::Resid r;
+            ftmpc_iso::residual(x, y, n, P.rsq, P.dsq, r);
+            ftmpc_iso::Scan s;
+            ftmpc_iso::scan_start(R, s);
+            ftmpc_prb::Lead hl;
+            ftmpc_prb::lead_start(R, hl);
+#pragma unroll 1
+            for (int i = 0; i < NT; ++i) {
+                const bool live = P.ub[b * NT + i] > 0.0;
+                const bool lst = ftmpc_prb::listed(i, live, cnt, P.det_thruster + b * P.K, P.det_level + b * P.K, L);
+                const double d[6] = {C.D[i], C.D[MAX_NT + i], C.D[2 * MAX_NT + i], C.D[3 * MAX_NT + i], C.D[4 * MAX_NT + i], C.D[5 * MAX_NT + i]};
+                double gh[6];
+                ftmpc_iso::unit_signature(C.dt, C.inv_mass, C.Jinv, d, gh);
+                const double stucki = P.stuck[b * NT + i];
+                ftmpc_iso::thruster(R, r, n, i, live, lst, P.acc[(int64_t)i * B + b], stucki, gh, P.llr + (int64_t)i * L * B + b, B,
+                                    hist ? hist + i * L : nullptr, s);
+                ftmpc_prb::healthy(R, r, n, i, lst, Q.pacc[(int64_t)i * B + b], stucki, gh, Q.health + (int64_t)i * B + b, s, hl);
+            }
+            ftmpc_prb::merge(hl, H, s);
+            if (s.eligible > 0) f0 = r.q0, f1 = s.qmin;
+            if (ftmpc_iso::is_void(R, r, s)) I.voided[b] += 1;
+            int lead = I.lead[b * 2], run = I.lead[b * 2 + 1];
+            if (ftmpc_iso::confirm(R, s, lead, run)) {
+                if (s.besth >= H) {
+                    ftmpc_prb::reinstate(PR, s.besth - H, P.cstep, cnt, P.ub + b * NT, P.stuck + b * NT, P.det_step + b * P.K,
+                                           P.det_thruster + b * P.K, P.det_level + b * P.K);
+#pragma unroll 1
+                    for (int k = 0; k < H; ++k) P.llr[(int64_t)k * B + b] = 0.0;
+                    lead = -1;
+                    run = 0;
+                    Q.reinstated[b] += 1;
+                } else {
+                    const int rev = ftmpc_iso::decide(R, s.besth, P.cstep, cnt, H, P.ub + b * NT, P.stuck + b * NT, P.det_step + b * P.K,
+                                                      P.det_thruster + b * P.K, P.det_level + b * P.K, P.llr + b, B, lead, run);
+                    if (rev) I.revised[b] += 1;
+                }
+#pragma unroll 1
+                for (int i = 0; i < NT; ++i) Q.health[(int64_t)i * B + b] = 0.0;
+                P.count[b] = cnt + 1;
+                sw = 1;
+            }
+            I.lead[b * 2] = lead;
+            I.lead[b * 2 + 1] = run;
+        }
+    }
+    if (hist && !tested) {
+#pragma unroll 1
+        for (int k = 0; k < H; ++k) hist[k] = P.llr[(int64_t)k * B + b];
+    }
+    if (fit) fit[0] = f0, fit[1] = f1;
+    P.switched[b] = sw;
+    if (P.init || P.anchor) {
+        for (int i = 0; i < 13; ++i) P.xt[b * 14 + i] = y[i];
+        P.xt[b * 14 + 13] = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < NT; ++i) {
+            P.acc[(int64_t)i * B + b] = 0.0;
+            Q.pacc[(int64_t)i * B + b] = 0.0;
+        }
+    }
+}
+
 }  // namespace ftmpc

@@ -46,6 +46,7 @@ SYMBOLS = (
     "ftmpc_simulate_outage_batch", "ftmpc_simulate_wrench_outage_batch", "ftmpc_multi_simulate_outage_batch",
     "ftmpc_simulate_environment_batch", "ftmpc_simulate_wrench_environment_batch", "ftmpc_multi_simulate_environment_batch",
     "ftmpc_simulate_isolation_batch", "ftmpc_simulate_wrench_isolation_batch", "ftmpc_multi_simulate_isolation_batch",
+    "ftmpc_simulate_probe_batch", "ftmpc_simulate_wrench_probe_batch",
 )
 
 
@@ -190,6 +191,16 @@ class ftmpc_isolation(C.Structure):
     ]
 
 
+class ftmpc_probe(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("amp", C.c_double), ("quiet", C.c_double), ("idle_steps", C.c_int32),
+        ("max_pulses", C.c_int32), ("reinstate", C.c_int32), ("restore_ub", C.c_double),
+        ("idle", C.POINTER(C.c_int32)), ("pulses", C.POINTER(C.c_int32)), ("impulse", C.POINTER(C.c_double)),
+        ("pacc", C.POINTER(C.c_double)), ("health", C.POINTER(C.c_double)), ("reinstated", C.POINTER(C.c_int32)),
+        ("thruster_hist", C.POINTER(C.c_int32)),
+    ]
+
+
 def library_path() -> Path:
     return _SO
 
@@ -293,6 +304,8 @@ def load_library() -> C.CDLL:
     lib.ftmpc_multi_simulate_isolation_batch.argtypes = lib.ftmpc_simulate_isolation_batch.argtypes
     lib.ftmpc_simulate_wrench_isolation_batch.argtypes = (lib.ftmpc_simulate_wrench_environment_batch.argtypes
                                                           + [C.POINTER(ftmpc_isolation)])
+    lib.ftmpc_simulate_probe_batch.argtypes = lib.ftmpc_simulate_isolation_batch.argtypes + [C.POINTER(ftmpc_probe)]
+    lib.ftmpc_simulate_wrench_probe_batch.argtypes = lib.ftmpc_simulate_wrench_isolation_batch.argtypes + [C.POINTER(ftmpc_probe)]
     lib.ftmpc_hull_offsets_batch.argtypes = [vp, C.c_int64, dp, dp, dp, C.c_int32, ip, C.c_int32, dp, ip]
     lib.ftmpc_eval_cost_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int64, dp, C.c_int64, dp, dp, dp]
     lib.ftmpc_solve_sqp_wrench_batch.argtypes = [vp, C.c_int64, dp, dp, dp, dp, C.c_int32, ip, dp, C.c_int32, dp, C.c_int64, dp, C.c_int64,

@@ -468,7 +468,7 @@ class BatchedMPC:
                  return_inputs=False, sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0,
                  faults=None, detect_delay=0, return_states=False, outcomes=None, return_status=False, index0=0, index_total=None,
                  plant=None, mission=None, actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None,
-                 bias_estimate=None, outage=None, environment=None, isolation=None):
+                 bias_estimate=None, outage=None, environment=None, isolation=None, probe=None):
         """T closed-loop steps (MPC step -> plant RK4 -> noise -> renormalise) without host round trips.
         sqp_iters > 0: every step solves the nonlinear program by that many major iterations of the line-search SQP
         (solve_sqp_device) instead of one QP step.  formulation="wrench": every step is the reference's two-stage structure
@@ -579,12 +579,18 @@ class BatchedMPC:
         leader and run, what a previous call returned; needs diagnosis['state']), voided=None ([B]) and revised=None ([B]),
         continued likewise, and fields=(...) among lead, voided, revised, fit [T,B,2] (q_0 and the smallest q_h of every tested
         step, else -1); they come back as out["isolation"].
+        probe: test pulses for thrusters that have been quiet (include/ftmpc.h, ftmpc_probe; ft_mpc_amd.probes restates the step
+        in NumPy; both formulations; needs `diagnosis`): amp (the pulse, N), quiet=0.0 (a command below it counts as idle),
+        idle_steps (idle steps before a pulse), max_pulses=0 (per thruster and vehicle; 0: no cap), reinstate=False (a detected
+        thruster is pulsed too and tested for "healthy after all": the entry (c, i, n_levels), ub_c,i = restore_ub), restore_ub,
+        the carried idle / pulses [B,NT], impulse [B], pacc / health [B,NT] (these two need the diagnosis' state), reinstated [B]
+        and fields=(...) among thruster_hist [T,B], idle, pulses, impulse, pacc, health, reinstated; they come back as out["probe"].
         Returns dict(x [B,13] final states, u [T,B,NT]|None (commanded), not_converged [T][, alloc_failed [T]][, x_hist][, outcomes]
-        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage][, environment][, isolation])."""
+        [, status_hist][, actuator][, sensor][, estimator][, diagnosis][, disturbance][, bias_estimate][, outage][, environment][, isolation][, probe])."""
         return _simulate(self, False, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total,
                          plant, mission, actuator, sensor, estimator, diagnosis, disturbance, bias_estimate, outage, environment,
-                         isolation)
+                         isolation, probe)
 
     def hull_offsets(self, ub, stuck, hull):
         """Offsets of the patterns ub / stuck [B,NT] on the normals of `hull` (a dict from input_bounds.hull_tables: A, set [B], rows),
@@ -951,10 +957,10 @@ def _estimator_request(estimator, B, T):
     return es, keep, out
 
 
-def _diagnosis_request(diagnosis, x0, B, T, NT, estimator, sensor):
+def _diagnosis_request(diagnosis, x0, B, T, NT, estimator, sensor, reinstating=False):
     """The ftmpc_diagnosis struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
     from .diagnosis import request
-    r = request(diagnosis, B, T, NT, estimator, sensor, F_MAX)
+    r = request(diagnosis, B, T, NT, estimator, sensor, F_MAX, reinstating)
     L, K = r["levels"].size, r["max_detect"]
     dg = _lib.ftmpc_diagnosis(struct_size=C.sizeof(_lib.ftmpc_diagnosis), every=r["every"], n_levels=L, max_detect=K,
                               threshold=r["threshold"])
@@ -1136,10 +1142,10 @@ def _environment_request(environment, B, T, sensor, disturbance, index0, index_t
     return ev, keep, out
 
 
-def _isolation_request(isolation, B, T, NT, diagnosis):
+def _isolation_request(isolation, B, T, NT, diagnosis, reinstating=False):
     """The ftmpc_isolation struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
     from .diagnosis import isolation_request
-    r = isolation_request(isolation, B, NT, diagnosis)
+    r = isolation_request(isolation, B, NT, diagnosis, reinstating)
     iso = _lib.ftmpc_isolation(struct_size=C.sizeof(_lib.ftmpc_isolation), consist=r["consist"], persist=r["persist"],
                                revise=int(r["revise"]))
     keep, out = [], {}
@@ -1161,10 +1167,34 @@ def _isolation_request(isolation, B, T, NT, diagnosis):
     return iso, keep, out
 
 
+def _probe_request(probe, B, T, NT, diagnosis):
+    """The ftmpc_probe struct of a simulate call, the arrays it points into (kept alive by the caller) and the dict of outputs."""
+    from .probes import request
+    r = request(probe, B, T, NT, diagnosis)
+    pb = _lib.ftmpc_probe(struct_size=C.sizeof(_lib.ftmpc_probe), amp=r["amp"], quiet=r["quiet"], idle_steps=r["idle_steps"],
+                          max_pulses=r["max_pulses"], reinstate=int(r["reinstate"]), restore_ub=r["restore_ub"])
+    keep, out = [], {}
+    # the carried arrays are in/out: asked back without being handed over, they start from 0 as the library's do
+    for name, dtype, shape in (("idle", np.int32, (B, NT)), ("pulses", np.int32, (B, NT)), ("impulse", np.float64, (B,)),
+                               ("pacc", np.float64, (B, NT)), ("health", np.float64, (B, NT)), ("reinstated", np.int32, (B,))):
+        a = r[name]
+        if a is None and name in r["fields"]:
+            a = np.zeros(shape, dtype)
+        if a is not None:
+            keep.append(a)
+            setattr(pb, name, _ptr(a, C.c_int32 if dtype is np.int32 else C.c_double))
+            if name in r["fields"]:
+                out[name] = a
+    if "thruster_hist" in r["fields"]:
+        out["thruster_hist"] = np.full((T, B), -1, np.int32)
+        pb.thruster_hist = _ptr(out["thruster_hist"], C.c_int32)
+    return pb, keep, out
+
+
 def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol, formulation,
               hull, penalty, faults, detect_delay, return_states, outcomes, return_status, index0, index_total, plant=None, mission=None,
               actuator=None, sensor=None, estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None,
-              isolation=None):
+              isolation=None, probe=None):
     """BatchedMPC.simulate (multi False) and MultiGPUMPC.simulate (multi True: the ftmpc_multi_* entries on the driver's handle)."""
     N, NT = self.cfg.N, self.cfg.NT
     x = _f64(x0).reshape(-1, 13).copy()
@@ -1186,6 +1216,9 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
         ms, mkeep, cost = _mission_request(mission, B, T, N, want_cost)
     se, skeep, sout, L = _sensor_request(sensor, B, T, NT) if sensor is not None else (None, None, None, 0)
     es, ekeep, eout = _estimator_request(estimator, B, T) if estimator is not None else (None, None, None)
+    if probe is not None and multi:
+        raise ValueError("probe: the probe on MultiGPUMPC is not built (use BatchedMPC)")
+    reinstating = probe is not None and bool(probe.get("reinstate", False))      # widens the detect level and the leader's range
     rebuild, d_hb, d_nh = False, None, None
     if diagnosis is not None:     # the wrench form's keys are taken out here: ft_mpc_amd.diagnosis.request knows the common ones
         diagnosis = dict(diagnosis)
@@ -1201,7 +1234,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             d_nh = np.full(B, -1, np.int32) if d_nh is None else np.array(d_nh, dtype=np.int32)      # (a copy: the call writes into it)
             if d_nh.shape != (B,) or (d_nh < -1).any():
                 raise ValueError(f"diagnosis['no_hull'] must have shape {(B,)} and no entry below -1")
-    dg, dkeep, dout = _diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor) if diagnosis is not None else (None, None, None)
+    dg, dkeep, dout = (_diagnosis_request(diagnosis, x, B, T, NT, estimator, sensor, reinstating) if diagnosis is not None
+                       else (None, None, None))
     db, bkeep, bout = (_disturbance_request(disturbance, B, T, estimator, sqp_iters, formulation) if disturbance is not None
                        else (None, None, None))
     if bias_estimate is not None and multi and formulation == "wrench":
@@ -1221,10 +1255,17 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     iso, isokeep, isoout = (None, None, None)
     if isolation is not None:
         # lead needs a state at the ABI: asked back (or handed over) on a run whose diagnosis carries no state, the call is refused here
-        iso, isokeep, isoout = _isolation_request(isolation, B, T, NT, diagnosis)
+        iso, isokeep, isoout = _isolation_request(isolation, B, T, NT, diagnosis, reinstating)
         if iso.lead and dg is not None and not dg.state:
             raise ValueError("isolation['lead'] (handed over or among fields) needs the diagnosis' state: put 'state' into "
                              "diagnosis['fields'] or hand diagnosis['state'] over")
+    pr, prkeep, prout = (None, None, None)
+    if probe is not None:
+        # pacc and health need a state at the ABI, as the isolation's lead does
+        pr, prkeep, prout = _probe_request(probe, B, T, NT, diagnosis)
+        if (pr.pacc or pr.health) and dg is not None and not dg.state:
+            raise ValueError("probe['pacc'] and probe['health'] (handed over or among fields) need the diagnosis' state: put 'state' "
+                             "into diagnosis['fields'] or hand diagnosis['state'] over")
     if L and mission is not None and mission.get("tables") is not None:
         off = np.asarray(0 if mission.get("offset") is None else mission["offset"])
         if int(off.max()) + T + N + L > np.shape(mission["tables"])[-1]:
@@ -1275,7 +1316,7 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
     new = (multi or (outcomes is not None and outcomes is not False) or return_status or index0 != 0 or index_total is not None
            or pm is not None or ms is not None or ac is not None or se is not None or es is not None or dg is not None
            or db is not None or be is not None or og is not None or environment is not None
-           or isolation is not None)
+           or isolation is not None or probe is not None)
     oc, orec, sh = _outcome_request(self, B, T, formulation == "wrench", outcomes, return_status, index0, index_total) if new else (None,) * 3
 
     if cost is not None:
@@ -1306,6 +1347,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             out["environment"] = evout
         if isoout is not None:
             out["isolation"] = isoout
+        if prout is not None:
+            out["probe"] = prout
         return out
     # One argument list, built once: the lead-in of the form, then the feature structs in the order every entry takes them.  The entry
     # is the narrowest one that carries every feature present, so that each ABI level keeps being exercised from here.
@@ -1344,7 +1387,8 @@ def _simulate(self, multi, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, 
             ("actuator", ac is not None, [ref(ac)]), ("sensor", se is not None, [ref(se)]), ("estimator", es is not None, [ref(es)]),
             ("diagnosis", dg is not None, [ref(dg)] + dgx), ("disturbance", db is not None, [ref(db)]),
             ("bias", be is not None, [ref(be)]), ("outage", og is not None, [ref(og)]),
-            ("environment", ev is not None, [ref(ev)]), ("isolation", iso is not None, [ref(iso)])]
+            ("environment", ev is not None, [ref(ev)]), ("isolation", iso is not None, [ref(iso)]),
+            ("probe", pr is not None, [ref(pr)])]
     last = max((i for i, (_, present, _) in enumerate(tail) if present), default=-1)
     if last >= 0:
         name = tail[last][0]

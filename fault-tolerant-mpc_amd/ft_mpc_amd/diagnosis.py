@@ -15,7 +15,8 @@ replay runs the loop's diagnosis for one vehicle from the recorded measurements 
 The signature is first order in dt; a dead thruster that is not commanded has none, and neither has a thruster stuck at the level it
 is commanded at; with isolation= (include/ftmpc.h, ftmpc_isolation; csrc/ftmpc_isolate.h) the decision gets a consistency gate on the
 fit q_h = q_0 - 2 z_h, confirmation over `persist` tests and the revision of a detected thruster's level; a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's test; a
-detection is never withdrawn; position and attitude are not used; the diagnosis is told neither the plant's dispersion nor the
+detection is withdrawn only under a reinstating probe (probe=, include/ftmpc.h, ftmpc_probe; ft_mpc_amd.probes), which pulses a detected
+thruster and adds the hypotheses "listed thruster i is healthy"; position and attitude are not used; the diagnosis is told neither the plant's dispersion nor the
 actuator."""
 from __future__ import annotations
 
@@ -70,14 +71,24 @@ def _isolation(isolation):
     return float(isolation.get("consist", 0.0)), int(isolation.get("persist", 1)), bool(isolation.get("revise", False))
 
 
-def test_step(llr, y, xt, n, acc, ub, spec, cfg, isolation=None, lead=None, stuck=None, listed=()):
+def test_step(llr, y, xt, n, acc, ub, spec, cfg, isolation=None, lead=None, stuck=None, listed=(), probe=None, pacc=None, health=None):
     """The statistics [NT,L] after the test of one step (after the max(0, .), before a detection's reset).
     isolation = dict(consist, persist, revise): the test under ftmpc_isolation's rule, with lead = (leader, run) as the last test left
     it (None: (-1, 0)), stuck [NT] the controller's levels and listed the thrusters of the vehicle's detection list (both looked at
     with revise only).  It then returns dict(llr [NT,L], q0, q [NT,L] (nan where the hypothesis is not eligible), qmin (nan without an
     eligible hypothesis), void, leader (-1: none), lead (leader, run) after the confirmation and before a decision's reset, decide
     (the leader is decided now), margin (the smallest |q_h - consist^2|, inf without a gate), gap (the leader's statistic minus the
-    runner-up's, inf without a leader))."""
+    runner-up's, inf without a leader)).
+    probe = dict(reinstate=True, ...) (include/ftmpc.h, ftmpc_probe; csrc/ftmpc_probe.h): the test with the NT further hypotheses
+    H + i "listed thruster i is healthy", under isolation's rule (None: the trivial rule).  listed is then ft_mpc_amd.probes.listed
+    (off, the newest entry below n_levels), pacc [NT] the applied command summed over the window, health [NT] the statistics; delta
+    = pacc_i - n stuck_i, z and q as for a level hypothesis; the gate counts H + i like any other, the leader is the first of equal
+    maxima over the H + NT statistics, so a level hypothesis wins a tie.  The dict then also holds health [NT] and qh [NT].  A probe
+    without reinstate changes nothing."""
+    if probe is not None and probe.get("reinstate") and isolation is None:
+        isolation = {}
+    if probe is not None and not probe.get("reinstate"):
+        probe = None
     lv = np.asarray(spec["levels"], dtype=np.float64).reshape(-1)
     rs = np.asarray(spec["resid_sigma"], dtype=np.float64).reshape(2)
     ds = np.asarray(spec.get("drift_sigma", (0.0, 0.0)), dtype=np.float64).reshape(2)
@@ -106,12 +117,40 @@ def test_step(llr, y, xt, n, acc, ub, spec, cfg, isolation=None, lead=None, stuc
             b_w = (float(cfg.dt) * np.linalg.solve(J, D[3:6]).T)[:, None, :] * delta[:, :, None]
             zr = (b_v @ rho_v - 0.5 * (b_v * b_v).sum(-1)) / s_v + (b_w @ r_w - 0.5 * (b_w * b_w).sum(-1)) / s_w
             z = np.where(off[:, None], zr, z)
+    if probe is not None:
+        # Every hypothesis of an off thruster, revised levels and "healthy" alike, through one elementwise formula: where two of
+        # them have the same delta (levels[0] = 0 and no pulse yet: "dead" and "healthy") they tie exactly, as they do on the device
+        D, m, J = _cfg_model(cfg)
+        u_v, u_w = (float(cfg.dt) / m) * D[0:3].T, float(cfg.dt) * np.linalg.solve(J, D[3:6]).T
+
+        def z_of(delta):      # delta [NT, k]
+            a, w = u_v[:, None, :] * delta[:, :, None], u_w[:, None, :] * delta[:, :, None]
+            return (((a[..., 0] * rho_v[0] + a[..., 1] * rho_v[1] + a[..., 2] * rho_v[2])
+                     - 0.5 * (a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1] + a[..., 2] * a[..., 2])) / s_v
+                    + ((w[..., 0] * r_w[0] + w[..., 1] * r_w[1] + w[..., 2] * r_w[2])
+                       - 0.5 * (w[..., 0] * w[..., 0] + w[..., 1] * w[..., 1] + w[..., 2] * w[..., 2])) / s_w)
+        st = np.asarray(stuck, dtype=np.float64).reshape(-1)
+        if off.any():
+            z = np.where(off[:, None], z_of(float(n) * lv[None, :] - float(n) * st[:, None]), z)
     eligible = live | off
     q0 = float(rho_v @ rho_v / s_v + r_w @ r_w / s_w)
     q = np.where(eligible[:, None], q0 - 2.0 * z, np.nan)
     counted = eligible[:, None] & ((q <= consist * consist) if consist > 0 else np.ones_like(z, bool))
     new = np.where(counted, np.maximum(0.0, old + z), np.where(eligible[:, None], old, 0.0))
     flat = new.reshape(-1)
+    extra = {}
+    if probe is not None:      # H + i: the applied command of a listed thruster against the model's stuck level
+        lst = np.zeros(NT, bool)
+        lst[[i for i in set(int(i) for i in listed) if not live[i]]] = True
+        zh = z_of((np.asarray(pacc, dtype=np.float64).reshape(NT) - float(n) * st)[:, None])[:, 0]
+        qh = np.where(lst, q0 - 2.0 * zh, np.nan)
+        cnth = lst & ((qh <= consist * consist) if consist > 0 else np.ones(NT, bool))
+        oldh = np.asarray(health, dtype=np.float64).reshape(NT)
+        newh = np.where(cnth, np.maximum(0.0, oldh + zh), np.where(lst, oldh, 0.0))
+        flat = np.concatenate([flat, newh])
+        extra = dict(health=newh, qh=qh)
+        qall = np.concatenate([q[eligible].reshape(-1), qh[lst]])
+        any_counted = bool(counted.any() or cnth.any())
     thr = float(spec["threshold"])
     leader = int(np.argmax(flat)) if flat.max() > thr else -1      # (the first of equal maxima)
     gap = np.inf
@@ -124,10 +163,12 @@ def test_step(llr, y, xt, n, acc, ub, spec, cfg, isolation=None, lead=None, stuc
         run += 1
     else:
         ld, run = leader, 1
-    margin = float(np.abs(q[eligible] - consist * consist).min()) if consist > 0 and eligible.any() else np.inf
-    return dict(llr=new, q0=q0, q=q, qmin=float(np.min(q[eligible])) if eligible.any() else np.nan,
-                void=bool(consist > 0 and q0 > consist * consist and not counted.any()), leader=leader, lead=(ld, run),
-                decide=leader >= 0 and run >= persist, margin=margin, gap=gap)
+    if probe is None:
+        qall, any_counted = q[eligible].reshape(-1), bool(counted.any())
+    margin = float(np.abs(qall - consist * consist).min()) if consist > 0 and qall.size else np.inf
+    return dict(llr=new, q0=q0, q=q, qmin=float(np.min(qall)) if qall.size else np.nan,
+                void=bool(consist > 0 and q0 > consist * consist and not any_counted), leader=leader, lead=(ld, run),
+                decide=leader >= 0 and run >= persist, margin=margin, gap=gap, **extra)
 
 
 test_step.__test__ = False      # (not a test of the suite, whatever its name)
@@ -147,7 +188,7 @@ def propagate(xt, n, acc, u, ub, stuck, cfg, force=None, torque=None):
 
 
 def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None, detections=None, force=None, torque=None, avail=None,
-           isolation=None, lead=None, voided=0, revised=0):
+           isolation=None, lead=None, voided=0, revised=0, probe=None, pacc=None, health=None, reinstated=0):
     """The loop's diagnosis for ONE vehicle.  meas [T,13]: the y_t; applied_u [T,NT]: the a_t (u_hist); ub, stuck [NT]: the
     controller's pattern at the call's start; spec: dict(every, levels, resid_sigma, drift_sigma, threshold, max_detect); state
     [14+NT] / llr [NT*L] / detections (list of (step, thruster, level)): what a previous call returned; force / torque [T,3]: the
@@ -158,6 +199,12 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
     previous call returned; a lost vehicle's lead and counters do not move.  The result then also holds lead, voided, revised,
     fit_hist [T,2] (q_0 and the smallest q_h of a tested step with an eligible hypothesis, else -1, -1), gate_margin (the smallest
     |q_h - consist^2| met, inf without a gate) and lead_gap (the smallest distance of a leader to its runner-up).
+    probe = dict(reinstate=True, restore_ub) (ftmpc_probe): the test with the hypotheses "listed thruster i is healthy" (test_step
+    with probe=), under isolation's rule (None: the trivial rule); pacc, health [NT] and reinstated what a previous call returned.
+    The decision for H + i appends (c, i, n_levels), sets ub_i = restore_ub, stuck_i = 0 and resets every statistic; pacc sums the
+    applied command of the listed thrusters and goes to 0 wherever the diagnosis re-anchors; a level revision looks at
+    ft_mpc_amd.probes.listed.  The result then also holds pacc, health, reinstated, health_hist [T,NT] (after each step's test,
+    before a decision's reset) and listed [T,NT] (of the pattern each solve saw).  A probe without reinstate changes nothing.
     Returns dict(llr_hist [T,NT*L], detections [(step, thruster, level)], ub [T,NT], stuck [T,NT] (the pattern each solve saw),
     ub_end, stuck_end, state [14+NT], llr [NT*L], peak [T] (the largest statistic of every step that tested, else nan))."""
     meas = np.asarray(meas, dtype=np.float64).reshape(-1, 13)
@@ -181,17 +228,34 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
     ld = (-1, 0) if lead is None else (int(lead[0]), int(lead[1]))
     voided, revised = int(voided), int(revised)
     fit, gate_margin, lead_gap = np.full((T, 2), -1.0), np.inf, np.inf
+    rein = probe is not None and bool(probe.get("reinstate"))
+    if rein:
+        from .probes import listed as probe_listed
+        if isolation is None:
+            isolation = {}
+        pa = np.zeros(NT) if pacc is None else np.array(pacc, dtype=np.float64).reshape(NT)
+        hs = np.zeros(NT) if health is None else np.array(health, dtype=np.float64).reshape(NT)
+        reinstated = int(reinstated)
+        hh, lsh = np.zeros((T, NT)), np.zeros((T, NT), bool)
     for t in range(T):
         c = int(step0) + t
         if xt is None:
             xt, n, acc, s = meas[t].copy(), 0, np.zeros(NT), np.zeros((NT, L))
             hist[t] = 0.0
+            if rein:
+                pa, hs = np.zeros(NT), np.zeros(NT)
         elif avail is not None and not avail[t]:
             hist[t] = s.reshape(-1)
         else:
             if c % every == 0 and n >= 1 and len(det) < K and isolation is not None:
-                r = test_step(s, meas[t], xt, n, acc, ub, spec, cfg, isolation=isolation, lead=ld, stuck=stuck,
-                              listed=[d[1] for d in det])
+                if rein:
+                    r = test_step(s, meas[t], xt, n, acc, ub, spec, cfg, isolation=isolation, lead=ld, stuck=stuck,
+                                  listed=np.flatnonzero(probe_listed(ub, det, L)), probe=probe, pacc=pa, health=hs)
+                    hs = r["health"]
+                    hh[t] = hs
+                else:
+                    r = test_step(s, meas[t], xt, n, acc, ub, spec, cfg, isolation=isolation, lead=ld, stuck=stuck,
+                                  listed=[d[1] for d in det])
                 s, ld = r["llr"], r["lead"]
                 hist[t] = s.reshape(-1)
                 peak[t] = hist[t].max()
@@ -199,12 +263,20 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
                     fit[t] = r["q0"], r["qmin"]
                 voided += int(r["void"])
                 gate_margin, lead_gap = min(gate_margin, r["margin"]), min(lead_gap, r["gap"])
-                if r["decide"]:
+                if r["decide"] and r["leader"] >= NT * L:      # "thruster i is healthy": reinstated
+                    i = r["leader"] - NT * L
+                    det.append((c, i, L))
+                    ub[i], stuck[i] = float(probe["restore_ub"]), 0.0
+                    reinstated += 1
+                    s, ld, hs = np.zeros((NT, L)), (-1, 0), np.zeros(NT)
+                elif r["decide"]:
                     i, l = divmod(r["leader"], L)
                     det.append((c, i, l))
                     revised += int(not ub[i] > 0)
                     ub[i], stuck[i] = 0.0, lv[l]
                     s, ld = np.zeros((NT, L)), (-1, 0)
+                    if rein:
+                        hs = np.zeros(NT)
             elif c % every == 0 and n >= 1 and len(det) < K:
                 s = test_step(s, meas[t], xt, n, acc, ub, spec, cfg)
                 hist[t] = s.reshape(-1)
@@ -218,21 +290,35 @@ def replay(meas, applied_u, ub, stuck, spec, cfg, step0=0, state=None, llr=None,
                 hist[t] = s.reshape(-1)
             if c % every == 0:
                 xt, n, acc = meas[t].copy(), 0, np.zeros(NT)
+                if rein:
+                    pa = np.zeros(NT)
         ubh[t], sth[t] = ub, stuck
+        if rein:
+            if np.isnan(peak[t]):
+                hh[t] = hs
+            lsh[t] = probe_listed(ub, det, L)
+            pa = pa + np.where(lsh[t], u[t], 0.0)
         xt, n, acc = propagate(xt, n, acc, u[t], ub, stuck, cfg, None if force is None else np.asarray(force)[t],
                                None if torque is None else np.asarray(torque)[t])
+    more = dict(pacc=pa, health=hs, reinstated=reinstated, health_hist=hh, listed=lsh) if rein else {}
     return dict(llr_hist=hist, detections=det, ub=ubh, stuck=sth, ub_end=ub, stuck_end=stuck,
                 state=np.concatenate([xt, [float(n)], acc]), llr=s.reshape(-1), peak=peak,
-                lead=ld, voided=voided, revised=revised, fit_hist=fit, gate_margin=gate_margin, lead_gap=lead_gap)
+                lead=ld, voided=voided, revised=revised, fit_hist=fit, gate_margin=gate_margin, lead_gap=lead_gap, **more)
 
 
-def pattern(ub, stuck, detections, levels):
-    """The controller's pattern (ub [NT], stuck [NT]) after the detections [(step, thruster, level)] of one vehicle."""
+def pattern(ub, stuck, detections, levels, restore_ub=None):
+    """The controller's pattern (ub [NT], stuck [NT]) after the detections [(step, thruster, level)] of one vehicle.  A level equal
+    to n_levels is a reinstatement (ftmpc_probe): the thruster is healthy from that step on, with ub = restore_ub."""
     ub = np.array(ub, dtype=np.float64)
     stuck = np.array(stuck, dtype=np.float64)
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
     for _, i, l in detections:
-        if i >= 0:
-            ub[i], stuck[i] = 0.0, float(np.asarray(levels).reshape(-1)[l])
+        if i >= 0 and l == lv.size:
+            if restore_ub is None:
+                raise ValueError("diagnosis.pattern: a reinstatement (level == n_levels) needs restore_ub")
+            ub[i], stuck[i] = float(restore_ub), 0.0
+        elif i >= 0:
+            ub[i], stuck[i] = 0.0, float(lv[l])
     return ub, stuck
 
 
@@ -243,7 +329,7 @@ def detections_of(step, thruster, level):
             for b in range(step.shape[0])]
 
 
-def score(faults, detections, final=False):
+def score(faults, detections, final=False, n_levels=None):
     """faults: per vehicle a list of (onset, thruster, level) events that happened; detections: per vehicle a list of
     (step, thruster, level).  An event is matched to the first unmatched detection of its thruster at or after its onset; an event
     left over is matched to the first unmatched detection at or after its onset, which then blames the wrong thruster; what is left
@@ -251,9 +337,18 @@ def score(faults, detections, final=False):
     final=True: an event is matched to the LAST detection of its thruster at or after its onset, so that a revised level counts as
     right; the earlier detections of that thruster from the onset on belong to the same match (they are no false alarms) and the
     delay is taken from the first of them.
-    Returns dict(delay [per event: detect_step - onset, or None when missed], missed, wrong_thruster, wrong_level, false_alarms)."""
-    delay, missed, wrong_t, wrong_l, false_alarms = [], 0, 0, 0, 0
+    n_levels: the diagnosis' number of levels; an entry (s, i, n_levels) is then a reinstatement (ftmpc_probe): thruster i is
+    healthy from step s on, so the vehicle's earlier detections of i are withdrawn: they take no part in the matching, are no false
+    alarms and are counted in `withdrawn` (an event whose every detection was withdrawn is missed).
+    Returns dict(delay [per event: detect_step - onset, or None when missed], missed, wrong_thruster, wrong_level, false_alarms
+    [, withdrawn])."""
+    delay, missed, wrong_t, wrong_l, false_alarms, withdrawn = [], 0, 0, 0, 0, 0
     for ev, det in zip(faults, detections):
+        if n_levels is not None:
+            back = [d for d in det if d[2] == n_levels]
+            gone = [d for d in det if d[2] != n_levels and any(r[1] == d[1] and r[0] > d[0] for r in back)]
+            withdrawn += len(gone)
+            det = [d for d in det if d[2] != n_levels and d not in gone]
         ev, det = sorted(ev), sorted(det)
         used, hit, first = [False] * len(det), [None] * len(ev), [None] * len(ev)
         for same in (True, False):
@@ -278,10 +373,13 @@ def score(faults, detections, final=False):
             elif det[hit[j]][2] != lvl:
                 wrong_l += 1
         false_alarms += used.count(False)
-    return dict(delay=delay, missed=missed, wrong_thruster=wrong_t, wrong_level=wrong_l, false_alarms=false_alarms)
+    out = dict(delay=delay, missed=missed, wrong_thruster=wrong_t, wrong_level=wrong_l, false_alarms=false_alarms)
+    if n_levels is not None:
+        out["withdrawn"] = withdrawn
+    return out
 
 
-def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None):
+def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None, reinstating=False):
     """The checks BatchedMPC.simulate makes on a diagnosis dict before the call reaches the library (the library's own refusals, raised
     from Python too); returns the dict with defaults filled in: every, levels (L,), resid_sigma (2,), drift_sigma (2,), threshold,
     max_detect, state [B,14+NT] | None, llr [B,NT*L] | None, detect (step, thruster, level) [B,K] | None, fields."""
@@ -343,7 +441,7 @@ def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None):
         used = det[0] >= 0
         if (det[0] < -1).any() or (used[:, 1:] & ~used[:, :-1]).any():
             raise ValueError("diagnosis['detect']: a step below -1, or a used slot after an unused one")
-        if ((det[1][used] < 0) | (det[1][used] >= NT)).any() or ((det[2][used] < 0) | (det[2][used] >= lv.size)).any():
+        if ((det[1][used] < 0) | (det[1][used] >= NT)).any() or ((det[2][used] < 0) | (det[2][used] >= lv.size + int(bool(reinstating)))).any():
             raise ValueError("diagnosis['detect']: a thruster outside [0, NT) or a level outside [0, n_levels)")
         out["detect"] = det
     if sensor is not None and sensor.get("predict") and estimator is None:
@@ -352,7 +450,7 @@ def request(diagnosis, B, T, NT, estimator=None, sensor=None, f_max=None):
     return out
 
 
-def isolation_request(isolation, B, NT, diagnosis):
+def isolation_request(isolation, B, NT, diagnosis, reinstating=False):
     """The checks BatchedMPC.simulate makes on an isolation dict before the call reaches the library (the library's own refusals, raised
     from Python too); diagnosis: the call's diagnosis dict or None.  Returns the dict with defaults filled in: consist, persist,
     revise, lead [B,2] | None, voided [B] | None, revised [B] | None (int32 copies: the call writes into them), fields."""
@@ -390,7 +488,7 @@ def isolation_request(isolation, B, NT, diagnosis):
             raise ValueError("isolation['lead'] requires the diagnosis' state (diagnosis['state'], or 'state' or 'detect' among its fields)")
     if out["lead"] is not None:
         lv = diagnosis.get("levels")
-        H = NT * (2 if lv is None else np.asarray(lv).size)
+        H = NT * (2 if lv is None else np.asarray(lv).size) + (NT if reinstating else 0)      # (a reinstating probe: H + i may lead)
         ld = out["lead"] = np.array(out["lead"], dtype=np.int32)
         if ld.shape != (B, 2):
             raise ValueError(f"isolation['lead'] must have shape {(B, 2)}")

@@ -127,7 +127,7 @@ class MultiGPUMPC:
                  sqp_iters=0, backtracks=8, tol=1e-9, formulation="thruster", hull=None, penalty=0.0, faults=None, detect_delay=0,
                  return_states=False, outcomes=None, return_status=False, plant=None, mission=None, actuator=None, sensor=None,
                  estimator=None, diagnosis=None, disturbance=None, bias_estimate=None, outage=None, environment=None,
-                 isolation=None):
+                 isolation=None, probe=None):
         """BatchedMPC.simulate over the device slots (ftmpc_multi_simulate_outcomes_batch / _wrench_outcomes_batch): slot g runs its
         shard as the slice [lo, hi) of the campaign, so the noise -- and wherever a vehicle's solve does not depend on its batch, every
         output -- is what one handle computes for the whole batch.  Same arguments and result, without index0 / index_total; the
@@ -147,12 +147,13 @@ class MultiGPUMPC:
         tau and period of `environment` are uniform, its amplitudes, phase, kick, window, state, error sums and wrench history per
         vehicle (ftmpc_multi_simulate_environment_batch; thruster formulation: the wrench form is not built on this driver and
         raises); consist, persist and revise of `isolation` are uniform, its lead, counters and fit history per vehicle
-        (ftmpc_multi_simulate_isolation_batch; thruster formulation: the wrench form is not built on this driver and raises)."""
+        (ftmpc_multi_simulate_isolation_batch; thruster formulation: the wrench form is not built on this driver and raises); a
+        `probe` is not built on this driver and raises."""
         from .batch import _simulate
         return _simulate(self, True, x0, ub, stuck, xref_traj, T, uref_traj, noise, seed, return_inputs, sqp_iters, backtracks, tol,
                          formulation, hull, penalty, faults, detect_delay, return_states, outcomes, return_status, 0, None, plant,
                          mission, actuator, sensor, estimator, diagnosis, disturbance,
-                         bias_estimate, outage, environment, isolation)
+                         bias_estimate, outage, environment, isolation, probe)
 
     # -- shards resident in HBM between steps ---------------------------------------------------
     def upload(self, x0, ub, stuck, xref, uref=None, warmU=None):

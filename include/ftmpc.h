@@ -885,7 +885,8 @@ int ftmpc_simulate_wrench_estimator_batch(ftmpc_handle* h, int64_t B, int32_t T,
  * thruster that is not commanded has no signature, and neither has a thruster stuck at the level it is commanded at (stuck on while the
  * controller saturates it); a fault that starts inside a window of every > 1 steps shows only a part of its signature in that window's
  * test; a detection is never withdrawn; position and attitude are not used; the diagnosis is told neither the plant dispersion nor the
- * actuator (resid_sigma / drift_sigma have to cover them).
+ * actuator (resid_sigma / drift_sigma have to cover them).  (ftmpc_probe below lifts the first and the fourth of these: it pulses
+ * thrusters that have been quiet, and with reinstate tests a detected thruster for "healthy after all".)
  * A continued run (state, llr and the detect arrays handed over, the returned ub / stuck as the call's pattern, the sensor's
  * pending / step0, the filter's xhat / cov, the schedule shifted) is the whole run bit for bit.
  * FTMPC_ERR_ARG, the message naming ftmpc_diagnosis.<field> and, for an array, the first offending vehicle, the call's x untouched:
@@ -1313,8 +1314,8 @@ int ftmpc_simulate_wrench_environment_batch(ftmpc_handle* h, int64_t B, int32_t 
  * unchanged.  ftmpc_diagnose_iso_kernel runs in place of the call's phase-0 diagnosis kernel.
  * isolation == NULL, or a trivial struct (consist = 0, persist = 1, revise = 0, every array NULL), launches exactly the kernels
  * of the _environment_ entries and returns their bits.
- * Limits: a detection is never withdrawn back to healthy (a thruster the controller no longer commands has no signature);
- * consist and persist are uniform over the call; the innovation gate of the filters is ftmpc_outage's, not this one.
+ * Limits: this rule alone never withdraws a detection back to healthy (a thruster the controller no longer commands has no
+ * signature; a reinstating ftmpc_probe pulses it and adds that hypothesis); consist and persist are uniform over the call; the innovation gate of the filters is ftmpc_outage's, not this one.
  * FTMPC_ERR_ARG, the message naming ftmpc_isolation.<field> and, for an array, the first offending vehicle, the call's x
  * untouched: a struct_size other than sizeof(ftmpc_isolation); reserved != 0; a non-trivial struct without an ftmpc_diagnosis in
  * the call; consist negative or not finite; persist < 1; revise outside {0, 1}; a lead entry with a hypothesis outside
@@ -1358,6 +1359,95 @@ int ftmpc_simulate_wrench_isolation_batch(ftmpc_handle* h, int64_t B, int32_t T,
                                           int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
                                           const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
                                           const ftmpc_environment* environment, const ftmpc_isolation* isolation);
+
+/* Probe pulses, as an opt-in: the diagnosis (ftmpc_diagnosis) is passive, it sees only what the controller commands.  A dead
+ * thruster that is not commanded has no signature, and a thruster the controller was told to leave alone can never clear itself.
+ * With this struct the loop briefly fires a thruster that has been quiet, after the step's solve (on the wrench form after the
+ * allocation and its alloc_failed count) and before the command enters the latency ring; everything downstream (the ring, the
+ * plant step, u_hist, the filters' time update, the diagnosis' phase 1, the outcomes) sees the pulsed command as it sees any
+ * command.  The parameters are uniform over the call; the counters are per vehicle and thruster.  With (ub_c, stuck_c) the
+ * controller's pattern of the step, u the solve's command and K = max_detect, NT, L, H of ftmpc_diagnosis:
+ *   listed: thruster i is off (ub_c,i == 0) and the newest entry for i in the vehicle's detection list has a level below
+ *     n_levels (see the reinstatement below).
+ *   probeable: live (ub_c,i > 0), or listed when reinstate = 1.
+ *   idle counter: e_i = ub_c,i > 0 ? u_i : 0;  idle_i = (probeable and e_i < quiet) ? idle_i + 1 : 0.  A NaN command compares
+ *     false: its counter resets.
+ *   candidate: the probeable thruster with the largest idle_i among those with idle_i >= idle_steps and, with max_pulses > 0,
+ *     pulses_i < max_pulses; the lowest index on a tie.  At most one thruster per vehicle and step.
+ *   pulse: on a live candidate u_i = min(u_i + amp, ub_c,i), on a listed one u_i = amp; then pulses_i += 1,
+ *     impulse += (u_i,new - e_i) dt, idle_i = 0 and thruster_hist[t] = i.  Without a candidate nothing changes and
+ *     thruster_hist[t] = -1.  (ftmpc_probe_kernel<0>; ft_mpc_amd.probes.step restates it.)
+ * reinstate = 1 adds the hypothesis "this listed thruster is healthy after all" to the decision rule.  After the plant step
+ * pacc_i += a_t,i for the listed thrusters (ftmpc_probe_kernel<1>; the model's c_i is 0 for a thruster that is off), and the
+ * call's phase-0 diagnosis kernel is replaced by ftmpc_diagnose_probe_kernel: the test of ftmpc_isolation (the call's struct, or
+ * the trivial rule when there is none; the availability word when the call has an outage) with NT further hypotheses, index
+ * H + i, for the listed thrusters: delta = pacc_i - n stuck_c,i, a_v, a_w, z and q from delta exactly as for a level hypothesis,
+ * the statistic in health[i] (0 for a thruster that is not listed).  The gate counts it like any other hypothesis and it
+ * competes for the leader like any other; on a tie the lower index wins, so a level hypothesis beats it: with levels[0] = 0 and
+ * no pulse yet "dead" is read before "healthy".  Confirmation is unchanged (lead may hold H + i).  The decision for H + i: the
+ * detection entry (c, i, n_levels), which uses a slot of max_detect; ub_c,i = restore_ub, stuck_c,i = 0; reinstated[b] += 1;
+ * every statistic (llr and health), lead and run reset; the vehicle flagged as switched, so the warm-start repair, the hull
+ * offsets and switch (wrench form) and the linearisation follow as after any detection.  Any decision resets health; pacc is
+ * set to 0 wherever the diagnosis re-anchors.  In that kernel a level revision (ftmpc_isolation.revise) looks at `listed` as
+ * defined here: a thruster that is off behind a reinstatement entry is the caller's.  With reinstate = 0 the phase-0 kernels are
+ * the ones the call launches without the struct, and pacc and health do not move.
+ * probe == NULL launches exactly the kernels of the _isolation_ entries and returns their bits.
+ * Limits: the pulse is not wrench-neutral, the controller sees its effect as a disturbance and corrects it on the next step; a
+ * thruster stuck at the level it is commanded at still has no signature; the parameters are uniform over the call; under a PWM
+ * actuator (ftmpc_actuator) a pulse below the minimum on-time is swallowed by the valve; the multi-GPU drivers have no probe.
+ * A continued run (every in/out array handed over, with the diagnosis' and the isolation's) is the whole run bit for bit.
+ * FTMPC_ERR_ARG, the message naming ftmpc_probe.<field> and, for an array, the first offending vehicle, the call's x untouched:
+ * a struct_size other than sizeof(ftmpc_probe); reserved != 0; a probe without an ftmpc_diagnosis in the call; amp not finite
+ * and > 0; quiet outside [0, amp); idle_steps < 1; max_pulses < 0; reinstate outside {0, 1}; restore_ub not finite and > 0 under
+ * reinstate; a negative idle, pulses or reinstated entry; a negative or non-finite impulse, pacc or health entry; pacc or health
+ * without ftmpc_diagnosis.state.  Under a reinstating probe a carried ftmpc_diagnosis.detect_level entry may equal n_levels and
+ * ftmpc_isolation.lead may name H + i; both stay refused without one.
+ */
+typedef struct ftmpc_probe {
+    int32_t struct_size, reserved;      /* sizeof(ftmpc_probe), 0 */
+    double amp;                         /* the pulse, N: finite, > 0 */
+    double quiet;                       /* a command below it counts as idle, N: 0 <= quiet < amp */
+    int32_t idle_steps;                 /* >= 1: idle steps before a thruster is pulsed */
+    int32_t max_pulses;                 /* per thruster and vehicle, counted with what `pulses` carries in; 0: no cap */
+    int32_t reinstate;                  /* 1: listed thrusters are pulsed and tested for "healthy", 0: not */
+    double restore_ub;                  /* the bound a reinstated thruster gets, N: finite, > 0 under reinstate */
+    int32_t* idle;                      /* NULL or [B*NT] in/out (NULL: from 0) */
+    int32_t* pulses;                    /* NULL or [B*NT] in/out */
+    double* impulse;                    /* NULL or [B] in/out, N s: what the pulses added to the commands */
+    double* pacc;                       /* NULL or [B*NT] in/out; needs diagnosis.state */
+    double* health;                     /* NULL or [B*NT] in/out; needs diagnosis.state */
+    int32_t* reinstated;                /* NULL or [B] in/out: reinstatements */
+    int32_t* thruster_hist;             /* NULL or [T*B] out: the pulsed thruster of the step, or -1 */
+} ftmpc_probe;
+
+/* ftmpc_simulate_isolation_batch with the probe `probe` (NULL: exactly ftmpc_simulate_isolation_batch, which IS this entry with
+ * NULL). */
+int ftmpc_simulate_probe_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                               const double* xref_traj, const double* uref_traj, const double noise[4], uint64_t seed,
+                               int32_t sqp_iters, int32_t backtracks, double tol, const ftmpc_fault_schedule* faults,
+                               double* u_hist, double* x_hist, int32_t* not_converged, const ftmpc_outcomes* out,
+                               const ftmpc_plant_model* plant, const ftmpc_mission* mission, const ftmpc_actuator* actuator,
+                               const ftmpc_sensor* sensor, const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis,
+                               const ftmpc_disturbance* disturbance, const ftmpc_bias_estimate* bias_estimate,
+                               const ftmpc_outage* outage, const ftmpc_environment* environment,
+                               const ftmpc_isolation* isolation, const ftmpc_probe* probe);
+
+/* The probe on the two-stage wrench form: ftmpc_simulate_wrench_isolation_batch with `probe` (NULL: exactly that entry's kernels
+ * and bits).  The kernels are the thruster form's; a reinstatement recomputes the hull offsets as any detection does (the
+ * reinstated thruster lies inside the starting index set of the hull tables). */
+int ftmpc_simulate_wrench_probe_batch(ftmpc_handle* h, int64_t B, int32_t T, double* x, const double* ub, const double* stuck,
+                                      const double* hull_A, int32_t n_sets, const int32_t* hull_set, const double* hull_b,
+                                      int32_t hull_rows, const double* xref_traj, const double* uref_traj,
+                                      const double noise[4], uint64_t seed, int32_t sqp_iters, int32_t backtracks, double tol,
+                                      double penalty, const ftmpc_fault_schedule* faults, double* u_hist, double* x_hist,
+                                      int32_t* not_converged, int32_t* alloc_failed, const ftmpc_outcomes* out,
+                                      const ftmpc_plant_model* plant, const ftmpc_mission* mission,
+                                      const ftmpc_actuator* actuator, const ftmpc_sensor* sensor,
+                                      const ftmpc_estimator* estimator, const ftmpc_diagnosis* diagnosis, double* out_hull_b,
+                                      int32_t* no_hull_step, const ftmpc_disturbance* disturbance,
+                                      const ftmpc_bias_estimate* bias_estimate, const ftmpc_outage* outage,
+                                      const ftmpc_environment* environment, const ftmpc_isolation* isolation,
+                                      const ftmpc_probe* probe);
 
 /* The wrench-form cost, QP step and SQP under a given estimate dist [B*6]: per vehicle f^ [3] (inertial, N), then t^ [3] (body, N m).
  * Each is its plain entry (ftmpc_eval_cost_wrench_batch, ftmpc_solve_wrench_batch, ftmpc_solve_sqp_wrench_batch) with `dist` inserted
